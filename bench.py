@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — rollouts/sec of one Optimizer::optimize() tick on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling strong|weak]
+    python bench.py --gpus N --steps K --warmup W [--scaling strong|weak] [--full] [--dump-outputs DIR]
 
 A "step" is one computeVelocityCommands() tick's optimize() call through the
 C-ABI (libsmpc.so): per-tick upload (control sequence, plan, tables), the
@@ -14,16 +14,21 @@ Workload (default, strong scaling): BASELINE.json configs[3] — 2 097 152 rollo
 x 64 steps in total on the 200x200 synthetic costmap, the batch the metric is
 quoted on; N GPUs own 2 097 152 / N rollouts each (N = 1 runs the whole batch on
 one GPU).  `--scaling weak` keeps 262 144 rollouts per GPU instead (N = 8 is then
-the same job).  At N = 1 the other BASELINE configs are timed too and reported
-under "other_configs", together with three variants of the headline workload:
-the tick without furthest-point speculation, a closed loop with a moving pose,
-and regenerate_noises = true.
+the same job).
+
+A plain run sets up, warms up, times the K steps and prints the headline.  Everything
+else takes runs of its own and comes with `--full` only: the same K ticks from the
+interpreter ("caller"), with HIP events for the roofline ("roofline") and with a moving
+pose ("moving_pose"); at N = 1 the other BASELINE configs ("other_configs": among them
+the tick without furthest-point speculation and regenerate_noises = true) and the CPU
+baseline ("cpu_baseline"); at N > 1 the exchanges that are not the headline.
+`--dump-outputs DIR` writes what the last timed tick handed its caller (dump_outputs).
 
 At N > 1 the exchange is RCCL called from inside libsmpc (smpc_shard_tick: one
 ncclAllGather of the shard tuples per tick on the ctx's stream).  The
-collective-free mailbox exchange (smpc_shard_p2p_*) is timed next to it (by
-default in the two-rank run only; SMPC_BENCH_ALTERNATIVES=1: at every N) and
-reported under "exchange_alternatives"; SMPC_BENCH_EXCHANGE=mailbox|torch
+collective-free mailbox exchange (smpc_shard_p2p_*) is timed next to it with
+--full (by default in the two-rank run only; SMPC_BENCH_ALTERNATIVES=1: at every N)
+and reported under "exchange_alternatives"; SMPC_BENCH_EXCHANGE=mailbox|torch
 makes another implementation the headline.  Every fall-through is recorded in
 the JSON line (config.exchange_fallbacks), not only on stderr.
 
@@ -140,6 +145,8 @@ def raise_clocks(g, ms, seed=1234, scn=None):
 
 def run_ticks(step_fn, scn, steps, warmup, sync, barrier, before_tick=None, after_tick=None, compiled=None):
     """W untimed ticks, then exactly K timed ones between barrier + synchronize on both sides.
+    -> (seconds of the K ticks, then per tick: score-pass ms, device ms, scoring passes; the last tick's
+    SmpcTickOut, the control sequence after it and its shift).
     before_tick / after_tick (e.g. smpc_redraw_noise_async) run inside the timed region when given.
     compiled = (Smpc, sortham_run_ticks flags): the same W + K closed-loop ticks issued by the
     compiled loop of host/tick_loop.cpp (one C call for the K timed ticks) instead of this
@@ -158,7 +165,7 @@ def run_ticks(step_fn, scn, steps, warmup, sync, barrier, before_tick=None, afte
         barrier()
         t1 = time.perf_counter()
         return ((t1 - t0), sum(o.score_pass_ms for o in outs) / steps, sum(o.device_ms for o in outs) / steps,
-                sum(o.passes for o in outs) / steps, outs[steps - 1])
+                sum(o.passes for o in outs) / steps, outs[steps - 1], u)
     u = scn.u0
     for _ in range(warmup):
         if before_tick:
@@ -185,7 +192,7 @@ def run_ticks(step_fn, scn, steps, warmup, sync, barrier, before_tick=None, afte
     sync()
     barrier()
     t1 = time.perf_counter()
-    return (t1 - t0), pass_ms / steps, dev_ms / steps, passes / steps, out
+    return (t1 - t0), pass_ms / steps, dev_ms / steps, passes / steps, out, u
 
 
 def last_pass_kernel(g):
@@ -195,6 +202,20 @@ def last_pass_kernel(g):
     f.restype = ctypes.c_char_p
     f.argtypes = []
     return f().decode()
+
+
+TICK_OUT_FIELDS = ("fail_flag", "furthest_valid", "furthest_reached_path_point", "non_colliding", "min_cost", "sum_w")
+
+
+def dump_outputs(d, g, u, out):
+    """--dump-outputs: what the timed path handed its caller in its last step, one .npy per array —
+    control_sequence [3, T] f32 (after the tick and its shift, as the loop leaves it), tick_out f64 (the
+    SmpcTickOut fields TICK_OUT_FIELDS, in that order; the timing fields are left out) and costs [B] f32
+    (the last tick's per-rollout costs of this rank's batch, smpc_get_costs: 8 MB at the headline batch)."""
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "control_sequence.npy"), np.asarray(u, dtype=np.float32))
+    np.save(os.path.join(d, "tick_out.npy"), np.array([getattr(out, f) for f in TICK_OUT_FIELDS], np.float64))
+    np.save(os.path.join(d, "costs.npy"), g.get_costs())
 
 
 class MovingScene:
@@ -269,11 +290,11 @@ def time_config(B, T, map_size, steps, warmup, flags=0, redraw=False, critics=No
     # it on the device, so in this back-to-back loop the whole draw is inside the timed region
     from mpcholonavigation_amd import host_optimizer as H
     loop = (g, H.TICKS_SHIFT | (H.TICKS_REDRAW_ASYNC if redraw else 0))
-    el, _, _, passes, out = run_ticks(g.optimize, scn, steps, warmup,
-                                      torch.cuda.synchronize, lambda: None, compiled=loop)
+    el, _, _, passes, out, _ = run_ticks(g.optimize, scn, steps, warmup,
+                                         torch.cuda.synchronize, lambda: None, compiled=loop)
     g.set_profile(True)
-    _, pass_ms, dev_ms, _, _ = run_ticks(g.optimize, scn, max(5, steps // 2), 2, torch.cuda.synchronize,
-                                         lambda: None, compiled=(g, H.TICKS_SHIFT))
+    _, pass_ms, dev_ms, _, _, _ = run_ticks(g.optimize, scn, max(5, steps // 2), 2, torch.cuda.synchronize,
+                                            lambda: None, compiled=(g, H.TICKS_SHIFT))
     P = len(scn.tick.path_x)
     by = algorithmic_bytes(B, T, map_size, map_size, P)
     tick_s = el / steps
@@ -473,8 +494,15 @@ def main():
                          "weak: --rollouts-per-gpu on every GPU")
     ap.add_argument("--total-rollouts", type=int, default=TOTAL_ROLLOUTS)
     ap.add_argument("--rollouts-per-gpu", type=int, default=SHARD_ROLLOUTS)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the interpreter-issued ticks, the "
+                         "roofline (a profiled run), the moving pose, the other exchanges (N > 1), the other "
+                         "configurations and the CPU baseline (N = 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: no other configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed ticks, write what the last one handed its caller as DIR/<name>.npy "
+                         "(control_sequence, tick_out, costs; rank 0)")
     ap.add_argument("--clock-warmup-ms", type=float, default=200.0,
                     help="milliseconds of device-RNG redraws in front of the warm-up ticks, so that the shader "
                          "clock has climbed (2.0 -> 2.34 GHz over ~150 ms of load) before anything is timed; "
@@ -621,21 +649,26 @@ def main():
         barrier()
     else:
         raise_clocks(g, args.clock_warmup_ms, scn=None if sharded else scn)
-    el, _, _, passes, out = run_ticks(step_fn, scn, args.steps, args.warmup,
-                                      torch.cuda.synchronize, barrier, compiled=loop)
-    # the same K ticks issued from this interpreter (Smpc.optimize + numpy shift per tick)
-    el_py = run_ticks(step_fn, scn, args.steps, 2, torch.cuda.synchronize, barrier)[0] if loop else el
-    # kernel duration for the roofline: the same K ticks again with HIP events around every
-    # scoring-pass launch, on the stream it is launched on (SMPC_FLAG_PROFILE; the event
-    # records cost ~15 us of queue time per tick, which is why they are not in the region above)
-    g.set_profile(True)
-    el_prof, pass_ms, dev_ms, _, _ = run_ticks(step_fn, scn, args.steps, 2,
-                                               torch.cuda.synchronize, barrier, compiled=loop)
-    g.set_profile(False)
-    # the same workload with a moving pose (closed loop; the furthest point changes as the robot
-    # advances, so the speculation of a frozen scene does not flatter the tick)
-    el_mv, passes_mv, mv = run_moving(step_fn, scn, cfg.model_dt, args.steps, min(args.warmup, 5),
-                                      torch.cuda.synchronize, barrier)
+    el, _, _, passes, out, u_last = run_ticks(step_fn, scn, args.steps, args.warmup,
+                                              torch.cuda.synchronize, barrier, compiled=loop)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, g, u_last, out)
+    if args.full:
+        # the same K ticks issued from this interpreter (Smpc.optimize + numpy shift per tick)
+        el_py = run_ticks(step_fn, scn, args.steps, 2, torch.cuda.synchronize, barrier)[0] if loop else el
+        # kernel duration for the roofline: the same K ticks again with HIP events around every
+        # scoring-pass launch, on the stream it is launched on (SMPC_FLAG_PROFILE; the event
+        # records cost ~15 us of queue time per tick, which is why they are not in the region above)
+        g.set_profile(True)
+        el_prof, pass_ms, dev_ms, _, _, _ = run_ticks(step_fn, scn, args.steps, 2,
+                                                      torch.cuda.synchronize, barrier, compiled=loop)
+        g.set_profile(False)
+        # the same workload with a moving pose (closed loop; the furthest point changes as the robot
+        # advances, so the speculation of a frozen scene does not flatter the tick)
+        el_mv, passes_mv, mv = run_moving(step_fn, scn, cfg.model_dt, args.steps, min(args.warmup, 5),
+                                          torch.cuda.synchronize, barrier)
+    else:
+        el_py = el_prof = el_mv = pass_ms = dev_ms = 0.0
     if sharded:
         t = torch.tensor([el, pass_ms, el_mv, el_py], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -647,7 +680,7 @@ def main():
     # of this N — with it; the N = 4 and N = 8 lines do not depend on it.  SMPC_BENCH_ALTERNATIVES=1
     # forces them at every N, =0 never.
     alt_env = os.environ.get("SMPC_BENCH_ALTERNATIVES", "")
-    if world > 1 and (alt_env == "1" or (alt_env == "" and world == 2)):
+    if args.full and world > 1 and (alt_env == "1" or (alt_env == "" and world == 2)):
         for kind in ("rccl", "mailbox", "torch"):
             if kind == headline_kind:
                 continue
@@ -659,8 +692,8 @@ def main():
                 continue
             ok, el_a, p_a = 1, 0.0, 0.0
             try:
-                el_a, _, _, p_a, _ = run_ticks(alt.optimize, scn, args.steps, args.warmup,
-                                               torch.cuda.synchronize, barrier, compiled=compiled_for(kind))
+                el_a, _, _, p_a, _, _ = run_ticks(alt.optimize, scn, args.steps, args.warmup,
+                                                  torch.cuda.synchronize, barrier, compiled=compiled_for(kind))
             except Exception as e:
                 ok = 0
                 alternatives[kind] = {"error": f"rank {rank}: {e}"}
@@ -677,13 +710,7 @@ def main():
         g.set_stream(-1)
 
     if rank == 0:
-        by = algorithmic_bytes(B, T, MAP, MAP, P)
-        achieved = by / (pass_ms * 1e-3) / 1e9 if pass_ms > 0 else 0.0
         tick_s = el / args.steps
-        # tick level, SURVEY §8(d): the GPU's algorithmic bytes of ONE scoring pass over the whole
-        # tick's wall time (uploads, every pass incl. re-scores, reduction, exchange, read-back)
-        achieved_tick = by / tick_s / 1e9
-        traffic, traffic_src = measured_traffic(B, T, f"{MAP}x{MAP}")
         total = world * B
         line = {
             "metric": "rollouts/sec per computeVelocityCommands() tick",
@@ -716,29 +743,11 @@ def main():
                 "furthest_reached_path_point": int(out.furthest_reached_path_point),
                 "scoring_passes_per_tick": passes,
             },
-            "roofline": {
-                "bound": "hbm",
-                "kernel": last_pass_kernel(g),
-                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                "algorithmic_bytes_per_launch": by,
-                "avg_launch_ms": pass_ms,
-                "achieved_tick": achieved_tick,
-                "frac_tick": achieved_tick / HBM_PEAK_GBS,
-                "frac_note": "frac: algorithmic bytes of one launch / average duration of the scoring-pass "
-                             "kernel; frac_tick: the same bytes / wall time of the whole tick (SURVEY 8(d))",
-                "device_ms_per_tick": dev_ms,
-                "timing": f"HIP events around each scoring-pass launch over {args.steps} further ticks "
-                          f"({1e3 * el_prof / args.steps:.4f} ms/tick with the event records in the stream)",
-            },
             "caller": {
                 "timed_loop": ("compiled: sortham_run_ticks (host/tick_loop.cpp) issues the W + K ticks — "
                                + ("smpc_optimize" if headline_kind == "single" else "smpc_shard_tick")
                                + " + shiftControlSequence per tick, as the reference's C++ controller does"
                                if loop else "this interpreter: Smpc.optimize + numpy shift per tick"),
-                "interpreted_ms_per_step": 1e3 * el_py / args.steps,
-                "note": "interpreted_ms_per_step: the same K ticks issued from bench.py's Python loop "
-                        "(a ctypes call and two numpy allocations between ticks)",
             },
             "clock_warmup": {
                 "ms": args.clock_warmup_ms,
@@ -751,14 +760,39 @@ def main():
                           "~150 ms of load (tools/clock_watch.py): without this, ticks 5-24 of a fresh process take 481 us, "
                           "in steady state ~400 us (tools/warm_ticks.py)",
             },
-            "moving_pose": {
-                "ms_per_step": 1e3 * el_mv / args.steps,
-                "rollouts_per_s": total * args.steps / el_mv,
-                "scoring_passes_per_tick": passes_mv,
-                "frac_tick": (by / (el_mv / args.steps) / 1e9) / HBM_PEAK_GBS,
-                "note": "closed loop: pose advanced by the emitted Twist every tick, plan pruned to the "
-                        f"robot; optimize() calls only ({mv.wraps} plan restarts)",
-            },
+        }
+    if rank == 0 and args.full:
+        by = algorithmic_bytes(B, T, MAP, MAP, P)
+        achieved = by / (pass_ms * 1e-3) / 1e9 if pass_ms > 0 else 0.0
+        # tick level, SURVEY §8(d): the GPU's algorithmic bytes of ONE scoring pass over the whole
+        # tick's wall time (uploads, every pass incl. re-scores, reduction, exchange, read-back)
+        achieved_tick = by / tick_s / 1e9
+        traffic, traffic_src = measured_traffic(B, T, f"{MAP}x{MAP}")
+        line["roofline"] = {
+            "bound": "hbm",
+            "kernel": last_pass_kernel(g),
+            "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+            "algorithmic_bytes_per_launch": by,
+            "avg_launch_ms": pass_ms,
+            "achieved_tick": achieved_tick,
+            "frac_tick": achieved_tick / HBM_PEAK_GBS,
+            "frac_note": "frac: algorithmic bytes of one launch / average duration of the scoring-pass "
+                         "kernel; frac_tick: the same bytes / wall time of the whole tick (SURVEY 8(d))",
+            "device_ms_per_tick": dev_ms,
+            "timing": f"HIP events around each scoring-pass launch over {args.steps} further ticks "
+                      f"({1e3 * el_prof / args.steps:.4f} ms/tick with the event records in the stream)",
+        }
+        line["caller"]["interpreted_ms_per_step"] = 1e3 * el_py / args.steps
+        line["caller"]["note"] = ("interpreted_ms_per_step: the same K ticks issued from bench.py's Python loop "
+                                  "(a ctypes call and two numpy allocations between ticks)")
+        line["moving_pose"] = {
+            "ms_per_step": 1e3 * el_mv / args.steps,
+            "rollouts_per_s": total * args.steps / el_mv,
+            "scoring_passes_per_tick": passes_mv,
+            "frac_tick": (by / (el_mv / args.steps) / 1e9) / HBM_PEAK_GBS,
+            "note": "closed loop: pose advanced by the emitted Twist every tick, plan pruned to the "
+                    f"robot; optimize() calls only ({mv.wraps} plan restarts)",
         }
         if alternatives:
             line["exchange_alternatives"] = alternatives
@@ -792,6 +826,7 @@ def main():
             line["cpu_baseline"]["configs[0] 1000x30"] = {
                 "cpu_rollouts_per_s": c0["value"], "cpu_ms_per_tick": 1e3 * 1000 / c0["value"],
                 "gpu_rollouts_per_s": g0["rollouts_per_s"], "gpu_ms_per_tick": g0["ms_per_tick"]}
+    if rank == 0:
         print(json.dumps(line), flush=True)
     g.close()
     if sharded:

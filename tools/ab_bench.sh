@@ -4,8 +4,8 @@
 set -e
 out=${2:-gpurun_out/ab}
 mkdir -p "$out"
-python bench.py --no-cpu-baseline > "$out/a.json" 2> "$out/a.err"
-env "$1" python bench.py --no-cpu-baseline > "$out/b.json" 2> "$out/b.err"
+python bench.py --full --no-cpu-baseline > "$out/a.json" 2> "$out/a.err"
+env "$1" python bench.py --full --no-cpu-baseline > "$out/b.json" 2> "$out/b.err"
 python - "$out" "$1" <<PY
 import json, sys
 out, what = sys.argv[1], sys.argv[2]
