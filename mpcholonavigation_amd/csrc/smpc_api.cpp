@@ -138,7 +138,7 @@ int launch_furthest(smpc_ctx* c, float* d_furthest)
   d.furthest_out = reinterpret_cast<uint32_t*>(d_furthest);
   SmpcLds L = make_lds(0, c->P, d.T, (pass_block(c->R) / 64), false);
   c->launched = true;
-  HIPCK(c, smpc_launch_pass(c->R, 1, d, L, c->grid, pass_block(c->R), c->stream));
+  HIPCK(c, wave_launch(wave_select(c->R, 1, d.T), d, L, c->plan.wave.grid, c->plan.wave.block, c->stream));
   return SMPC_OK;
 }
 
@@ -165,7 +165,7 @@ void fill_score_args(smpc_ctx* c, uint32_t flags, const float* u_dev, const floa
   fin.enabled = finish ? 1 : 0;
   fin.vx_max = c->c_vx_max; fin.vx_min = c->c_vx_min; fin.vy_max = c->c_vy; fin.wz_max = c->c_wz;
   fin.u_dev = c->d_out; fin.u_host = c->h_out_dev; fin.furthest_used = finish_furthest;
-  if (finish && c->poll_enabled) {
+  if (finish && c->knobs.poll) {
     fin.done_counter = reinterpret_cast<uint32_t*>(c->d_furthest) + 2;
     fin.seq = ++c->seq;
     if (fin.seq == 0) fin.seq = ++c->seq;
@@ -178,6 +178,32 @@ void fill_score_args(smpc_ctx* c, uint32_t flags, const float* u_dev, const floa
   }
 }
 
+// The pass that scores `flags` this tick: what plan_launch chose, or — for a pass whose flags were
+// stripped after the launch was planned: fail_flag_in (the retry after fallback(), which scores
+// nothing: critic_manager.cpp:70-73) or the later iterations of an all-collide tick — the next
+// family down that has an instance for them.  The split form scores the plain five with
+// ObstaclesCritic on: its stripped tick takes the lane pass.  The re-read form has instances with
+// ObstaclesCritic scored only, and no lane instance writes trajectories: such a pass takes the
+// wave-per-rollout pass (its geometry is planned for every tick).  A parking-form tick without an
+// instance is an error, as it always was.
+struct PassChoice {
+  PassPlan::Kind kind;
+  const void* inst;        // WaveInst, LaneInst or SplitInst by kind; null: no instance
+  const PassGeom* geom;
+};
+static PassChoice pass_for(const smpc_ctx* c, uint32_t flags)
+{
+  const PassPlan& pl = c->plan;
+  const uint32_t T = c->dev.T;
+  if (pl.kind == PassPlan::kSplit)
+    if (const SplitInst* k = split_select(flags, T, c->dev.step, pl.split_nseg)) return {PassPlan::kSplit, k, &pl.split};
+  if (pl.kind != PassPlan::kWave) {
+    const LaneInst* k = lane_select(flags, T, pl.rr, false, c->acker_r);
+    if (k || !(pl.rr || (flags & SD_STORE_TRAJ))) return {PassPlan::kLane, k, &pl.lane};
+  }
+  return {PassPlan::kWave, wave_select(c->R, c->score_mode, T), &pl.wave};
+}
+
 int launch_score(smpc_ctx* c, uint32_t flags, const float* u_dev, const float* d_furthest,
                  uint32_t furthest_hint, float* d_tuple, bool finish, const float* finish_furthest)
 {
@@ -186,20 +212,13 @@ int launch_score(smpc_ctx* c, uint32_t flags, const float* u_dev, const float* d
   fill_score_args(c, flags, u_dev, d_furthest, furthest_hint, finish, finish_furthest, d, fin);
   const bool prof = (c->cfg.flags & SMPC_FLAG_PROFILE) && c->evp_used + 2 <= 8;
   if (prof) HIPCK(c, hipEventRecord(c->evp[c->evp_used], c->stream));
-  uint32_t nblk = c->grid;
-  // The re-read form has instances with a collision critic scored only.  A tick whose flags were
-  // stripped after the launch was planned — fail_flag_in (the retry after fallback(), which scores
-  // nothing: critic_manager.cpp:70-73) or the later iterations of an all-collide tick — takes the
-  // wave-per-rollout pass instead (its geometry is planned for every tick).
-  const bool lane = c->lane_now && !(flags & SD_STORE_TRAJ) &&
-    !(c->lane_rr && !(flags & (SD_OBSTACLES | SD_COST)));
-  // (the split form scores the plain five with ObstaclesCritic on: a tick whose flags were stripped takes the lane pass)
-  const bool split = lane && c->split_now && (flags & SD_OBSTACLES) && !(flags & (SD_GOAL_ANGLE | SD_EXTRA_CRITICS));
-  if (lane) nblk = split ? c->grid_split : c->grid_tpr;
+  const PassChoice pass = pass_for(c, flags);
+  const uint32_t nblk = pass.geom->grid;
   // The block that finishes last reduces the partials inside the scoring launch (smpc_tail.h);
   // larger grids, and launches whose LDS was not sized for it, take the separate reduction.
-  const bool tail = !split && c->fused_reduce && nblk <= SMPC_TAIL_MAX_GRID && (!lane || c->lane_block == smpc_lane_block()) &&
-    (lane ? c->lds_tpr.total : c->lds.total) >= smpc_tail_lds_bytes(d.T);
+  // (The lane pass: full-size blocks only.)
+  const bool tail = pass.kind != PassPlan::kSplit && c->knobs.fused_reduce && nblk <= SMPC_TAIL_MAX_GRID &&
+    (pass.kind != PassPlan::kLane || pass.geom->block == smpc_lane_block()) && pass.geom->lds.total >= smpc_tail_lds_bytes(d.T);
   // completion words: one per block of smpc_reduce_partials, or per reducing block of the tail
   c->poll_words = (fin.enabled && fin.done_counter) ? (4u + 3u * d.T + 31u) / 32u : 0u;
   static_assert((4u + 3u * 64u * SMPC_MAX_R + 31u) / 32u <= kPollWords, "one completion word per reducing block");
@@ -216,18 +235,15 @@ int launch_score(smpc_ctx* c, uint32_t flags, const float* u_dev, const float* d
     d.fin = fin;
   }
   c->launched = true;
-  // the lane-per-rollout pass scores with the full lean critic stack only
-  if (split) {
-    HIPCK(c, smpc_launch_pass_split(d, c->lds_split, nblk, c->split_nseg, c->stream));
-    c->last_pass_kind = 2;
-  } else if (lane) {
-    HIPCK(c, smpc_launch_pass_lane(d, c->lds_tpr, nblk, c->lane_rr, c->lane_block, c->stream));
-    c->last_pass_kind = 1;
+  c->last_pass_kind = pass.kind;
+  if (pass.kind == PassPlan::kSplit) {
+    HIPCK(c, split_launch(static_cast<const SplitInst*>(pass.inst), d, pass.geom->lds, nblk, c->stream));
+  } else if (pass.kind == PassPlan::kLane) {
+    HIPCK(c, lane_launch(static_cast<const LaneInst*>(pass.inst), d, nullptr, 1, pass.geom->lds, nblk, pass.geom->block, c->stream));
   } else {
-    c->last_pass_kind = 0;
-    const int rc_rm = ensure_row_major(c);
+    const int rc_rm = ensure_row_major(c);   // the wave-per-rollout pass reads the [B,T] tensors
     if (rc_rm != SMPC_OK) return rc_rm;
-    HIPCK(c, smpc_launch_pass(c->R, c->score_mode, d, c->lds, c->grid, pass_block(c->R), c->stream));
+    HIPCK(c, wave_launch(static_cast<const WaveInst*>(pass.inst), d, pass.geom->lds, nblk, pass.geom->block, c->stream));
   }
   if (prof) {
     HIPCK(c, hipEventRecord(c->evp[c->evp_used + 1], c->stream));
@@ -244,7 +260,7 @@ int launch_combine(smpc_ctx* c, const float* d_tuples, uint32_t n, const float* 
 {
   const uint32_t T = c->cfg.time_steps;
   uint32_t seq = 0;
-  if (c->poll_enabled) {
+  if (c->knobs.poll) {
     seq = ++c->seq;
     if (seq == 0) seq = ++c->seq;
     c->poll_seq = seq;
@@ -484,6 +500,33 @@ int redraw_async(smpc_ctx* c)
   c->redraw_pending = true;
   return SMPC_OK;
 }
+
+// the developer knobs (smpc_ctx.h: Knobs), read once per context
+static Knobs read_knobs()
+{
+  Knobs k;
+  auto set = [](const char* name) {return getenv(name) != nullptr;};
+  auto number = [](const char* name, int unset) {const char* e = getenv(name); return e ? atoi(e) : unset;};
+  if (const char* e = getenv("SMPC_PASS"))
+    k.pass = !strcmp(e, "wave") ? Knobs::kWave : !strcmp(e, "lane") ? Knobs::kLane : !strcmp(e, "split") ? Knobs::kSplit : Knobs::kAuto;
+  k.no_split = set("SMPC_NO_SPLIT");
+  k.split_nseg = static_cast<uint32_t>(std::max(0, number("SMPC_SPLIT_NSEG", 0)));
+  k.lane_reread = number("SMPC_LANE_REREAD", 0) != 0;
+  k.half_blocks = !set("SMPC_NO_HALF_BLOCKS");
+  k.max_blocks_per_cu = static_cast<uint32_t>(std::max(0, number("SMPC_MAX_BLOCKS_PER_CU", 0)));
+  k.balanced_grid = !set("SMPC_NO_BALANCED_GRID");
+  k.fused_reduce = set("SMPC_FUSED_REDUCE");   // (per context: tests compare the two)
+  k.no_inline_tick = set("SMPC_NO_INLINE_TICK");
+  k.pinned_tick = set("SMPC_PINNED_TICK");
+  k.poll = !set("SMPC_NO_POLL");
+  k.bar_tick = !set("SMPC_NO_BAR_TICK");
+  k.hdp_flush = !set("SMPC_NO_HDP_FLUSH");
+  k.repeat_pass = set("SMPC_DEBUG_REPEAT_PASS");
+  k.stale_tick = static_cast<uint32_t>(number("SMPC_DEBUG_STALE_TICK", 0));
+  k.small_window = set("SMPC_SMALL_WINDOW");
+  k.window_side_max = number("SMPC_WINDOW_SIDE_MAX", -1);
+  return k;
+}
 }  // namespace smpc_impl
 
 using namespace smpc_impl;
@@ -564,6 +607,7 @@ int smpc_create(const smpc_config* cfg, smpc_ctx** out)
   smpc_ctx* c = new (std::nothrow) smpc_ctx();
   if (!c) return fail(nullptr, SMPC_ERR_NOMEM, "out of host memory");
   c->cfg = *cfg;
+  c->knobs = read_knobs();
   smpc_critic_params_default(&c->critics);
   c->holonomic = cfg->motion_model == SMPC_MODEL_OMNI;
   c->acker_r = cfg->motion_model == SMPC_MODEL_ACKERMANN ? cfg->ackermann_min_turning_r : -1.f;
@@ -589,8 +633,8 @@ int smpc_create(const smpc_config* cfg, smpc_ctx** out)
   {
     int large_bar = 0;
     if (hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, dev) != hipSuccess) large_bar = 0;
-    c->bar_tick = large_bar != 0 && getenv("SMPC_NO_BAR_TICK") == nullptr;
-    if (c->bar_tick && !getenv("SMPC_NO_HDP_FLUSH")) {
+    c->bar_tick = large_bar != 0 && c->knobs.bar_tick;
+    if (c->bar_tick && c->knobs.hdp_flush) {
       c->hdp_flush = find_hdp_flush(dev);
       // without the device's HDP flush register the stores may sit in the host data path's
       // cache when the pass starts: such a device takes the stream copy (SMPC_NO_HDP_FLUSH=1, an
@@ -600,7 +644,6 @@ int smpc_create(const smpc_config* cfg, smpc_ctx** out)
   }
   CK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
   c->stream = c->own_stream;
-  c->poll_enabled = getenv("SMPC_NO_POLL") == nullptr;
   if (getenv("SMPC_LANE_TIMELINE")) {
     static_assert(SMPC_TAIL_STAMPS_AT == 8192 + kMaxGrid * 8, "the tail's stamps sit behind the lane pass's");
     CK(hipMalloc(&c->d_timeline, (8192 + kMaxGrid * 8 + 8 * 16) * sizeof(unsigned long long)));
@@ -624,29 +667,18 @@ int smpc_create(const smpc_config* cfg, smpc_ctx** out)
     // (smpc_pass_split, T = 64: the group-major noise from kSplitMinBatch rollouts up; plan_launch keeps
     // the lane pass itself for batches from kLaneMinBatch up, unless it is asked for)
     if (cfg->time_steps <= 64 && cfg->time_steps >= 36 && (cfg->time_steps & 3u) == 0 && cfg->batch_size >= kSplitMinBatch &&
-        !getenv("SMPC_NO_SPLIT"))
+        !c->knobs.no_split)
       tpr = true;
     if (cfg->flags & SMPC_FLAG_WAVE_PER_ROLLOUT) tpr = false;
     if (cfg->flags & SMPC_FLAG_LANE_PER_ROLLOUT) {
       tpr = true;
       c->lane_forced = true;
     }
-    if (const char* e = getenv("SMPC_PASS")) {
-      if (!strcmp(e, "wave")) tpr = false;
-      if (!strcmp(e, "lane")) {
-        tpr = true;
-        c->lane_forced = true;
-      }
-      if (!strcmp(e, "split")) {
-        tpr = true;
-        c->lane_forced = true;
-        c->knob_force_split = true;
-      }
+    if (c->knobs.pass == Knobs::kWave) tpr = false;
+    if (c->knobs.pass == Knobs::kLane || c->knobs.pass == Knobs::kSplit) {   // (split: wherever the instance applies, whatever the batch)
+      tpr = true;
+      c->lane_forced = true;
     }
-    c->knob_no_split = getenv("SMPC_NO_SPLIT") != nullptr;
-    c->knob_repeat_pass = getenv("SMPC_DEBUG_REPEAT_PASS") != nullptr;
-    if (const char* e = getenv("SMPC_DEBUG_STALE_TICK")) c->knob_stale_tick = static_cast<uint32_t>(atoi(e));
-    if (const char* e = getenv("SMPC_SPLIT_NSEG")) c->knob_split_nseg = static_cast<uint32_t>(std::max(0, atoi(e)));
     if (cfg->flags & SMPC_FLAG_STORE_TRAJECTORIES) tpr = false;   // visualisation path: wave pass
     // the group-major copies (smpc_dev.h: SMPC_GM_INDEX): the batch padded to whole groups of 64
     const size_t ngm = static_cast<size_t>(SMPC_GM_ROLLOUTS(cfg->batch_size)) * T * sizeof(float);
@@ -658,8 +690,8 @@ int smpc_create(const smpc_config* cfg, smpc_ctx** out)
       c->d_tvy = c->d_tvx + ngm / sizeof(float);
       c->d_twz = c->d_tvy + ngm / sizeof(float);
       if (!c->holonomic) CK(hipMemset(c->d_tvy, 0, ngm));
-      CK(smpc_lane_set_lds_limit(static_cast<int>(kLdsPerCu)));
-      CK(smpc_split_set_lds_limit(static_cast<int>(kLdsPerCu)));
+      CK(lane_set_lds_limit(static_cast<int>(kLdsPerCu)));
+      CK(split_set_lds_limit(static_cast<int>(kLdsPerCu)));
     }
   }
   CK(hipMalloc(&c->d_costs[0], cfg->batch_size * sizeof(float)));
@@ -691,16 +723,9 @@ int smpc_create(const smpc_config* cfg, smpc_ctx** out)
   CK(hipHostMalloc(&c->h_out, (3 * T + 8 + kPollWords) * sizeof(float), hipHostMallocMapped));
   memset(c->h_out, 0, (3 * T + 8 + kPollWords) * sizeof(float));
   CK(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->h_out_dev), c->h_out, 0));
-  c->half_blocks = getenv("SMPC_NO_HALF_BLOCKS") == nullptr;
-  if (const char* e = getenv("SMPC_MAX_BLOCKS_PER_CU")) c->knob_max_blocks_per_cu = static_cast<uint32_t>(std::max(0, atoi(e)));
-  if (const char* e = getenv("SMPC_LANE_REREAD")) c->knob_lane_reread = atoi(e) != 0;
-  c->knob_no_inline_tick = getenv("SMPC_NO_INLINE_TICK") != nullptr;
-  c->knob_pinned_tick = getenv("SMPC_PINNED_TICK") != nullptr;
-  c->knob_balanced_grid = getenv("SMPC_NO_BALANCED_GRID") == nullptr;
-  c->fused_reduce = getenv("SMPC_FUSED_REDUCE") != nullptr;   // (read per context: tests compare the two)
   CK(hipMalloc(&c->d_furthest, 32));
   CK(hipMemset(c->d_furthest, 0, 32));
-  CK(smpc_set_pass_lds_limit(static_cast<int>(kLdsPerCu)));
+  CK(wave_set_lds_limit(static_cast<int>(kLdsPerCu)));
   // the memsets above went to the default stream; the ctx works on its own non-blocking one
   CK(hipDeviceSynchronize());
 #undef CK
@@ -1034,7 +1059,7 @@ int smpc_optimize(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_tick
         if (rc != SMPC_OK) return rc;
       }
     }
-    if (c->knob_repeat_pass) {   // (tests: a second pass of the iteration must see the first one's inputs)
+    if (c->knobs.repeat_pass) {   // (tests: a second pass of the iteration must see the first one's inputs)
       rc = launch_score(c, flags & ~SD_LOCAL_FURTHEST, u_dev, nullptr, S_known ? S_host : hintS, c->d_tuple, true, nullptr);
       if (rc != SMPC_OK) return rc;
       rc = fetch_out(c);
@@ -1230,7 +1255,7 @@ int smpc_debug_lane_timeline(smpc_ctx* c, double* out, uint32_t* n_blocks)
   if (!c || !out || !c->d_timeline) return SMPC_ERR_INVALID;
   HIPCK(c, hipSetDevice(c->device));
   HIPCK(c, hipStreamSynchronize(c->stream));
-  const uint32_t nb = c->grid_tpr;
+  const uint32_t nb = c->plan.lane.grid;
   std::vector<unsigned long long> h(static_cast<size_t>(nb) * 8);
   HIPCK(c, hipMemcpy(h.data(), c->d_timeline, h.size() * sizeof(h[0]), hipMemcpyDeviceToHost));
   unsigned long long t0 = ~0ull;

@@ -25,15 +25,11 @@
 
 #include "../../include/smpc.h"
 #include "smpc_dev.h"
+#include "smpc_inst.h"   // the scoring-pass instances: tables, selectors, launch
 
 // nothing below is part of the C-ABI: keep it out of the dynamic symbol table
 #pragma GCC visibility push(hidden)
 
-hipError_t smpc_launch_pass(int R, int mode, const SmpcDev& p, const SmpcLds& L,
-                            uint32_t grid, uint32_t block, hipStream_t st);
-hipError_t smpc_pass_occupancy(int R, int mode, bool full, uint32_t block, uint32_t lds_bytes,
-                               int* blocks_per_cu);
-hipError_t smpc_set_pass_lds_limit(int bytes);
 hipError_t smpc_launch_reduce(const float* partials, uint32_t nblk, uint32_t T,
                               float neg_inv_temp, float* tuple, const SmpcFinal& fin,
                               hipStream_t st);
@@ -54,25 +50,14 @@ hipError_t smpc_launch_p2p_exchange(const float* my_tuple, const SmpcP2P& x, uin
                                     hipStream_t st);
 
 hipError_t smpc_launch_relayout(const float* src, float* dst, uint32_t B, uint32_t T, bool to_gm, hipStream_t st);
-hipError_t smpc_launch_pass_lane(const SmpcDev& p, const SmpcLds& L, uint32_t grid, bool rr, uint32_t block, hipStream_t st);
 uint32_t smpc_lane_block();
 uint32_t smpc_lane_block_rr();
-hipError_t smpc_lane_occupancy(bool full, uint32_t lds_bytes, int* blocks_per_cu);
-hipError_t smpc_lane_occupancy_rr(uint32_t T, uint32_t lds_bytes, int* blocks_per_cu);
-hipError_t smpc_lane_set_lds_limit(int bytes);
 hipError_t smpc_launch_lane_reduce(const float* v, const float* w, float* out, hipStream_t st);
 // smpc_split.hip: lane = (rollout, quarter of the horizon), for batches of at most one round of waves
-hipError_t smpc_launch_pass_split(const SmpcDev& p, const SmpcLds& L, uint32_t grid, uint32_t nseg, hipStream_t st);
 hipError_t smpc_launch_row_reduce(const float* v, float* out, uint32_t n, hipStream_t st);
 uint32_t smpc_split_block();
 uint32_t smpc_split_rollouts_per_block(uint32_t nseg);
-hipError_t smpc_split_occupancy(uint32_t nseg, uint32_t lds_bytes, int* blocks_per_cu);
-hipError_t smpc_split_set_lds_limit(int bytes);
-hipError_t smpc_launch_pass_lane_many(const SmpcDev* d_many, uint32_t n, bool full, bool obst, bool dep, uint32_t T,
-                                      const SmpcLds& L, uint32_t grid, uint32_t block, hipStream_t st);
 hipError_t smpc_launch_reduce_many(const SmpcReduceArgs* d_many, uint32_t n, uint32_t T, hipStream_t st);
-// developer aid: the scoring-pass instance launched last, as rocprofv3 names it
-extern char smpc_last_pass_kernel[96];
 hipError_t smpc_launch_sincos(const float* x, uint32_t n, float* sn, float* cs, hipStream_t st);
 
 namespace smpc_impl {
@@ -140,6 +125,63 @@ inline bool within_tol(float tol, double rx, double ry, double gx, double gy)
   return dist_sq < tol_sq;
 }
 
+// Developer knobs: read from the environment once, when the context is created (read_knobs,
+// smpc_api.cpp), never per tick.  Experiments and tests; the defaults are the product.
+struct Knobs {
+  enum Pass {kAuto, kWave, kLane, kSplit} pass = kAuto;   // SMPC_PASS=wave|lane|split: the streaming pass, whatever the batch
+  bool no_split = false;           // SMPC_NO_SPLIT=1
+  uint32_t split_nseg = 0;         // SMPC_SPLIT_NSEG=2|4
+  bool lane_reread = false;        // SMPC_LANE_REREAD=1: the re-read form for T = 64 too
+  bool half_blocks = true;         // SMPC_NO_HALF_BLOCKS=1 turns it off
+  uint32_t max_blocks_per_cu = 0;  // SMPC_MAX_BLOCKS_PER_CU
+  bool balanced_grid = true;       // SMPC_NO_BALANCED_GRID=1 turns it off: re-read form, launch only the waves that fill every round
+  bool fused_reduce = false;       // SMPC_FUSED_REDUCE=1: smpc_grid_tail reduces inside the scoring launch (an experiment
+                                   // that measured no faster than the separate launch: DESIGN.md 4.3)
+  bool no_inline_tick = false;     // SMPC_NO_INLINE_TICK
+  bool pinned_tick = false;        // SMPC_PINNED_TICK=1: kernels read the tick block from pinned host memory
+  bool poll = true;                // SMPC_NO_POLL=1 disables completion polling on the host-mapped result
+  bool bar_tick = true;            // SMPC_NO_BAR_TICK=1: the per-tick upload as a copy on the stream
+  bool hdp_flush = true;           // SMPC_NO_HDP_FLUSH=1: the BAR stores without the flush (the canary then guards every tick)
+  bool repeat_pass = false;        // SMPC_DEBUG_REPEAT_PASS=1 (tests): every iteration's scoring pass is launched twice
+  uint32_t stale_tick = 0;         // SMPC_DEBUG_STALE_TICK=n (tests): the BAR hand-over skips tick n's block
+  bool small_window = false;       // SMPC_SMALL_WINDOW: the 96-cell costmap window for T > 64 too
+  int window_side_max = -1;        // SMPC_WINDOW_SIDE_MAX=cells, < 0: kWindowSideMax
+};
+
+// blocks per CU of the instance asked about last (the answer moves with the LDS a tick needs)
+struct OccCache {
+  const void* fn = nullptr;
+  uint32_t block = 0, lds = 0;
+  uint32_t blocks = 1;
+  uint32_t get(const void* f, uint32_t blk, uint32_t lds_bytes)
+  {
+    if (f != fn || blk != block || lds_bytes != lds) {
+      int nb = 0;
+      if (inst_occupancy(f, blk, lds_bytes, &nb) != hipSuccess || nb < 1) nb = 1;
+      fn = f; block = blk; lds = lds_bytes;
+      blocks = static_cast<uint32_t>(nb);
+    }
+    return blocks;
+  }
+};
+
+// Which scoring pass takes the tick, and its launch geometry.  Written by plan_launch
+// (smpc_prepare.cpp) only; pass_for (smpc_api.cpp) picks the instance for a pass's flags from it.
+struct PassGeom {
+  uint32_t grid = 0, block = 0;
+  SmpcLds lds{};
+};
+struct PassPlan {
+  enum Kind : uint32_t {kWave = 0, kLane = 1, kSplit = 2};   // (the values of smpc_tick_out.pass_kind)
+  Kind kind = kWave;
+  PassGeom wave;              // planned for every tick: a pass whose flags have no lane instance falls back to it
+  PassGeom lane;              // kind != kWave (a split tick whose flags were stripped takes the lane pass)
+  PassGeom split;             // kind == kSplit
+  bool rr = false;            // the lane pass in its re-read form (no parked controls; T > 64 or SMPC_LANE_REREAD=1)
+  uint32_t split_nseg = 4;    // lanes per rollout of the split pass: 4 or 2
+  uint32_t window_bytes = 0;  // first LDS region of the lane pass
+};
+
 }  // namespace smpc_impl
 
 struct smpc_ctx {
@@ -176,26 +218,15 @@ struct smpc_ctx {
   bool use_tpr = false;      // group-major noise kept: the lane-per-rollout pass may run
   bool rm_valid = true;      // the [B,T] tensors hold the current noise (a device-RNG draw fills the
                              // group-major copy only; ensure_row_major() makes the other on demand)
-  bool lane_now = false;     // ... and does for this tick (lean scoring mode)
-  bool split_now = false;    // ... as smpc_pass_split (lane = rollout x quarter of the horizon): small batches at T = 64
-  SmpcLds lds_split{};
-  uint32_t grid_split = 0;
-  uint32_t split_nseg = 4;               // lanes per rollout of this tick's split pass: 4 or 2
-  int occ_split_blocks = -1;
-  uint32_t occ_split_lds = 0xffffffffu;
-  uint32_t knob_split_nseg = 0;          // SMPC_SPLIT_NSEG=2|4: experiments
+  smpc_impl::Knobs knobs;
+  smpc_impl::PassPlan plan;              // this tick's scoring pass (plan_launch)
+  smpc_impl::OccCache occ_wave, occ_lane, occ_split;
   bool lane_forced = false;              // SMPC_FLAG_LANE_PER_ROLLOUT / SMPC_PASS=lane|split: the lane pass below kLaneMinBatch too
-  bool knob_no_split = false;            // SMPC_NO_SPLIT=1
-  bool knob_repeat_pass = false;         // SMPC_DEBUG_REPEAT_PASS=1 (tests): every iteration's scoring pass is launched twice
-  uint32_t knob_stale_tick = 0;          // SMPC_DEBUG_STALE_TICK=n (tests): the BAR hand-over skips tick n's block
   bool two_coll_fp = false;              // this tick: BOTH collision critics scored and a consider_footprint switch set —
                                          // they then disagree on which rollouts collide (smpc_optimize: a counting pass)
-  bool knob_force_split = false;         // SMPC_PASS=split: wherever the instance applies, whatever the batch
-  bool lane_rr = false;      // ... in its re-read form (no parked controls; T > 64 or SMPC_LANE_REREAD=1)
   uint32_t last_pass_kind = 0;
   // member of a smpc_group: the group uploads every member's tick block in one copy
   bool defer_upload = false;
-  uint32_t lane_window_bytes = 0;   // first LDS region of the lane pass this tick
   // consider_footprint: robot footprint (smpc_set_footprint) and the LUT pair built for it
   std::vector<double> fp_x, fp_y;
   double fp_circumscribed_radius = 0.0, fp_layer_scale = -1.0;
@@ -212,19 +243,8 @@ struct smpc_ctx {
   uint32_t p2p_xseq = 0;
   uint32_t p2p_timeout_ms = 10000;   // bound of the in-kernel wait for the peers (smpc_shard_p2p_set_timeout)
   bool p2p_failed = false;           // an exchange timed out: no further mailbox tick until re-init
-  SmpcLds lds_tpr{};
-  uint32_t grid_tpr = 0;
-  uint32_t lane_block = 0;      // threads per block of the lane pass this tick
   bool pang_any = false;        // this tick: PathAngleCritic is live for some candidate furthest point (prepare_tick)
   bool in_group = false;        // member of an smpc_group: full-size blocks always (the group fills the CUs by itself)
-  // developer knobs, read from the environment when the context is created (never per tick)
-  uint32_t knob_max_blocks_per_cu = 0;   // SMPC_MAX_BLOCKS_PER_CU
-  bool knob_lane_reread = false;         // SMPC_LANE_REREAD=1: the re-read form for T = 64 too
-  bool knob_no_inline_tick = false;      // SMPC_NO_INLINE_TICK
-  bool knob_balanced_grid = true;        // SMPC_NO_BALANCED_GRID=1 turns it off: re-read form, launch only the waves that fill every round
-  bool knob_pinned_tick = false;         // SMPC_PINNED_TICK=1: kernels read the tick block from pinned host memory
-  bool half_blocks = true;      // (SMPC_NO_HALF_BLOCKS, read when the context is created: experiments)
-  uint32_t occ_tpr_blocks = 0, occ_tpr_lds = 0xffffffffu;
   float* d_costs[2] = {nullptr, nullptr};
   float* d_traj[3] = {nullptr, nullptr, nullptr};
   int costs_cur = 0;
@@ -250,6 +270,7 @@ struct smpc_ctx {
   // The per-tick upload as CPU stores straight into device memory (large-BAR systems: every
   // MI355X host maps the whole HBM) instead of a copy on the stream: no blit kernel (3.4 us) and
   // no dependent-dispatch gap (4 us) in front of the scoring pass.  SMPC_NO_BAR_TICK=1: the copy.
+  // (Tick state, not a knob: a device capability, cleared at run time when a hand-over fails.)
   bool bar_tick = false;
   volatile uint32_t* hdp_flush = nullptr;   // HDP_MEM_FLUSH_CNTL of this device, or null
   size_t tick_used = 0;         // bytes of the tick block this tick fills (a multiple of 16)
@@ -264,20 +285,13 @@ struct smpc_ctx {
                                 // second pass of the same iteration (a re-score) reads what the first one read
   float* h_out = nullptr;       // pinned, device-mapped: kernels write the result here
   float* h_out_dev = nullptr;   // its device-side address
-  bool fused_reduce = false;    // SMPC_FUSED_REDUCE=1: smpc_grid_tail reduces inside the scoring launch (an experiment
-                                // that measured no faster than the separate launch: DESIGN.md 4.3)
   float* d_furthest = nullptr;  // word 0: the furthest point (atomicMax on its bits); 2: smpc_reduce_partials' block count;
                                 // 3: the mailbox exchange's state; 4: smpc_grid_tail's block count
-  // launch geometry
-  int R = 1;
-  uint32_t grid = 0;
-  SmpcLds lds{};
+  int R = 1;                 // horizon in chunks of 64 steps per wave of the wave-per-rollout pass: 1, 2 or 4
   // per-tick prepared state
   SmpcDev dev{};
   uint32_t gate_flags = 0;   // critics past their host-side gates this tick
   int score_mode = 0;        // 0: every cost_power == 1 (one fused reduction), 2: general
-  uint32_t occ_blocks = 1, occ_lds = 0xffffffffu;
-  int occ_mode = -1;
   static int score_mode_for(const smpc_critic_params& cr)
   {
     return (cr.obstacles.cost_power == 1 && cr.path_align.cost_power == 1 &&
@@ -310,8 +324,6 @@ struct smpc_ctx {
   double anchor_ex = 0, anchor_ey = 0, cur_ex = 0, cur_ey = 0;
   bool anchor_e_valid = false, cur_e_valid = false;
   std::vector<float> anchor_px, anchor_py;
-  // completion polling on the host-mapped result (SMPC_NO_POLL=1 disables)
-  bool poll_enabled = true;
   // Optimizer::isHolonomic (optimizer.cpp:235).  A non-holonomic model is the Omni data path
   // with the vy noise, control_sequence.vy and state.vy[:,0] all zero: then state.vy = 0,
   // dx = vx cos - 0 sin, the vy gamma term and the weighted vy update are exactly 0 — what the

@@ -109,7 +109,7 @@ int smpc_group_optimize(smpc_group* g, const smpc_tick_in* ins, float* const* u_
   // ---- prepare every member; decide whether the batched launch applies -----------------
   bool batched = true;
   uint32_t Pmax = 0, window_bytes = 0, gridx = 0;
-  bool obst = false, dep = false;
+  const LaneInst* inst = nullptr;   // the grouped instance: one for all members
   std::vector<uint32_t> flags(n);
   for (uint32_t i = 0; i < n; ++i) {
     smpc_ctx* c = g->ctxs[i];
@@ -123,22 +123,21 @@ int smpc_group_optimize(smpc_group* g, const smpc_tick_in* ins, float* const* u_
     const bool need_f = (flags[i] & SD_NEED_FURTHEST) != 0;
     if (need_f) flags[i] |= SD_LOCAL_FURTHEST;
     // (a near-goal member scores GoalAngle: instances of the lane pass the batched launch does not
-    // have; members with the deployed critic list — Constraint / Cost / Twirling — have theirs)
-    if (flags[i] & (SD_CONSTRAINT | SD_COST | SD_TWIRLING)) dep = true;
-    const bool ok = c->lane_now && !c->lane_rr && !(flags[i] & SD_GOAL_ANGLE) &&
-      c->cfg.iteration_count == 1 && !c->fail_in &&
+    // have; members with the deployed critic list — Constraint / Cost / Twirling — have theirs, and
+    // a member without those critics runs them unchanged)
+    const LaneInst* k = c->plan.kind == PassPlan::kLane && !c->plan.rr
+      ? lane_select(flags[i], c->cfg.time_steps, false, true, c->acker_r) : nullptr;
+    const bool ok = k && c->cfg.iteration_count == 1 && !c->fail_in &&
       !(c->cfg.flags & (SMPC_FLAG_NO_SPECULATION | SMPC_FLAG_PROFILE)) && (!need_f || c->hint_valid) &&
-      c->poll_enabled && c->acker_r < 0.f && !c->two_coll_fp;
+      c->knobs.poll && c->acker_r < 0.f && !c->two_coll_fp;
     if (!ok) batched = false;
-    if (i == 0) {
-      window_bytes = c->lane_window_bytes;
-      obst = (flags[i] & (SD_OBSTACLES | SD_COST)) != 0;    // (either one: the costmap lookups)
-    } else if (c->lane_window_bytes != window_bytes || ((flags[i] & (SD_OBSTACLES | SD_COST)) != 0) != obst ||
-               c->lane_block != c0->lane_block) {
+    if (i == 0) window_bytes = c->plan.window_bytes;
+    // the members agree on the window, the block and on whether a costmap lookup is scored
+    else if (c->plan.window_bytes != window_bytes || (k && inst && k->obst != inst->obst) || c->plan.lane.block != c0->plan.lane.block)
       batched = false;
-    }
+    if (k && (!inst || k->dep)) inst = k;
     Pmax = std::max(Pmax, c->P);
-    gridx = std::max(gridx, c->grid_tpr);
+    gridx = std::max(gridx, c->plan.lane.grid);
   }
   const uint32_t T = c0->cfg.time_steps;
   const SmpcLds L = lane_lds(window_bytes, Pmax, T);
@@ -179,8 +178,8 @@ int smpc_group_optimize(smpc_group* g, const smpc_tick_in* ins, float* const* u_
     bar_flush(c0);
   }
   else HIPCK(c0, hipMemcpyAsync(g->d_all, g->h_all, g->total, hipMemcpyHostToDevice, g->stream));
-  HIPCK(c0, smpc_launch_pass_lane_many(reinterpret_cast<const SmpcDev*>(g->d_all + g->off_dev), n,
-                                       T == 64, obst, dep, T, L, gridx, c0->lane_block, g->stream));
+  HIPCK(c0, lane_launch(inst, c0->dev, reinterpret_cast<const SmpcDev*>(g->d_all + g->off_dev), n, L, gridx,
+                        c0->plan.lane.block, g->stream));
   HIPCK(c0, smpc_launch_reduce_many(reinterpret_cast<const SmpcReduceArgs*>(g->d_all + g->off_red), n,
                                     T, g->stream));
   g->batched_ticks++;

@@ -1,0 +1,76 @@
+// smpc_inst.h — the scoring-pass instances as data.  Each kernel family keeps ONE table next to its
+// kernel (smpc_kernels.hip, smpc_lane.hip, smpc_split.hip): a row holds the template arguments and
+// the instance's address, written by one macro.  The kernel's name, the LDS limit, occupancy, the
+// selector ("which instance scores these flags?") and the launch all read that table.  Internal:
+// not part of the C-ABI.
+#ifndef SMPC_INST_H_
+#define SMPC_INST_H_
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "smpc_dev.h"
+
+#pragma GCC visibility push(hidden)
+
+struct WaveInst { int r, mode; bool full; const void* fn; };                                       // smpc_pass<R, MODE, FULL>
+struct LaneInst { bool full, obst, many; int nch; bool rr, ga, quads; int tc; bool dep; const void* fn; };   // smpc_pass_lane<...>
+struct SplitInst { int nseg; bool full; const void* fn; };                                         // smpc_pass_split<NSEG, FULL>
+
+// Selectors: the instance that scores these flags at this horizon, or null when there is none.
+// mode: 0 score (all cost_power == 1), 1 furthest only, 3 score (all cost_power == 1, with the
+// additive forms of Cost, Goal, Constraint, Twirling, PathAngle), anything else: the general pass
+const WaveInst* wave_select(int R, int mode, uint32_t T);
+// rr: the re-read form (no parked controls; required for T > 64); many: the grouped instances
+// (smpc_group_optimize); acker_r: the Ackermann min_turning_r, < 0 for the other models
+const LaneInst* lane_select(uint32_t flags, uint32_t T, bool rr, bool many, float acker_r);
+// step: PathAlign's trajectory_point_step; nseg: lanes per rollout, 4 or 2
+const SplitInst* split_select(uint32_t flags, uint32_t T, uint32_t step, uint32_t nseg);
+
+// Occupancy is asked about one REPRESENTATIVE of the instances a tick shape may run (they share the
+// launch bounds; the grids were measured with these): the plain ObstaclesCritic instance of the
+// parking form (whole horizon or ragged), the re-read instance with one or two chunks, and the
+// whole-horizon instance of the split form.
+const LaneInst* lane_occupancy_row(uint32_t T, bool rr);
+const SplitInst* split_occupancy_row(uint32_t nseg);
+
+// Launch a row; each records the instance's name for smpc_debug_last_pass_kernel().
+hipError_t wave_launch(const WaveInst* k, const SmpcDev& p, const SmpcLds& L, uint32_t grid, uint32_t block, hipStream_t st);
+// d_many == nullptr: one planning instance, p its parameter block; else n instances in one launch,
+// their parameter blocks in device memory (p is not read)
+hipError_t lane_launch(const LaneInst* k, const SmpcDev& p, const SmpcDev* d_many, uint32_t n, const SmpcLds& L,
+                       uint32_t grid, uint32_t block, hipStream_t st);
+hipError_t split_launch(const SplitInst* k, const SmpcDev& p, const SmpcLds& L, uint32_t grid, hipStream_t st);
+
+hipError_t wave_set_lds_limit(int bytes);
+hipError_t lane_set_lds_limit(int bytes);
+hipError_t split_set_lds_limit(int bytes);
+
+// developer aid: the scoring-pass instance launched last, as rocprofv3 names it
+extern char smpc_last_pass_kernel[96];
+
+// ---- what the three tables share -------------------------------------------------------------
+template <typename Inst, size_t N>
+inline hipError_t inst_set_lds_limit(const Inst (&table)[N], int bytes)
+{
+  hipError_t e = hipSuccess;
+  for (size_t k = 0; k < N && e == hipSuccess; ++k)
+    e = hipFuncSetAttribute(table[k].fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  return e;
+}
+
+inline hipError_t inst_occupancy(const void* fn, uint32_t block, uint32_t lds_bytes, int* blocks_per_cu)
+{
+  if (!fn) return hipErrorInvalidValue;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, fn, static_cast<int>(block), lds_bytes);
+}
+
+inline hipError_t inst_launch(const void* fn, dim3 grid, uint32_t block, void** args, uint32_t lds_bytes, hipStream_t st)
+{
+  (void)hipLaunchKernel(fn, grid, dim3(block), args, lds_bytes, st);   // (what hipLaunchKernelGGL wraps)
+  return hipGetLastError();
+}
+
+#pragma GCC visibility pop
+
+#endif  // SMPC_INST_H_

@@ -26,6 +26,7 @@
 #include "smpc_dev.h"
 #include "smpc_device_math.h"
 #include "smpc_tail.h"
+#include "smpc_inst.h"
 
 #define WAVE 64
 
@@ -1600,68 +1601,33 @@ hipError_t smpc_launch_sincos(const float* x, uint32_t n, float* sn, float* cs, 
 // ---------------------------------------------------------------------------
 char smpc_last_pass_kernel[96] = "";   // (a developer aid: not per thread)
 
-template <int MODE, bool FULL>
-static hipError_t launch_pass_r(int R, const SmpcDev& p, const SmpcLds& L, uint32_t grid,
-                                uint32_t block, hipStream_t st)
+// the instances of the wave-per-rollout pass (smpc_inst.h): one row each
+#define WAVE_INST(...) {__VA_ARGS__, reinterpret_cast<const void*>(&smpc_pass<__VA_ARGS__>)}
+#define WAVE_INST_R(MODE) WAVE_INST(1, MODE, true), WAVE_INST(1, MODE, false), WAVE_INST(2, MODE, true), \
+                          WAVE_INST(2, MODE, false), WAVE_INST(4, MODE, true), WAVE_INST(4, MODE, false)
+static const WaveInst kWaveInst[] = {WAVE_INST_R(0), WAVE_INST_R(1), WAVE_INST_R(2), WAVE_INST_R(3)};
+#undef WAVE_INST_R
+#undef WAVE_INST
+
+// FULL: T == 64 R, every step slot is live
+const WaveInst* wave_select(int R, int mode, uint32_t T)
 {
-  snprintf(smpc_last_pass_kernel, sizeof(smpc_last_pass_kernel), "smpc_pass<%d, %d, %s>", R, MODE, FULL ? "true" : "false");
-  switch (R) {
-    case 1: hipLaunchKernelGGL((smpc_pass<1, MODE, FULL>), dim3(grid), dim3(block), L.total, st, p, L); break;
-    case 2: hipLaunchKernelGGL((smpc_pass<2, MODE, FULL>), dim3(grid), dim3(block), L.total, st, p, L); break;
-    case 4: hipLaunchKernelGGL((smpc_pass<4, MODE, FULL>), dim3(grid), dim3(block), L.total, st, p, L); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  const int m = (mode == 0 || mode == 1 || mode == 3) ? mode : 2;
+  const bool full = T == 64u * (uint32_t)R;
+  for (const WaveInst& k : kWaveInst)
+    if (k.r == R && k.mode == m && k.full == full) return &k;
+  return nullptr;
 }
 
-// mode: 0 score (all cost_power == 1), 1 furthest only, 2 score (general cost_power),
-// 3 score (all cost_power == 1, with the additive forms of Cost, Goal, Constraint, Twirling, PathAngle)
-hipError_t smpc_launch_pass(int R, int mode, const SmpcDev& p, const SmpcLds& L,
-                            uint32_t grid, uint32_t block, hipStream_t st)
+hipError_t wave_launch(const WaveInst* k, const SmpcDev& p, const SmpcLds& L, uint32_t grid, uint32_t block, hipStream_t st)
 {
-  const bool full = p.T == 64u * (uint32_t)R;
-  switch (mode) {
-    case 0: return full ? launch_pass_r<0, true>(R, p, L, grid, block, st)
-                        : launch_pass_r<0, false>(R, p, L, grid, block, st);
-    case 1: return full ? launch_pass_r<1, true>(R, p, L, grid, block, st)
-                        : launch_pass_r<1, false>(R, p, L, grid, block, st);
-    case 3: return full ? launch_pass_r<3, true>(R, p, L, grid, block, st)
-                        : launch_pass_r<3, false>(R, p, L, grid, block, st);
-    default: return full ? launch_pass_r<2, true>(R, p, L, grid, block, st)
-                         : launch_pass_r<2, false>(R, p, L, grid, block, st);
-  }
+  if (!k) return hipErrorInvalidValue;
+  snprintf(smpc_last_pass_kernel, sizeof(smpc_last_pass_kernel), "smpc_pass<%d, %d, %s>", k->r, k->mode, k->full ? "true" : "false");
+  void* args[] = {const_cast<SmpcDev*>(&p), const_cast<SmpcLds*>(&L)};
+  return inst_launch(k->fn, dim3(grid), block, args, L.total, st);
 }
 
-template <typename F>
-static void for_each_pass_kernel(F&& f)
-{
-#define EACH(RR, MM) f(reinterpret_cast<const void*>(&smpc_pass<RR, MM, true>), RR, MM, true); \
-                     f(reinterpret_cast<const void*>(&smpc_pass<RR, MM, false>), RR, MM, false);
-  EACH(1, 0) EACH(2, 0) EACH(4, 0) EACH(1, 1) EACH(2, 1) EACH(4, 1) EACH(1, 2) EACH(2, 2) EACH(4, 2)
-  EACH(1, 3) EACH(2, 3) EACH(4, 3)
-#undef EACH
-}
-
-hipError_t smpc_pass_occupancy(int R, int mode, bool full, uint32_t block, uint32_t lds_bytes,
-                               int* blocks_per_cu)
-{
-  const void* fn = nullptr;
-  for_each_pass_kernel([&](const void* f, int r, int m, bool fl) {
-    if (r == R && m == mode && fl == full) fn = f;
-  });
-  if (!fn) return hipErrorInvalidValue;
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, fn, (int)block, lds_bytes);
-}
-
-hipError_t smpc_set_pass_lds_limit(int bytes)
-{
-  hipError_t e = hipSuccess;
-  for_each_pass_kernel([&](const void* f, int, int, bool) {
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  });
-  return e;
-}
+hipError_t wave_set_lds_limit(int bytes) {return inst_set_lds_limit(kWaveInst, bytes);}
 
 hipError_t smpc_launch_reduce(const float* partials, uint32_t nblk, uint32_t T,
                               float neg_inv_temp, float* tuple, const SmpcFinal& fin,

@@ -34,6 +34,7 @@
 #include "smpc_device_math.h"
 #include "smpc_tail.h"
 #include "smpc_lane_common.h"
+#include "smpc_inst.h"
 
 #ifndef WAVE
 #define WAVE 64
@@ -1069,156 +1070,96 @@ smpc_pass_lane(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ ma
   }
 }
 
-extern char smpc_last_pass_kernel[96];   // smpc_kernels.hip
-// the instance's name with every template argument written out, as rocprofv3 prints it
-static void lane_name(bool full, bool obst, bool many, int nch, bool rr, bool ga, bool quads, int tc, bool dep)
+// ---------------------------------------------------------------------------
+// The instances (smpc_inst.h): one row each.  Name, LDS limit, occupancy, selection and launch
+// all read this table; adding an instance is adding a row and, if need be, a rule in lane_select.
+// ---------------------------------------------------------------------------
+#define LANE_INST(...) {__VA_ARGS__, reinterpret_cast<const void*>(&smpc_pass_lane<__VA_ARGS__>)}
+//                          FULL   OBST   MANY  NCH RR     GA     QUADS  TC  DEP
+static const LaneInst kLaneInst[] = {
+  LANE_INST(false, false, false, 1, false, false, false, 0, false),   // the five critics: ragged horizon
+  LANE_INST(true, false, false, 1, false, false, true, 0, false),     // ... T = 64
+  LANE_INST(false, true, false, 1, false, false, false, 0, false),
+  LANE_INST(true, true, false, 1, false, false, true, 0, false),
+  LANE_INST(false, true, false, 1, false, false, true, 0, false),     // whole quads
+  LANE_INST(false, true, false, 1, false, false, true, 56, false),    // T = 56: the reference's default horizon, at compile time
+  LANE_INST(false, false, true, 1, false, false, false, 0, false),    // grouped (smpc_group_optimize)
+  LANE_INST(true, false, true, 1, false, false, true, 0, false),
+  LANE_INST(false, true, true, 1, false, false, false, 0, false),
+  LANE_INST(true, true, true, 1, false, false, true, 0, false),
+  LANE_INST(true, true, false, 1, true, false, true, 0, false),       // re-read: one chunk, two chunks
+  LANE_INST(true, true, false, 2, true, false, true, 0, false),
+  LANE_INST(false, true, false, 1, false, true, false, 0, false),     // near-goal: the GoalAngle term
+  LANE_INST(true, true, false, 1, false, true, true, 0, false),
+  LANE_INST(true, true, false, 1, false, false, true, 0, true),       // deployed list: Constraint / Cost / Twirling
+  LANE_INST(false, true, false, 1, false, false, true, 56, true),
+  LANE_INST(true, true, true, 1, false, false, true, 0, true),        // ... grouped
+  LANE_INST(false, true, true, 1, false, false, true, 56, true),
+};
+#undef LANE_INST
+
+static const LaneInst* lane_find(bool full, bool obst, bool many, int nch, bool rr, bool ga, bool quads, int tc, bool dep)
 {
-  auto b = [](bool v) {return v ? "true" : "false";};
-  snprintf(smpc_last_pass_kernel, sizeof(smpc_last_pass_kernel), "smpc_pass_lane<%s, %s, %s, %d, %s, %s, %s, %d, %s>", b(full),
-           b(obst), b(many), nch, b(rr), b(ga), b(quads), tc, b(dep));
+  for (const LaneInst& k : kLaneInst)
+    if (k.full == full && k.obst == obst && k.many == many && k.nch == nch && k.rr == rr && k.ga == ga &&
+        k.quads == quads && k.tc == tc && k.dep == dep)
+      return &k;
+  return nullptr;
 }
 
-// rr: the re-read instances (no parked controls; required for T > 64; ObstaclesCritic scored)
-// block: threads per block of the parking form — LANE_BLOCK, or LANE_BLOCK / 2 for batches of at
-// most one group per SIMD (a wave alone on its SIMD runs a group in 2/3 of the time)
-hipError_t smpc_launch_pass_lane(const SmpcDev& p, const SmpcLds& L, uint32_t grid, bool rr, uint32_t block, hipStream_t st)
+const LaneInst* lane_select(uint32_t flags, uint32_t T, bool rr, bool many, float acker_r)
 {
-  if (!rr && block != LANE_BLOCK && block != LANE_BLOCK / 2) return hipErrorInvalidValue;
-  const bool obst = (p.flags & (SD_OBSTACLES | SD_COST)) != 0;   // (Cost: the deployed-list instances, same lookup)
+  const uint32_t dep_set = SD_CONSTRAINT | SD_COST | SD_TWIRLING, lean_extra = dep_set | SD_GOAL | SD_PATH_ANGLE;
+  // what no instance scores: trajectory write-out, path orientations, the general pass's critics
+  if (flags & (SD_STORE_TRAJ | SD_USE_PATH_YAW | (SD_EXTRA_CRITICS & ~lean_extra))) return nullptr;
+  const bool obst = (flags & (SD_OBSTACLES | SD_COST)) != 0;   // (Cost: the deployed-list instances, same lookup)
+  const bool full = T == 64u;
   if (rr) {
-    // whole chunks only (T = 64 or 128): the ragged instances spill registers, and a spill in
-    // the time loop costs the noise prefetch its depth (every scratch access waits vmcnt(0))
-    if (!obst || (p.T != 64u && p.T != 128u)) return hipErrorInvalidValue;
-#define SMPC_LANE_LAUNCH_RR(N) \
-  hipLaunchKernelGGL((smpc_pass_lane<true, true, false, N, true>), dim3(grid), dim3(LANE_BLOCK_RR), L.total, st, p, L, \
-                     static_cast<const SmpcDev*>(nullptr))
-    if (p.T > 64u) SMPC_LANE_LAUNCH_RR(2);
-    else SMPC_LANE_LAUNCH_RR(1);
-#undef SMPC_LANE_LAUNCH_RR
-    lane_name(true, true, false, p.T > 64u ? 2 : 1, true, false, true, 0, false);
-    return hipGetLastError();
+    // the five critics with ObstaclesCritic scored, whole chunks only (T = 64 or 128): the ragged
+    // instances spill registers, and a spill in the time loop costs the noise prefetch its depth
+    // (every scratch access waits vmcnt(0))
+    if (!(flags & SD_OBSTACLES) || (flags & (lean_extra | SD_GOAL_ANGLE)) || (T != 64u && T != 128u)) return nullptr;
+    return lane_find(true, true, many, T > 64u ? 2 : 1, true, false, true, 0, false);
   }
-  const bool full = p.T == 64u;
-  if (p.flags & (SD_CONSTRAINT | SD_COST | SD_TWIRLING)) {   // cruise tick of the deployed critic list
-    if (!obst || (p.flags & (SD_GOAL_ANGLE | SD_GOAL)) || ((p.flags & SD_COST) && (p.flags & SD_OBSTACLES)) ||
-        p.con_acker_r >= 0.f || (!full && p.T != 56u))
-      return hipErrorInvalidValue;
-    if (full)
-      hipLaunchKernelGGL((smpc_pass_lane<true, true, false, 1, false, false, true, 0, true>), dim3(grid), dim3(block), L.total,
-                         st, p, L, static_cast<const SmpcDev*>(nullptr));
-    else
-      hipLaunchKernelGGL((smpc_pass_lane<false, true, false, 1, false, false, true, 56, true>), dim3(grid), dim3(block), L.total,
-                         st, p, L, static_cast<const SmpcDev*>(nullptr));
-    lane_name(full, true, false, 1, false, false, true, full ? 0 : 56, true);
-    return hipGetLastError();
+  if (T > 64u) return nullptr;   // the parking form: 3 x 64 noised controls per lane
+  if (flags & dep_set) {   // cruise tick of the deployed critic list (PathAngle: the host knows it inert)
+    if (!obst || (flags & (SD_GOAL_ANGLE | SD_GOAL)) || ((flags & SD_COST) && (flags & SD_OBSTACLES)) ||
+        acker_r >= 0.f || (!full && T != 56u))
+      return nullptr;
+    return lane_find(full, true, many, 1, false, false, true, full ? 0 : 56, true);
   }
-  if (p.flags & SD_GOAL_ANGLE) {   // near-goal tick: the instances with the GoalAngle term
-    if (!obst) return hipErrorInvalidValue;
-#define SMPC_LANE_LAUNCH_GA(F) \
-  hipLaunchKernelGGL((smpc_pass_lane<F, true, false, 1, false, true>), dim3(grid), dim3(block), L.total, st, p, L, \
-                     static_cast<const SmpcDev*>(nullptr))
-    if (full) SMPC_LANE_LAUNCH_GA(true);
-    else SMPC_LANE_LAUNCH_GA(false);
-#undef SMPC_LANE_LAUNCH_GA
-    lane_name(full, true, false, 1, false, true, full, 0, false);
-    return hipGetLastError();
-  }
-#define SMPC_LANE_LAUNCH(F, O) \
-  hipLaunchKernelGGL((smpc_pass_lane<F, O, false, 1, false>), dim3(grid), dim3(block), L.total, st, p, L, \
-                     static_cast<const SmpcDev*>(nullptr))
-  if (full) lane_name(true, obst, false, 1, false, false, true, 0, false);
-  else if (obst && p.T == 56u) lane_name(false, true, false, 1, false, false, true, 56, false);
-  else if (obst && (p.T & 3u) == 0u) lane_name(false, true, false, 1, false, false, true, 0, false);
-  else lane_name(false, obst, false, 1, false, false, false, 0, false);
-  if (full && obst) SMPC_LANE_LAUNCH(true, true);
-  else if (full) SMPC_LANE_LAUNCH(true, false);
-  else if (obst && p.T == 56u)         // the reference's default horizon, at compile time
-    hipLaunchKernelGGL((smpc_pass_lane<false, true, false, 1, false, false, true, 56>), dim3(grid), dim3(block), L.total, st, p, L,
-                       static_cast<const SmpcDev*>(nullptr));
-  else if (obst && (p.T & 3u) == 0u)   // whole quads
-    hipLaunchKernelGGL((smpc_pass_lane<false, true, false, 1, false, false, true>), dim3(grid), dim3(block), L.total, st, p, L,
-                       static_cast<const SmpcDev*>(nullptr));
-  else if (obst) SMPC_LANE_LAUNCH(false, true);
-  else SMPC_LANE_LAUNCH(false, false);
-#undef SMPC_LANE_LAUNCH
-  return hipGetLastError();
+  if (flags & (SD_GOAL | SD_PATH_ANGLE)) return nullptr;
+  if (flags & SD_GOAL_ANGLE)   // near-goal tick: the instances with the GoalAngle term
+    return obst ? lane_find(full, true, many, 1, false, true, full, 0, false) : nullptr;
+  if (many) return lane_find(full, obst, true, 1, false, false, full, 0, false);
+  if (obst && T == 56u) return lane_find(false, true, false, 1, false, false, true, 56, false);
+  return lane_find(full, obst, false, 1, false, false, full || (obst && (T & 3u) == 0u), 0, false);
 }
 
-// n planning instances (same T, same critic set) in one launch; d_many: their parameter
-// blocks in device memory
-// dep: some instance scores Constraint / Cost / Twirling (the deployed critic list's cruise tick):
-// the DEP instances, T = 64 (full) or 56; an instance without those critics runs them unchanged
-hipError_t smpc_launch_pass_lane_many(const SmpcDev* d_many, uint32_t n, bool full, bool obst, bool dep, uint32_t T,
-                                      const SmpcLds& L, uint32_t grid, uint32_t block, hipStream_t st)
+const LaneInst* lane_occupancy_row(uint32_t T, bool rr)   // (a representative: smpc_inst.h)
 {
-  if (block != LANE_BLOCK && block != LANE_BLOCK / 2) return hipErrorInvalidValue;
-  const SmpcDev none{};
-  if (dep) lane_name(full, true, true, 1, false, false, true, full ? 0 : 56, true);
-  else lane_name(full, obst, true, 1, false, false, full, 0, false);
-  if (dep) {
-    if (!obst || (!full && T != 56u)) return hipErrorInvalidValue;
-    if (full)
-      hipLaunchKernelGGL((smpc_pass_lane<true, true, true, 1, false, false, true, 0, true>), dim3(grid, n), dim3(block), L.total,
-                         st, none, L, d_many);
-    else
-      hipLaunchKernelGGL((smpc_pass_lane<false, true, true, 1, false, false, true, 56, true>), dim3(grid, n), dim3(block), L.total,
-                         st, none, L, d_many);
-    return hipGetLastError();
-  }
-#define SMPC_LANE_LAUNCH(F, O) \
-  hipLaunchKernelGGL((smpc_pass_lane<F, O, true, 1, false>), dim3(grid, n), dim3(block), L.total, st, none, L, \
-                     d_many)
-  if (full && obst) SMPC_LANE_LAUNCH(true, true);
-  else if (full) SMPC_LANE_LAUNCH(true, false);
-  else if (obst) SMPC_LANE_LAUNCH(false, true);
-  else SMPC_LANE_LAUNCH(false, false);
-#undef SMPC_LANE_LAUNCH
-  return hipGetLastError();
+  if (rr) return lane_find(true, true, false, T > 64u ? 2 : 1, true, false, true, 0, false);
+  return lane_find(T == 64u, true, false, 1, false, false, T == 64u, 0, false);
+}
+
+// block: threads per block — LANE_BLOCK_RR for the re-read form; LANE_BLOCK for the parking form, or
+// LANE_BLOCK / 2 for batches of at most one group per SIMD (a wave alone on its SIMD runs a group
+// in 2/3 of the time)
+hipError_t lane_launch(const LaneInst* k, const SmpcDev& p, const SmpcDev* d_many, uint32_t n, const SmpcLds& L,
+                       uint32_t grid, uint32_t block, hipStream_t st)
+{
+  if (!k || k->many != (d_many != nullptr)) return hipErrorInvalidValue;
+  if (k->rr ? block != LANE_BLOCK_RR : (block != LANE_BLOCK && block != LANE_BLOCK / 2)) return hipErrorInvalidValue;
+  // the instance's name with every template argument written out, as rocprofv3 prints it
+  auto b = [](bool v) {return v ? "true" : "false";};
+  snprintf(smpc_last_pass_kernel, sizeof(smpc_last_pass_kernel), "smpc_pass_lane<%s, %s, %s, %d, %s, %s, %s, %d, %s>", b(k->full),
+           b(k->obst), b(k->many), k->nch, b(k->rr), b(k->ga), b(k->quads), k->tc, b(k->dep));
+  static const SmpcDev none{};   // (the grouped instances read their parameter blocks from device memory)
+  void* args[] = {const_cast<SmpcDev*>(d_many ? &none : &p), const_cast<SmpcLds*>(&L), &d_many};
+  return inst_launch(k->fn, d_many ? dim3(grid, n) : dim3(grid), block, args, L.total, st);
 }
 
 uint32_t smpc_lane_block() {return LANE_BLOCK;}
 uint32_t smpc_lane_block_rr() {return LANE_BLOCK_RR;}
 
-static const void* lane_kernel(int k)   // bit 0 FULL, bit 1 OBST, bit 2 MANY; 8, 9: re-read with one, two chunks; 10, 11: GoalAngle
-{
-  switch (k) {
-    case 0: return reinterpret_cast<const void*>(&smpc_pass_lane<false, false, false, 1, false>);
-    case 1: return reinterpret_cast<const void*>(&smpc_pass_lane<true, false, false, 1, false>);
-    case 2: return reinterpret_cast<const void*>(&smpc_pass_lane<false, true, false, 1, false>);
-    case 3: return reinterpret_cast<const void*>(&smpc_pass_lane<true, true, false, 1, false>);
-    case 4: return reinterpret_cast<const void*>(&smpc_pass_lane<false, false, true, 1, false>);
-    case 5: return reinterpret_cast<const void*>(&smpc_pass_lane<true, false, true, 1, false>);
-    case 6: return reinterpret_cast<const void*>(&smpc_pass_lane<false, true, true, 1, false>);
-    case 7: return reinterpret_cast<const void*>(&smpc_pass_lane<true, true, true, 1, false>);
-    case 8: return reinterpret_cast<const void*>(&smpc_pass_lane<true, true, false, 1, true>);
-    case 9: return reinterpret_cast<const void*>(&smpc_pass_lane<true, true, false, 2, true>);
-    case 10: return reinterpret_cast<const void*>(&smpc_pass_lane<false, true, false, 1, false, true>);   // near-goal
-    case 11: return reinterpret_cast<const void*>(&smpc_pass_lane<true, true, false, 1, false, true>);
-    case 12: return reinterpret_cast<const void*>(&smpc_pass_lane<false, true, false, 1, false, false, true>);   // whole quads
-    case 13: return reinterpret_cast<const void*>(&smpc_pass_lane<false, true, false, 1, false, false, true, 56>);   // T = 56
-    case 14: return reinterpret_cast<const void*>(&smpc_pass_lane<true, true, false, 1, false, false, true, 0, true>);   // deployed list
-    case 15: return reinterpret_cast<const void*>(&smpc_pass_lane<false, true, false, 1, false, false, true, 56, true>);
-    case 16: return reinterpret_cast<const void*>(&smpc_pass_lane<true, true, true, 1, false, false, true, 0, true>);    // ... grouped
-    default: return reinterpret_cast<const void*>(&smpc_pass_lane<false, true, true, 1, false, false, true, 56, true>);
-  }
-}
-
-hipError_t smpc_lane_occupancy(bool full, uint32_t lds_bytes, int* blocks_per_cu)
-{
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, lane_kernel((full ? 1 : 0) | 2),
-                                                      LANE_BLOCK, lds_bytes);
-}
-
-hipError_t smpc_lane_occupancy_rr(uint32_t T, uint32_t lds_bytes, int* blocks_per_cu)
-{
-  const int k = T > 64u ? 9 : 8;
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, lane_kernel(k), LANE_BLOCK_RR, lds_bytes);
-}
-
-hipError_t smpc_lane_set_lds_limit(int bytes)
-{
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < 18 && e == hipSuccess; ++k)
-    e = hipFuncSetAttribute(lane_kernel(k), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  return e;
-}
+hipError_t lane_set_lds_limit(int bytes) {return inst_set_lds_limit(kLaneInst, bytes);}

@@ -443,16 +443,13 @@ static int plan_launch(smpc_ctx* c, const smpc_tick_in* in, uint32_t gates, uint
     // the reach at the largest constrained speed plus four standard deviations of the mean
     // noise, up to kWindowSideMax cells; the passes that run T > 64 (the re-read form, the
     // wave-per-rollout pass) have the LDS for it.
-    static const bool small_window = getenv("SMPC_SMALL_WINDOW") != nullptr;              // (experiments; read once)
-    static const char* const side_max_env = getenv("SMPC_WINDOW_SIDE_MAX");
-    if (T > 64 && !small_window) {
+    if (T > 64 && !c->knobs.small_window) {
       const float sigma = std::max(c->cfg.vx_std, c->holonomic ? c->cfg.vy_std : 0.f);
       const float vmax = std::max(std::max(std::fabs(c->c_vx_max), std::fabs(c->c_vx_min)), std::fabs(c->c_vy)) +
         4.f * sigma / std::sqrt(static_cast<float>(T));
       const double reach_cells = static_cast<double>(T) * c->cfg.model_dt * vmax / c->map.res;
       const uint32_t want = (static_cast<uint32_t>(2.0 * reach_cells) + 8u + 3u) & ~3u;
-      uint32_t side_max = kWindowSideMax;
-      if (side_max_env) side_max = static_cast<uint32_t>(atoi(side_max_env)) & ~3u;
+      const uint32_t side_max = c->knobs.window_side_max < 0 ? kWindowSideMax : static_cast<uint32_t>(c->knobs.window_side_max) & ~3u;
       side = std::max(side, std::min(want, side_max));
     }
     const uint32_t ww = std::min(c->map.W, side), wh = std::min(c->map.H, side);
@@ -466,12 +463,14 @@ static int plan_launch(smpc_ctx* c, const smpc_tick_in* in, uint32_t gates, uint
     d.win_w = static_cast<int32_t>(ww); d.win_h = static_cast<int32_t>(wh);
     window_bytes = ww * wh;
   }
-  c->lds = make_lds(window_bytes, P, T, (pass_block(c->R) / 64), window_bytes != 0, nsamp);
-  if (c->lds.total > kLdsPerCu) return fail(c, SMPC_ERR_UNSUPPORTED, "LDS budget exceeded");
+  PassPlan pl;
+  pl.wave.block = pass_block(c->R);
+  pl.wave.lds = make_lds(window_bytes, P, T, (pass_block(c->R) / 64), window_bytes != 0, nsamp);
+  if (pl.wave.lds.total > kLdsPerCu) return fail(c, SMPC_ERR_UNSUPPORTED, "LDS budget exceeded");
   // room for the reduction inside the scoring launch (smpc_tail.h works in the launch's LDS) —
   // only for contexts that run that experiment: for 128 < T <= 256 the padding would halve the
   // wave pass's blocks per CU
-  if (c->fused_reduce) c->lds.total = std::max(c->lds.total, smpc_tail_lds_bytes(T));
+  if (c->knobs.fused_reduce) pl.wave.lds.total = std::max(pl.wave.lds.total, smpc_tail_lds_bytes(T));
 
   // persistent grid: as many blocks as stay resident, never more than the work
   const uint32_t waves_per_block = (pass_block(c->R) / 64);
@@ -490,70 +489,50 @@ static int plan_launch(smpc_ctx* c, const smpc_tick_in* in, uint32_t gates, uint
       (!(gates & SD_GOAL_ANGLE) || cr.goal_angle.cost_power == 1);
     mode_now = (mode_now == 0 && unit_powers) ? 3 : 2;
   }
-  if (c->occ_lds != c->lds.total || c->occ_mode != mode_now) {
-    int nb = 0;
-    if (smpc_pass_occupancy(c->R, mode_now, T == 64u * static_cast<uint32_t>(c->R), pass_block(c->R), c->lds.total, &nb) != hipSuccess || nb < 1) nb = 1;
-    c->occ_blocks = static_cast<uint32_t>(nb);
-    c->occ_lds = c->lds.total;
-    c->occ_mode = mode_now;
-  }
-  uint32_t per_cu = std::min(c->occ_blocks, 32u / waves_per_block);
-  if (c->knob_max_blocks_per_cu >= 1) per_cu = std::min(per_cu, c->knob_max_blocks_per_cu);   // SMPC_MAX_BLOCKS_PER_CU
+  const WaveInst* wave = wave_select(c->R, mode_now, T);
+  if (!wave) return fail(c, SMPC_ERR_UNSUPPORTED, "no instance of the wave-per-rollout pass for this horizon");
+  uint32_t per_cu = std::min(c->occ_wave.get(wave->fn, pl.wave.block, pl.wave.lds.total), 32u / waves_per_block);
+  if (c->knobs.max_blocks_per_cu >= 1) per_cu = std::min(per_cu, c->knobs.max_blocks_per_cu);   // SMPC_MAX_BLOCKS_PER_CU
   uint32_t grid = std::min((B + waves_per_block - 1) / waves_per_block,
                            static_cast<uint32_t>(c->num_cu) * per_cu);
-  c->grid = std::max(1u, std::min(grid, kMaxGrid));
-  // the lane-per-rollout pass scores the north star's five, GoalAngle (power 1) included
-  // (its GoalAngle instances: the parking form with ObstaclesCritic scored, T <= 64)
-  const bool lane_ga = mode_now == 3 && !(gates & (lean_extra & ~SD_GOAL_ANGLE)) && (gates & SD_OBSTACLES) && T <= 64;
-  // (its deployed-list instances, DEP: Constraint / Cost / Twirling on a cruise tick — Goal and
-  // GoalAngle gated off, PathAngle inside its angle for every candidate furthest point, Cost
-  // without Obstacles next to it, no Ackermann term, T = 64 or the default 56)
-  const uint32_t dep_set = SD_CONSTRAINT | SD_COST | SD_TWIRLING;
-  const bool lane_dep = mode_now == 3 && (gates & dep_set) && !(gates & (SD_GOAL | SD_GOAL_ANGLE)) &&
-    !((gates & SD_PATH_ANGLE) && c->pang_any) && !((gates & SD_COST) && (gates & SD_OBSTACLES)) &&
-    (gates & (SD_COST | SD_OBSTACLES)) && c->acker_r < 0.f && (T == 64 || T == 56);
-  const bool lane_mode = mode_now == 0 || lane_ga || lane_dep;
-  c->lane_now = c->use_tpr && lane_mode && T <= kLaneMaxT;
-  // the lane pass samples PathAlign's trajectory points at the first step of every quad:
-  // trajectory_point_step = 4, the reference's default (path_align_critic.cpp:36)
-  if ((gates & SD_PATH_ALIGN) && step != 4) c->lane_now = false;
-  // the re-read form (no parked controls): the only one for T > 64; instances exist with
-  // ObstaclesCritic scored.  SMPC_LANE_REREAD=1 selects it for T <= 64 too (experiments).
-  const bool force_rr = c->knob_lane_reread;
-  c->lane_rr = (T > 64 || force_rr) && (gates & SD_OBSTACLES) != 0 && (T == 64 || T == 128);
-  if (T > 64 && !c->lane_rr) c->lane_now = false;
-  if (c->lane_now) {
-    const SmpcLds Lt = lane_lds(window_bytes, P, T, c->lane_rr);
-    c->lane_window_bytes = window_bytes;
-    c->lds_tpr = Lt;
-    if (Lt.total > kLdsPerCu) c->lane_now = false;   // long paths: the parked wz no longer fits
+  pl.wave.grid = std::max(1u, std::min(grid, kMaxGrid));
+
+  // The lane-per-rollout pass takes the tick when the kernels score with unit cost powers (MODE 0
+  // or 3) and lane_select has an instance for the gates: the north star's five, with the near-goal
+  // GoalAngle term (ObstaclesCritic scored, T <= 64), or with the deployed list's Constraint / Cost /
+  // Twirling on a cruise tick (T = 64 or the default 56).  Known to the host only: PathAngle must
+  // be inside its angle for every candidate furthest point (it then adds nothing), and the lane
+  // pass samples PathAlign's trajectory points at the first step of every quad
+  // (trajectory_point_step = 4, the reference's default: path_align_critic.cpp:36).
+  // The re-read form (no parked controls) is the only one for T > 64; SMPC_LANE_REREAD=1 selects
+  // it for T <= 64 too (experiments) where it has an instance.
+  pl.rr = (T > 64 || c->knobs.lane_reread) && lane_select(gates, T, true, false, c->acker_r) != nullptr;
+  bool lane_now = c->use_tpr && (mode_now == 0 || mode_now == 3) && T <= kLaneMaxT &&
+    lane_select(gates, T, T > 64, false, c->acker_r) != nullptr &&
+    !((gates & SD_PATH_ANGLE) && c->pang_any) && !((gates & SD_PATH_ALIGN) && step != 4);
+  if (lane_now) {
+    pl.window_bytes = window_bytes;
+    pl.lane.lds = lane_lds(window_bytes, P, T, pl.rr);
+    if (pl.lane.lds.total > kLdsPerCu) lane_now = false;   // long paths: the parked wz no longer fits
     // (the re-read form: no in-launch reduction, smpc_lane.hip)
-    if (!c->lane_rr && c->fused_reduce) c->lds_tpr.total = std::max(Lt.total, smpc_tail_lds_bytes(T));
+    if (!pl.rr && c->knobs.fused_reduce) pl.lane.lds.total = std::max(pl.lane.lds.total, smpc_tail_lds_bytes(T));
   }
-  if (c->lane_now) {
-    const uint32_t lblock = c->lane_rr ? smpc_lane_block_rr() : smpc_lane_block();
-    const SmpcLds& Lt = c->lds_tpr;
-    const uint32_t occ_key = Lt.total ^ (c->lane_rr ? 0x80000000u : 0u);
-    if (c->occ_tpr_lds != occ_key) {
-      int nb = 0;
-      const hipError_t e = c->lane_rr ? smpc_lane_occupancy_rr(T, Lt.total, &nb) : smpc_lane_occupancy(T == 64, Lt.total, &nb);
-      if (e != hipSuccess || nb < 1) nb = 1;
-      if (c->lane_rr && nb > 3) nb = 3;   // (four-wave blocks: launch bounds of three waves per SIMD)
-      c->occ_tpr_blocks = static_cast<uint32_t>(nb);
-      c->occ_tpr_lds = occ_key;
-    }
+  if (lane_now) {
+    const uint32_t lblock = pl.rr ? smpc_lane_block_rr() : smpc_lane_block();
+    uint32_t occ_blocks = c->occ_lane.get(lane_occupancy_row(T, pl.rr)->fn, lblock, pl.lane.lds.total);
+    if (pl.rr) occ_blocks = std::min(occ_blocks, 3u);   // (four-wave blocks: launch bounds of three waves per SIMD)
     const uint32_t groups = (B + 63) / 64;
     uint32_t wpb = lblock / 64;
-    c->lane_block = lblock;
+    pl.lane.block = lblock;
     // Small batches: when every group can have a SIMD to itself (at most four groups per CU),
     // blocks of four waves, one per CU.  Two waves on a SIMD share its VALU and each runs its
     // group in 22.5 us; a wave alone runs it in 20.5 (tools/lane_timeline.py) — and a batch
     // this small is one group per wave anyway: -2 us per tick at 65 536 x 64.
-    if (!c->lane_rr && c->half_blocks && !c->in_group && groups <= static_cast<uint32_t>(c->num_cu) * 4u) {
+    if (!pl.rr && c->knobs.half_blocks && !c->in_group && groups <= static_cast<uint32_t>(c->num_cu) * 4u) {
       wpb = 4;
-      c->lane_block = 256;
+      pl.lane.block = 256;
     }
-    uint32_t g = std::min((groups + wpb - 1) / wpb, static_cast<uint32_t>(c->num_cu) * c->occ_tpr_blocks);
+    uint32_t g = std::min((groups + wpb - 1) / wpb, static_cast<uint32_t>(c->num_cu) * occ_blocks);
     g = std::max(1u, std::min(g, kMaxGrid));
     // Every wave takes whole groups, so a launch lasts ceil(groups / waves) group-times whatever
     // the remainder: launch only the waves that fill every round, and — where several blocks fit
@@ -561,19 +540,19 @@ static int plan_launch(smpc_ctx* c, const smpc_tick_in* in, uint32_t gates, uint
     // the re-read form's first shape, four-wave blocks at three per CU: 4096 groups on 3072 waves;
     // with the eight-wave blocks it has now the grid is one block per CU and this trims nothing
     // at the benchmarked sizes.  SMPC_NO_BALANCED_GRID=1: off.)
-    if (c->lane_rr && c->knob_balanced_grid) {
+    if (pl.rr && c->knobs.balanced_grid) {
       const uint32_t waves = g * wpb;
       const uint32_t rounds = (groups + waves - 1) / waves;
       const uint32_t need = (groups + rounds - 1) / rounds;
       const uint32_t g2 = (need + wpb - 1) / wpb;
       const uint32_t per_cu = (g2 + c->num_cu - 1) / static_cast<uint32_t>(c->num_cu);
-      if (g2 < g && per_cu < c->occ_tpr_blocks) {
+      if (g2 < g && per_cu < occ_blocks) {
         g = g2;
         const uint32_t pad = align_up(kLdsPerCu / (per_cu + 1) + 1024u, 16);
-        if (pad <= kLdsPerCu / per_cu) c->lds_tpr.total = std::max(c->lds_tpr.total, pad);
+        if (pad <= kLdsPerCu / per_cu) pl.lane.lds.total = std::max(pl.lane.lds.total, pad);
       }
     }
-    c->grid_tpr = g;
+    pl.lane.grid = g;
     // window-relative float cell index and its guard band.  The pass forms
     //   q~ = fma(ax, (1/res)_f, cxf),   cxf = ((x0 - window corner) / res)_f
     // from the accumulated displacement ax; the reference truncates
@@ -603,10 +582,10 @@ static int plan_launch(smpc_ctx* c, const smpc_tick_in* in, uint32_t gates, uint
   // at most two groups each, the horizon split over four lanes runs the tick's one scoring pass in
   // a fraction of a 64-step chain (65 536 x 64: one wave per SIMD on the lane pass).  The plain five
   // critics only; the geometry above (window, cell index constants) is shared.
-  c->split_now = false;
-  if (c->lane_now && !c->lane_rr && !lane_ga && !lane_dep && mode_now == 0 && T <= 64 && T >= 36 && (T & 3u) == 0 &&
-      (gates & SD_OBSTACLES) &&
-      !c->in_group && !c->knob_no_split && !c->fused_reduce && (!c->lane_forced || c->knob_force_split)) {
+  const bool force_split = c->knobs.pass == Knobs::kSplit;
+  bool split_now = false;
+  if (lane_now && !pl.rr && mode_now == 0 && T >= 36 && !c->in_group && !c->knobs.no_split && !c->knobs.fused_reduce &&
+      (!c->lane_forced || force_split)) {
     // (a context that ASKS for the lane pass — SMPC_FLAG_LANE_PER_ROLLOUT, SMPC_PASS=lane — gets it)
     // one block per CU (two waves per SIMD: the kernel's registers), and ONE group per wave: four
     // lanes per rollout while 16-rollout groups fit (32 768 rollouts on 256 CUs), two up to twice that
@@ -618,27 +597,23 @@ static int plan_launch(smpc_ctx* c, const smpc_tick_in* in, uint32_t gates, uint
     if ((B + 15u) / 16u <= waves) nseg = 4;
     // (horizons below 64 run the masked instance: 16 384 x 56 takes 38.0 us against 37.2 on the wave
     // pass, 20 000 x 60 37.0 against 39.5, 32 768 x 56 39.0 against 43.5)
-    if (T != 64 && B < kSplitMinBatchShort && !c->knob_force_split) nseg = 0;
-    if (c->knob_split_nseg == 2 || c->knob_split_nseg == 4) nseg = (nseg || c->knob_force_split) ? c->knob_split_nseg : 0;
+    if (T != 64 && B < kSplitMinBatchShort && !force_split) nseg = 0;
+    if (c->knobs.split_nseg == 2 || c->knobs.split_nseg == 4) nseg = (nseg || force_split) ? c->knobs.split_nseg : 0;
     if (nseg == 2 && T != 64) nseg = 4;   // (the two-segment instance: T = 64 only)
-    if (!nseg && c->knob_force_split) nseg = 4;
-    if (nseg) {
+    if (!nseg && force_split) nseg = 4;
+    // (the plain five critics with ObstaclesCritic on, whole quads: split_select)
+    if (nseg && split_select(gates, T, step, nseg)) {
       const SmpcLds Ls = split_lds(window_bytes, P, T, nseg);
       if (Ls.total <= kLdsPerCu) {
-        const uint32_t key = Ls.total ^ (nseg << 28);
-        if (c->occ_split_lds != key) {
-          int nb = 0;
-          if (smpc_split_occupancy(nseg, Ls.total, &nb) != hipSuccess || nb < 1) nb = 1;
-          c->occ_split_blocks = nb;
-          c->occ_split_lds = key;
-        }
+        const uint32_t occ_blocks = c->occ_split.get(split_occupancy_row(nseg)->fn, smpc_split_block(), Ls.total);
         const uint32_t per_block = smpc_split_rollouts_per_block(nseg);
         const uint32_t blocks = (B + per_block - 1) / per_block;
-        const uint32_t resident = static_cast<uint32_t>(c->num_cu) * static_cast<uint32_t>(c->occ_split_blocks);
-        c->split_now = true;
-        c->split_nseg = nseg;
-        c->lds_split = Ls;
-        c->grid_split = std::max(1u, std::min(std::min(blocks, resident), kMaxGrid));   // (persistent: forced runs loop over groups)
+        const uint32_t resident = static_cast<uint32_t>(c->num_cu) * occ_blocks;
+        split_now = true;
+        pl.split_nseg = nseg;
+        pl.split.lds = Ls;
+        pl.split.block = smpc_split_block();
+        pl.split.grid = std::max(1u, std::min(std::min(blocks, resident), kMaxGrid));   // (persistent: forced runs loop over groups)
       }
     }
   }
@@ -646,8 +621,10 @@ static int plan_launch(smpc_ctx* c, const smpc_tick_in* in, uint32_t gates, uint
   // below kLaneMinBatch the lane pass itself loses to the wave pass (one group per CU's worth of
   // waves: crossover measured at ~50 k rollouts); such contexts keep the group-major noise only
   // for the split form
-  if (c->lane_now && !c->split_now && B < kLaneMinBatch && !c->lane_forced) c->lane_now = false;
+  if (lane_now && !split_now && B < kLaneMinBatch && !c->lane_forced) lane_now = false;
 
+  pl.kind = split_now ? PassPlan::kSplit : (lane_now ? PassPlan::kLane : PassPlan::kWave);
+  c->plan = pl;
   mode_out = mode_now;
   return SMPC_OK;
 }
@@ -844,11 +821,11 @@ int prepare_tick(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
   // their own; the CostCritic table (general pass only) is not part of that
   // (contexts of the wave-per-rollout pass only: see smpc_lane.hip for why not the other)
   const bool inline_tick = !c->defer_upload && !c->use_tpr && T <= 64 && tl.lut_cost - tl.px <= SMPC_INLINE_TICK_CAP &&
-    !c->knob_no_inline_tick;
+    !c->knobs.no_inline_tick;
   // SMPC_PINNED_TICK=1 (experiment): no copy at all — the kernels read the tick block where the
   // host assembled it, in pinned host memory.  Measured (tools/tail_ab.py SMPC_PINNED_TICK=1) and
   // not the default: every block of the grid fetches its ~2 KB across PCIe, uncached.
-  const bool pinned_tick = c->knob_pinned_tick && !c->defer_upload && !inline_tick;
+  const bool pinned_tick = c->knobs.pinned_tick && !c->defer_upload && !inline_tick;
   const uint8_t* const tb = pinned_tick ? h : c->d_tick;
   // the tick block's number: written last, echoed by block 0 of every pass that reads the block
   // from device memory (SmpcDev::canary)
@@ -857,7 +834,7 @@ int prepare_tick(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
   c->tick_used = tl.total;
   const bool bar = c->bar_tick && !c->defer_upload && !pinned_tick && !inline_tick;
   // (whoever uploads: this ctx or its group; the in-launch reduction experiment does not carry it)
-  c->canary_expect = (!pinned_tick && !inline_tick && !c->fused_reduce) ? c->tick_no : 0u;
+  c->canary_expect = (!pinned_tick && !inline_tick && !c->knobs.fused_reduce) ? c->tick_no : 0u;
   if (bar) {
     // no kernel of an earlier tick may still read the block (every tick ends with fetch_out;
     // a tick abandoned on an error does not)
@@ -867,7 +844,7 @@ int prepare_tick(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
     }
     // SMPC_DEBUG_STALE_TICK=n (tests of the guard): tick n's block is NOT handed over — the pass
     // reads the previous tick's, echoes its number, and fetch_out has to fail the tick
-    if (c->knob_stale_tick && c->tick_no == c->knob_stale_tick) {
+    if (c->knobs.stale_tick && c->tick_no == c->knobs.stale_tick) {
     } else {
       bar_copy(c->d_tick, h, tl.total);
       bar_flush(c);

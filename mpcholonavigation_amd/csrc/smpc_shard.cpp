@@ -304,7 +304,7 @@ int smpc_shard_tick(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_ti
     SmpcP2P x = c->p2p;
     x.xseq = ++c->p2p_xseq;
     uint32_t seq = 0;
-    if (mode == 0 && c->poll_enabled) {
+    if (mode == 0 && c->knobs.poll) {
       seq = ++c->seq;
       if (seq == 0) seq = ++c->seq;
       c->poll_seq = seq;

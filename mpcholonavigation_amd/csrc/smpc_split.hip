@@ -41,6 +41,7 @@
 #include "smpc_dev.h"
 #include "smpc_device_math.h"
 #include "smpc_lane_common.h"
+#include "smpc_inst.h"
 
 #define SPLIT_BLOCK 512   // 8 waves, one block per CU: two waves per SIMD (the parked controls, the segment's displacements and
                           // PathAlign's samples take ~215 registers; at 128 for four waves per SIMD 89 of them spill)
@@ -719,40 +720,43 @@ __global__ void __launch_bounds__(SPLIT_BLOCK, 2) smpc_pass_split(const SmpcDev 
 #undef SLOT
 }
 
-extern char smpc_last_pass_kernel[96];   // smpc_kernels.hip
+// the instances (smpc_inst.h): one row each
+#define SPLIT_INST(...) {__VA_ARGS__, reinterpret_cast<const void*>(&smpc_pass_split<__VA_ARGS__>)}
+static const SplitInst kSplitInst[] = {
+  SPLIT_INST(4, true),
+  SPLIT_INST(4, false),   // horizons below 64: the step slots behind the horizon are masked
+  SPLIT_INST(2, true),    // (the two-segment instance: experiments at T = 64 only)
+};
+#undef SPLIT_INST
 
-hipError_t smpc_launch_pass_split(const SmpcDev& p, const SmpcLds& L, uint32_t grid, uint32_t nseg, hipStream_t st)
+static const SplitInst* split_find(int nseg, bool full)
 {
-  if (nseg != 2u && nseg != 4u) return hipErrorInvalidValue;
+  for (const SplitInst& k : kSplitInst)
+    if (k.nseg == nseg && k.full == full) return &k;
+  return nullptr;
+}
+
+const SplitInst* split_select(uint32_t flags, uint32_t T, uint32_t step, uint32_t nseg)
+{
+  // the plain five critics with ObstaclesCritic on, whole quads, PathAlign sampled at the first step of every quad
   const uint32_t need = SD_OBSTACLES, never = SD_GOAL_ANGLE | SD_EXTRA_CRITICS | SD_STORE_TRAJ | SD_USE_PATH_YAW;
-  if (p.T > 64u || p.T < 20u || (p.T & 3u) || (p.flags & need) != need || (p.flags & never) ||
-      ((p.flags & SD_PATH_ALIGN) && p.step != 4u))
-    return hipErrorInvalidValue;
-  const bool full = p.T == 64u;
-  snprintf(smpc_last_pass_kernel, sizeof(smpc_last_pass_kernel), "smpc_pass_split<%u, %s>", nseg, full ? "true" : "false");
-  if (nseg == 4u && full) hipLaunchKernelGGL((smpc_pass_split<4, true>), dim3(grid), dim3(SPLIT_BLOCK), L.total, st, p, L);
-  else if (nseg == 4u) hipLaunchKernelGGL((smpc_pass_split<4, false>), dim3(grid), dim3(SPLIT_BLOCK), L.total, st, p, L);
-  else if (full) hipLaunchKernelGGL((smpc_pass_split<2, true>), dim3(grid), dim3(SPLIT_BLOCK), L.total, st, p, L);
-  else return hipErrorInvalidValue;   // (the two-segment instance: experiments at T = 64 only)
-  return hipGetLastError();
+  if (T > 64u || T < 20u || (T & 3u) || (flags & need) != need || (flags & never) ||
+      ((flags & SD_PATH_ALIGN) && step != 4u))
+    return nullptr;
+  return split_find(static_cast<int>(nseg), T == 64u);
+}
+
+const SplitInst* split_occupancy_row(uint32_t nseg) {return split_find(static_cast<int>(nseg), true);}   // (a representative: smpc_inst.h)
+
+hipError_t split_launch(const SplitInst* k, const SmpcDev& p, const SmpcLds& L, uint32_t grid, hipStream_t st)
+{
+  if (!k) return hipErrorInvalidValue;
+  snprintf(smpc_last_pass_kernel, sizeof(smpc_last_pass_kernel), "smpc_pass_split<%d, %s>", k->nseg, k->full ? "true" : "false");
+  void* args[] = {const_cast<SmpcDev*>(&p), const_cast<SmpcLds*>(&L)};
+  return inst_launch(k->fn, dim3(grid), SPLIT_BLOCK, args, L.total, st);
 }
 
 uint32_t smpc_split_block() {return SPLIT_BLOCK;}
 uint32_t smpc_split_rollouts_per_block(uint32_t nseg) {return SPLIT_BLOCK / WAVE * (64u / nseg);}
 
-hipError_t smpc_split_occupancy(uint32_t nseg, uint32_t lds_bytes, int* blocks_per_cu)
-{
-  const void* k = nseg == 4u ? reinterpret_cast<const void*>(&smpc_pass_split<4, true>)
-                             : reinterpret_cast<const void*>(&smpc_pass_split<2, true>);
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k, SPLIT_BLOCK, lds_bytes);
-}
-
-hipError_t smpc_split_set_lds_limit(int bytes)
-{
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&smpc_pass_split<4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&smpc_pass_split<4, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&smpc_pass_split<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  return e;
-}
+hipError_t split_set_lds_limit(int bytes) {return inst_set_lds_limit(kSplitInst, bytes);}
