@@ -1,0 +1,175 @@
+"""Costmap lookups at cell edges hit the reference's cell: every kernel family, zero flips.
+
+The three kernel families each find a rollout point's costmap cell with a float fast path of
+their own — cost_at (smpc_device_math.h) in the wave pass, the window-relative fma(ax, 1/res, cxf)
+in smpc_lane.hip and in smpc_split.hip — and fall back to the reference's double arithmetic inside
+a guard band whose width the host derives (cell_eps, cell_eps_w in smpc_prepare.cpp).  The parity
+tests tolerate a budget of flipped cells, because GPU and oracle positions differ in the last ulp;
+a band slightly too narrow would hide inside it.  On the scenes of tests/edge_scenes.py the
+positions are bit-identical on both sides and sit on cell edges (tests/test_cell_index_cpu.py pins
+that premise, and that the scenes are adversarial, on the oracle alone), so here
+
+  * fail_flag, non_colliding and furthest_reached_path_point equal the oracle's,
+  * EVERY rollout's cost is within tol of the oracle's: no flip allowance, nothing skipped,
+  * tol = 0.25 * min_single_lookup_shift (a quarter of the least that one wrong lookup moves a
+    cost), asserted to exceed ten times the oracle's own distance from the float64 model,
+  * the intended family and form scored the tick: pass_kind and the instance's name.
+
+With the guard bands forced to zero (cell_eps = cell_eps_w = 0 in smpc_prepare.cpp; every index
+stays bounds-checked) this file fails in every family: DESIGN.md section 7 has the counts.
+"""
+import ctypes
+
+import numpy as np
+import pytest
+
+from tests import edge_scenes as E
+from tests.helpers import assert_parity
+
+pytestmark = pytest.mark.gpu
+
+CASES = sorted(((name, key) for name, f in E.FORMS.items() for key in f.scenes),
+               key=lambda c: (E.scene_name(c[1]), c[0]))       # (forms that share a scene: side by side)
+
+
+@pytest.fixture(scope="module")
+def Smpc():
+    from mpcholonavigation_amd.optimizer import Smpc as S
+    return S
+
+
+def last_kernel(g):
+    f = g.lib.smpc_debug_last_pass_kernel
+    f.restype, f.argtypes = ctypes.c_char_p, []
+    return f().decode()
+
+
+_oracle_cache = {}
+
+
+def oracle_run(oracle_lib, key, names):
+    """(tick out, per-rollout costs, control sequence) of the oracle on a scene; the last few kept."""
+    from oracle.loader import Oracle
+    k = (key, tuple(names))
+    if k not in _oracle_cache:
+        while len(_oracle_cache) >= 4:
+            _oracle_cache.pop(next(iter(_oracle_cache)))
+        scn = E.scene(key)
+        o = Oracle(scn.config())
+        scn.configure(o, E.critics_of(names))
+        u, out = o.optimize(scn.tick, scn.u0)
+        _oracle_cache[k] = (out, o.get_costs(), u)
+        o.close()
+    return _oracle_cache[k]
+
+
+def make_ctx(Smpc, monkeypatch, scn, flags, env, names):
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)          # (the knobs are read when the context is created)
+    g = Smpc(scn.config(flags=flags))
+    for k in env:
+        monkeypatch.delenv(k)
+    scn.configure(g, E.critics_of(names))
+    return g
+
+
+def tolerance(oracle_lib, key, names, critic):
+    """tol = a quarter of the least one wrong lookup moves a cost; it must stand ten times clear
+    of what separates the oracle's float32 sums from the float64 model of the same critic (over
+    the rollouts that do not collide: a collision's cost, 2e5, has a float ulp of 1.6e-2)."""
+    scn = E.scene(key)
+    only = E.critics_of((critic,))
+    tol = 0.25 * E.min_single_lookup_shift(only, scn.T, scn, critic)
+    m = E.model(scn, only, critic)
+    _, c_only, _ = oracle_run(oracle_lib, key, (critic,))
+    d = np.abs(c_only.astype(np.float64) - m["costs"])[~m["collided"]].max(initial=0.0)
+    assert tol > 10.0 * d, f"tol {tol:.3e} against oracle-vs-model {d:.3e}"
+    return tol, d, m
+
+
+def check_against_oracle(label, out, c_gpu, out_ref, c_ref, tol):
+    d = np.abs(c_gpu.astype(np.float64) - c_ref.astype(np.float64))
+    bad = int(np.sum(~(d <= tol)))
+    print(f"[edge] {label}: max |cost - oracle| {d.max():.3e} (tol {tol:.3e}), rollouts beyond it {bad} of {d.size}; "
+          f"non-colliding {out.non_colliding} / {out_ref.non_colliding}, fail {out.fail_flag} / {out_ref.fail_flag}")
+    assert out.fail_flag == out_ref.fail_flag, label
+    assert out.non_colliding == out_ref.non_colliding, label
+    assert bool(out.furthest_valid) == bool(out_ref.furthest_valid), label
+    if out_ref.furthest_valid:
+        assert out.furthest_reached_path_point == out_ref.furthest_reached_path_point, label
+    assert bad == 0, f"{label}: {bad} rollouts read another cell (worst {d.max():.3e} at rollout {int(d.argmax())})"
+
+
+@pytest.mark.parametrize("case", CASES, ids=[f"{c[0]}/{E.scene_name(c[1])}" for c in CASES])
+def test_every_lookup_reads_the_reference_cell(Smpc, oracle_lib, monkeypatch, case):
+    name, key = case
+    form = E.FORMS[name]
+    scn = E.scene(key)
+    assert (scn.B, scn.T) == (form.B, form.T)
+    label = f"{name}/{scn.label}"
+    # (forms that need other critics on, the near-goal one, score the default five: positions stay
+    # exact, and the other critics see the same points on both sides: about 1e-6 relative)
+    tol, d_om, m = tolerance(oracle_lib, key, form.critics, form.critic)
+    out_ref, c_ref, _ = oracle_run(oracle_lib, key, form.critics)
+    g = make_ctx(Smpc, monkeypatch, scn, form.flags, form.env, form.critics)
+    try:
+        _, out = g.optimize(scn.tick, scn.u0)
+        kernel = last_kernel(g)
+        print(f"[edge] {label}: pass_kind {out.pass_kind} kernel {kernel}; oracle vs float64 model {d_om:.2e}")
+        assert (out.pass_kind, kernel) == (form.kind, form.kernel), label
+        check_against_oracle(label, out, g.get_costs(), out_ref, c_ref, tol)
+        if form.flags & E.STORE:
+            # any summation order is exact on these scenes: the DPP scan's points, bit for bit
+            tx, ty, _ = g.get_generated_trajectories()
+            assert np.array_equal(tx, m["x"]) and np.array_equal(ty, m["y"]), label
+    finally:
+        g.close()
+
+
+def test_grouped_launch_reads_the_reference_cell(Smpc, oracle_lib):
+    """smpc_group_optimize, two members on different origins: the `many` instances.  The default
+    five critics (the grouped forms are pinned for them in tests/test_gpu_pass_selection.py); the
+    first tick has no furthest-point prediction and scores each member alone, the later ones in
+    one launch: every tick is checked."""
+    from mpcholonavigation_amd.optimizer import SmpcGroup
+    scns = [E.scene(k) for k in E.GROUP_SCENES]
+    members = []
+    for scn in scns:
+        g = Smpc(scn.config(flags=E.LANE))
+        scn.configure(g, E.critics_of(E.FIVE))
+        members.append(g)
+    grp = SmpcGroup(members)
+    seen = []
+    try:
+        for tick in range(4):
+            res = grp.optimize([s.tick for s in scns], [s.u0 for s in scns])
+            seen.append(last_kernel(members[0]))
+            for i, (key, scn) in enumerate(zip(E.GROUP_SCENES, scns)):
+                tol, _, _ = tolerance(oracle_lib, key, E.FIVE, "obstacles")
+                out_ref, c_ref, _ = oracle_run(oracle_lib, key, E.FIVE)
+                assert res[i][1].pass_kind == 1
+                check_against_oracle(f"group tick {tick} member {i} {scn.label}", res[i][1], members[i].get_costs(),
+                                     out_ref, c_ref, tol)
+        print(f"[edge] group: kernel launched last, per tick: {seen}")
+        assert E.GROUP_KERNEL in seen, seen
+    finally:
+        grp.close()
+        for g in members:
+            g.close()
+
+
+@pytest.mark.parametrize("key", E.PARITY_SCENES, ids=[E.scene_name(k) for k in E.PARITY_SCENES])
+@pytest.mark.parametrize("flags", [E.WAVE, E.LANE], ids=["wave", "lane"])
+def test_standard_parity_bar_with_no_flip_budget(Smpc, oracle_lib, monkeypatch, key, flags):
+    """tests/helpers.assert_parity with the default five critics on an edge scene and a flip budget
+    of zero, hard and soft."""
+    scn = E.scene(key)
+    out_ref, c_ref, u_ref = oracle_run(oracle_lib, key, E.FIVE)
+    g = make_ctx(Smpc, monkeypatch, scn, flags, {}, E.FIVE)
+    try:
+        u, out = g.optimize(scn.tick, scn.u0)
+        assert out.pass_kind == (0 if flags == E.WAVE else 1)
+        assert_parity(u, out, u_ref, out_ref, g.get_costs(), c_ref, max_flips=0, max_soft=0,
+                      label=f"edge parity {scn.label} {last_kernel(g)}")
+    finally:
+        g.close()
