@@ -76,8 +76,16 @@ extern "C" {
                                              pre-pass (exact two-pass mode)  */
 #define SMPC_FLAG_WAVE_PER_ROLLOUT 0x8u   /* always the wave-per-rollout pass             */
 #define SMPC_FLAG_LANE_PER_ROLLOUT 0x10u  /* the lane-per-rollout pass (csrc/smpc_lane.hip)
-                                             on every tick it supports: time_steps <= 64,
-                                             every cost_power 1, no GoalAngle term active */
+                                             on every tick it has an instance for, whatever
+                                             the batch size: the five critics (near the goal
+                                             with the GoalAngle term) or the deployed list's
+                                             cruise tick, time_steps <= 64 (128 for the
+                                             re-read form), every cost_power 1.  A tick whose
+                                             only departure from that is a cost_power other
+                                             than 1 among the five critics takes the lane pass
+                                             too (smpc_pass_lane_pow), but only from 61 440
+                                             rollouts up, with or without this flag: below
+                                             that it stays on the wave-per-rollout pass */
 #define SMPC_FLAG_PROFILE 0x4u            /* bracket each scoring pass with HIP
                                              events (smpc_tick_out.score_pass_ms) */
 
@@ -292,7 +300,9 @@ typedef struct smpc_tick_out {
   float score_pass_ms;      /* SMPC_FLAG_PROFILE: mean GPU time of one scoring-pass
                                kernel of this call, HIP events around it            */
   uint32_t pass_kind;       /* which streaming pass scored the last iteration:
-                               0 smpc_pass (wave per rollout), 1 smpc_pass_lane     */
+                               0 smpc_pass (wave per rollout), 1 smpc_pass_lane or
+                               smpc_pass_lane_pow (lane per rollout), 2 smpc_pass_split
+                               (split horizon)                                      */
 } smpc_tick_out;
 
 typedef struct smpc_ctx smpc_ctx;

@@ -185,7 +185,8 @@ void fill_score_args(smpc_ctx* c, uint32_t flags, const float* u_dev, const floa
 // ObstaclesCritic on: its stripped tick takes the lane pass.  The re-read form has instances with
 // ObstaclesCritic scored only, and no lane instance writes trajectories: such a pass takes the
 // wave-per-rollout pass (its geometry is planned for every tick).  A parking-form tick without an
-// instance is an error, as it always was.
+// instance is an error, as it always was.  A tick that scores with cost powers (pl.pow) picks among
+// the rows of smpc_pass_lane_pow, which include the two without a costmap lookup for its stripped passes.
 struct PassChoice {
   PassPlan::Kind kind;
   const void* inst;        // WaveInst, LaneInst or SplitInst by kind; null: no instance
@@ -198,7 +199,7 @@ static PassChoice pass_for(const smpc_ctx* c, uint32_t flags)
   if (pl.kind == PassPlan::kSplit)
     if (const SplitInst* k = split_select(flags, T, c->dev.step, pl.split_nseg)) return {PassPlan::kSplit, k, &pl.split};
   if (pl.kind != PassPlan::kWave) {
-    const LaneInst* k = lane_select(flags, T, pl.rr, false, c->acker_r);
+    const LaneInst* k = lane_select(flags, T, pl.rr, false, c->acker_r, pl.pow);
     if (k || !(pl.rr || (flags & SD_STORE_TRAJ))) return {PassPlan::kLane, k, &pl.lane};
   }
   return {PassPlan::kWave, wave_select(c->R, c->score_mode, T), &pl.wave};

@@ -178,6 +178,7 @@ struct PassPlan {
   PassGeom lane;              // kind != kWave (a split tick whose flags were stripped takes the lane pass)
   PassGeom split;             // kind == kSplit
   bool rr = false;            // the lane pass in its re-read form (no parked controls; T > 64 or SMPC_LANE_REREAD=1)
+  bool pow = false;           // the lane pass scores with cost powers other than 1: the rows of smpc_pass_lane_pow
   uint32_t split_nseg = 4;    // lanes per rollout of the split pass: 4 or 2
   uint32_t window_bytes = 0;  // first LDS region of the lane pass
 };

@@ -41,6 +41,24 @@ __device__ __forceinline__ float add_cost_pow(float c, double v, uint32_t power)
   return (float)((double)c + powu(v, power));
 }
 
+// sqrt(double) for arguments that are squares of float distances (no subnormal or huge inputs): the
+// Goldschmidt iteration of the compiler's own expansion of sqrt — seed, one coupled step, two
+// fused corrections of the residual a - g^2 — from the float reciprocal square root, and without
+// that expansion's range scaling, whose three literal constants the compiler keeps in vector
+// registers across whatever loop surrounds the call (smpc_lane_pass.inc has none to spare).
+// Within an ulp of the correctly rounded root; callers round the result's product to float.
+__device__ __forceinline__ double sqrt_unscaled(double a)
+{
+  const double y = (double)__builtin_amdgcn_rsqf((float)a);
+  double g = a * y, h = 0.5 * y;
+  const double r = fma(-h, g, 0.5);
+  g = fma(g, r, g);
+  h = fma(h, r, h);
+  g = fma(fma(-g, g, a), h, g);
+  g = fma(fma(-g, g, a), h, g);
+  return a > 0.0 ? g : 0.0;
+}
+
 // utils::normalize_angles (tools/utils.hpp:258-263), double like the reference
 __device__ __forceinline__ double normalize_angle(double a)
 {

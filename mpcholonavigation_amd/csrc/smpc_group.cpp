@@ -124,9 +124,10 @@ int smpc_group_optimize(smpc_group* g, const smpc_tick_in* ins, float* const* u_
     if (need_f) flags[i] |= SD_LOCAL_FURTHEST;
     // (a near-goal member scores GoalAngle: instances of the lane pass the batched launch does not
     // have; members with the deployed critic list — Constraint / Cost / Twirling — have theirs, and
-    // a member without those critics runs them unchanged)
-    const LaneInst* k = c->plan.kind == PassPlan::kLane && !c->plan.rr
-      ? lane_select(flags[i], c->cfg.time_steps, false, true, c->acker_r) : nullptr;
+    // a member without those critics runs them unchanged; a member that scores with cost powers
+    // has no batched instance either and is ticked on its own)
+    const LaneInst* k = c->plan.kind == PassPlan::kLane && !c->plan.rr && !c->plan.pow
+      ? lane_select(flags[i], c->cfg.time_steps, false, true, c->acker_r, false) : nullptr;
     const bool ok = k && c->cfg.iteration_count == 1 && !c->fail_in &&
       !(c->cfg.flags & (SMPC_FLAG_NO_SPECULATION | SMPC_FLAG_PROFILE)) && (!need_f || c->hint_valid) &&
       c->knobs.poll && c->acker_r < 0.f && !c->two_coll_fp;

@@ -14,7 +14,8 @@
 #pragma GCC visibility push(hidden)
 
 struct WaveInst { int r, mode; bool full; const void* fn; };                                       // smpc_pass<R, MODE, FULL>
-struct LaneInst { bool full, obst, many; int nch; bool rr, ga, quads; int tc; bool dep; const void* fn; };   // smpc_pass_lane<...>
+// pow: the instance is smpc_pass_lane_pow<...>, the same template arguments with general cost powers
+struct LaneInst { bool full, obst, many; int nch; bool rr, ga, quads; int tc; bool dep; const void* fn; bool pow; };   // smpc_pass_lane<...>
 struct SplitInst { int nseg; bool full; const void* fn; };                                         // smpc_pass_split<NSEG, FULL>
 
 // Selectors: the instance that scores these flags at this horizon, or null when there is none.
@@ -23,7 +24,9 @@ struct SplitInst { int nseg; bool full; const void* fn; };                      
 const WaveInst* wave_select(int R, int mode, uint32_t T);
 // rr: the re-read form (no parked controls; required for T > 64); many: the grouped instances
 // (smpc_group_optimize); acker_r: the Ackermann min_turning_r, < 0 for the other models
-const LaneInst* lane_select(uint32_t flags, uint32_t T, bool rr, bool many, float acker_r);
+// pow: the tick scores with a cost_power other than 1 among the five critics — only then is a row of
+// smpc_pass_lane_pow returned (single context, parking form); false behaves as it always did
+const LaneInst* lane_select(uint32_t flags, uint32_t T, bool rr, bool many, float acker_r, bool pow);
 // step: PathAlign's trajectory_point_step; nseg: lanes per rollout, 4 or 2
 const SplitInst* split_select(uint32_t flags, uint32_t T, uint32_t step, uint32_t nseg);
 

@@ -478,7 +478,8 @@ static int plan_launch(smpc_ctx* c, const smpc_tick_in* in, uint32_t gates, uint
   // the lean kernels: MODE 0 scores the north star's five away from the goal, MODE 3 also the
   // additive forms of Cost, Goal, Constraint, Twirling, PathAngle (the deployed list) and of the
   // near-goal GoalAngle term; everything else (a cost_power other than 1, trajectory write-out,
-  // path orientations, a footprint, VelocityDeadband) takes the general pass
+  // path orientations, a footprint, VelocityDeadband) takes the general pass — or, for a cost_power
+  // among the five and nothing else, the lane pass's power rows (below)
   const uint32_t lean_extra = SD_CONSTRAINT | SD_COST | SD_GOAL | SD_TWIRLING | SD_PATH_ANGLE | SD_GOAL_ANGLE;
   if (gates & (SD_STORE_TRAJ | SD_USE_PATH_YAW | (SD_EXTRA_CRITICS & ~lean_extra))) {
     mode_now = 2;
@@ -506,10 +507,22 @@ static int plan_launch(smpc_ctx* c, const smpc_tick_in* in, uint32_t gates, uint
   // (trajectory_point_step = 4, the reference's default: path_align_critic.cpp:36).
   // The re-read form (no parked controls) is the only one for T > 64; SMPC_LANE_REREAD=1 selects
   // it for T <= 64 too (experiments) where it has an instance.
-  pl.rr = (T > 64 || c->knobs.lane_reread) && lane_select(gates, T, true, false, c->acker_r) != nullptr;
+  pl.rr = (T > 64 || c->knobs.lane_reread) && lane_select(gates, T, true, false, c->acker_r, false) != nullptr;
   bool lane_now = c->use_tpr && (mode_now == 0 || mode_now == 3) && T <= kLaneMaxT &&
-    lane_select(gates, T, T > 64, false, c->acker_r) != nullptr &&
+    lane_select(gates, T, T > 64, false, c->acker_r, false) != nullptr &&
     !((gates & SD_PATH_ANGLE) && c->pang_any) && !((gates & SD_PATH_ALIGN) && step != 4);
+  // A cost_power other than 1 among the five critics (near the goal: GoalAngle's too) puts the tick
+  // in MODE 2.  When that power is the ONLY reason — no trajectory write-out, no path orientations,
+  // no critic beyond the five — the tick still takes the lane pass, on the rows of
+  // smpc_pass_lane_pow (parking form: T <= 64, trajectory_point_step 4), which apply each power to
+  // its critic's per-rollout total in the epilogue.  From kLaneMinBatch rollouts up only, also for
+  // a context that asks for the lane pass (SMPC_FLAG_LANE_PER_ROLLOUT, SMPC_PASS=lane): that is the
+  // crossover below which the lane pass loses to the wave pass, and the power rows have not been
+  // measured below it.  Never the split or the re-read form.
+  pl.pow = mode_now == 2 && c->score_mode_for(cr) == 2 && c->use_tpr && !pl.rr && T <= 64 && step == 4 &&
+    B >= kLaneMinBatch && !(gates & (SD_STORE_TRAJ | SD_USE_PATH_YAW | SD_EXTRA_CRITICS)) &&
+    lane_select(gates, T, false, false, c->acker_r, true) != nullptr;
+  if (pl.pow) lane_now = true;
   if (lane_now) {
     pl.window_bytes = window_bytes;
     pl.lane.lds = lane_lds(window_bytes, P, T, pl.rr);
@@ -623,6 +636,7 @@ static int plan_launch(smpc_ctx* c, const smpc_tick_in* in, uint32_t gates, uint
   // for the split form
   if (lane_now && !split_now && B < kLaneMinBatch && !c->lane_forced) lane_now = false;
 
+  pl.pow = pl.pow && lane_now;   // (a path too long for the lane pass's LDS: the wave pass after all)
   pl.kind = split_now ? PassPlan::kSplit : (lane_now ? PassPlan::kLane : PassPlan::kWave);
   c->plan = pl;
   mode_out = mode_now;
