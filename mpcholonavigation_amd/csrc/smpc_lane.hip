@@ -83,6 +83,16 @@
 #define LANE_X_CONST_VGPR 0  // the cell index's loop constants in vector registers
 #endif
 
+#ifndef LANE_X_PFW_BARE
+#define LANE_X_PFW_BARE 1    // PreferForward's min(vx, 0) as the bare v_min_f32 (no canonicalising v_max in front)
+#endif
+#ifndef LANE_X_NOISE_QUAD
+#define LANE_X_NOISE_QUAD 1  // noise prefetch: one scalar offset per tensor and quad, the step inside the quad in the vector offset
+#endif
+#ifndef LANE_X_PRIO_ITER
+#define LANE_X_PRIO_ITER 1   // priority swap once per loop iteration (two quads), one branch
+#endif
+
 // ---------------------------------------------------------------------------
 // [B][T] row-major <-> group-major (SMPC_GM_INDEX, smpc_dev.h): one-off, after the noise is supplied
 // (or drawn row-major), and back when something asks for the [B, T] tensors of a group-major draw

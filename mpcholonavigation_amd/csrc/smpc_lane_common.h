@@ -118,6 +118,18 @@ __device__ __forceinline__ int cvt_floor_i32(float q)
   return r;
 }
 
+// acc + min(x, 0) with the bare v_min_f32.  fminf() puts a canonicalising v_max_f32 x, x in front
+// of it wherever the compiler cannot prove x free of signalling NaNs, and a value that arrives
+// from another basic block is such a value; quiet NaNs and numbers give fminf's answer.  The sum
+// is part of the statement: left to the scheduler the eight minima of a loop iteration are
+// held in registers of their own until the iteration's end, which the pass has not got.
+__device__ __forceinline__ float add_min_zero(float acc, float x)
+{
+  float m;
+  asm("v_min_f32 %1, 0, %2\n\tv_add_f32 %0, %0, %1" : "+v"(acc), "=&v"(m) : "v"(x));
+  return acc;
+}
+
 // The reference's own double arithmetic (nav2_costmap_2d worldToMap) for the lanes whose
 // float quotient is near a cell edge, outside the LDS window or off the map.  Returns the
 // index of the LDS byte that holds the cell's cost: a window cell, the NO_INFORMATION byte

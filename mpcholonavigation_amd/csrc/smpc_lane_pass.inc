@@ -219,6 +219,8 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
   // scheduler from overlapping the costmap lookups with it); it only notes whether some
   // |yaw| left the range of the fast reduction, commits nothing in that case and returns
   // true, and the group is redone by the SAFE instance.
+  using T_ = std::true_type;
+  using F_ = std::false_type;
   auto group_body = [&](auto safe_c, const uint32_t grp) -> bool {
     constexpr bool SAFE = decltype(safe_c)::value;
     const uint32_t b = grp * WAVE + lane;
@@ -302,7 +304,7 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
     // sample_slot: this step is a multiple of four (known at compile time in the unrolled quad)
     auto do_step = [&](const uint32_t t, const bool sample_slot, const float ux, const float uy, const float uz,
                        const float n0, const float n1, const float n2, float& cvx, float& cvy,
-                       float& cwz) {
+                       float& cwz) __attribute__((always_inline)) {
       // NoiseGenerator::setNoisedControls (noise_generator.cpp:65-74)
       cvx = ux + n0;
       cvy = uy + n1;
@@ -394,7 +396,9 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
       }
       // PreferForwardCritic (prefer_forward_critic.cpp:42-46): sum_t max(-vx, 0) dt, here as
       // -dt sum_t min(vx, 0) — the factor once per rollout instead of once per step
-#if LANE_X_PFW_MIN
+#if LANE_X_PFW_MIN && LANE_X_PFW_BARE
+      pfw = add_min_zero(pfw, vx);
+#elif LANE_X_PFW_MIN
       pfw = pfw + fminf(vx, 0.f);
 #else
       pfw = fmaf(fmaxf(-vx, 0.f), dt, pfw);
@@ -501,17 +505,29 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
     uint64_t clk = __builtin_amdgcn_s_memtime();
     // four steps; each parks its noised controls at once (LANE_X_PARK_STEP) or the quad returns
     // them in cq[3 i + ctrl] for the caller to park
-    auto run_quad = [&](auto hi_c, const uint32_t q, float (&cq)[12]) {
+    // swap_c: this quad looks at the clock and sets the wave's priority
+    auto run_quad = [&](auto hi_c, auto swap_c, const uint32_t q, float (&cq)[12]) __attribute__((always_inline)) {
       [[maybe_unused]] constexpr bool HI = decltype(hi_c)::value;
+      constexpr bool SWAP = decltype(swap_c)::value;
       // The two waves of a SIMD do not share it evenly by themselves: the older one wins every
       // tie and finishes its groups ~25 % sooner (41 us against 51 us for two groups), then the
       // younger one runs alone.  Swapping their priorities every 2^15 shader clocks — by the clock,
       // read a quad earlier: the same for both whatever their progress, in anti-phase between
       // waves w and w + 4 — lets both finish together at 47 us (measured: tools/lane_timeline.py;
       // shorter periods share less evenly, 2^12: 45 / 48 us).
-      if (((uint32_t)(clk >> 15) + (uint32_t)(wave >> 2)) & 1u) __builtin_amdgcn_s_setprio(1);
-      else __builtin_amdgcn_s_setprio(0);
-      clk = __builtin_amdgcn_s_memtime();
+      // LANE_X_PRIO_ITER: once per loop iteration, two quads or ~6 000 clocks of the period's 32 768,
+      // and as "low, then high if the bit says so": one branch over one instruction where the
+      // if / else compiled to two branches and a mask.
+      if constexpr (SWAP) {
+#if LANE_X_PRIO_ITER
+        __builtin_amdgcn_s_setprio(0);
+        if (((uint32_t)(clk >> 15) + (uint32_t)(wave >> 2)) & 1u) __builtin_amdgcn_s_setprio(1);
+#else
+        if (((uint32_t)(clk >> 15) + (uint32_t)(wave >> 2)) & 1u) __builtin_amdgcn_s_setprio(1);
+        else __builtin_amdgcn_s_setprio(0);
+#endif
+        clk = __builtin_amdgcn_s_memtime();
+      }
       float uc[12];
 #pragma unroll
       for (int j = 0; j < 12; ++j) uc[j] = uq[j];
@@ -526,15 +542,33 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
 #pragma unroll
           for (int k = 0; k < 3; ++k) uq[3 * i + k] = ldu(k, 4 * (q + 1) + i);
       }
+      // LANE_X_NOISE_QUAD (whole quads): one scalar offset per tensor and QUAD — the next quad's first
+      // step, clamped to the last quad where the fetch is unconditional — instead of three scalar
+      // instructions per step; the step inside the quad, 0 / 256 / 512 / 768 bytes, is added to the
+      // lane's offset.  (Meant for the load's immediate offset; the compiler hoists the four sums
+      // out of the loop instead, three more vector registers.  The plain instances have them: the
+      // GoalAngle, deployed-list, grouped and cost-power ones spill 12-20 bytes to scratch with it.)
+      constexpr bool kQuadOff = LANE_X_NOISE_QUAD && QUADS && !GA && !DEP && !MANY && !POW;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const uint32_t t = 4 * q + i;
         // this step's noise; its registers are refilled at once with step t + 4
         const float n0 = nq[3 * i], n1 = nq[3 * i + 1], n2 = nq[3 * i + 2];
         if (kAlwaysAhead || q + 1 < nquad) {
-          nq[3 * i + 0] = ld(0, t + 4);
-          nq[3 * i + 1] = ld(1, t + 4);
-          nq[3 * i + 2] = ld(2, t + 4);
+          if constexpr (kQuadOff) {
+            const uint32_t tq = (FULL || TC || 4 * (q + 1) < T) ? 4 * (q + 1) : T - 4;
+            const uint32_t so0 = tq * step_bytes, so1 = noise_bytes + so0, so2 = noise_bytes + so1;
+            auto ldq = [&](uint32_t so) -> float {
+              return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rn, loff + (uint32_t)i * step_bytes, so, 0));
+            };
+            nq[3 * i + 0] = ldq(so0);
+            nq[3 * i + 1] = ldq(so1);
+            nq[3 * i + 2] = ldq(so2);
+          } else {
+            nq[3 * i + 0] = ld(0, t + 4);
+            nq[3 * i + 1] = ld(1, t + 4);
+            nq[3 * i + 2] = ld(2, t + 4);
+          }
         }
         cq[3 * i] = cq[3 * i + 1] = cq[3 * i + 2] = 0.f;
         if (QUADS || t < T)
@@ -554,12 +588,63 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
 #endif
       }
     };
+    // (the horizons known at compile time only: with this form of the loops the whole-quads
+    // instance spills 12 bytes to scratch and the ragged GoalAngle instance with cost powers 4.7 KB)
+    constexpr bool kPairLoops = LANE_X_PRIO_ITER && (FULL || TC != 0);
+    if constexpr (kPairLoops) {
+    // Two quads per loop iteration, by hand, the odd one behind its loop: the first quad of an
+    // iteration swaps the priority, the second does not.  Steps [0, 32) park into the <..>0 tuples,
+    // [32, 64) into <..>1, element t % 32; the re-read form parks nothing (the controls are formed
+    // again from the noise once the weights are known).
+    // (macros, not lambdas: behind lambdas the main instance spills 640 bytes to scratch)
+#if LANE_X_PARK_STEP
+#define LANE_PARK_QUAD(HI, Q)
+#else
+#define LANE_PARK_QUAD(HI, Q) \
+      if constexpr (!RR) { \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i) { \
+          if constexpr (HI) { \
+            PX1[8 * i + ((Q) - 8)] = cq[3 * i]; \
+            PY1[8 * i + ((Q) - 8)] = cq[3 * i + 1]; \
+          } else { \
+            PX0[8 * i + (Q)] = cq[3 * i]; \
+            PY0[8 * i + (Q)] = cq[3 * i + 1]; \
+          } \
+          park[(4 * (Q) + i) * LANE_PARK_STRIDE + lane] = cq[3 * i + 2]; \
+        } \
+      }
+#endif
+#define LANE_QUAD(HI, SWAP, Q) \
+    { \
+      float cq[12]; \
+      run_quad(std::bool_constant<HI>{}, std::bool_constant<SWAP>{}, (Q), cq); \
+      LANE_PARK_QUAD(HI, Q) \
+    }
+#define LANE_QUADS(HI, Q0, QE)   /* quads [Q0, QE) */ \
+    { \
+      uint32_t q = (Q0); \
+      const uint32_t qe = (QE); \
+      for (; q + 1 < qe; q += 2) { \
+        LANE_QUAD(HI, true, q) \
+        LANE_QUAD(HI, false, q + 1) \
+      } \
+      if (q < qe) LANE_QUAD(HI, true, q) \
+    }
     if constexpr (RR) {
+      LANE_QUADS(false, 0u, nquad)
+    } else {
+      LANE_QUADS(false, 0u, nquad < 8u ? nquad : 8u)
+      LANE_QUADS(true, 8u, nquad)
+    }
+#undef LANE_QUADS
+#undef LANE_QUAD
+#undef LANE_PARK_QUAD
+    } else if constexpr (RR) {
       // nothing is parked: the controls are formed again from the noise once the weights are known
 #pragma unroll 2
       for (uint32_t q = 0; q < nquad; ++q) {
         float cq[12];
-        run_quad(std::false_type{}, q, cq);
+        run_quad(F_{}, T_{}, q, cq);
       }
     } else {
       // steps [0, 32) park into the <..>0 tuples, [32, 64) into <..>1, element t % 32
@@ -567,7 +652,7 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
       if constexpr (QUADS && !FULL && TC == 0) {
         auto quad_lo = [&](const uint32_t q) {
           float cq[12];
-          run_quad(std::false_type{}, q, cq);
+          run_quad(F_{}, T_{}, q, cq);
 #if !LANE_X_PARK_STEP
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
@@ -579,7 +664,7 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
         };
         auto quad_hi = [&](const uint32_t q) {
           float cq[12];
-          run_quad(std::true_type{}, q, cq);
+          run_quad(T_{}, T_{}, q, cq);
 #if !LANE_X_PARK_STEP
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
@@ -610,7 +695,7 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
 #pragma unroll 2
         for (uint32_t q = 0; q < qh; ++q) {
           float cq[12];
-          run_quad(std::false_type{}, q, cq);
+          run_quad(F_{}, T_{}, q, cq);
 #if !LANE_X_PARK_STEP
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
@@ -623,7 +708,7 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
 #pragma unroll 2
         for (uint32_t q = 8; q < nquad; ++q) {
           float cq[12];
-          run_quad(std::true_type{}, q, cq);
+          run_quad(T_{}, T_{}, q, cq);
 #if !LANE_X_PARK_STEP
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
@@ -912,7 +997,7 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
   stamp(2);
   int stamp_k = 3;
   for (uint32_t grp = gw; grp < ngroups; grp += nW) {
-    if (__builtin_expect(group_body(std::false_type{}, grp), 0)) group_body(std::true_type{}, grp);
+    if (__builtin_expect(group_body(F_{}, grp), 0)) group_body(T_{}, grp);
     if (stamp_k < 5) stamp(stamp_k++);
   }
 
