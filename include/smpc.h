@@ -437,6 +437,15 @@ int smpc_get_costs(smpc_ctx* ctx, float* costs);
  * ref src/optimizer.cpp:326-329), evaluated on n host values; tests pin its error. */
 int smpc_selftest_sincos(smpc_ctx* ctx, const float* x, uint32_t n, float* sin_out,
                          float* cos_out);
+/* Diagnostics: the device Philox4x32-10 of the noise generator on n caller-given counters
+ * ctr[4n] under one key; out[4n] are the four words of each block.  Tests compare them with
+ * the published known answers and an integer model, bit for bit. */
+int smpc_selftest_philox(smpc_ctx* ctx, const uint32_t* ctr, const uint32_t key[2], uint32_t n,
+                         uint32_t* out);
+/* Diagnostics: the device Box-Muller of the noise generator on n pairs of Philox words:
+ * z0 = radius cos, z1 = radius sin of N(0, 1), before the multiplication by a std. */
+int smpc_selftest_box_muller(smpc_ctx* ctx, const uint32_t* r0, const uint32_t* r1, uint32_t n,
+                             float* z0, float* z1);
 /* Diagnostics: the in-register 64 x 64 transpose-reduce of the lane-per-rollout pass
  * (updateControlSequence's weighted sum, ref src/optimizer.cpp:382-393):
  * out[t] = sum_b w[b] * v[b*64 + t], b, t = 0..63. */

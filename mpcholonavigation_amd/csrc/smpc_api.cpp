@@ -1198,6 +1198,43 @@ int smpc_selftest_sincos(smpc_ctx* c, const float* x, uint32_t n, float* sin_out
   return SMPC_OK;
 }
 
+int smpc_selftest_philox(smpc_ctx* c, const uint32_t* ctr, const uint32_t* key, uint32_t n, uint32_t* out)
+{
+  if (!c || !ctr || !key || !out || n == 0 || n > (1u << 26)) return fail(c, SMPC_ERR_INVALID, "bad argument");
+  HIPCK(c, hipSetDevice(c->device));
+  const size_t bytes = static_cast<size_t>(n) * 4 * sizeof(uint32_t);
+  uint32_t *dc = nullptr, *dout = nullptr;
+  HIPCK(c, hipMalloc(&dc, bytes));
+  HIPCK(c, hipMalloc(&dout, bytes));
+  HIPCK(c, hipMemcpyAsync(dc, ctr, bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCK(c, smpc_launch_philox(dc, key[0], key[1], n, dout, c->stream));
+  HIPCK(c, hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCK(c, hipStreamSynchronize(c->stream));
+  (void)hipFree(dc); (void)hipFree(dout);
+  return SMPC_OK;
+}
+
+int smpc_selftest_box_muller(smpc_ctx* c, const uint32_t* r0, const uint32_t* r1, uint32_t n, float* z0, float* z1)
+{
+  if (!c || !r0 || !r1 || !z0 || !z1 || n == 0 || n > (1u << 26)) return fail(c, SMPC_ERR_INVALID, "bad argument");
+  HIPCK(c, hipSetDevice(c->device));
+  const size_t bytes = static_cast<size_t>(n) * sizeof(uint32_t);
+  uint32_t *d0 = nullptr, *d1 = nullptr;
+  float *dz0 = nullptr, *dz1 = nullptr;
+  HIPCK(c, hipMalloc(&d0, bytes));
+  HIPCK(c, hipMalloc(&d1, bytes));
+  HIPCK(c, hipMalloc(&dz0, bytes));
+  HIPCK(c, hipMalloc(&dz1, bytes));
+  HIPCK(c, hipMemcpyAsync(d0, r0, bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCK(c, hipMemcpyAsync(d1, r1, bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCK(c, smpc_launch_box_muller(d0, d1, n, dz0, dz1, c->stream));
+  HIPCK(c, hipMemcpyAsync(z0, dz0, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCK(c, hipMemcpyAsync(z1, dz1, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCK(c, hipStreamSynchronize(c->stream));
+  (void)hipFree(d0); (void)hipFree(d1); (void)hipFree(dz0); (void)hipFree(dz1);
+  return SMPC_OK;
+}
+
 int smpc_selftest_lane_reduce(smpc_ctx* c, const float* v, const float* w, float* out)
 {
   if (!c || !v || !w || !out) return fail(c, SMPC_ERR_INVALID, "null argument");

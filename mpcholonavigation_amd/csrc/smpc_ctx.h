@@ -59,6 +59,10 @@ uint32_t smpc_split_block();
 uint32_t smpc_split_rollouts_per_block(uint32_t nseg);
 hipError_t smpc_launch_reduce_many(const SmpcReduceArgs* d_many, uint32_t n, uint32_t T, hipStream_t st);
 hipError_t smpc_launch_sincos(const float* x, uint32_t n, float* sn, float* cs, hipStream_t st);
+hipError_t smpc_launch_philox(const uint32_t* ctr, uint32_t k0, uint32_t k1, uint32_t n, uint32_t* out,
+                              hipStream_t st);
+hipError_t smpc_launch_box_muller(const uint32_t* r0, const uint32_t* r1, uint32_t n, float* z0, float* z1,
+                                  hipStream_t st);
 
 namespace smpc_impl {
 

@@ -1510,10 +1510,13 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
 }
 
 // Box–Muller on one pair of Philox words: {radius cos, radius sin} of N(0, 1).  The hardware's
-// log2 and square root (1 ulp) and the rollout's own sin/cos (absolute error 1.3e-7): the normals
-// stay within 1e-6 of the CPU twin's libm evaluation (tests: test_device_rng_matches_cpu_twin),
-// at a third of the instructions of logf / sincosf — with regenerate_noises the draw is 3 x B x T
-// normals per tick.
+// log2 and square root (1 ulp) and the rollout's own sin/cos (absolute error 1.3e-7): a normal
+// of radius r = sqrt(-2 ln u1) lies within 4.5e-7 r of the float64 evaluation of the same u1 and
+// float angle (measured: 2.3e-7 r at most, 9.6e-7 absolute at r = 5.1; r <= 5.887; the hardware
+// log2 keeps its relative accuracy up to u1 = 1 - 2^-24, and u1 = 1 gives exactly 0) — tests:
+// test_gpu_noise_stream.py::test_device_box_muller_against_float64 through smpc_selftest_box_muller
+// — at a third of the instructions of logf / sincosf: with regenerate_noises the draw is
+// 3 x B x T normals per tick.
 __device__ __forceinline__ void box_muller(uint32_t r0, uint32_t r1, float& z0, float& z1)
 {
   const float u1 = ((float)(r0 >> 8) + 0.5f) * (1.0f / 16777216.0f);
@@ -1593,6 +1596,47 @@ __global__ void smpc_sincos_kernel(const float* __restrict__ x, uint32_t n,
 hipError_t smpc_launch_sincos(const float* x, uint32_t n, float* sn, float* cs, hipStream_t st)
 {
   hipLaunchKernelGGL(smpc_sincos_kernel, dim3((n + 255) / 256), dim3(256), 0, st, x, n, sn, cs);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Self-test hooks: the noise fills' own philox4x32_10 and box_muller on caller data.
+// ---------------------------------------------------------------------------
+__global__ void smpc_philox_kernel(const uint32_t* __restrict__ ctr, uint32_t k0, uint32_t k1, uint32_t n,
+                                   uint32_t* __restrict__ out)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    uint32_t r[4];
+    philox4x32_10(ctr[4 * i], ctr[4 * i + 1], ctr[4 * i + 2], ctr[4 * i + 3], k0, k1, r);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) out[4 * i + k] = r[k];
+  }
+}
+
+__global__ void smpc_box_muller_kernel(const uint32_t* __restrict__ r0, const uint32_t* __restrict__ r1,
+                                       uint32_t n, float* __restrict__ z0, float* __restrict__ z1)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    float a, b;
+    box_muller(r0[i], r1[i], a, b);
+    z0[i] = a;
+    z1[i] = b;
+  }
+}
+
+hipError_t smpc_launch_philox(const uint32_t* ctr, uint32_t k0, uint32_t k1, uint32_t n, uint32_t* out,
+                              hipStream_t st)
+{
+  hipLaunchKernelGGL(smpc_philox_kernel, dim3((n + 255) / 256), dim3(256), 0, st, ctr, k0, k1, n, out);
+  return hipGetLastError();
+}
+
+hipError_t smpc_launch_box_muller(const uint32_t* r0, const uint32_t* r1, uint32_t n, float* z0, float* z1,
+                                  hipStream_t st)
+{
+  hipLaunchKernelGGL(smpc_box_muller_kernel, dim3((n + 255) / 256), dim3(256), 0, st, r0, r1, n, z0, z1);
   return hipGetLastError();
 }
 

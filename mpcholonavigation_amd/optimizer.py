@@ -177,6 +177,24 @@ class Smpc:
         self._ck(self.lib.smpc_selftest_sincos(self.h, _ptr(x), x.size, _ptr(s), _ptr(c)))
         return s, c
 
+    def selftest_philox(self, ctr, key):
+        """The noise generator's Philox4x32-10: ctr uint32 [n, 4], key (k0, k1) -> uint32 [n, 4]."""
+        ctr = np.ascontiguousarray(ctr, dtype=np.uint32).reshape(-1, 4)
+        key = np.ascontiguousarray(key, dtype=np.uint32).reshape(2)
+        out = np.empty_like(ctr)
+        self._ck(self.lib.smpc_selftest_philox(self.h, _ptr(ctr), _ptr(key), ctr.shape[0], _ptr(out)))
+        return out
+
+    def selftest_box_muller(self, r0, r1):
+        """The noise generator's Box-Muller on pairs of Philox words -> (radius cos, radius sin)."""
+        r0 = np.ascontiguousarray(r0, dtype=np.uint32).reshape(-1)
+        r1 = np.ascontiguousarray(r1, dtype=np.uint32).reshape(-1)
+        if r0.shape != r1.shape:
+            raise ValueError("one second word per first word")
+        z0, z1 = np.empty(r0.size, np.float32), np.empty(r0.size, np.float32)
+        self._ck(self.lib.smpc_selftest_box_muller(self.h, _ptr(r0), _ptr(r1), r0.size, _ptr(z0), _ptr(z1)))
+        return z0, z1
+
     def selftest_lane_reduce(self, v, w):
         """out[t] = sum_b w[b] v[b, t] through the lane pass's in-register transpose-reduce."""
         v = np.ascontiguousarray(v, dtype=np.float32).reshape(64, 64)

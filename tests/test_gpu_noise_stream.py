@@ -1,0 +1,268 @@
+"""The device noise generator (smpc_fill_noise, smpc_fill_noise_tm, box_muller, philox4x32_10)
+against its specification, tests/noise_model.py: integer Philox pinned by the published known
+answers, Box-Muller in float64.  The hooks run the very device functions the fills call; the
+tensors come through smpc_seed / smpc_get_noise.
+
+Tolerances (derived, not tuned):
+  hook    |z - model| <= 4.5e-7 radius: hardware log2 and sqrt at 1 ulp each with the float
+          multiply in between (radius within 2.1e-7 relative), the device sin/cos at its asserted
+          1.5e-7 absolute, the final product's 2^-24;
+  tensor  |n - sigma model| <= sigma 6e-7 radius: the hook bound plus 2 * 2^-24 |z| for the
+          multiplication by sigma and the division that undoes it.
+"""
+import numpy as np
+import pytest
+
+from mpcholonavigation_amd import _abi as A
+from mpcholonavigation_amd.synthetic import make_scenario
+from mpcholonavigation_amd.tick import default_config
+from tests import noise_model as nm
+from tests.helpers import configure
+
+pytestmark = pytest.mark.gpu
+
+LANE = A.SMPC_FLAG_LANE_PER_ROLLOUT
+
+
+@pytest.fixture(scope="module")
+def Smpc():
+    from mpcholonavigation_amd.optimizer import Smpc as S
+    return S
+
+
+@pytest.fixture(scope="module")
+def hook(Smpc):
+    g = Smpc(default_config(batch_size=64, time_steps=8))
+    yield g
+    g.close()
+
+
+def _cfg(B, T, flags=0, off=0, **kw):
+    return default_config(batch_size=B, time_steps=T, flags=flags, shard_offset=off, global_batch_size=off + B,
+                          **nm.STDS, **kw)
+
+
+# ---- hooks -----------------------------------------------------------------------------------
+
+def test_device_philox_is_philox4x32_10(hook):
+    """The fills' philox4x32_10, exact integers: the published known answers, 65 536 random
+    counters under each of 4 random keys, every counter word at 0, 1, 0x7fffffff, 0x80000000 and
+    0xffffffff, and the counters around q = 2^32 that a shard at offset 2^28 reaches."""
+    for ctr, key, expect in nm.KNOWN_ANSWERS:
+        assert hook.selftest_philox(np.array([ctr], np.uint32), key).tolist() == [list(expect)]
+    rng = np.random.default_rng(2024)
+    for _ in range(4):
+        key = rng.integers(0, 2**32, 2, dtype=np.uint64)
+        ctr = rng.integers(0, 2**32, (65536, 4), dtype=np.uint64).astype(np.uint32)
+        assert np.array_equal(hook.selftest_philox(ctr, key), nm.philox4x32_10(ctr, key))
+    edges = (0, 1, 0x7FFFFFFF, 0x80000000, 0xFFFFFFFF)
+    rows = []
+    for fill in [np.zeros(4, np.uint64), np.full(4, 0xFFFFFFFF, np.uint64)] + [rng.integers(0, 2**32, 4, dtype=np.uint64)
+                                                                               for _ in range(14)]:
+        for word in range(4):
+            for v in edges:
+                c = fill.copy()
+                c[word] = v
+                rows.append(c)
+    q = np.arange(2**32 - 64, 2**32 + 64, dtype=np.uint64)            # the straddle, as the fills split q
+    for stream, epoch in ((0, 0), (1, 3), (2, 0xFFFFFFFF)):
+        rows += list(np.stack([q & np.uint64(0xFFFFFFFF), q >> np.uint64(32), np.full_like(q, stream),
+                               np.full_like(q, epoch)], axis=1))
+    ctr = np.array(rows, np.uint64).astype(np.uint32)
+    for key in ((0, 0), (0xFFFFFFFF, 0xFFFFFFFF), (2024, 5), (0x80000000, 0x7FFFFFFF)):
+        assert np.array_equal(hook.selftest_philox(ctr, key), nm.philox4x32_10(ctr, key)), key
+
+
+def test_device_box_muller_against_float64(hook):
+    """The fills' box_muller on the directed table (u1 at 2^-25, around 0.5, just below 1 and
+    exactly 1; angles at and next to multiples of pi/2 and 2 pi; both values of the discarded
+    low byte) and on 2^20 random word pairs, against the float64 model: within 4.5e-7 radius,
+    finite, exactly zero at u1 == 1, never beyond the largest radius, the low byte ignored.
+
+    Measured on MI355X: largest |delta| / radius 2.24e-7 (k1 979 283, radius 2.38), largest |delta|
+    9.62e-7 (k1 38, radius 5.10); for u1 > 0.5 2.00e-7 radius, for u1 > 1 - 2^-12 1.38e-7 radius: the
+    hardware log2 keeps its relative accuracy up to u1 = 1."""
+    r0, r1, k1, k2 = nm.edge_words()
+    n = r0.size // 2
+    rng = np.random.default_rng(7)
+    x0 = rng.integers(0, 2**32, 2**20, dtype=np.uint64).astype(np.uint32)
+    x1 = rng.integers(0, 2**32, 2**20, dtype=np.uint64).astype(np.uint32)
+    a0, a1 = np.concatenate([r0, x0]), np.concatenate([r1, x1])
+    ka = np.concatenate([k1, (x0 >> np.uint32(8)).astype(np.int64)])
+    z0, z1 = hook.selftest_box_muller(a0, a1)
+    zc, zs, radius = nm.normals64(a0, a1)
+    ar = np.abs(radius)
+    d = np.maximum(np.abs(z0.astype(np.float64) - zc), np.abs(z1.astype(np.float64) - zs))
+    rel = np.where(ar > 0, d / np.maximum(ar, 1e-300), 0.0)
+    i, j = int(np.argmax(d)), int(np.argmax(rel))
+    print(f"[noise] box_muller hook, {a0.size} pairs: max |delta| {d[i]:.3e} at k1 {ka[i]} (radius {ar[i]:.4f}); "
+          f"max |delta|/radius {rel[j]:.3e} at k1 {ka[j]} (radius {ar[j]:.3e})")
+    for lo, hi, name in ((0, 2**23, "u1 <= 0.5"), (2**23, 2**24 - 4096, "0.5 < u1"), (2**24 - 4096, 2**24, "u1 > 1 - 2^-12")):
+        m = (ka >= lo) & (ka < hi)
+        print(f"[noise]   {name}: max |delta|/radius {rel[m].max():.3e}, max |delta| {d[m].max():.3e}")
+    m = ka == 0
+    print(f"[noise]   u1 = 2^-25 (radius {ar[m].max():.5f}): max |delta| {d[m].max():.3e}")
+    assert np.all(np.isfinite(z0)) and np.all(np.isfinite(z1))
+    one = ka == 2**24 - 1
+    assert one.any() and np.all(z0[one] == 0.0) and np.all(z1[one] == 0.0)
+    assert max(np.abs(z0).max(), np.abs(z1).max()) <= nm.MAX_RADIUS
+    for z in (z0, z1):
+        assert np.array_equal(z[:n].view(np.uint32), z[n:2 * n].view(np.uint32)), "the discarded low byte changed a sample"
+    bad = d > nm.HOOK_RTOL * ar
+    assert not bad.any(), (f"{np.count_nonzero(bad)} pairs beyond {nm.HOOK_RTOL} radius; worst |delta|/radius {rel[j]:.3e} "
+                           f"at k1 {ka[j]}, radius {ar[j]:.3e}")
+
+
+# ---- tensors through smpc_seed / smpc_get_noise ----------------------------------------------
+
+def _all_seeds(Smpc, cfg, label, holonomic=True):
+    """One context through the three seeds: every tensor on the model; returns the tensors."""
+    g = Smpc(cfg)
+    drawn, worst = [], nm.NO_ERROR
+    for seed in nm.SEEDS:
+        g.seed(seed)
+        noise = g.get_noise()
+        worst = nm.merge(worst, nm.check_noise(noise, cfg, seed, 0, label=f"{label} seed {seed:#x}", holonomic=holonomic))
+        drawn.append(noise)
+    g.close()
+    nm.report(label, worst)
+    # the high key word is used: seeds 2024 and (5 << 32) | 2024 differ only there
+    assert not np.array_equal(drawn[0][0], drawn[1][0]) and not np.array_equal(drawn[0][2], drawn[1][2])
+    return drawn
+
+
+@pytest.mark.parametrize("B,T", nm.SHAPES_LANE)
+def test_lane_flag_noise_is_the_model_on_both_fills(Smpc, monkeypatch, B, T):
+    """A lane-per-rollout context draws group-major (smpc_fill_noise_tm); with SMPC_NO_FUSED_FILL
+    it fills [B, T] and transposes.  Both are the model's stream, and bit for bit each other's."""
+    monkeypatch.delenv("SMPC_NO_FUSED_FILL", raising=False)
+    fused = _all_seeds(Smpc, _cfg(B, T, LANE), f"{B}x{T} lane fused")
+    monkeypatch.setenv("SMPC_NO_FUSED_FILL", "1")
+    plain = _all_seeds(Smpc, _cfg(B, T, LANE), f"{B}x{T} lane plain")
+    for f, p in zip(fused, plain):
+        for a, b in zip(f, p):
+            assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+@pytest.mark.parametrize("B,T", nm.SHAPES_LANE + nm.SHAPES_PLAIN)
+def test_default_flags_noise_is_the_model(Smpc, monkeypatch, B, T):
+    """flags 0 (smpc_fill_noise into [B, T]); T = 33 and 30 take that fill whatever the flags."""
+    monkeypatch.delenv("SMPC_NO_FUSED_FILL", raising=False)
+    _all_seeds(Smpc, _cfg(B, T), f"{B}x{T} flags 0")
+
+
+@pytest.mark.parametrize("B,T,flags", [(64, 30, 0), (100, 64, LANE), (100, 64, 0)])
+def test_epochs_by_reset_redraw_and_background_redraw(Smpc, monkeypatch, B, T, flags):
+    """Epoch 0 after seed, +1 by reset(), by redraw_noise() and by redraw_noise_async() once a
+    tick has taken the draw; the default scene at the smallest shapes the suite ticks."""
+    monkeypatch.delenv("SMPC_NO_FUSED_FILL", raising=False)
+    cfg = _cfg(B, T, flags)
+    scn = make_scenario(T)
+    g = Smpc(cfg)
+    configure(g, scn)
+    seed = nm.SEEDS[1]
+    g.seed(seed)
+    label = f"{B}x{T} flags {flags:#x}"
+    worst = nm.check_noise(g.get_noise(), cfg, seed, 0, label=f"{label} epoch 0")
+    g.reset()
+    worst = nm.merge(worst, nm.check_noise(g.get_noise(), cfg, seed, 1, label=f"{label} epoch 1 (reset)"))
+    g.redraw_noise()
+    worst = nm.merge(worst, nm.check_noise(g.get_noise(), cfg, seed, 2, label=f"{label} epoch 2 (redraw)"))
+    g.redraw_noise_async()
+    nm.check_noise(g.get_noise(), cfg, seed, 2, label=f"{label} epoch 2 (draw pending)")
+    g.optimize(scn.tick, scn.u0)
+    worst = nm.merge(worst, nm.check_noise(g.get_noise(), cfg, seed, 3, label=f"{label} epoch 3 (background redraw)"))
+    g.seed(seed)
+    nm.check_noise(g.get_noise(), cfg, seed, 0, label=f"{label} epoch 0 again")
+    g.close()
+    nm.report(label + " epochs 0-3", worst)
+
+
+@pytest.mark.parametrize("flags", [0, LANE])
+@pytest.mark.parametrize("B,T,off", nm.SHARDS)
+def test_shards_draw_their_part_of_the_global_stream(Smpc, monkeypatch, B, T, off, flags):
+    """shard_offset 67 with T = 33: a base that is no multiple of four.  Offsets 2^28 and 2^28 - 3
+    with T = 64: block counters at and across q = 2^32, the high counter word and the 64-bit
+    element index of both fills."""
+    monkeypatch.delenv("SMPC_NO_FUSED_FILL", raising=False)
+    cfg = _cfg(B, T, flags, off)
+    seed = nm.SEEDS[0]
+    g = Smpc(cfg)
+    g.seed(seed)
+    label = f"{B}x{T} shard at {off} flags {flags:#x}"
+    worst = nm.check_noise(g.get_noise(), cfg, seed, 0, label=label)
+    g.reset()
+    worst = nm.merge(worst, nm.check_noise(g.get_noise(), cfg, seed, 1, label=label + " epoch 1"))
+    g.close()
+    nm.report(label, worst)
+
+
+@pytest.mark.parametrize("flags", [0, LANE])
+@pytest.mark.parametrize("model", [A.SMPC_MODEL_DIFF_DRIVE, A.SMPC_MODEL_ACKERMANN])
+def test_non_holonomic_models_keep_vy_zero(Smpc, monkeypatch, model, flags):
+    """DiffDrive and Ackermann: vy all zero; vx and wz still streams 0 and 1."""
+    monkeypatch.delenv("SMPC_NO_FUSED_FILL", raising=False)
+    _all_seeds(Smpc, _cfg(257, 60, flags, motion_model=model), f"257x60 model {model} flags {flags:#x}", holonomic=False)
+
+
+@pytest.mark.parametrize("B,T", [(257, 60), (4099, 64)])
+def test_drawn_noise_scores_like_the_same_noise_given(Smpc, monkeypatch, B, T):
+    """A lane-per-rollout context that drew its noise group-major and one handed the same tensors
+    through smpc_set_noise: ticks of the default scene bit for bit alike, u and costs."""
+    monkeypatch.delenv("SMPC_NO_FUSED_FILL", raising=False)
+    cfg = _cfg(B, T, LANE)
+    scn = make_scenario(T)
+    drew = Smpc(cfg)
+    configure(drew, scn)
+    drew.seed(nm.SEEDS[0])
+    given = Smpc(cfg)
+    configure(given, scn, noise=drew.get_noise())
+    ud = ug = scn.u0
+    for k in range(2):                       # the second tick speculates: the lane pass proper
+        ud, od = drew.optimize(scn.tick, ud)
+        ug, og = given.optimize(scn.tick, ug)
+        assert np.array_equal(ud.view(np.uint32), ug.view(np.uint32)), k
+        assert np.array_equal(drew.get_costs().view(np.uint32), given.get_costs().view(np.uint32)), k
+        assert od.pass_kind == og.pass_kind and od.min_cost == og.min_cost
+    assert od.pass_kind == 1
+    drew.close()
+    given.close()
+
+
+# ---- distribution ----------------------------------------------------------------------------
+
+def test_distribution_of_the_drawn_noise(Smpc, monkeypatch):
+    """65 536 x 64 per tensor, seeds 2024 and (5 << 32) | 2024: moments, lag-1 products along t
+    and along b, tail counts, chi-square over 64 equiprobable bins, and the product means between
+    tensors, epochs and seeds, each in its own standard errors.  Caps: |statistic| < 5, chi2(63)
+    < 130 (upper tail ~1e-6), max |z| <= 5.8871.  test_noise_stream_cpu.py asserts the same
+    caps on the model for the same seeds; a sample within 3e-6 of the model moves no statistic
+    by more than 0.01 standard errors.
+
+    Measured on MI355X: every standard-error statistic within +-2.61 (kurtosis of wz under the
+    second seed), chi2 51.8 .. 74.1, max |z| 4.92 .. 5.57, cross products within +-1.05: the
+    model's own figures to the second decimal."""
+    monkeypatch.delenv("SMPC_NO_FUSED_FILL", raising=False)
+    B, T = nm.STAT_SHAPE
+    cfg = _cfg(B, T, LANE)
+    g = Smpc(cfg)
+    sig = (cfg.vx_std, cfg.vy_std, cfg.wz_std)
+    z = {}
+    for seed in nm.STAT_SEEDS:
+        g.seed(seed)
+        z[seed] = [n.astype(np.float64) / s for n, s in zip(g.get_noise(), sig)]      # vx, vy, wz
+        for name, x in zip(("vx", "vy", "wz"), z[seed]):
+            st = nm.statistics(x)
+            print(f"[noise] device seed {seed:#x} {name}: " + " ".join(f"{k} {v:+.2f}" for k, v in st.items()))
+            nm.assert_caps(st, f"seed {seed:#x} {name}")
+    a, b = nm.STAT_SEEDS
+    g.seed(a)
+    g.redraw_noise()
+    vx1 = g.get_noise()[0].astype(np.float64) / sig[0]
+    g.close()
+    cr = {"vx.wz": nm.cross(z[a][0], z[a][2]), "vx.vy": nm.cross(z[a][0], z[a][1]),
+          "vx.wz (2nd seed)": nm.cross(z[b][0], z[b][2]), "vx.vy (2nd seed)": nm.cross(z[b][0], z[b][1]),
+          "epoch 0.1": nm.cross(z[a][0], vx1), "seed.seed": nm.cross(z[a][0], z[b][0])}
+    print("[noise] device cross products: " + " ".join(f"{k} {v:+.2f}" for k, v in cr.items()))
+    for k, v in cr.items():
+        assert abs(v) < nm.SE_CAP, f"{k}: {v} standard errors"
