@@ -19,9 +19,13 @@
 // propagation, clip, shift, speed limit, setOffset, GoalAngle 9.42,
 // PreferForward 15.0, PathFollow 750, PathAlign 6600 / blocked 0, furthest and
 // initial path point = 5, path validity, tolerance gate, angle range).
+// The softmax update (update_control_sequence, apply_constraints), for which
+// the reference asserts no value, is pinned by a float64 model of its formula
+// written from the reference's source: tests/test_softmax_update_cpu.py
+// (tests/softmax_model.py), within 4 units of the last place.
 // UNPINNED (no value assertion exists in the reference): ObstaclesCritic
-// arithmetic, the softmax update, Savitzky-Golay edge handling, the noise
-// stream.  Those follow the reference source literally.
+// arithmetic, Savitzky-Golay edge handling, the noise stream.  Those follow
+// the reference source literally.
 //
 // Third-party arithmetic that is not under /root/reference is restated from
 // its published behaviour: nav2_costmap_2d (ROS 2 Humble, Nav2 1.1.x)

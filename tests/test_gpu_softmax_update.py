@@ -1,0 +1,274 @@
+"""The softmax control update on the device, judged by the float64 model of tests/softmax_model.py.
+
+Every case: one tick, get_costs() (what the update consumed, gamma terms included), the pinned
+kernel name and pass_kind, then u, min_cost and sum_w against the judge on the device's OWN costs.
+The bar is (ceil(log2 B) + 3 A + 12) units per entry (derived in tests/softmax_model.py), or the
+float-summing oracle's own error on that entry where that is larger (up to 70 001 rollouts);
+min_cost must equal min(costs).  No flip budget, no conditioning term: the judge and the device
+start from the same costs.
+
+Which branch of reduce_partials_body (smpc_kernels.hip) a case reaches, from plan_launch
+(smpc_prepare.cpp) on 256 CUs: every case, and every tick the library can run there, takes the
+first branch, nblk <= 512 (sixteen rows per slice held in registers).  A pass is a persistent grid
+of at most the blocks that stay resident, and no instance keeps more than one block per CU:
+  * wave R = 1 and R = 2: blocks of 16 waves; 128 registers are four waves per SIMD, one block per
+    CU: min(ceil(B / 16), 256) blocks (63 at 1000 rollouts, 125 at 2000, 33 at 513, 1, 2 and 5 at
+    1, 17 and 65);
+  * wave R = 4: blocks of eight waves.  By its launch bounds (512 threads, two blocks per CU) and
+    its LDS it could have up to four per CU, 1024 blocks, and 6000 x 200 asks for 750; but the
+    instance takes 248 registers, two waves per SIMD, one block per CU: 256 blocks.  The case is
+    kept for R = 4's own block combine over eight waves and a persistent loop of three rounds;
+  * lane, parking form: four-wave blocks while there are at most 1024 groups (16 blocks at 4096
+    rollouts, 17 at 4100, 241 at 61 441), eight-wave blocks above (137 at 70 001); re-read form:
+    eight-wave blocks, one per CU (136 registers): 9 blocks at 4100 and 256 at 196 700, the
+    largest grid the lane pass has.  No batch gives it more than 512 blocks; the large case is kept
+    for its 3074 groups on 2048 waves, a persistent loop with a ragged second round (the test takes
+    under a second);
+  * split: one block per CU, 128 (four segments) or 256 (two) rollouts each: 128 blocks at
+    16 384 x 64, 8 at 1000, 129 at 16 400, 64 with two segments.
+So the g >= 512 column loop and the second header slot (nblk > 1024) of reduce_partials_body are
+not reachable on this device; the code is left as it is (a device with more CUs, or an instance
+with fewer registers, reaches them).
+
+Shards: G = 3 contexts on 3001 rollouts cut at 1000 and 1937, each through smpc_shard_score, the
+tuples combined on the device (combine_tuples_body); costs are each shard's get_costs() after
+shard_score (the pass writes them exactly as in a whole tick).  Groups: three members with
+temperatures 0.3, 0.05 and 0.01 in one smpc_group_optimize; the second tick is judged (the first has
+no furthest-point prediction and re-scores every member alone).
+
+Every test prints its largest error in units, per row.
+"""
+import ctypes
+
+import numpy as np
+import pytest
+
+from mpcholonavigation_amd.synthetic import make_scenario
+from mpcholonavigation_amd.tick import default_config
+from tests import softmax_model as sm
+
+pytestmark = pytest.mark.gpu
+
+TABLE = [c for c in sm.CASES if c.path not in ("shards", "group")]
+SHARDS = [c for c in sm.CASES if c.path == "shards"]
+GROUP = [c for c in sm.CASES if c.path == "group"]
+FLOOR_MAX_B = 70001
+
+
+@pytest.fixture(scope="module")
+def Smpc():
+    from oracle import loader
+    from mpcholonavigation_amd.optimizer import Smpc as S
+    loader.build()
+    return S
+
+
+def last_kernel(g):
+    f = g.lib.smpc_debug_last_pass_kernel
+    f.restype, f.argtypes = ctypes.c_char_p, []
+    return f().decode()
+
+
+def create(Smpc, monkeypatch, case, cfg):
+    for k, v in case.env:
+        monkeypatch.setenv(k, v)          # (the knobs are read when the context is created)
+    g = Smpc(cfg)
+    for k, _ in case.env:
+        monkeypatch.delenv(k)
+    return g
+
+
+def tick(Smpc, monkeypatch, bt, u_in=None, **cfg_kw):
+    """One tick of a fresh context: (u, out, costs, kernel)."""
+    g = create(Smpc, monkeypatch, bt.case, bt.config(**cfg_kw))
+    bt.configure(g)
+    u, out = g.optimize(bt.scn.tick, bt.u0 if u_in is None else u_in)
+    costs, kernel = g.get_costs(), last_kernel(g)
+    g.close()
+    return u, out, costs, kernel
+
+
+def floors(case):
+    """The float-summing oracle's own error against the judge (on the oracle's costs): per entry of
+    u, and of sum_w in units."""
+    if case.device_noise or case.B > FLOOR_MAX_B:
+        return None, 0.0
+    _, res = sm.reference(case.name)
+    r = res[False]
+    return (np.abs(r["u"].astype(np.float64) - r["m"].u),
+            abs(r["out"].sum_w - r["m"].sum_w) / (sm.EPS * r["m"].sum_w))
+
+
+def report(case, m, j, out, extra=""):
+    print(f"[softmax-gpu] {case.name} ({case.path}): vx {j['units'][0]:.2f} vy {j['units'][1]:.2f} wz {j['units'][2]:.2f} "
+          f"sum_w {j['sum_w_units']:.2f} units, bar {j['bar']:.1f}; sum_w {m.sum_w:.6g} A {m.A:.3f} "
+          f"non_colliding {out.non_colliding} fail_flag {out.fail_flag}{extra}")
+
+
+@pytest.mark.parametrize("case", TABLE, ids=[c.name for c in TABLE])
+def test_update_against_the_judge(Smpc, monkeypatch, case):
+    if case.device_noise:
+        return device_noise_case(Smpc, monkeypatch, case)
+    bt = sm.build(case)
+    u_in = bt.u0
+    if case.iterations == 2:      # u_1 from a one-iteration context on the same inputs (the kernels are deterministic)
+        u_in, _, _, _ = tick(Smpc, monkeypatch, bt, iteration_count=1)
+    u, out, costs, kernel = tick(Smpc, monkeypatch, bt)
+    assert (out.pass_kind, kernel) == (case.kind, case.kernel), case.name
+    m = sm.update(costs, u_in, bt.noise, bt.cfg, bt.constraints, case.model)
+    floor, floor_sw = floors(case)
+    j = sm.judge(m, case.B, u, out.min_cost, out.sum_w, floor=floor, floor_sum_w=floor_sw, label=case.name)
+    report(case, m, j, out)
+    assert out.fail_flag == (1 if case.all_lethal else 0)
+
+
+def device_noise_case(Smpc, monkeypatch, case):
+    """The largest lane grid: noise drawn on the device and read back, the judge in chunks."""
+    cfg = default_config(batch_size=case.B, time_steps=case.T, temperature=case.temperature, gamma=case.gamma,
+                         flags=case.flags)
+    scn = make_scenario(case.T)
+    g = create(Smpc, monkeypatch, case, cfg)
+    g.set_critics(sm.critics_of(case))
+    g.set_costmap(scn.cells, scn.origin_x, scn.origin_y, scn.resolution, inscribed_radius=scn.inscribed_radius,
+                  cost_scaling_factor=scn.cost_scaling_factor, inflation_radius=scn.inflation_radius)
+    g.seed(0x5EED)
+    noise = g.get_noise()
+    u0 = sm.warm_start(case.T, (0.3, 0.02, 0.05))
+    u, out = g.optimize(scn.tick, u0)
+    costs, kernel = g.get_costs(), last_kernel(g)
+    g.close()
+    assert (out.pass_kind, kernel) == (case.kind, case.kernel), case.name
+    m = sm.update(costs, u0, noise, cfg, (cfg.vx_max, cfg.vx_min, cfg.vy_max, cfg.wz_max), case.model)
+    j = sm.judge(m, case.B, u, out.min_cost, out.sum_w, label=case.name)
+    report(case, m, j, out)
+
+
+@pytest.mark.parametrize("case", SHARDS, ids=[c.name for c in SHARDS])
+def test_shards_against_the_judge(Smpc, monkeypatch, case):
+    import torch
+    bt = sm.build(case)
+    cuts = case.cuts
+    G = len(cuts) - 1
+    shards = []
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        g = Smpc(bt.config(batch_size=b - a, shard_offset=a, global_batch_size=case.B))
+        bt.configure(g, [n[a:b] for n in bt.noise])
+        shards.append(g)
+    dev = torch.device("cuda", 0)
+    L = shards[0].tuple_len
+    t_f = torch.zeros(G, dtype=torch.float32, device=dev)
+    t_all = torch.zeros(G * L, dtype=torch.float32, device=dev)
+    stream = torch.cuda.current_stream().cuda_stream
+    for s in shards:
+        s.set_stream(stream)
+        s.shard_begin(bt.scn.tick, bt.u0)
+    for i, s in enumerate(shards):
+        s.shard_furthest(t_f[i:].data_ptr())
+    t_max = t_f.max().reshape(1).contiguous()         # stands in for all_reduce(MAX)
+    for i, s in enumerate(shards):
+        s.shard_score(t_max.data_ptr(), 0, t_all[i * L:].data_ptr())
+    u, out = shards[0].shard_combine(t_all.data_ptr(), G)
+    costs = np.concatenate([s.get_costs() for s in shards])
+    tuples = t_all.cpu().numpy().reshape(G, L)
+    kernels = [last_kernel(s) for s in shards]
+    for s in shards:
+        s.close()
+    assert set(kernels) == {case.kernel}
+    # each shard's tuple carries the minimum of its own costs: what combine_tuples_body rescales by
+    mins = [float(costs[a:b].min()) for a, b in zip(cuts[:-1], cuts[1:])]
+    assert [float(t[0]) for t in tuples] == mins
+    assert int(np.argmin(mins)) == G - 1, "the best rollout is in the last shard"
+    if case.collide_rows:
+        assert mins[1] > 1e5 and float(tuples[1][3]) == 0.0, "one whole shard collides"
+    m = sm.update(costs, bt.u0, bt.noise, bt.cfg, bt.constraints, case.model)
+    floor, floor_sw = floors(case)
+    j = sm.judge(m, case.B, u, out.min_cost, out.sum_w, floor=floor, floor_sum_w=floor_sw, label=case.name)
+    report(case, m, j, out, extra=f" shard minima {mins}")
+
+
+def test_group_against_the_judge(Smpc):
+    """smpc_reduce_partials_many: one neg_inv_temp per member."""
+    from mpcholonavigation_amd.optimizer import SmpcGroup
+    built = [sm.build(c) for c in GROUP]
+    members = []
+    for bt in built:
+        g = Smpc(bt.config())
+        bt.configure(g)
+        members.append(g)
+    grp = SmpcGroup(members)
+    ticks, us = [bt.scn.tick for bt in built], [bt.u0 for bt in built]
+    grp.optimize(ticks, us)                       # no prediction yet: every member is re-scored alone
+    res = grp.optimize(ticks, us)                 # the same inputs again: the batched launch stands
+    kernel = last_kernel(members[0])
+    costs = [g.get_costs() for g in members]
+    grp.close()
+    for g in members:
+        g.close()
+    assert kernel == GROUP[0].kernel
+    for bt, (u, out), c in zip(built, res, costs):
+        case = bt.case
+        assert out.pass_kind == case.kind
+        m = sm.update(c, bt.u0, bt.noise, bt.cfg, bt.constraints, case.model)
+        floor, floor_sw = floors(case)
+        j = sm.judge(m, case.B, u, out.min_cost, out.sum_w, floor=floor, floor_sum_w=floor_sw, label=case.name)
+        report(case, m, j, out)
+
+
+UC_FORM = ("lane", "split")      # paths whose gamma sums are sum u c - sum u^2 (see gamma_uc_bound)
+
+
+@pytest.mark.parametrize("gamma", sm.GAMMAS)
+@pytest.mark.parametrize("name,warm", sm.GAMMA_CASES, ids=[f"{n}-vx{w[0]}-wz{w[2]}" for n, w in sm.GAMMA_CASES])
+def test_gamma_terms_on_the_device(Smpc, monkeypatch, name, warm, gamma):
+    """costs(gamma) - costs(0) of two contexts on the same tick against gamma_terms.  The bar: four
+    times the oracle's largest error against the model on the same inputs (four: a summation order
+    other than the oracle's sequential one), at least 4 ulp of the cost.
+
+    The lane and the split pass exceed that bar, and that is a finding, not noise: they form the
+    sums as sum u c - sum u^2, whose running sums reach T |u| |c|.  Measured, in ulp
+    of the cost, device / oracle / that bar: lane 4096 x 64, default warm start, gamma 0.015:
+    5.7 / 1.9 / 7.8, gamma 0.1: 26 / 3.0 / 12; warm start (0.5, 0.02, 1.5), gamma 0.015: 24 / 2.6 /
+    11, gamma 0.1: 157 / 11 / 46; split 16 384 x 64, warm start (0.5, 0.02, 1.5), gamma 0.1: 67 / 14 /
+    57 (its other three inside the bar).  The form stays (the lane pass's time loop has no register
+    and no instruction to spare: c - u as its own operation is three more per step, the noise
+    itself as the factor spills), so on these two paths the bar is the worst case of the form's own
+    float32 arithmetic, softmax_model.gamma_uc_bound, plus the three additions into the cost —
+    where that is the larger of the two.  What the excess does to the update is measured with the
+    judge at temperature 0.05 and printed: the control sequence from the device's costs against the
+    one from costs(0) + the float64 gamma terms."""
+    bt = sm.build(sm.BY_NAME[name], warm)
+    case = bt.case
+    cfg_g = bt.config(gamma=gamma)
+    model = sm.gamma_terms(bt.u0, bt.noise, cfg_g, case.model)
+
+    def ulp_of(c0, cg):
+        return np.spacing(np.maximum(np.abs(cg), np.abs(c0)).astype(np.float32)).astype(np.float64)
+
+    def error(c0, cg):
+        return np.abs((cg.astype(np.float64) - c0.astype(np.float64)) - model) / ulp_of(c0, cg)
+    _, _, o0 = sm.run_oracle(bt, False, gamma=0.0)
+    _, _, og = sm.run_oracle(bt, False, gamma=gamma)
+    e_oracle = float(error(o0, og).max())
+    _, out0, c0, k0 = tick(Smpc, monkeypatch, bt, gamma=0.0)
+    _, outg, cg, kg = tick(Smpc, monkeypatch, bt, gamma=gamma)
+    assert (outg.pass_kind, kg) == (out0.pass_kind, k0) == (case.kind, case.kernel)
+    e = error(c0, cg)
+    bar = np.full(case.B, max(4.0, 4.0 * e_oracle))
+    if case.path in UC_FORM:
+        bar = np.maximum(bar, 1.5 + sm.gamma_uc_bound(bt.u0, bt.noise, cfg_g, case.model) / ulp_of(c0, cg))
+    own = f", worst case of the form {bar.min():.0f} .. {bar.max():.0f}" if case.path in UC_FORM else ""
+    print(f"[softmax-gpu] gamma {gamma} {name} warm {warm}: device {e.max():.2f} ulp of the cost (rollout "
+          f"{int(e.argmax())}), oracle {e_oracle:.2f}, bar {max(4.0, 4.0 * e_oracle):.2f}{own}; "
+          f"term {model.min():.4g} .. {model.max():.4g}")
+    if case.path in UC_FORM:
+        # the same costs under a sharp softmax: temperature enters the update only
+        cfg_s = bt.config(gamma=gamma, temperature=0.05)
+        c_fix = (c0.astype(np.float64) + model).astype(np.float32)
+        m_dev = sm.update(cg, bt.u0, bt.noise, cfg_s, bt.constraints, case.model)
+        m_fix = sm.update(c_fix, bt.u0, bt.noise, cfg_s, bt.constraints, case.model)
+        d = np.abs(m_dev.u - m_fix.u)
+        print(f"[softmax-gpu] gamma {gamma} {name} warm {warm}: at temperature 0.05 (sum_w {m_fix.sum_w:.3g}) the form "
+              f"moves the Twist by vx {d[0, 1]:.2e} vy {d[1, 1]:.2e} wz {d[2, 1]:.2e} "
+              f"({(d[:, 1] / np.maximum(np.abs(m_fix.u[:, 1]), 1e-30)).max():.1e} relative; "
+              f"{(d / m_fix.unit).max():.1f} units at the worst entry of the sequence)")
+    assert np.all(e <= bar), (name, warm, gamma, float(np.max(e / bar)))
