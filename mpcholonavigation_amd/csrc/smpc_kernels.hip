@@ -49,7 +49,6 @@ __device__ __forceinline__ uint32_t dpp_u(uint32_t old, uint32_t v)
 // 16-lane DPP rows, then row_bcast:15 / :31 carry the row totals.  Written as one asm
 // block so that every step is a single v_add_f32_dpp (hipcc leaves the two broadcast steps
 // as mov + add + re-zeroing) and the VALU-write -> DPP-read wait states are explicit.
-#define SCAN_STEP1(op, ctl) op " %0, %0, %0 " ctl "\n\t"
 __device__ __forceinline__ float wave_scan_add(float v)
 {
   asm volatile(
@@ -104,21 +103,6 @@ __device__ __forceinline__ double wave_sum_d(double v)
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
   return v;
-}
-__device__ __forceinline__ uint32_t wave_min_u(uint32_t v)
-{
-  v = min(v, dpp_u<0x111>(0xffffffffu, v));
-  v = min(v, dpp_u<0x112>(0xffffffffu, v));
-  v = min(v, dpp_u<0x114>(0xffffffffu, v));
-  v = min(v, dpp_u<0x118>(0xffffffffu, v));
-  v = min(v, dpp_u<0x142, 0xA>(0xffffffffu, v));
-  v = min(v, dpp_u<0x143, 0xC>(0xffffffffu, v));
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-// min of non-negative floats: unsigned min of the bit patterns (one v_min_u32_dpp per step)
-__device__ __forceinline__ float wave_min_nonneg(float v)
-{
-  return __uint_as_float(wave_min_u(__float_as_uint(v)));
 }
 // shr1(src) + addend in ONE instruction: lane l gets src[l-1] + addend[l], lane 0 gets
 // 0 + addend[0] (bound_ctrl).  With addend = {first, 0, 0, ...} it is the reference's

@@ -43,55 +43,13 @@
 #ifndef WAVE
 #define WAVE 64
 #endif
-#ifndef LANE_X_RR_NOLOAD
-#define LANE_X_RR_NOLOAD 0   // timing experiment: the re-read form without its second read (wrong results)
-#endif
 #define LANE_BLOCK 512   // 8 waves: 2 per SIMD, 256 registers each
-#ifndef LANE_BLOCK_RR
 // the re-read instances: 8 waves, one block per CU like the parking form.  (First built with 4
 // waves and three blocks per CU: 136 registers allow three waves per SIMD.  The pass is
 // VALU-bound either way, three blocks stage three copies of the window, and 4096 groups on 3072
 // waves leave a ragged second round: 262 144 x 128 the same within noise, 131 072 x 128: 86 -> 78 us,
 // 70 000 x 128: 73 -> 67 us.)
 #define LANE_BLOCK_RR 512
-#endif
-
-// experiment switches (tools/variants.sh builds the library with some of them off)
-#ifndef LANE_X_GAMMA_N
-#define LANE_X_GAMMA_N 0     // gamma terms from the noise itself instead of c - u (measured: the noise
-                             // registers' longer life breaks the four-step prefetch, +35 % at 2 M rollouts)
-#endif
-#ifndef LANE_X_GAMMA_UC
-#define LANE_X_GAMMA_UC 1    // gamma terms as sum u c - sum u^2 (one fma per control and step; the constant from LDS)
-#endif
-#ifndef LANE_X_FURTHEST_WINDOW
-#define LANE_X_FURTHEST_WINDOW 1   // the endpoint's nearest-path-point scan from three blocks below the scored index up, the rest verified for the wave's winner
-#endif
-#ifndef LANE_X_PFW_MIN
-#define LANE_X_PFW_MIN 1     // PreferForward as -dt sum min(vx, 0)
-#endif
-#ifndef LANE_X_CELL_AX
-#define LANE_X_CELL_AX 1     // cell index from the accumulated displacement (no double add per step)
-#endif
-#ifndef LANE_X_PIN_LDS
-#define LANE_X_PIN_LDS 0     // lookup pipeline as inline-asm LDS reads at the end of the step
-#endif
-#ifndef LANE_X_PARK_STEP
-#define LANE_X_PARK_STEP 0   // park the noised controls step by step instead of quad by quad
-#endif
-#ifndef LANE_X_CONST_VGPR
-#define LANE_X_CONST_VGPR 0  // the cell index's loop constants in vector registers
-#endif
-
-#ifndef LANE_X_PFW_BARE
-#define LANE_X_PFW_BARE 1    // PreferForward's min(vx, 0) as the bare v_min_f32 (no canonicalising v_max in front)
-#endif
-#ifndef LANE_X_NOISE_QUAD
-#define LANE_X_NOISE_QUAD 1  // noise prefetch: one scalar offset per tensor and quad, the step inside the quad in the vector offset
-#endif
-#ifndef LANE_X_PRIO_ITER
-#define LANE_X_PRIO_ITER 1   // priority swap once per loop iteration (two quads), one branch
-#endif
 
 // ---------------------------------------------------------------------------
 // [B][T] row-major <-> group-major (SMPC_GM_INDEX, smpc_dev.h): one-off, after the noise is supplied
@@ -167,7 +125,8 @@ hipError_t smpc_launch_lane_reduce(const float* v, const float* w, float* out, h
 // registers the transpose-reduce consumes — and forms c = u + n again (the same single rounding).
 // The second read comes seconds of microseconds after the first: from the Infinity Cache, not
 // from HBM.  Without the 128 parked registers and the per-wave LDS slot a lane needs ~1/2 of
-// the register file's per-wave share: 256-thread blocks, three per CU (three waves per SIMD).
+// the register file's per-wave share, but the blocks are the parking form's all the same:
+// LANE_BLOCK_RR = 512 threads, one block per CU (see there for what three smaller blocks cost).
 // The only form for T > 64 (3 T parked values per lane do not fit any register budget).
 #define LANE_PASS_KERNEL smpc_pass_lane
 #define LANE_PASS_POW false

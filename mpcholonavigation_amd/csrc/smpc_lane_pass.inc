@@ -12,7 +12,7 @@
 // compiled to before (a body shared through a __forceinline__ function kept their register counts
 // but not their instructions).
 template <bool FULL, bool OBST, bool MANY, int NCH, bool RR, bool GA = false, bool QUADS = FULL, int TC = 0, bool DEP = false>
-__global__ void __launch_bounds__(RR ? LANE_BLOCK_RR : LANE_BLOCK, (RR && LANE_BLOCK_RR == 256) ? 3 : 1)
+__global__ void __launch_bounds__(RR ? LANE_BLOCK_RR : LANE_BLOCK, 1)
 LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ many)
 {
   constexpr bool POW = LANE_PASS_POW;
@@ -122,7 +122,6 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
       if (seg_on) s_D[tid] = g_D;
       s_pts4[tid] = f32x4{g_px, g_py, g_valid ? 1.0f : 0.f, 0.f};
     }
-#if LANE_X_GAMMA_UC
     if (tid < WAVE) {   // (one wave: lane t squares u[.][t], then a butterfly)
       float a = 0.f, b = 0.f, c = 0.f;
       const uint32_t Tn = FULL ? 64u * NCH : (TC ? (uint32_t)TC : p.T);
@@ -143,7 +142,6 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
         s_su2[2] = c;
       }
     }
-#endif
     for (uint32_t i = tid + blk; i < p.P; i += blk) {   // paths beyond one point per thread
       const float qx = tk.px[i], qy = tk.py[i];
       const bool seg = i + 1 < p.P;
@@ -249,41 +247,26 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
     // entry) feeding an in-order accumulation.  It runs as a pipeline two steps deep whose three
     // stages all sit at the END of a step, behind one wait: accumulate the entry of step t - 2,
     // issue the table read for the byte of step t - 1, issue the byte read of step t's own cell —
-    // every read has had a whole step to land, so the wait is free.  The reads are inline
-    // assembly (the wait too: the compiler's own waitcnt pass does not see them), which pins
-    // their place in the step; left to the scheduler the byte read sinks to just in front of
-    // its use and every step waits out an LDS round trip.  Primed with the all-zero table
+    // every read has had a whole step to land, so the wait is free.  The reads are plain C++
+    // loads carried from one step to the next in cell_q and e_q: the compiler's scheduler places
+    // them and its waitcnt pass their waits.  (Pinning their place in the step with
+    // inline-assembly reads and a hand-placed wait, which the waitcnt pass does not see, was
+    // tried and rejected: neutral on its own, DESIGN.md 4.2.)  Primed with the all-zero table
     // entry 256; drained after the loop.
     uint32_t cell_q = 256u;
     f32x2 e_q = {0.f, 0.f};   // {crit, rep} of SmpcLut
-    [[maybe_unused]] const uint32_t lds_lut = (uint32_t)(uintptr_t)s_lut, lds_map = (uint32_t)(uintptr_t)s_map;   // (LANE_X_PIN_LDS)
-    auto lookup_wait = [&]() {   // both reads of the previous step have landed
-#if LANE_X_PIN_LDS
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(cell_q), "+v"(e_q));
-#endif
-    };
+    auto lookup_wait = [&]() {};   // (empty on purpose: without it and its calls some instances' instructions reorder)
     auto lookup_accumulate = [&]() {
       // steps after the first collision are never visited in the reference (masked)
       alive = e_q.x < 0.f ? 0.f : alive;   // inCollision
       crit = fmaf(alive, e_q.x, crit);
       rep = fmaf(alive, e_q.y, rep);
     };
-#if LANE_X_PIN_LDS
     auto lookup_issue_entry = [&]() {          // e_q <- s_lut[cell_q]
-      const uint32_t a = lds_lut + (cell_q << 3);
-      asm volatile("ds_read_b64 %0, %1" : "=v"(e_q) : "v"(a));
-    };
-    auto lookup_issue_byte = [&](uint32_t idx) {   // cell_q <- s_map[idx]
-      const uint32_t a = lds_map + idx;
-      asm volatile("ds_read_u8 %0, %1" : "=v"(cell_q) : "v"(a));
-    };
-#else
-    auto lookup_issue_entry = [&]() {
       const SmpcLut e = s_lut[cell_q];
       e_q = f32x2{e.crit, e.rep};
     };
-    auto lookup_issue_byte = [&](uint32_t idx) {cell_q = s_map[idx];};
-#endif
+    auto lookup_issue_byte = [&](uint32_t idx) {cell_q = s_map[idx];};   // cell_q <- s_map[idx]
     float pfw = 0.f, gx = 0.f, gy = 0.f, gz = 0.f;
     float ga_sum = 0.f;   // GoalAngleCritic: sum over the steps of |shortest angular distance to the goal's yaw|
     float ext = 0.f;      // DEP: ConstraintCritic + TwirlingCritic, weights and 1/T folded in
@@ -292,13 +275,10 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
     float traj_dist = 0.f, pa_sum = 0.f, pa_num = 0.f, sx_prev = p.x00f, sy_prev = p.y00f;
     uint32_t path_pt = 0;
 
-    // loop constants of the cell index, in vector registers: a scalar operand halves the issue
-    // rate of the instruction that reads it (tools/ubench)
-#if LANE_X_CONST_VGPR
-    const float k_rinv = in_vgpr(p.rinvf), k_cx = in_vgpr(p.cxf), k_cy = in_vgpr(p.cyf);
-#else
+    // loop constants of the cell index, in scalar registers.  (A scalar operand halves the issue
+    // rate of the instruction that reads it, tools/ubench; held in vector registers instead they
+    // push the parking form into scratch, 514.5 against 380.0 us at 2 097 152 x 64: DESIGN.md 4.2.)
     const float k_rinv = p.rinvf, k_cx = p.cxf, k_cy = p.cyf;
-#endif
     const float k_edge = 0.5f - p.cell_eps_w;
     // one time step for the 64 rollouts of this wave; t, ux, uy, uz are wave-uniform
     // sample_slot: this step is a multiple of four (known at compile time in the unrolled quad)
@@ -363,13 +343,7 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
       // the sin/cos below.
       uint32_t idx = 0;
       if (OBST) {
-#if LANE_X_CELL_AX
         const float qx = fmaf(ax, k_rinv, k_cx), qy = fmaf(ay, k_rinv, k_cy);
-#else
-        x = (float)(x0 + (double)ax);
-        y = (float)(y0 + (double)ay);
-        const float qx = (x - p.wxf) * p.rinvf, qy = (y - p.wyf) * p.rinvf;
-#endif
         const float rx = __builtin_amdgcn_fractf(qx), ry = __builtin_amdgcn_fractf(qy);
         const int lx = cvt_floor_i32(qx), ly = cvt_floor_i32(qy);
         // guard band as ONE compare: both fractions at least eps away from a cell edge <=>
@@ -395,34 +369,21 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
         smpc_sincos_fast(yaw, sn_prev, cs_prev);
       }
       // PreferForwardCritic (prefer_forward_critic.cpp:42-46): sum_t max(-vx, 0) dt, here as
-      // -dt sum_t min(vx, 0) — the factor once per rollout instead of once per step
-#if LANE_X_PFW_MIN && LANE_X_PFW_BARE
+      // -dt sum_t min(vx, 0) — the factor once per rollout instead of once per step; minimum and
+      // sum in one statement (add_min_zero: the bare v_min_f32, no canonicalising v_max in front)
       pfw = add_min_zero(pfw, vx);
-#elif LANE_X_PFW_MIN
-      pfw = pfw + fminf(vx, 0.f);
-#else
-      pfw = fmaf(fmaxf(-vx, 0.f), dt, pfw);
-#endif
-      // updateControlSequence gamma terms (optimizer.cpp:365-380): sum_t u (c - u).  c - u is
-      // the noise up to the rounding of c = u + n (|c - u - n| <= ulp(c) / 2: a few 1e-8 on
-      // terms that gamma / sigma^2 scales to ~1e-7 of a cost): the noise itself is used
-#if LANE_X_GAMMA_UC
-      // ... as sum_t u c - sum_t u^2: one fused multiply-add per control here, the constant
+      // updateControlSequence gamma terms (optimizer.cpp:365-380): sum_t u (c - u), here
+      // as sum_t u c - sum_t u^2: one fused multiply-add per control here, the constant
       // (s_su2, formed once per launch) subtracted once per rollout.  Half the instructions of
       // u (c - u); the running sums reach T |u| |c| instead of staying near zero, which is ~1e-6
       // absolute on a cost after the gamma / sigma^2 scaling (costs are compared at 2e-4).
+      // (c - u is the noise up to the rounding of c = u + n, |c - u - n| <= ulp(c) / 2: a few 1e-8
+      // on terms that gamma / sigma^2 scales to ~1e-7 of a cost.  The noise itself as the factor,
+      // sum_t u n, is not used: the noise registers' longer life breaks the four-step prefetch,
+      // +35 % at 2 M rollouts.)
       gx = fmaf(ux, cvx, gx);
       gz = fmaf(uz, cwz, gz);
       gy = fmaf(uy, cvy, gy);
-#elif LANE_X_GAMMA_N
-      gx = fmaf(ux, n0, gx);
-      gz = fmaf(uz, n2, gz);
-      gy = fmaf(uy, n1, gy);
-#else
-      gx = fmaf(ux, cvx - ux, gx);
-      gz = fmaf(uz, cwz - uz, gz);
-      gy = fmaf(uy, cvy - uy, gy);
-#endif
 
       // PathAlignCritic sample (uniform in t): trajectory points step, 2 step, ...
       // (trajectory_point_step is 4 here, the reference's default — the host sends any other
@@ -503,11 +464,12 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
       for (int k = 0; k < 3; ++k) uq[3 * i + k] = ldu(k, i);
     }
     uint64_t clk = __builtin_amdgcn_s_memtime();
-    // four steps; each parks its noised controls at once (LANE_X_PARK_STEP) or the quad returns
-    // them in cq[3 i + ctrl] for the caller to park
+    // four steps; the quad returns their noised controls in cq[3 i + ctrl] for the caller to park
+    // (parking step by step inside the quad was tried: the parked tuples fall out of registers)
     // swap_c: this quad looks at the clock and sets the wave's priority
+    // hi_c: steps [32, 64); not read (the caller parks), kept because without it the instances'
+    // scalar register assignment changes
     auto run_quad = [&](auto hi_c, auto swap_c, const uint32_t q, float (&cq)[12]) __attribute__((always_inline)) {
-      [[maybe_unused]] constexpr bool HI = decltype(hi_c)::value;
       constexpr bool SWAP = decltype(swap_c)::value;
       // The two waves of a SIMD do not share it evenly by themselves: the older one wins every
       // tie and finishes its groups ~25 % sooner (41 us against 51 us for two groups), then the
@@ -515,17 +477,12 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
       // read a quad earlier: the same for both whatever their progress, in anti-phase between
       // waves w and w + 4 — lets both finish together at 47 us (measured: tools/lane_timeline.py;
       // shorter periods share less evenly, 2^12: 45 / 48 us).
-      // LANE_X_PRIO_ITER: once per loop iteration, two quads or ~6 000 clocks of the period's 32 768,
-      // and as "low, then high if the bit says so": one branch over one instruction where the
-      // if / else compiled to two branches and a mask.
+      // Once per loop iteration where the loops are pairs of quads (kPairLoops: two quads or
+      // ~6 000 clocks of the period's 32 768), and as "low, then high if the bit says so": one
+      // branch over one instruction where the if / else compiled to two branches and a mask.
       if constexpr (SWAP) {
-#if LANE_X_PRIO_ITER
         __builtin_amdgcn_s_setprio(0);
         if (((uint32_t)(clk >> 15) + (uint32_t)(wave >> 2)) & 1u) __builtin_amdgcn_s_setprio(1);
-#else
-        if (((uint32_t)(clk >> 15) + (uint32_t)(wave >> 2)) & 1u) __builtin_amdgcn_s_setprio(1);
-        else __builtin_amdgcn_s_setprio(0);
-#endif
         clk = __builtin_amdgcn_s_memtime();
       }
       float uc[12];
@@ -542,13 +499,13 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
 #pragma unroll
           for (int k = 0; k < 3; ++k) uq[3 * i + k] = ldu(k, 4 * (q + 1) + i);
       }
-      // LANE_X_NOISE_QUAD (whole quads): one scalar offset per tensor and QUAD — the next quad's first
+      // kQuadOff (whole quads): one scalar offset per tensor and QUAD — the next quad's first
       // step, clamped to the last quad where the fetch is unconditional — instead of three scalar
       // instructions per step; the step inside the quad, 0 / 256 / 512 / 768 bytes, is added to the
       // lane's offset.  (Meant for the load's immediate offset; the compiler hoists the four sums
       // out of the loop instead, three more vector registers.  The plain instances have them: the
       // GoalAngle, deployed-list, grouped and cost-power ones spill 12-20 bytes to scratch with it.)
-      constexpr bool kQuadOff = LANE_X_NOISE_QUAD && QUADS && !GA && !DEP && !MANY && !POW;
+      constexpr bool kQuadOff = QUADS && !GA && !DEP && !MANY && !POW;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const uint32_t t = 4 * q + i;
@@ -574,32 +531,15 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
         if (QUADS || t < T)
           do_step(t, i == 0, uc[3 * i], uc[3 * i + 1], uc[3 * i + 2], n0, n1, n2, cq[3 * i], cq[3 * i + 1],
                   cq[3 * i + 2]);
-#if LANE_X_PARK_STEP
-        // park this step's controls now: three values live per step instead of twelve per quad
-        if constexpr (RR) {
-        } else if constexpr (HI) {
-          PX1[8 * i + (q - 8)] = cq[3 * i];
-          PY1[8 * i + (q - 8)] = cq[3 * i + 1];
-        } else {
-          PX0[8 * i + q] = cq[3 * i];
-          PY0[8 * i + q] = cq[3 * i + 1];
-        }
-        if constexpr (!RR) park[(4 * q + i) * LANE_PARK_STRIDE + lane] = cq[3 * i + 2];
-#endif
       }
     };
     // (the horizons known at compile time only: with this form of the loops the whole-quads
     // instance spills 12 bytes to scratch and the ragged GoalAngle instance with cost powers 4.7 KB)
-    constexpr bool kPairLoops = LANE_X_PRIO_ITER && (FULL || TC != 0);
-    if constexpr (kPairLoops) {
-    // Two quads per loop iteration, by hand, the odd one behind its loop: the first quad of an
-    // iteration swaps the priority, the second does not.  Steps [0, 32) park into the <..>0 tuples,
-    // [32, 64) into <..>1, element t % 32; the re-read form parks nothing (the controls are formed
-    // again from the noise once the weights are known).
-    // (macros, not lambdas: behind lambdas the main instance spills 640 bytes to scratch)
-#if LANE_X_PARK_STEP
-#define LANE_PARK_QUAD(HI, Q)
-#else
+    constexpr bool kPairLoops = FULL || TC != 0;
+    // Park the quad cq came from: steps [0, 32) into the <..>0 tuples, [32, 64) into <..>1, element
+    // t % 32; the re-read form parks nothing (the controls are formed again from the noise once the
+    // weights are known).
+    // (a macro, not a lambda: behind lambdas the main instance spills 640 bytes to scratch)
 #define LANE_PARK_QUAD(HI, Q) \
       if constexpr (!RR) { \
         _Pragma("unroll") for (int i = 0; i < 4; ++i) { \
@@ -613,7 +553,10 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
           park[(4 * (Q) + i) * LANE_PARK_STRIDE + lane] = cq[3 * i + 2]; \
         } \
       }
-#endif
+    if constexpr (kPairLoops) {
+    // Two quads per loop iteration, by hand, the odd one behind its loop: the first quad of an
+    // iteration swaps the priority, the second does not.
+    // (macros, not lambdas: see LANE_PARK_QUAD)
 #define LANE_QUAD(HI, SWAP, Q) \
     { \
       float cq[12]; \
@@ -638,7 +581,6 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
     }
 #undef LANE_QUADS
 #undef LANE_QUAD
-#undef LANE_PARK_QUAD
     } else if constexpr (RR) {
       // nothing is parked: the controls are formed again from the noise once the weights are known
 #pragma unroll 2
@@ -647,32 +589,17 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
         run_quad(F_{}, T_{}, q, cq);
       }
     } else {
-      // steps [0, 32) park into the <..>0 tuples, [32, 64) into <..>1, element t % 32
       const uint32_t qh = nquad < 8u ? nquad : 8u;
       if constexpr (QUADS && !FULL && TC == 0) {
         auto quad_lo = [&](const uint32_t q) {
           float cq[12];
           run_quad(F_{}, T_{}, q, cq);
-#if !LANE_X_PARK_STEP
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            PX0[8 * i + q] = cq[3 * i];
-            PY0[8 * i + q] = cq[3 * i + 1];
-            park[(4 * q + i) * LANE_PARK_STRIDE + lane] = cq[3 * i + 2];
-          }
-#endif
+          LANE_PARK_QUAD(false, q)
         };
         auto quad_hi = [&](const uint32_t q) {
           float cq[12];
           run_quad(T_{}, T_{}, q, cq);
-#if !LANE_X_PARK_STEP
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            PX1[8 * i + (q - 8)] = cq[3 * i];
-            PY1[8 * i + (q - 8)] = cq[3 * i + 1];
-            park[(4 * q + i) * LANE_PARK_STRIDE + lane] = cq[3 * i + 2];
-          }
-#endif
+          LANE_PARK_QUAD(true, q)
         };
         // two quads per iteration by hand: with a run-time trip count "#pragma unroll 2" is not
         // honoured here, and one quad per iteration leaves the scheduler nothing to overlap
@@ -696,30 +623,17 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
         for (uint32_t q = 0; q < qh; ++q) {
           float cq[12];
           run_quad(F_{}, T_{}, q, cq);
-#if !LANE_X_PARK_STEP
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            PX0[8 * i + q] = cq[3 * i];
-            PY0[8 * i + q] = cq[3 * i + 1];
-            park[(4 * q + i) * LANE_PARK_STRIDE + lane] = cq[3 * i + 2];
-          }
-#endif
+          LANE_PARK_QUAD(false, q)
         }
 #pragma unroll 2
         for (uint32_t q = 8; q < nquad; ++q) {
           float cq[12];
           run_quad(T_{}, T_{}, q, cq);
-#if !LANE_X_PARK_STEP
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            PX1[8 * i + (q - 8)] = cq[3 * i];
-            PY1[8 * i + (q - 8)] = cq[3 * i + 1];
-            park[(4 * q + i) * LANE_PARK_STRIDE + lane] = cq[3 * i + 2];
-          }
-#endif
+          LANE_PARK_QUAD(true, q)
         }
       }
     }
+#undef LANE_PARK_QUAD
     if (OBST) {   // drain the lookup pipeline: the entries of the last two steps
       lookup_wait();
       lookup_accumulate();
@@ -760,7 +674,7 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
       // checked for the ONE lane that ends up holding the wave's maximum (below).  (The plain
       // instances only: in the GoalAngle, deployed-list and grouped ones the extra code costs
       // 16-48 bytes of scratch.)
-      constexpr bool kWindow = LANE_X_FURTHEST_WINDOW && !GA && !DEP && !MANY;
+      constexpr bool kWindow = !GA && !DEP && !MANY;
       const uint32_t j_lo = (kWindow && (S >> 2) > 3u) ? ((S >> 2) - 3u) << 2 : 0u;
       for (uint32_t j = j_lo; j < P4; j += 4) {
         float dd[4];
@@ -856,20 +770,10 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
         const double Td = (FULL || TC) ? (double)T : (double)in_vgpr((float)T);
         cost = add_cost_pow(cost, (double)ga_sum / Td * (double)in_vgpr(p.ga_weight), p.ga_power);
       }
-#if LANE_X_PFW_MIN
       if (p.flags & SD_PREFER_FORWARD) cost = add_cost_pow(cost, (double)((pfw * -dt) * p.pfw_weight), p.pfw_power);
-#else
-      if (p.flags & SD_PREFER_FORWARD) cost = add_cost_pow(cost, (double)(pfw * p.pfw_weight), p.pfw_power);
-#endif
-#if LANE_X_GAMMA_UC
       cost += p.g_vx * (gx - s_su2[0]);
       cost += p.g_wz * (gz - s_su2[2]);
       cost += p.g_vy * (gy - s_su2[1]);
-#else
-      cost += p.g_vx * gx;
-      cost += p.g_wz * gz;
-      cost += p.g_vy * gy;
-#endif
     } else {
       // costs (every cost_power == 1): the lean association of smpc_pass MODE 0
       float lin = 0.f, uni = 0.f;
@@ -892,21 +796,11 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
         const float fdx = x - pf_x, fdy = y - pf_y;
         uni += p.pf_weight * fast_sqrt(fdx * fdx + fdy * fdy);
       }
-#if LANE_X_PFW_MIN
       if (p.flags & SD_PREFER_FORWARD) lin += (pfw * -dt) * p.pfw_weight;
-#else
-      if (p.flags & SD_PREFER_FORWARD) lin += pfw * p.pfw_weight;
-#endif
       if (ga_on) uni += (ga_sum / (float)T) * p.ga_weight;
-#if LANE_X_GAMMA_UC
       lin += p.g_vx * (gx - s_su2[0]);
       lin += p.g_wz * (gz - s_su2[2]);
       lin += p.g_vy * (gy - s_su2[1]);
-#else
-      lin += p.g_vx * gx;
-      lin += p.g_wz * gz;
-      lin += p.g_vy * gy;
-#endif
       cost += uni + lin;
       if (pa_on) {
         const float c_pa = pa_num > 0.f ? pa_sum * fast_rcp(pa_num) : 0.f;
@@ -939,7 +833,7 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
           // with its add and waits for each in turn: 192 memory round trips per group)
           float V[64];
 #pragma unroll
-          for (int t = 0; t < 64; ++t) V[t] = LANE_X_RR_NOLOAD ? (float)t : ld(ctrl, 64u * h + t);
+          for (int t = 0; t < 64; ++t) V[t] = ld(ctrl, 64u * h + t);
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int t = 0; t < 64; ++t) {

@@ -193,7 +193,7 @@ def gamma_magnitude(u_in, noise, cfg, model=OMNI):
 
 def gamma_uc_bound(u_in, noise, cfg, model=OMNI):
     """Worst case of the lane and split passes' form of the gamma sums, sum_t u c - sum_t u^2
-    (smpc_lane_pass.inc LANE_X_GAMMA_UC, smpc_split.hip): one fused multiply-add per control and
+    (smpc_lane_pass.inc s_su2, smpc_split.hip): one fused multiply-add per control and
     step, the constant subtracted once per rollout.  Each of the T fused multiply-adds rounds a
     partial sum no larger than sum_t |u c|, the T terms of sum u^2 likewise, then the difference
     and the product with gamma / std^2: (T + 2) roundings of 2^-24 on sum |u c| + sum u^2 per

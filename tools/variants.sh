@@ -1,7 +1,10 @@
 #!/bin/bash
-# Developer tool: build variants of libsmpc.so that differ in experiment switches of the lane pass
-# (smpc_lane.hip LANE_X_*, smpc_device_math.h SMPC_X_*), side by side under
-# mpcholonavigation_amd/variants/, for tools/kbench_all.py.   tools/variants.sh name "-DFLAG=0 ..." ...
+# Developer tool: build variants of libsmpc.so whose lane pass is compiled with extra flags, side by
+# side under mpcholonavigation_amd/variants/, for tools/kbench_all.py to time against the product
+# library in one call.   tools/variants.sh name "-DFLAG=0 ..." ...
+# The rule: a compile-time switch for an experiment lives in a working tree while it is being
+# measured.  What is committed is the winner, plus one sentence with the numbers where the loser
+# would have stood (and in DESIGN.md); the committed sources define no such switch.
 set -e
 cd "$(dirname "$0")/../mpcholonavigation_amd/csrc"
 make -s
