@@ -131,7 +131,9 @@ typedef struct smpc_config {
 typedef struct smpc_obstacles_params {
   int32_t enabled;
   int32_t consider_footprint; /* 1: SE2 footprint check near obstacles (needs
-                                 smpc_set_footprint; general pass only).  With
+                                 smpc_set_footprint; the wave-per-rollout pass
+                                 at any batch: its lean instance with every
+                                 cost_power 1, else the general one).  With
                                  BOTH ObstaclesCritic and CostCritic in the list
                                  and either one's consider_footprint set, the
                                  two disagree on which rollouts collide and a
@@ -190,7 +192,9 @@ typedef struct smpc_prefer_forward_params {
 typedef struct smpc_cost_params {
   int32_t enabled;
   int32_t consider_footprint; /* 1: SE2 footprint check near obstacles (needs
-                                 smpc_set_footprint; general pass only)            */
+                                 smpc_set_footprint; the wave-per-rollout pass
+                                 at any batch: its lean instance with every
+                                 cost_power 1, else the general one)               */
   uint32_t cost_power;
   float cost_weight;          /* as in the YAML (3.81); divided by 254 inside    */
   float critical_cost;

@@ -51,6 +51,15 @@ int sortham_optimizer_set_costmap(sortham_optimizer* o, const uint8_t* cells, ui
                                   uint32_t height, double origin_x, double origin_y,
                                   double resolution, int track_unknown, float inscribed_radius,
                                   int has_inflation_layer);
+/* The robot footprint for consider_footprint = true, with the arguments, the limit
+ * (SMPC_MAX_FOOTPRINT points) and the meaning of smpc_set_footprint: n_points (x, y) pairs in the
+ * robot frame, the layered costmap's circumscribed radius, the inflation layer's own
+ * cost_scaling_factor (< 0: no inflation layer).  What the C++ class takes in
+ * CostmapView::footprint_xy and its neighbours.  Applies from the next tick on, whatever the order
+ * of this call and sortham_optimizer_set_costmap, and survives sortham_optimizer_initialize.
+ * SMPC_ERR_INVALID for a null argument or no point, SMPC_ERR_UNSUPPORTED for too many. */
+int sortham_optimizer_set_footprint(sortham_optimizer* o, const double* xy, uint32_t n_points,
+                                    double circumscribed_radius, double layer_cost_scaling_factor);
 int sortham_optimizer_set_noise(sortham_optimizer* o, const float* nvx, const float* nvy,
                                 const float* nwz);
 /* Optimizer::evalControl: in carries pose / speed / plan / goal (fail_flag_in ignored);

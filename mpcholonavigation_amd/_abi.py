@@ -288,6 +288,7 @@ PROTOTYPES = {
                                   C.c_int]),
 }
 SMPC_COMM_ID_BYTES = 128
+SMPC_MAX_FOOTPRINT = 16
 
 
 def bind(lib, prototypes=None):

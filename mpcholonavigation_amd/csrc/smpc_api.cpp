@@ -526,6 +526,7 @@ static Knobs read_knobs()
   k.stale_tick = static_cast<uint32_t>(number("SMPC_DEBUG_STALE_TICK", 0));
   k.small_window = set("SMPC_SMALL_WINDOW");
   k.window_side_max = number("SMPC_WINDOW_SIDE_MAX", -1);
+  if (const char* e = getenv("SMPC_FOOTPRINT_PASS")) k.footprint_general = !strcmp(e, "general");
   return k;
 }
 }  // namespace smpc_impl

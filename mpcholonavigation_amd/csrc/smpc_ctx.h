@@ -150,6 +150,8 @@ struct Knobs {
   uint32_t stale_tick = 0;         // SMPC_DEBUG_STALE_TICK=n (tests): the BAR hand-over skips tick n's block
   bool small_window = false;       // SMPC_SMALL_WINDOW: the 96-cell costmap window for T > 64 too
   int window_side_max = -1;        // SMPC_WINDOW_SIDE_MAX=cells, < 0: kWindowSideMax
+  bool footprint_general = false;  // SMPC_FOOTPRINT_PASS=general: consider_footprint ticks keep the general pass (MODE 2)
+                                   // instead of the lean MODE 4 — to measure the two routes in one process, and a way back
 };
 
 // blocks per CU of the instance asked about last (the answer moves with the LDS a tick needs)
@@ -296,7 +298,7 @@ struct smpc_ctx {
   // per-tick prepared state
   SmpcDev dev{};
   uint32_t gate_flags = 0;   // critics past their host-side gates this tick
-  int score_mode = 0;        // 0: every cost_power == 1 (one fused reduction), 2: general
+  int score_mode = 0;        // this tick's wave-pass MODE (plan_launch): 0, 3, 4 lean (every cost_power == 1), 2 general
   static int score_mode_for(const smpc_critic_params& cr)
   {
     return (cr.obstacles.cost_power == 1 && cr.path_align.cost_power == 1 &&

@@ -229,6 +229,9 @@ __device__ __forceinline__ float seg_scan_add(float v, uint32_t seg_shift)
 //           TwirlingCritic and PathAngleCritic (every cost_power == 1): the deployed critic
 //           list (robot_bringup/config/nav2_params.yaml:222) in ONE wave reduction instead of
 //           one double-precision reduction and one pow per critic
+//   MODE 4: MODE 3 plus consider_footprint for the list's one collision critic (the deployed
+//           YAML as written, nav2_params.yaml:258): a step whose centre cost reaches the
+//           possibly-inscribed cost walks the footprint, up to 64 steps of a rollout side by side
 //   FULL:   T == 64*R, every lane owns R valid steps (no tail predicates)
 //
 // A wave rolls out one rollout at a time (lane = time step) and PARKS it: its noised
@@ -245,8 +248,11 @@ __global__ void __launch_bounds__((R == 4 ? 512 : 1024), (R == 4 ? 2 : 4)) smpc_
   // MODE 0 is the lean kernel: the rarely used features (trajectory write-out, path
   // orientations) live only in MODE 2, so their pointers and parameters do not occupy scalar
   // registers in the hot loop; the near-goal GoalAngle term is scored by MODE 3 (power 1) or 2
-  constexpr bool RARE = MODE != 0 && MODE != 3;
-  constexpr bool EXTRA = MODE == 3;
+  constexpr bool RARE = MODE == 1 || MODE == 2;
+  constexpr bool EXTRA = MODE == 3 || MODE == 4;
+  // MODE 4 is MODE 3 with the footprint check of ONE collision critic (consider_footprint): the
+  // walk sits behind a wave-uniform branch in the lookup loop below
+  constexpr bool FOOTPRINT = MODE == 4;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint8_t* s_map = smem;
   const SmpcLut* s_lut = reinterpret_cast<const SmpcLut*>(smem + L.off_lut);
@@ -329,6 +335,9 @@ __global__ void __launch_bounds__((R == 4 ? 512 : 1024), (R == 4 ? 2 : 4)) smpc_
   const float obs_cw = in_vgpr(p.obs_critical_w), obs_rt = in_vgpr(p.obs_rep_over_T);
   const float pfw_w = in_vgpr(p.pfw_weight), pf_w = in_vgpr(p.pf_weight), pa_w = in_vgpr(p.pa_weight);
   const float k2_v = in_vgpr(p.k2);
+  // MODE 4: centre cost from which a step looks at the footprint tables (never, without a switch)
+  float fp_enter = 3.0e38f;
+  if (FOOTPRINT && (p.flags & (SD_FP_OBSTACLES | SD_FP_COST))) fp_enter = p.fp_pic < 1.0f ? 0.f : fminf(p.fp_pic, 253.f);
   // {initial value in lane 0, 0 elsewhere}: addends of the fused shift (dpp_shr1_add)
   const float first_vx = lane == 0 ? p.svx : 0.f, first_vy = lane == 0 ? p.svy : 0.f;
   const float first_wz = lane == 0 ? p.swz : 0.f;
@@ -753,7 +762,8 @@ __global__ void __launch_bounds__((R == 4 ? 512 : 1024), (R == 4 ? 2 : 4)) smpc_
       }
     }
 
-    // ---- consider_footprint = true for either collision critic: MODE 2 only ----------
+    // ---- consider_footprint = true for either collision critic, general pass (MODE 4 carries
+    //      its lean form in the lookup loop below) ----------
     // (obstacles_critic.cpp:139-171,203-224; cost_critic.cpp:128-166,175-201.)  The centre
     // cost is looked up as always; a step whose centre cost reaches the possibly-inscribed
     // cost gets the SE2 footprint cost.  Obstacles scores the footprint cost, Cost scores the
@@ -841,7 +851,33 @@ __global__ void __launch_bounds__((R == 4 ? 512 : 1024), (R == 4 ? 2 : 4)) smpc_
           // point 0 is the same for every rollout (v[:,0] is the measured speed): its
           // cell was looked up once on the host with the same arithmetic
           const uint32_t c = (t0 + r == 0) ? p.cost_t0 : cost_at(p, cellk, s_map, x[r], y[r]);
-          const SmpcLut e = s_lut[c];
+          SmpcLut e = s_lut[c];
+          // MODE 4, consider_footprint (obstacles_critic.cpp:139-171,203-224; cost_critic.cpp:
+          // 128-166,175-201; the general pass's block above, one critic).  Below fp_enter the
+          // point table and the footprint tables agree (they differ from cost 253 on), so only a
+          // wave with a lane at or above it leaves MODE 3's stream; those lanes take their entry
+          // from the footprint tables: [0..255] for a centre cost, [256..511] for a walked one.
+          if (FOOTPRINT) {
+            const bool enter = (float)c >= fp_enter;
+            if (__builtin_expect(__any(enter), 0)) {
+              if (enter) {
+                bool want = (float)c >= p.fp_pic || p.fp_pic < 1.0f;
+                if (p.flags & SD_COST) {
+                  // inCollision checks the footprint for every scored step (c >= 1), also off the
+                  // map; the centre cost stays the one scored, the walk gives the collision marker
+                  want = want && c >= 1u;
+                } else if (want && c == 255u) {
+                  // costAtPose returns NO_INFORMATION for an off-map centre before any footprint
+                  uint32_t mxe = 0, mye = 0;
+                  want = cell_index_exact((double)x[r], p.ox, p.res, p.W, mxe);
+                  want = cell_index_exact((double)y[r], p.oy, p.res, p.H, mye) && want;
+                }
+                uint32_t cc = c;
+                if (want) cc = (uint32_t)footprint_cost_at_pose_inl(p, s_map, x[r], y[r], yaw[r]);
+                e = p.lut_fp[((want && !(p.flags & SD_COST)) ? 256u : 0u) + cc];
+              }
+            }
+          }
           if (e.crit < 0.f) {   // inCollision
             first_r = r;
           } else {
@@ -1633,14 +1669,14 @@ char smpc_last_pass_kernel[96] = "";   // (a developer aid: not per thread)
 #define WAVE_INST(...) {__VA_ARGS__, reinterpret_cast<const void*>(&smpc_pass<__VA_ARGS__>)}
 #define WAVE_INST_R(MODE) WAVE_INST(1, MODE, true), WAVE_INST(1, MODE, false), WAVE_INST(2, MODE, true), \
                           WAVE_INST(2, MODE, false), WAVE_INST(4, MODE, true), WAVE_INST(4, MODE, false)
-static const WaveInst kWaveInst[] = {WAVE_INST_R(0), WAVE_INST_R(1), WAVE_INST_R(2), WAVE_INST_R(3)};
+static const WaveInst kWaveInst[] = {WAVE_INST_R(0), WAVE_INST_R(1), WAVE_INST_R(2), WAVE_INST_R(3), WAVE_INST_R(4)};
 #undef WAVE_INST_R
 #undef WAVE_INST
 
 // FULL: T == 64 R, every step slot is live
 const WaveInst* wave_select(int R, int mode, uint32_t T)
 {
-  const int m = (mode == 0 || mode == 1 || mode == 3) ? mode : 2;
+  const int m = (mode == 0 || mode == 1 || mode == 3 || mode == 4) ? mode : 2;
   const bool full = T == 64u * (uint32_t)R;
   for (const WaveInst& k : kWaveInst)
     if (k.r == R && k.mode == m && k.full == full) return &k;

@@ -477,18 +477,26 @@ static int plan_launch(smpc_ctx* c, const smpc_tick_in* in, uint32_t gates, uint
   int mode_now = c->score_mode_for(cr);
   // the lean kernels: MODE 0 scores the north star's five away from the goal, MODE 3 also the
   // additive forms of Cost, Goal, Constraint, Twirling, PathAngle (the deployed list) and of the
-  // near-goal GoalAngle term; everything else (a cost_power other than 1, trajectory write-out,
-  // path orientations, a footprint, VelocityDeadband) takes the general pass — or, for a cost_power
-  // among the five and nothing else, the lane pass's power rows (below)
+  // near-goal GoalAngle term; MODE 4 is MODE 3 with the footprint check of the list's one collision
+  // critic (consider_footprint: the deployed YAML as written).  Everything else (a cost_power other
+  // than 1, trajectory write-out, path orientations, VelocityDeadband, PathAlignLegacy, a footprint
+  // with BOTH collision critics in the list: its counting pass is the general one's) takes the
+  // general pass — or, for a cost_power among the five and nothing else, the lane pass's power rows
+  // (below).  No lane or split instance carries a footprint: such a tick runs the wave pass at any
+  // batch.  SMPC_FOOTPRINT_PASS=general keeps footprint ticks on the general pass.
+  const uint32_t fp_gates = SD_FP_OBSTACLES | SD_FP_COST;
   const uint32_t lean_extra = SD_CONSTRAINT | SD_COST | SD_GOAL | SD_TWIRLING | SD_PATH_ANGLE | SD_GOAL_ANGLE;
-  if (gates & (SD_STORE_TRAJ | SD_USE_PATH_YAW | (SD_EXTRA_CRITICS & ~lean_extra))) {
+  const bool fp_general = c->knobs.footprint_general || ((gates & SD_OBSTACLES) && (gates & SD_COST));
+  if (gates & (SD_STORE_TRAJ | SD_USE_PATH_YAW | (SD_EXTRA_CRITICS & ~(lean_extra | fp_gates)))) {
     mode_now = 2;
-  } else if (gates & lean_extra) {
+  } else if ((gates & fp_gates) && fp_general) {
+    mode_now = 2;
+  } else if (gates & (lean_extra | fp_gates)) {
     const bool unit_powers = (!cr.constraint.enabled || cr.constraint.cost_power == 1) &&
       (!cr.cost.enabled || cr.cost.cost_power == 1) && (!cr.goal.enabled || cr.goal.cost_power == 1) &&
       (!cr.twirling.enabled || cr.twirling.cost_power == 1) && (!cr.path_angle.enabled || cr.path_angle.cost_power == 1) &&
       (!(gates & SD_GOAL_ANGLE) || cr.goal_angle.cost_power == 1);
-    mode_now = (mode_now == 0 && unit_powers) ? 3 : 2;
+    mode_now = (mode_now == 0 && unit_powers) ? ((gates & fp_gates) ? 4 : 3) : 2;
   }
   const WaveInst* wave = wave_select(c->R, mode_now, T);
   if (!wave) return fail(c, SMPC_ERR_UNSUPPORTED, "no instance of the wave-per-rollout pass for this horizon");

@@ -2,17 +2,38 @@
 #include <cstring>
 #include <exception>
 #include <new>
+#include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "../../include/smpc_host.h"
 #include "optimizer.hpp"
 
 namespace sortham_ns = SORTHAM_HOST_NS;
 
+namespace
+{
+// the class plus the one call the C face adds: a footprint handed over on its own, not with a costmap
+struct OptimizerWithFootprint : sortham_ns::Optimizer
+{
+  void applyFootprint(const std::vector<double> & xy, double radius, double layer_scale)
+  {
+    if (!ctx_ || xy.empty()) {return;}
+    if (smpc_set_footprint(ctx_, xy.data(), static_cast<uint32_t>(xy.size() / 2), radius, layer_scale) != SMPC_OK) {
+      throw std::runtime_error(std::string("smpc_set_footprint: ") + smpc_last_error(ctx_));
+    }
+  }
+};
+}  // namespace
+
 struct sortham_optimizer
 {
-  sortham_ns::Optimizer opt;
+  OptimizerWithFootprint opt;
   std::string err;
+  // sortham_optimizer_set_footprint: kept for the contexts initialize() builds later
+  std::vector<double> footprint_xy;
+  double circumscribed_radius{0};
+  double layer_cost_scaling_factor{-1.0};
 };
 
 namespace
@@ -63,6 +84,7 @@ void initialize_from(sortham_optimizer * o, const sortham_optimizer_config * cfg
   o->opt.initialize(
     s, cfg->motion_model ? cfg->motion_model : "DiffDrive", cfg->controller_frequency, cc,
     cfg->regenerate_noises != 0, cfg->noise_seed, b.device);
+  o->opt.applyFootprint(o->footprint_xy, o->circumscribed_radius, o->layer_cost_scaling_factor);
 }
 }  // namespace
 
@@ -123,7 +145,25 @@ int sortham_optimizer_set_costmap(
       m.track_unknown = track_unknown != 0;
       m.inscribed_radius = inscribed_radius;
       m.has_inflation_layer = has_inflation_layer != 0;
+      m.footprint_xy = o->footprint_xy;
+      m.circumscribed_radius = o->circumscribed_radius;
+      m.layer_cost_scaling_factor = o->layer_cost_scaling_factor;
       o->opt.setCostmap(m);
+    });
+}
+
+int sortham_optimizer_set_footprint(
+  sortham_optimizer * o, const double * xy, uint32_t n_points, double circumscribed_radius,
+  double layer_cost_scaling_factor)
+{
+  if (!o || !xy || n_points == 0) {return SMPC_ERR_INVALID;}
+  if (n_points > SMPC_MAX_FOOTPRINT) {return SMPC_ERR_UNSUPPORTED;}
+  return guarded(
+    o, [&]() {
+      o->footprint_xy.assign(xy, xy + 2 * static_cast<size_t>(n_points));
+      o->circumscribed_radius = circumscribed_radius;
+      o->layer_cost_scaling_factor = layer_cost_scaling_factor;
+      o->opt.applyFootprint(o->footprint_xy, circumscribed_radius, layer_cost_scaling_factor);
     });
 }
 

@@ -45,6 +45,7 @@ PROTOTYPES = {
     "sortham_optimizer_set_costmap": (C.c_int, [_ctx, C.c_void_p, C.c_uint32, C.c_uint32,
                                                 C.c_double, C.c_double, C.c_double, C.c_int,
                                                 C.c_float, C.c_int]),
+    "sortham_optimizer_set_footprint": (C.c_int, [_ctx, C.c_void_p, C.c_uint32, C.c_double, C.c_double]),
     "sortham_optimizer_set_noise": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sortham_optimizer_eval_control": (C.c_int, [_ctx, C.POINTER(A.SmpcTickIn), C.c_void_p,
                                                  C.POINTER(A.SmpcTickOut)]),
@@ -159,6 +160,18 @@ class Optimizer:
         self._ck(self.lib.sortham_optimizer_set_costmap(
             self.h, _ptr(cells), w, h, origin_x, origin_y, resolution, int(track_unknown),
             inscribed_radius, int(has_inflation_layer)))
+
+    def set_footprint(self, xy, circumscribed_radius, layer_cost_scaling_factor=10.0):
+        """The robot footprint for consider_footprint = true: [n, 2] points in the robot frame, the
+        layered costmap's circumscribed radius, the inflation layer's cost_scaling_factor (< 0: no
+        inflation layer).  Applies from the next tick on and survives initialize()."""
+        xy = np.ascontiguousarray(xy, dtype=np.float64)
+        if xy.ndim != 2 or xy.shape[1] != 2:
+            raise ValueError("xy must be [n, 2]")
+        if not 1 <= xy.shape[0] <= A.SMPC_MAX_FOOTPRINT:
+            raise ValueError(f"a footprint has 1 to {A.SMPC_MAX_FOOTPRINT} points")
+        self._ck(self.lib.sortham_optimizer_set_footprint(
+            self.h, _ptr(xy), xy.shape[0], float(circumscribed_radius), float(layer_cost_scaling_factor)))
 
     def set_noise(self, nvx, nvy, nwz):
         a = [np.ascontiguousarray(x, dtype=np.float32) for x in (nvx, nvy, nwz)]

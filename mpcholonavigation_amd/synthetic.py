@@ -110,6 +110,32 @@ def make_scenario(time_steps, map_size=200, seed=42, near_goal=False, all_lethal
     return Scenario(cells=cells, origin_x=0.0, origin_y=0.0, resolution=res, tick=tick, u0=u0)
 
 
+def wall_beside_path(scn, offset=0.35, x_from=0.3, x_to=1.3, both_sides=False):
+    """uint8 costmap the size of scn.cells, empty but for a wall two cells thick beside the path —
+    `offset` metres to the left of the robot, from x_from to x_to metres ahead of it (both_sides:
+    mirrored to the right too) — with nav2's inflation around it (inscribed radius 0.1 m, inflation
+    radius 0.55 m, scaling 10): sideways rollouts graze or hit it.  NumPy only: the distance of a cell
+    to a filled rectangle of cells is the distance to its own coordinates clamped into the rectangle."""
+    res, t = scn.resolution, scn.tick
+    H, W = scn.cells.shape
+    ix0, ix1 = int((t.pose_x + x_from) / res), int((t.pose_x + x_to) / res)
+    rows = [int((t.pose_y + offset) / res)]
+    if both_sides:
+        rows.append(int((t.pose_y - offset) / res) - 1)
+    yy, xx = np.mgrid[0:H, 0:W]
+    d2 = np.full((H, W), np.iinfo(np.int64).max, np.int64)
+    for iy in rows:
+        dx = np.maximum(np.maximum(ix0 - xx, xx - (ix1 - 1)), 0)
+        dy = np.maximum(np.maximum(iy - yy, yy - (iy + 1)), 0)
+        d2 = np.minimum(d2, dx * dx + dy * dy)
+    d = np.sqrt(d2.astype(np.float64)) * res
+    cells = np.where(d <= INSCRIBED_RADIUS, 253,
+                     np.floor(252 * np.exp(-COST_SCALING_FACTOR * (d - INSCRIBED_RADIUS)))).astype(np.uint8)
+    cells[d > INFLATION_RADIUS] = 0
+    cells[d2 == 0] = 254
+    return cells
+
+
 def make_noise(batch, time_steps, std=(0.2, 0.2, 0.4), seed=1234):
     """Host noise tensors for parity runs: draw order vx, wz, vy
     (reference src/noise_generator.cpp:107-122); returns (nvx, nvy, nwz)."""

@@ -1,12 +1,23 @@
 #!/usr/bin/env python3
 """Developer tool: tick time of the deployed configuration (robot_bringup/config/nav2_params.yaml:
-2000 rollouts x 56 steps, nine critics) against the north star's five on the same batch."""
+2000 rollouts x 56 steps, nine critics) against the north star's five on the same batch.
+
+Three rows per size: the five, the deployed nine with CostCritic in point mode, and the deployed
+nine as written — CostCritic consider_footprint on, a 0.5 x 0.36 m rectangle.  The last row is timed
+on both routes in one process: the lean wave pass with the footprint check (smpc_pass MODE 4) and
+the general pass (SMPC_FOOTPRINT_PASS=general, what every footprint tick ran before MODE 4
+existed), in interleaved blocks of ticks (as tools/tail_ab.py does), every block's time printed.
+
+    deployed_tick.py [--scene open|wall] [BxT ...]
+
+open: the make_scenario map (no obstacle near the path: no step wants the footprint walk);
+wall: an inflated wall 0.35 m beside the path (synthetic.wall_beside_path: the walk runs)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from mpcholonavigation_amd import _abi as A
 from mpcholonavigation_amd.optimizer import Smpc
-from mpcholonavigation_amd.synthetic import make_scenario
+from mpcholonavigation_amd.synthetic import make_scenario, wall_beside_path
 from mpcholonavigation_amd.tick import default_config, default_critics
 
 DEPLOYED = ("constraint", "cost", "goal", "goal_angle", "path_align", "path_follow", "path_angle",
@@ -14,31 +25,77 @@ DEPLOYED = ("constraint", "cost", "goal", "goal_angle", "path_align", "path_foll
 FIVE = ("obstacles", "path_align", "path_follow", "goal_angle", "prefer_forward")
 ALL = ("obstacles", "path_align", "path_follow", "goal_angle", "prefer_forward", "cost", "goal", "constraint",
        "twirling", "path_angle", "velocity_deadband")
-SIZES = [tuple(int(v) for v in a.split("x")) for a in sys.argv[1:]] or [(2000, 56), (65536, 56)]
+FOOTPRINT = np.array([[0.25, 0.18], [0.25, -0.18], [-0.25, -0.18], [-0.25, 0.18]])
+# (label, critic names, CostCritic consider_footprint, environment at smpc_create)
+ROWS = [("five", FIVE, False, {}),
+        ("deployed nine", DEPLOYED, False, {}),
+        ("deployed nine as written, mode 4", DEPLOYED, True, {}),
+        ("deployed nine as written, general", DEPLOYED, True, {"SMPC_FOOTPRINT_PASS": "general"})]
+BLOCKS = 5
+
+args = sys.argv[1:]
+scene = "open"
+if "--scene" in args:
+    i = args.index("--scene")
+    scene = args[i + 1]
+    del args[i:i + 2]
+if scene not in ("open", "wall"):
+    sys.exit("--scene open|wall")
+SIZES = [tuple(int(v) for v in a.split("x")) for a in args] or [(2000, 56), (65536, 56)]
+
+
+def make(B, T, names, footprint, env):
+    cr = default_critics()
+    for n in ALL:
+        getattr(cr, n).enabled = 1 if n in names else 0
+    cr.cost.consider_footprint = int(footprint)
+    scn = make_scenario(T)
+    if scene == "wall":
+        scn.cells = wall_beside_path(scn)
+    os.environ.update(env)          # (the knobs are read when the context is created)
+    g = Smpc(default_config(batch_size=B, time_steps=T, flags=A.SMPC_FLAG_PROFILE))
+    for k in env:
+        os.environ.pop(k, None)
+    g.set_critics(cr)
+    g.set_costmap(scn.cells, scn.origin_x, scn.origin_y, scn.resolution)
+    if footprint:
+        g.set_footprint(FOOTPRINT, circumscribed_radius=float(np.hypot(0.25, 0.18)), layer_cost_scaling_factor=10.0)
+    g.seed(1)
+    return g, scn
+
+
+def ticks(g, scn, u, n):
+    """n closed-loop ticks -> (u, wall us per tick, the ticks' outputs)"""
+    outs = []
+    t0 = time.perf_counter()
+    for _ in range(n):
+        un, out = g.optimize(scn.tick, u)
+        u = np.concatenate([un[:, 1:], un[:, -1:]], axis=1)
+        outs.append(out)
+    return u, (time.perf_counter() - t0) / n * 1e6, outs
+
+
 for B, T in SIZES:
-    for label, names in (("five", FIVE), ("deployed nine", DEPLOYED)):
-        cr = default_critics()
-        for n in ALL:
-            getattr(cr, n).enabled = 1 if n in names else 0
-        cfg = default_config(batch_size=B, time_steps=T, flags=A.SMPC_FLAG_PROFILE)
-        scn = make_scenario(T)
-        g = Smpc(cfg)
-        g.set_critics(cr)
-        g.set_costmap(scn.cells, scn.origin_x, scn.origin_y, scn.resolution)
-        g.seed(1)
-        u = scn.u0
-        ps, ds = [], []
-        for k in range(60):
-            un, out = g.optimize(scn.tick, u)
-            u = np.concatenate([un[:, 1:], un[:, -1:]], axis=1)
-            if k >= 10:
-                ps.append(out.score_pass_ms); ds.append(out.device_ms)
+    n = 400 if B <= 4096 else 200
+    ctx = []
+    for label, names, footprint, env in ROWS:
+        g, scn = make(B, T, names, footprint, env)
+        u, _, _ = ticks(g, scn, scn.u0, 10)
+        # the scoring pass by HIP events (SMPC_FLAG_PROFILE), in a block of its own
+        u, _, outs = ticks(g, scn, u, 50)
+        ps, ds = [o.score_pass_ms for o in outs], [o.device_ms for o in outs]
         g.set_profile(False)
-        t0 = time.perf_counter()
-        for k in range(200):
-            un, out = g.optimize(scn.tick, u)
-            u = np.concatenate([un[:, 1:], un[:, -1:]], axis=1)
-        el = (time.perf_counter() - t0) / 200
-        print(f"{B}x{T} {label:14s}: tick {el*1e6:7.1f} us, scoring pass {np.median(ps)*1e3:7.1f} us, device {np.median(ds)*1e3:7.1f} us, "
-              f"pass_kind {out.pass_kind}, passes {out.passes}")
+        u, _, _ = ticks(g, scn, u, 50)
+        ctx.append([label, g, scn, u, np.median(ps) * 1e3, np.median(ds) * 1e3, [], outs[-1]])
+    # wall time per tick over a device synchronise: blocks of n ticks, the rows taking turns
+    for rep in range(BLOCKS):
+        for c in ctx:
+            c[3], us, outs = ticks(c[1], c[2], c[3], n)
+            c[6].append(us)
+            c[7] = outs[-1]
+    for label, g, scn, u, ps, ds, blocks, out in ctx:
+        print(f"{B}x{T} {scene:4s} {label:34s}: tick median {np.median(blocks):7.1f} us "
+              f"(blocks of {n}: {' '.join(f'{b:.1f}' for b in blocks)}; spread {max(blocks) - min(blocks):.1f}), "
+              f"scoring pass {ps:7.1f} us, device {ds:7.1f} us, pass_kind {out.pass_kind}, passes {out.passes}, "
+              f"non-colliding {out.non_colliding}")
         g.close()
