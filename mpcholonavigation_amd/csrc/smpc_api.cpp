@@ -526,6 +526,7 @@ static Knobs read_knobs()
   k.stale_tick = static_cast<uint32_t>(number("SMPC_DEBUG_STALE_TICK", 0));
   k.small_window = set("SMPC_SMALL_WINDOW");
   k.window_side_max = number("SMPC_WINDOW_SIDE_MAX", -1);
+  k.furthest_prune = number("SMPC_FURTHEST_PRUNE", 1) != 0;
   if (const char* e = getenv("SMPC_FOOTPRINT_PASS")) k.footprint_general = !strcmp(e, "general");
   return k;
 }
@@ -648,8 +649,8 @@ int smpc_create(const smpc_config* cfg, smpc_ctx** out)
   c->stream = c->own_stream;
   if (getenv("SMPC_LANE_TIMELINE")) {
     static_assert(SMPC_TAIL_STAMPS_AT == 8192 + kMaxGrid * 8, "the tail's stamps sit behind the lane pass's");
-    CK(hipMalloc(&c->d_timeline, (8192 + kMaxGrid * 8 + 8 * 16) * sizeof(unsigned long long)));
-    CK(hipMemset(c->d_timeline, 0, (8192 + kMaxGrid * 8 + 8 * 16) * sizeof(unsigned long long)));
+    CK(hipMalloc(&c->d_timeline, (SMPC_SCAN_COUNT_AT + kMaxGrid * 8) * sizeof(unsigned long long)));
+    CK(hipMemset(c->d_timeline, 0, (SMPC_SCAN_COUNT_AT + kMaxGrid * 8) * sizeof(unsigned long long)));
   }
   CK(hipEventCreate(&c->ev0));
   CK(hipEventCreateWithFlags(&c->ev_map, hipEventDisableTiming));
@@ -1319,6 +1320,43 @@ int smpc_debug_lane_timeline(smpc_ctx* c, double* out, uint32_t* n_blocks)
     out[21 + w] = v.empty() ? 0 : v[v.size() / 2];
   }
   if (n_blocks) *n_blocks = nb;
+  return SMPC_OK;
+}
+
+// developer aid (SMPC_LANE_TIMELINE=1): how many groups of the lane pass took the furthest-point scan
+// since the last call (the instances with the prune test count; smpc_lane_furthest.inc), and how
+// many groups a launch of the current plan has; the counts are cleared
+int smpc_debug_lane_scan_count(smpc_ctx* c, unsigned long long* scanned, uint32_t* groups_per_launch)
+{
+  if (!c || !scanned || !c->d_timeline) return SMPC_ERR_INVALID;
+  HIPCK(c, hipSetDevice(c->device));
+  HIPCK(c, hipStreamSynchronize(c->stream));
+  std::vector<unsigned long long> h(static_cast<size_t>(kMaxGrid) * 8);
+  HIPCK(c, hipMemcpy(h.data(), c->d_timeline + SMPC_SCAN_COUNT_AT, h.size() * sizeof(h[0]), hipMemcpyDeviceToHost));
+  HIPCK(c, hipMemset(c->d_timeline + SMPC_SCAN_COUNT_AT, 0, h.size() * sizeof(h[0])));
+  unsigned long long sum = 0;
+  for (unsigned long long v : h) sum += v;
+  *scanned = sum;
+  if (groups_per_launch) *groups_per_launch = (c->cfg.batch_size + 63u) / 64u;
+  return SMPC_OK;
+}
+
+// developer aid (tests): the float F = index + fraction the last tick's scoring pass reported (the
+// tuple's slot 2, smpc_dev.h), as remember_furthest kept it for the next prediction — the value
+// itself while the stored noise stays the same from tick to tick
+int smpc_debug_furthest_f(const smpc_ctx* c, float* F)
+{
+  if (!c || !F || !c->hint_valid) return SMPC_ERR_INVALID;
+  *F = c->hint_F;
+  return SMPC_OK;
+}
+
+// developer aid, host only (tests/test_furthest_prune_cpu.py): the prune table prepare_tick would
+// write for this plan and first index; out: SMPC_PRUNE_FLOATS floats
+int smpc_debug_prune_table(const float* px, const float* py, uint32_t P, uint32_t k0, int on, float* out)
+{
+  if (!px || !py || !out) return SMPC_ERR_INVALID;
+  build_prune_table(px, py, P, k0, on != 0, out);
   return SMPC_OK;
 }
 

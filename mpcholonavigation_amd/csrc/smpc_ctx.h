@@ -150,6 +150,8 @@ struct Knobs {
   uint32_t stale_tick = 0;         // SMPC_DEBUG_STALE_TICK=n (tests): the BAR hand-over skips tick n's block
   bool small_window = false;       // SMPC_SMALL_WINDOW: the 96-cell costmap window for T > 64 too
   int window_side_max = -1;        // SMPC_WINDOW_SIDE_MAX=cells, < 0: kWindowSideMax
+  bool furthest_prune = true;      // SMPC_FURTHEST_PRUNE=0: the lane pass's prune table is written empty (every entry "never
+                                   // prune"): same kernel, every group scans — the A/B switch and the tests' unpruned answer
   bool footprint_general = false;  // SMPC_FOOTPRINT_PASS=general: consider_footprint ticks keep the general pass (MODE 2)
                                    // instead of the lean MODE 4 — to measure the two routes in one process, and a way back
 };
@@ -251,6 +253,10 @@ struct smpc_ctx {
   uint32_t p2p_timeout_ms = 10000;   // bound of the in-kernel wait for the peers (smpc_shard_p2p_set_timeout)
   bool p2p_failed = false;           // an exchange timed out: no further mailbox tick until re-init
   bool pang_any = false;        // this tick: PathAngleCritic is live for some candidate furthest point (prepare_tick)
+  // the lane pass's prune table as last built, and what it was built for (prepare_tick)
+  float prune_table[SMPC_PRUNE_FLOATS] = {};
+  std::vector<float> prune_px, prune_py;
+  uint32_t prune_k0 = 0;
   bool in_group = false;        // member of an smpc_group: full-size blocks always (the group fills the CUs by itself)
   float* d_costs[2] = {nullptr, nullptr};
   float* d_traj[3] = {nullptr, nullptr, nullptr};
@@ -367,9 +373,11 @@ void free_ctx(smpc_ctx* c);
 
 // tick block layout (offsets in bytes), sized for the ctx's T and SMPC_MAX_PATH
 struct TickLayout {
-  size_t u, px, py, pyaw, D, pf_idx, pvalid, pa_active, pang_active, pal_active, lut_cost, canary, total;
+  size_t u, px, py, pyaw, D, pf_idx, pvalid, pa_active, pang_active, pal_active, lut_cost, canary, prune, total;
 };
 TickLayout tick_layout(uint32_t T, uint32_t P);
+// the lane pass's furthest-point prune table for K = k0 .. k0 + 15 (out: SMPC_PRUNE_FLOATS floats)
+void build_prune_table(const float* px, const float* py, uint32_t P, uint32_t k0, bool on, float* out);
 
 // LDS carve-up of the streaming pass.  nsamp = PathAlign samples per rollout (0: off).
 SmpcLds make_lds(uint32_t window_bytes, uint32_t P, uint32_t T, uint32_t nwave, bool with_map,

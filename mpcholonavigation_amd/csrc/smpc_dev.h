@@ -102,6 +102,7 @@ struct SmpcDev {
   const uint8_t* pvalid;     // P-1 entries
   const uint8_t* pa_active;  // [P] PathAlign gate per candidate furthest point
   const uint32_t* pf_idx;    // [P] PathFollow target index per candidate furthest point
+  const float* prune;        // [SMPC_PRUNE_FLOATS] the lane pass's furthest-point prune table (below)
   // furthest point: device value (float) if non-null, else the hint
   const float* d_furthest;
   uint32_t furthest_hint;
@@ -188,6 +189,12 @@ struct SmpcDev {
 #define SMPC_CANARY_SLOT(T) (SMPC_MAX_GRID * (4u + 3u * (T)))   /* float index into SmpcDev::partials */
 #define SMPC_TAIL_MAX_GRID 512u
 #define SMPC_TAIL_STAMPS_AT (8192u + 2048u * 8u)   /* behind the lane pass's stamps in SmpcDev::timeline */
+#define SMPC_SCAN_COUNT_AT (SMPC_TAIL_STAMPS_AT + 8u * 16u)   /* [grid][8]: groups of each wave that took the furthest-point scan */
+// The lane pass's furthest-point prune table (smpc_prepare.cpp build_prune_table, smpc_lane_furthest.inc):
+// a header of four words {first index k0, entries n, the block-shared bound (zero), 0} and n <= 16
+// entries of eight floats for K = k0 .. k0 + n - 1.
+#define SMPC_PRUNE_ENTRIES 16u
+#define SMPC_PRUNE_FLOATS (4u + 8u * SMPC_PRUNE_ENTRIES)
 // LDS floats smpc_grid_tail works in (from offset 0 of the launch's dynamic LDS, which the pass
 // no longer needs by then): 512 rescale factors, 4 x 16 wave results, [32][64] slice sums per 64 tuple
 // columns, a flag
@@ -272,6 +279,7 @@ struct SmpcReduceArgs {
 struct SmpcLds {
   uint32_t off_lut, off_px, off_py, off_pyaw, off_D, off_valid, off_scr;
   uint32_t off_pts4;    // lane pass: path points as {x, y, segment valid ? 1 : 0, 0} [P]
+  uint32_t off_prune;   // lane pass: the furthest-point prune table [SMPC_PRUNE_FLOATS]
   uint32_t scr_stride;  // floats per wave of scratch
   uint32_t scr_pts;     // float offsets inside a wave's scratch: sample points [3][64],
   uint32_t scr_ring;    //   parked endpoints [2][64],

@@ -52,6 +52,13 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
   // sum_t u[ctrl][t]^2 of this launch's control sequence, ctrl = vx, vy, wz (the gamma terms):
   // the 16 bytes in front of the per-wave scratch (smpc_prepare.cpp lane_lds)
   float* s_su2 = reinterpret_cast<float*>(smem + L.off_scr) - 4;
+  // kPrune: the furthest-point section sits at the END of the group body, with the prune test in
+  // front of its scan (smpc_lane_furthest.inc).  Per instance, like kWindow: there the parked
+  // registers are dead and the plain instances keep 256 VGPRs without scratch; moved in the
+  // grouped deployed-list instances it costs 8 bytes of scratch, in the re-read one 30 VGPRs.
+  constexpr bool kPrune = !GA && !DEP && !MANY && !RR && !POW;
+  // the host's table for it: {k0, n, block-shared bound, 0} and n entries of eight floats (smpc_dev.h)
+  float* s_prune = reinterpret_cast<float*>(smem + L.off_prune);
 
   constexpr int BLK = RR ? LANE_BLOCK_RR : LANE_BLOCK;   // the largest block; small batches launch half of it
   const int blk = blockDim.x;
@@ -93,6 +100,7 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
     const float g_px = pt_on ? tk.px[tid] : 0.f, g_py = pt_on ? tk.py[tid] : 0.f;
     const float g_D = seg_on ? tk.D[tid] : 0.f;
     const bool g_valid = seg_on && tk.pvalid[tid] != 0;
+    const float g_prune = (kPrune && tid < (int)SMPC_PRUNE_FLOATS) ? p.prune[tid] : 0.f;
 
     if (OBST) {
 #pragma unroll
@@ -116,6 +124,7 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
       if (tid == 0) s_map[ww * wh] = 255;
     }
     for (uint32_t i = p.P + tid; i < ((p.P + 3u) & ~3u); i += blockDim.x) s_px[i] = s_py[i] = 1.0e18f;
+    if (kPrune && tid < (int)SMPC_PRUNE_FLOATS) s_prune[tid] = g_prune;
     if (pt_on) {
       s_px[tid] = g_px;
       s_py[tid] = g_py;
@@ -206,6 +215,7 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
 #pragma unroll
   for (int h = 0; h < NCH; ++h) Ux[h] = Uy[h] = Uz[h] = 0.f;
   float F_local = 0.f;   // furthest point of this wave's rollouts, index + fraction (smpc_dev.h)
+  bool furthest_pending = false;   // kPrune: the first group's endpoints wait in LDS (smpc_lane_furthest.inc)
   uint32_t n_noncoll = 0;
 
   const uint32_t ngroups = (B + WAVE - 1) / WAVE;
@@ -649,97 +659,10 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
     y = (float)(y0 + (double)ay);
 
     // ================= per-rollout epilogue, lane = rollout ==============================
-    // nearest path point of the endpoint (utils.hpp:292-319): first minimum wins
-    if (want_local_furthest) {
-      // Four path points per pair of LDS broadcast reads (the arrays are padded to a multiple
-      // of four with far-away points that never win).  The strict "<" scan runs over the
-      // MINIMUM of each block of four — the first block that holds the overall minimum wins —
-      // and the first point of that block that attains it is found afterwards, from the same
-      // arithmetic: the reference's first minimum at a third of the compare/select work.
-      auto block_d2 = [&](const float* bx, const float* by, float (&dd)[4]) {
-        const f32x4 qx = *reinterpret_cast<const f32x4*>(bx);
-        const f32x4 qy = *reinterpret_cast<const f32x4*>(by);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float ex = qx[e] - x, ey = qy[e] - y;
-          dd[e] = ex * ex + ey * ey;
-        }
-      };
-      float best = 3.4028234663852886e38f;
-      uint32_t bj = 0;
-      const uint32_t P4 = (p.P + 3u) & ~3u;
-      // The scan is 15 blocks for a 60-point path and only its batch-wide MAXIMUM is consumed.  So
-      // it starts three blocks below the block of the index this tick is scored with (where the
-      // maximum has been every tick so far) and runs to the path's end; what that leaves out is
-      // checked for the ONE lane that ends up holding the wave's maximum (below).  (The plain
-      // instances only: in the GoalAngle, deployed-list and grouped ones the extra code costs
-      // 16-48 bytes of scratch.)
-      constexpr bool kWindow = !GA && !DEP && !MANY;
-      const uint32_t j_lo = (kWindow && (S >> 2) > 3u) ? ((S >> 2) - 3u) << 2 : 0u;
-      for (uint32_t j = j_lo; j < P4; j += 4) {
-        float dd[4];
-        block_d2(s_px + j, s_py + j, dd);
-        const float mn = fminf(fminf(dd[0], dd[1]), fminf(dd[2], dd[3]));
-        if (mn < best) {      // a NaN or infinite distance never wins, as in the plain scan
-          best = mn;
-          bj = j;
-        }
-      }
-      // index + how far the endpoint sits towards the next point, in segment lengths (what the
-      // host predicts the next tick's index from; smpc_dev.h)
-      auto point_F = [&]() -> float {
-        float dd[4];
-        block_d2(s_px + bj, s_py + bj, dd);
-        const uint32_t bi = bj + (dd[0] == best ? 0u : dd[1] == best ? 1u : dd[2] == best ? 2u : dd[3] == best ? 3u : 0u);
-        float F = (float)bi;
-        if (bi + 1 < p.P) {
-          const float nx = s_px[bi + 1], ny = s_py[bi + 1];
-          const float sgx = nx - s_px[bi], sgy = ny - s_py[bi];
-          const float d_next = (nx - x) * (nx - x) + (ny - y) * (ny - y);
-          const float seg2 = sgx * sgx + sgy * sgy;
-          const float tt = seg2 > 0.f ? 0.5f + 0.5f * (best - d_next) * fast_rcp(seg2) : 0.f;
-          F = fmaxf(F + fminf(fmaxf(tt, -0.45f), 0.45f), 0.f);
-        }
-        return F;
-      };
-      float F = point_F();
-      float m = live ? F : 0.f;
-      for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, WAVE));
-      if (kWindow && j_lo) {
-        // A lane whose true nearest point lies BELOW the window holds a value that is too high,
-        // never too low: max over the lanes of the windowed values >= the true maximum, with
-        // equality as soon as ONE lane that attains it is exact.  So: take a lane holding the
-        // maximum and test every point below the window against its endpoint — one point per
-        // lane of the wave, "<=" because an equal distance at a lower index wins the reference's
-        // strict scan.  If one of them beats it (a path that doubles back under the endpoint),
-        // every lane scans the lower blocks after all and the maximum is formed again.
-        const unsigned long long holders = __ballot(live && F == m);
-        bool below = false;
-        if (holders) {
-          const int wl = __builtin_ctzll(holders);
-          const float wx = __shfl(x, wl, WAVE), wy = __shfl(y, wl, WAVE), wbest = __shfl(best, wl, WAVE);
-          for (uint32_t k = (uint32_t)lane; k < j_lo; k += WAVE) {
-            const float ex = s_px[k] - wx, ey = s_py[k] - wy;
-            below = below || (ex * ex + ey * ey <= wbest);
-          }
-        }
-        if (__builtin_expect(__any(below), 0)) {
-          for (uint32_t jj = j_lo; jj > 0; jj -= 4) {      // downwards: ties go to the lower block
-            const uint32_t j = jj - 4;
-            float dd[4];
-            block_d2(s_px + j, s_py + j, dd);
-            const float mn = fminf(fminf(dd[0], dd[1]), fminf(dd[2], dd[3]));
-            if (mn <= best) {
-              best = mn;
-              bj = j;
-            }
-          }
-          F = point_F();
-          m = live ? F : 0.f;
-          for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, WAVE));
-        }
-      }
-      F_local = fmaxf(F_local, m);
+    if constexpr (!kPrune) {
+#define LANE_FURTHEST_PRUNE false
+#include "smpc_lane_furthest.inc"
+#undef LANE_FURTHEST_PRUNE
     }
     float cost = (p.flags & SD_ACCUMULATE) ? p.costs_prev[bl] : 0.f;
     if constexpr (POW) {
@@ -884,6 +807,11 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
         Uz[0] = fmaf(Uz[0], f, acc0 + acc1);
         __builtin_amdgcn_wave_barrier();
       }
+    }
+    if constexpr (kPrune) {
+#define LANE_FURTHEST_PRUNE true
+#include "smpc_lane_furthest.inc"
+#undef LANE_FURTHEST_PRUNE
     }
     return false;
   };

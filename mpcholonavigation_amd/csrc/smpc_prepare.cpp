@@ -24,6 +24,7 @@ TickLayout tick_layout(uint32_t T, uint32_t P)
   l.pang_active = o; o += align_up(P, 16);
   l.pal_active = o; o += align_up(P, 16);   // PathAlignLegacy gate per candidate furthest point
   l.lut_cost = o; o += 256 * 4;   // CostCritic repulsive term per 8-bit cost
+  l.prune = o; o += SMPC_PRUNE_FLOATS * 4;   // lane pass: furthest-point prune table (build_prune_table)
   l.total = o;
   return l;
 }
@@ -67,8 +68,10 @@ SmpcLds lane_lds(uint32_t window_bytes, uint32_t P, uint32_t T, bool rr)
   const uint32_t lblock = rr ? smpc_lane_block_rr() : smpc_lane_block();
   SmpcLds Lt = make_lds(window_bytes ? window_bytes + 1 + lblock : 0, P, T, lblock / 64,
                         window_bytes != 0, 0);
-  Lt.off_pts4 = Lt.off_scr;
-  Lt.off_scr += align_up(std::max(P, 1u) * 16, 16) + 16;   // + sum u^2 per control (the gamma terms), 16 bytes
+  // the furthest-point prune table (528 bytes; the parked wz dominates: 8 x 17.7 KB of the 160 KB)
+  Lt.off_prune = Lt.off_scr;
+  Lt.off_pts4 = Lt.off_prune + SMPC_PRUNE_FLOATS * 4;
+  Lt.off_scr = Lt.off_pts4 + align_up(std::max(P, 1u) * 16, 16) + 16;   // + sum u^2 per control (the gamma terms), 16 bytes
   Lt.scr_stride = rr ? align_up(4u + 3u * T, 4) : align_up(std::max(64u * 68u + 64u, 4u + 3u * T), 4);
   Lt.total = Lt.off_scr + (lblock / 64) * Lt.scr_stride * 4;
   return Lt;
@@ -140,6 +143,113 @@ static void build_lut(const smpc_ctx* c, bool near_goal, SmpcLut* lut, bool cons
     } else if (!near_goal) {
       lut[v].rep = m.inflation_radius - d;                   // :167
     }
+  }
+}
+
+// The lane pass's furthest-point prune table (smpc_lane_furthest.inc reads it).
+//
+// A speculating lane pass reports max over the live rollouts of F_b = bi + clamp(tt, +-0.45), bi the
+// first nearest path point of the rollout's endpoint e and tt the endpoint's projection parameter on
+// the segment behind p_bi.  Given a bound theta = K + phi (K = rint(theta)) that some rollout has
+// already attained, a rollout with F_b <= theta adds nothing to the maximum.  Entry K lets a lane
+// prove that in ~12 instructions.  With e' = e - p_K, n the unit vector along p_K -> p_K+1,
+// s = n.e', t = n_perp.e', all divided by a radius R = 64 segment lengths (so that the entry is
+// scale-free: {p_K, n / R, kappa, rho~, R / seg, m'}):
+//   (0) max(|s|, |t|) <= 1            the endpoint is within R of p_K: bounds every rounding error
+//                                     below, and a NaN or far-away endpoint fails it;
+//   (a) s + kappa |t| <= rho~         p_K is at least as near as every LATER point p_j, so the first
+//                                     nearest index is <= K.  With v_j = p_j - p_K = alpha_j n +
+//                                     beta_j n_perp: d_j - d_K = |v_j|^2 - 2 e'.v_j and e'.v_j <=
+//                                     alpha_j (s + kappa |t|) for kappa = max |beta_j| / alpha_j, so
+//                                     rho = min |v_j|^2 / (2 alpha_j) suffices.  Points further than
+//                                     3 R away cannot be nearer than p_K under (0) and are left out;
+//                                     an alpha_j <= 0 among the rest (the plan doubles back, points
+//                                     repeat) makes the entry "never prune" (rho~ = -4: (0) has s >= -1);
+//   (b) K + max(s R / seg + m',       if the nearest index IS K: s R / seg + m' >= the kernel's tt,
+//       -0.45) <= theta               and the clamp, the float sum with K and the final max(., 0) are
+//                                     monotone, so the left side is >= F_b (the upper clamp is left
+//                                     out: beyond it the left side exceeds K + 0.45 >= theta anyway).
+//                                     A nearest index below K gives F_b <= K - 0.55 <= theta whatever
+//                                     (b) says.
+//   K = P - 1: no later point, F_b = K exactly: R / seg = 0 and m' = 0, (b) reads K <= theta.
+// Margins, u = 2^-24.  The kernel's dd = ex * ex + ey * ey (ex = q - x rounded, no contraction) is
+// within 5 u dd of the true squared distance.  (a) must make the FLOAT d_K <= the float d_j: the
+// true difference has to exceed 5 u (d_j + d_K), where d_K <= 2 R^2 and d_j <= (sqrt 2 R + |v_j|)^2
+// <= 4 R^2 + 2 |v_j|^2 under (0); rho is lowered by m = 4 max_j 5 u (d_j + d_K) / (2 alpha_j) (four times what is
+// needed).  The test's own arithmetic (e' rounded, n / R rounded, two products, a sum, kappa |t|)
+// is off by less than 16 u (1 + kappa) in units of R; rho~ is lowered by 64 u (1 + kappa), kappa is
+// rounded up and rho~ down.  (b): the kernel's tt = 0.5 + 0.5 (d_K - d_K+1) * rcp(seg2) differs from
+// the true parameter by at most 0.5 * 5 u (d_K + d_K+1) / seg^2 (the two distances) plus 10 u |tt -
+// 0.5| + u (difference, reciprocal of a rounded seg2, products, sum; |tt| <= 92 under (0)), the
+// test's s R / seg by 16 u * 64 + 2 u * 92: m' is twice the sum of all of them, ~5.2e-3; m is 3 % of
+// half a segment on a straight plan.
+// A false "cannot raise the maximum" would be a wrong result, a false "can" costs one scan.
+// on = false (SMPC_FURTHEST_PRUNE=0, plans beyond kPruneMaxPath points): every entry "never prune".
+void build_prune_table(const float* px, const float* py, uint32_t P, uint32_t k0, bool on, float* out)
+{
+  const double u = 5.9604644775390625e-08;   // 2^-24
+  const uint32_t n = P > k0 ? std::min(P - k0, SMPC_PRUNE_ENTRIES) : 0u;
+  memset(out, 0, SMPC_PRUNE_FLOATS * sizeof(float));
+  memcpy(out, &k0, 4);
+  memcpy(out + 1, &n, 4);
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t K = k0 + i;
+    float* e = out + 4 + 8 * i;
+    const double kx = px[K], ky = py[K];
+    e[0] = px[K];
+    e[1] = py[K];
+    e[5] = -4.0f;   // never prune, until everything below holds
+    if (!on) continue;
+    // the segment behind p_K; at the plan's last point the one in front of it gives the frame
+    const bool last = K + 1 >= P;
+    double gx = 1.0, gy = 0.0;
+    if (!last) {
+      gx = static_cast<double>(px[K + 1]) - kx;
+      gy = static_cast<double>(py[K + 1]) - ky;
+    } else if (K > 0) {
+      gx = kx - px[K - 1];
+      gy = ky - py[K - 1];
+    }
+    const double seg = std::sqrt(gx * gx + gy * gy);
+    if (!(seg > 0.0) || !std::isfinite(seg)) {
+      if (!last) continue;
+      gx = 1.0; gy = 0.0;   // (a one-point plan, or its last two points coincide: any frame)
+    } else {
+      gx /= seg; gy /= seg;
+    }
+    const double R = 64.0 * (seg > 0.0 && std::isfinite(seg) ? seg : 1.0);
+    double kappa = 0.0, rho = 1.0e30, m = 0.0;
+    bool ok = true;
+    for (uint32_t j = K + 1; j < P; ++j) {
+      const double vx = static_cast<double>(px[j]) - kx, vy = static_cast<double>(py[j]) - ky;
+      const double v2 = vx * vx + vy * vy;
+      if (v2 >= 9.0 * R * R) continue;      // cannot be nearer than p_K while (0) holds
+      const double al = gx * vx + gy * vy, be = gx * vy - gy * vx;
+      if (!(al > 0.0)) {
+        ok = false;
+        break;
+      }
+      // d_j <= (sqrt 2 R + |v_j|)^2 <= 4 R^2 + 2 |v_j|^2 (no square root: this runs 16 P times a tick)
+      const double ial = 1.0 / al, dj = 4.0 * R * R + 2.0 * v2;
+      kappa = std::max(kappa, std::fabs(be) * ial);
+      rho = std::min(rho, 0.5 * v2 * ial);
+      m = std::max(m, 2.5 * u * (dj + 2.0 * R * R) * ial);
+    }
+    if (!ok || !std::isfinite(kappa) || kappa > 64.0) continue;
+    const double rho_s = (rho - 4.0 * m) / R - 64.0 * u * (1.0 + kappa);
+    double inv = 0.0, mb = 0.0;
+    if (!last) {
+      const double dsum = 2.0 * R * R + (1.4142136 * R + seg) * (1.4142136 * R + seg);
+      inv = R / seg;
+      mb = 2.0 * (0.5 * 5.0 * u * dsum / (seg * seg) + 10.0 * u * 92.0 + u + 16.0 * u * inv + 2.0 * u * 92.0);
+    }
+    e[2] = static_cast<float>(gx / R);
+    e[3] = static_cast<float>(gy / R);
+    e[4] = kappa > 0.0 ? std::nextafter(static_cast<float>(kappa * (1.0 + 4.0 * u)), 3.0e38f) : 0.f;
+    e[6] = static_cast<float>(inv);
+    e[7] = mb > 0.0 ? std::nextafter(static_cast<float>(mb), 3.0e38f) : 0.f;
+    // (1e30: no later point)
+    e[5] = std::nextafter(static_cast<float>(std::min(rho_s, 1.0e30)), -3.0e38f);
   }
 }
 
@@ -838,6 +948,42 @@ int prepare_tick(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
     const int rc_map = wait_map_upload(c);
     if (rc_map != SMPC_OK) return rc_map;
   }
+  // The index this tick is first scored with (it does not depend on the launch plan), and the lane
+  // pass's prune table for the 16 indices around it: the batch's furthest point — what the table is
+  // indexed with — lands within one or two of the prediction.  O(16 P), ~0.5 us for 60 points, so:
+  // only where it is read — a speculating tick of a context whose LAST tick took the parking form of
+  // the lane pass on its own (this tick's plan is made after the block has gone to the device; a
+  // wrong guess costs scans or a table nobody reads, never a result) — once per plan and first index
+  // (a plan is handed over unchanged for several ticks), and not beyond kPruneMaxPath points.
+  // SMPC_FURTHEST_PRUNE=0 gets the empty table, every entry "never prune" (the same work in the
+  // kernel: the A/B switch); a tick that does not read the table gets only its header with no
+  // entries (a pass that reads it after all scans every group), and the block handed to the device
+  // ends behind that header: 512 bytes less through the BAR on every small tick.
+  predict_hint(c, in, u_in);
+  size_t tick_bytes = tl.total;
+  {
+    constexpr uint32_t kPruneMaxPath = 256;
+    float* table = reinterpret_cast<float*>(h + tl.prune);
+    uint32_t k0 = (c->hint_valid && c->hint > SMPC_PRUNE_ENTRIES / 2) ? c->hint - SMPC_PRUNE_ENTRIES / 2 : 0u;
+    k0 = std::min(k0, P > SMPC_PRUNE_ENTRIES ? P - SMPC_PRUNE_ENTRIES : 0u);
+    const bool read = c->plan.kind == PassPlan::kLane && !c->plan.rr && !c->plan.pow && !c->in_group && c->hint_valid &&
+      !(c->cfg.flags & SMPC_FLAG_NO_SPECULATION);
+    if (!read || P > kPruneMaxPath) {
+      memset(table, 0, 16);
+      tick_bytes = tl.prune + 16;
+    } else if (!c->knobs.furthest_prune) {
+      build_prune_table(px, py, P, k0, false, table);
+    } else if (c->prune_k0 == k0 && c->prune_px.size() == P && !memcmp(c->prune_px.data(), px, P * 4) &&
+               !memcmp(c->prune_py.data(), py, P * 4)) {
+      memcpy(table, c->prune_table, sizeof(c->prune_table));
+    } else {
+      build_prune_table(px, py, P, k0, true, table);
+      memcpy(c->prune_table, table, sizeof(c->prune_table));
+      c->prune_px.assign(px, px + P);
+      c->prune_py.assign(py, py + P);
+      c->prune_k0 = k0;
+    }
+  }
   if (c->cfg.flags & SMPC_FLAG_PROFILE) HIPCK(c, hipEventRecord(c->ev0, c->stream));
   // small ticks travel inside the kernel arguments (SmpcDev::tick_bytes) instead of a copy of
   // their own; the CostCritic table (general pass only) is not part of that
@@ -853,7 +999,7 @@ int prepare_tick(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
   // from device memory (SmpcDev::canary)
   if (++c->tick_no == 0) ++c->tick_no;
   *reinterpret_cast<uint32_t*>(h + tl.canary) = c->tick_no;
-  c->tick_used = tl.total;
+  c->tick_used = tick_bytes;
   const bool bar = c->bar_tick && !c->defer_upload && !pinned_tick && !inline_tick;
   // (whoever uploads: this ctx or its group; the in-launch reduction experiment does not carry it)
   c->canary_expect = (!pinned_tick && !inline_tick && !c->knobs.fused_reduce) ? c->tick_no : 0u;
@@ -868,12 +1014,12 @@ int prepare_tick(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
     // reads the previous tick's, echoes its number, and fetch_out has to fail the tick
     if (c->knobs.stale_tick && c->tick_no == c->knobs.stale_tick) {
     } else {
-      bar_copy(c->d_tick, h, tl.total);
+      bar_copy(c->d_tick, h, tick_bytes);
       bar_flush(c);
     }
   } else if (!c->defer_upload && !pinned_tick) {
     if (!inline_tick)
-      HIPCK(c, hipMemcpyAsync(c->d_tick, h, tl.total, hipMemcpyHostToDevice, c->stream));
+      HIPCK(c, hipMemcpyAsync(c->d_tick, h, tick_bytes, hipMemcpyHostToDevice, c->stream));
     else if (gates & SD_COST)
       HIPCK(c, hipMemcpyAsync(c->d_tick + tl.lut_cost, h + tl.lut_cost, 256 * sizeof(float), hipMemcpyHostToDevice,
                               c->stream));
@@ -914,6 +1060,7 @@ int prepare_tick(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
   d.pvalid = tb + tl.pvalid;
   d.pa_active = tb + tl.pa_active;
   d.pf_idx = reinterpret_cast<const uint32_t*>(tb + tl.pf_idx);
+  d.prune = reinterpret_cast<const float*>(tb + tl.prune);
   d.obs_critical_w = cr.obstacles.critical_weight;
   d.obs_repulsion_w = cr.obstacles.repulsion_weight;
   d.obs_collision_cost = cr.obstacles.collision_cost;
@@ -1009,7 +1156,6 @@ int prepare_tick(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
   rc = plan_launch(c, in, gates, nsamp, mode_now);
   if (rc != SMPC_OK) return rc;
 
-  predict_hint(c, in, u_in);
   c->gate_flags = gates;
   // with a footprint the two collision critics no longer see the same set of colliding rollouts,
   // and a pass reports one non-colliding count (CostCritic's, scored first): smpc_optimize counts

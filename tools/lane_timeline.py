@@ -18,6 +18,21 @@ u = scn.u0
 for _ in range(5):
     u_new, out = g.optimize(scn.tick, u)
     u = shift(u_new)
+# share of the groups that took the furthest-point scan (the instances with the prune test count
+# them; SMPC_FURTHEST_PRUNE=0: all of them), over a few more ticks
+sc = g.lib.smpc_debug_lane_scan_count
+sc.restype = C.c_int
+sc.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint32)]
+scanned, groups = C.c_ulonglong(0), C.c_uint32(0)
+assert sc(g.h, C.byref(scanned), C.byref(groups)) == 0     # (clears the counts)
+passes = 0
+for _ in range(8):
+    u_new, out = g.optimize(scn.tick, u)
+    u = shift(u_new)
+    passes += out.passes
+assert sc(g.h, C.byref(scanned), C.byref(groups)) == 0
+print(f"furthest-point scan: {scanned.value} of {passes * groups.value} groups "
+      f"({100.0 * scanned.value / max(1, passes * groups.value):.1f} %) over {passes} passes")
 fn = g.lib.smpc_debug_lane_timeline
 fn.restype = C.c_int
 fn.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
