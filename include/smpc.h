@@ -63,7 +63,15 @@ extern "C" {
  *      334-337,374-389,404-410; src/noise_generator.cpp:117-121]; Ackermann
  *      also bounds the turning radius of the updated control sequence
  *      [ref motion_models.hpp:110-117] and adds a ConstraintCritic term
- *      [ref src/critics/constraint_critic.cpp:54-69].                       */
+ *      [ref src/critics/constraint_critic.cpp:54-69].  They run the Omni
+ *      kernels with vy held at zero, except the plain cruise tick of the
+ *      lane-per-rollout pass from 61 440 rollouts up — the five critics with
+ *      ObstaclesCritic scored, every cost_power 1, no GoalAngle term, no
+ *      deployed-list critic, trajectory_point_step 4, time_steps <= 64 and a
+ *      multiple of four, the context not in a group — which runs
+ *      smpc_pass_lane_nh: the same pass without a vy stream, the same results
+ *      bit for bit.  SMPC_NONHOLO_PASS=omni in the environment at smpc_create
+ *      keeps the Omni kernels for those ticks too.                          */
 #define SMPC_MODEL_OMNI 0
 #define SMPC_MODEL_DIFF_DRIVE 1
 #define SMPC_MODEL_ACKERMANN 2
@@ -85,7 +93,11 @@ extern "C" {
                                              than 1 among the five critics takes the lane pass
                                              too (smpc_pass_lane_pow), but only from 61 440
                                              rollouts up, with or without this flag: below
-                                             that it stays on the wave-per-rollout pass */
+                                             that it stays on the wave-per-rollout pass.
+                                             Likewise the rows without a vy stream of a
+                                             non-holonomic model (smpc_pass_lane_nh): from
+                                             61 440 rollouts up, with or without this flag;
+                                             below that such a tick runs the Omni-form rows */
 #define SMPC_FLAG_PROFILE 0x4u            /* bracket each scoring pass with HIP
                                              events (smpc_tick_out.score_pass_ms) */
 

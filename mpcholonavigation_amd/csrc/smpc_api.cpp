@@ -187,6 +187,9 @@ void fill_score_args(smpc_ctx* c, uint32_t flags, const float* u_dev, const floa
 // wave-per-rollout pass (its geometry is planned for every tick).  A parking-form tick without an
 // instance is an error, as it always was.  A tick that scores with cost powers (pl.pow) picks among
 // the rows of smpc_pass_lane_pow, which include the two without a costmap lookup for its stripped passes.
+// A non-holonomic tick on the rows of smpc_pass_lane_nh (pl.nh) runs them for every pass whose flags
+// have one — a speculation miss, a later iteration, the all-collide re-score — and the plain row of
+// the flags where they have none (no ObstaclesCritic left: the Omni-form row reads the zero vy stream).
 struct PassChoice {
   PassPlan::Kind kind;
   const void* inst;        // WaveInst, LaneInst or SplitInst by kind; null: no instance
@@ -199,7 +202,7 @@ static PassChoice pass_for(const smpc_ctx* c, uint32_t flags)
   if (pl.kind == PassPlan::kSplit)
     if (const SplitInst* k = split_select(flags, T, c->dev.step, pl.split_nseg)) return {PassPlan::kSplit, k, &pl.split};
   if (pl.kind != PassPlan::kWave) {
-    const LaneInst* k = lane_select(flags, T, pl.rr, false, c->acker_r, pl.pow);
+    const LaneInst* k = lane_select(flags, T, pl.rr, false, c->acker_r, pl.pow, pl.nh);
     if (k || !(pl.rr || (flags & SD_STORE_TRAJ))) return {PassPlan::kLane, k, &pl.lane};
   }
   return {PassPlan::kWave, wave_select(c->R, c->score_mode, T), &pl.wave};
@@ -528,6 +531,7 @@ static Knobs read_knobs()
   k.window_side_max = number("SMPC_WINDOW_SIDE_MAX", -1);
   k.furthest_prune = number("SMPC_FURTHEST_PRUNE", 1) != 0;
   if (const char* e = getenv("SMPC_FOOTPRINT_PASS")) k.footprint_general = !strcmp(e, "general");
+  if (const char* e = getenv("SMPC_NONHOLO_PASS")) k.nonholo_omni = !strcmp(e, "omni");
   return k;
 }
 }  // namespace smpc_impl

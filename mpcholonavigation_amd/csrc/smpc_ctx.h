@@ -154,6 +154,9 @@ struct Knobs {
                                    // prune"): same kernel, every group scans — the A/B switch and the tests' unpruned answer
   bool footprint_general = false;  // SMPC_FOOTPRINT_PASS=general: consider_footprint ticks keep the general pass (MODE 2)
                                    // instead of the lean MODE 4 — to measure the two routes in one process, and a way back
+  bool nonholo_omni = false;       // SMPC_NONHOLO_PASS=omni: DiffDrive and Ackermann ticks keep the Omni-form lane rows (the
+                                   // zero vy stream read and carried along) instead of smpc_pass_lane_nh — to measure the
+                                   // two routes in one process, and a way back
 };
 
 // blocks per CU of the instance asked about last (the answer moves with the LDS a tick needs)
@@ -187,6 +190,7 @@ struct PassPlan {
   PassGeom split;             // kind == kSplit
   bool rr = false;            // the lane pass in its re-read form (no parked controls; T > 64 or SMPC_LANE_REREAD=1)
   bool pow = false;           // the lane pass scores with cost powers other than 1: the rows of smpc_pass_lane_pow
+  bool nh = false;            // the lane pass of a non-holonomic model without the vy stream: the rows of smpc_pass_lane_nh
   uint32_t split_nseg = 4;    // lanes per rollout of the split pass: 4 or 2
   uint32_t window_bytes = 0;  // first LDS region of the lane pass
 };

@@ -15,7 +15,8 @@
 
 struct WaveInst { int r, mode; bool full; const void* fn; };                                       // smpc_pass<R, MODE, FULL>
 // pow: the instance is smpc_pass_lane_pow<...>, the same template arguments with general cost powers
-struct LaneInst { bool full, obst, many; int nch; bool rr, ga, quads; int tc; bool dep; const void* fn; bool pow; };   // smpc_pass_lane<...>
+// nh: the instance is smpc_pass_lane_nh<...>, the same template arguments without the vy stream
+struct LaneInst { bool full, obst, many; int nch; bool rr, ga, quads; int tc; bool dep; const void* fn; bool pow, nh; };   // smpc_pass_lane<...>
 struct SplitInst { int nseg; bool full; const void* fn; };                                         // smpc_pass_split<NSEG, FULL>
 
 // Selectors: the instance that scores these flags at this horizon, or null when there is none.
@@ -26,7 +27,10 @@ const WaveInst* wave_select(int R, int mode, uint32_t T);
 // (smpc_group_optimize); acker_r: the Ackermann min_turning_r, < 0 for the other models
 // pow: the tick scores with a cost_power other than 1 among the five critics — only then is a row of
 // smpc_pass_lane_pow returned (single context, parking form); false behaves as it always did
-const LaneInst* lane_select(uint32_t flags, uint32_t T, bool rr, bool many, float acker_r, bool pow);
+// nh: the tick runs a non-holonomic model on the rows of smpc_pass_lane_nh — flags that select a
+// plain ObstaclesCritic row of whole quads get that row's twin without the vy stream, every other
+// flags the row they always got (a pass stripped of ObstaclesCritic, say)
+const LaneInst* lane_select(uint32_t flags, uint32_t T, bool rr, bool many, float acker_r, bool pow, bool nh = false);
 // step: PathAlign's trajectory_point_step; nseg: lanes per rollout, 4 or 2
 const SplitInst* split_select(uint32_t flags, uint32_t T, uint32_t step, uint32_t nseg);
 

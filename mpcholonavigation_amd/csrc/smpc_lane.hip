@@ -25,8 +25,9 @@
 // T = 64 or 128 in the re-read form.  smpc_pass_lane scores with every cost_power == 1;
 // smpc_pass_lane_pow is the same body with general powers on the five critics, applied to each
 // critic's per-rollout total in the epilogue (single context, parking form; the host sends it
-// ticks of at least kLaneMinBatch rollouts).  smpc_prepare.cpp routes every other tick to
-// smpc_pass.  Compiled with -ffp-contract=off like smpc_kernels.hip.
+// ticks of at least kLaneMinBatch rollouts); smpc_pass_lane_nh is the same body without a vy stream,
+// for the plain cruise tick of the non-holonomic motion models (single context, parking form, whole
+// quads; same batch rule).  smpc_prepare.cpp routes every other tick to smpc_pass.  Compiled with -ffp-contract=off like smpc_kernels.hip.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -130,22 +131,36 @@ hipError_t smpc_launch_lane_reduce(const float* v, const float* w, float* out, h
 // The only form for T > 64 (3 T parked values per lane do not fit any register budget).
 #define LANE_PASS_KERNEL smpc_pass_lane
 #define LANE_PASS_POW false
+#define LANE_PASS_NH false
 #include "smpc_lane_pass.inc"
 #undef LANE_PASS_KERNEL
 #undef LANE_PASS_POW
+#undef LANE_PASS_NH
 // the same pass with general cost powers on the five critics (single context, parking form)
 #define LANE_PASS_KERNEL smpc_pass_lane_pow
 #define LANE_PASS_POW true
+#define LANE_PASS_NH false
 #include "smpc_lane_pass.inc"
 #undef LANE_PASS_KERNEL
 #undef LANE_PASS_POW
+#undef LANE_PASS_NH
+// the same pass without the vy stream, for the non-holonomic motion models (single context, parking
+// form, the plain ObstaclesCritic rows of whole quads)
+#define LANE_PASS_KERNEL smpc_pass_lane_nh
+#define LANE_PASS_POW false
+#define LANE_PASS_NH true
+#include "smpc_lane_pass.inc"
+#undef LANE_PASS_KERNEL
+#undef LANE_PASS_POW
+#undef LANE_PASS_NH
 
 // ---------------------------------------------------------------------------
 // The instances (smpc_inst.h): one row each.  Name, LDS limit, occupancy, selection and launch
 // all read this table; adding an instance is adding a row and, if need be, a rule in lane_select.
 // ---------------------------------------------------------------------------
-#define LANE_INST(...) {__VA_ARGS__, reinterpret_cast<const void*>(&smpc_pass_lane<__VA_ARGS__>), false}
-#define LANE_INST_POW(...) {__VA_ARGS__, reinterpret_cast<const void*>(&smpc_pass_lane_pow<__VA_ARGS__>), true}
+#define LANE_INST(...) {__VA_ARGS__, reinterpret_cast<const void*>(&smpc_pass_lane<__VA_ARGS__>), false, false}
+#define LANE_INST_POW(...) {__VA_ARGS__, reinterpret_cast<const void*>(&smpc_pass_lane_pow<__VA_ARGS__>), true, false}
+#define LANE_INST_NH(...) {__VA_ARGS__, reinterpret_cast<const void*>(&smpc_pass_lane_nh<__VA_ARGS__>), false, true}
 //                          FULL   OBST   MANY  NCH RR     GA     QUADS  TC  DEP
 static const LaneInst kLaneInst[] = {
   LANE_INST(false, false, false, 1, false, false, false, 0, false),   // the five critics: ragged horizon
@@ -175,22 +190,34 @@ static const LaneInst kLaneInst[] = {
   LANE_INST_POW(false, true, false, 1, false, true, false, 0, false),
   LANE_INST_POW(true, false, false, 1, false, false, true, 0, false),     // no costmap lookup (a tick stripped of
   LANE_INST_POW(false, false, false, 1, false, false, false, 0, false),   // ObstaclesCritic after it was planned)
+  // smpc_pass_lane_nh: no vy stream, the twins of the plain ObstaclesCritic rows of whole quads
+  LANE_INST_NH(true, true, false, 1, false, false, true, 0, false),       // T = 64
+  LANE_INST_NH(false, true, false, 1, false, false, true, 56, false),     // T = 56
+  LANE_INST_NH(false, true, false, 1, false, false, true, 0, false),      // whole quads, T < 64
 };
 #undef LANE_INST
 #undef LANE_INST_POW
+#undef LANE_INST_NH
 
 static const LaneInst* lane_find(bool full, bool obst, bool many, int nch, bool rr, bool ga, bool quads, int tc, bool dep,
-                                 bool pow = false)
+                                 bool pow = false, bool nh = false)
 {
   for (const LaneInst& k : kLaneInst)
     if (k.full == full && k.obst == obst && k.many == many && k.nch == nch && k.rr == rr && k.ga == ga &&
-        k.quads == quads && k.tc == tc && k.dep == dep && k.pow == pow)
+        k.quads == quads && k.tc == tc && k.dep == dep && k.pow == pow && k.nh == nh)
       return &k;
   return nullptr;
 }
 
-const LaneInst* lane_select(uint32_t flags, uint32_t T, bool rr, bool many, float acker_r, bool pow)
+const LaneInst* lane_select(uint32_t flags, uint32_t T, bool rr, bool many, float acker_r, bool pow, bool nh)
 {
+  if (nh) {
+    // the row these flags always got; where that is a plain ObstaclesCritic row of whole quads, its
+    // twin without the vy stream
+    const LaneInst* k = lane_select(flags, T, rr, many, acker_r, pow, false);
+    if (!k || !k->obst || k->many || k->rr || k->ga || k->dep || k->pow || !k->quads) return k;
+    return lane_find(k->full, true, false, 1, false, false, true, k->tc, false, false, true);
+  }
   const uint32_t dep_set = SD_CONSTRAINT | SD_COST | SD_TWIRLING, lean_extra = dep_set | SD_GOAL | SD_PATH_ANGLE;
   // what no instance scores: trajectory write-out, path orientations, the general pass's critics
   if (flags & (SD_STORE_TRAJ | SD_USE_PATH_YAW | (SD_EXTRA_CRITICS & ~lean_extra))) return nullptr;
@@ -243,7 +270,7 @@ hipError_t lane_launch(const LaneInst* k, const SmpcDev& p, const SmpcDev* d_man
   // the instance's name with every template argument written out, as rocprofv3 prints it
   auto b = [](bool v) {return v ? "true" : "false";};
   snprintf(smpc_last_pass_kernel, sizeof(smpc_last_pass_kernel), "smpc_pass_lane%s<%s, %s, %s, %d, %s, %s, %s, %d, %s>",
-           k->pow ? "_pow" : "", b(k->full), b(k->obst), b(k->many), k->nch, b(k->rr), b(k->ga), b(k->quads), k->tc, b(k->dep));
+           k->pow ? "_pow" : (k->nh ? "_nh" : ""), b(k->full), b(k->obst), b(k->many), k->nch, b(k->rr), b(k->ga), b(k->quads), k->tc, b(k->dep));
   static const SmpcDev none{};   // (the grouped instances read their parameter blocks from device memory)
   void* args[] = {const_cast<SmpcDev*>(d_many ? &none : &p), const_cast<SmpcLds*>(&L), &d_many};
   return inst_launch(k->fn, d_many ? dim3(grid, n) : dim3(grid), block, args, L.total, st);

@@ -1,13 +1,19 @@
 // smpc_lane_pass.inc — the lane-per-rollout scoring pass (see smpc_lane.hip, which includes this file
-// twice).  LANE_PASS_KERNEL names the kernel, LANE_PASS_POW says whether its per-rollout epilogue
-// scores with general cost powers:
+// three times).  LANE_PASS_KERNEL names the kernel, LANE_PASS_POW says whether its per-rollout epilogue
+// scores with general cost powers, LANE_PASS_NH whether the motion model is non-holonomic:
 //   smpc_pass_lane      every cost_power == 1 (the lean association of smpc_pass MODE 0)
 //   smpc_pass_lane_pow  a cost_power other than 1 among the five critics (a legal tuning value:
 //                       obstacles_critic.cpp:173-177, path_align_critic.cpp:135).  The power applies to a
 //                       critic's per-rollout TOTAL, so time loop, lookup pipeline, furthest-point scan,
 //                       softmax and transpose-reduce are the same text; only the epilogue differs: five
 //                       small double-precision powers per rollout, where the loop's registers are dead.
-// Two kernels from one text, not a tenth template argument and not a shared inlined body: the
+//   smpc_pass_lane_nh   DiffDrive and Ackermann on a plain cruise tick: vy is zero at every step of
+//                       every rollout, so this kernel has no vy — no vy noise load (two tensors of the
+//                       three per step), no vy control, no vy term in the rotation or the gamma sum,
+//                       nothing parked for it and one transpose-reduce less per group.  Everything
+//                       else is the same text; every line it leaves out is marked "NH".  It reads
+//                       neither p.svy nor the vy row of the tick block nor the vy noise tensor.
+// Three kernels from one text, not a tenth template argument and not a shared inlined body: the
 // power-1 instances keep their names (profiles and tests know them) and compile to the code they
 // compiled to before (a body shared through a __forceinline__ function kept their register counts
 // but not their instructions).
@@ -16,6 +22,9 @@ __global__ void __launch_bounds__(RR ? LANE_BLOCK_RR : LANE_BLOCK, 1)
 LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ many)
 {
   constexpr bool POW = LANE_PASS_POW;
+  constexpr bool NH = LANE_PASS_NH;
+  static_assert(!NH || (OBST && !MANY && !RR && !GA && !DEP && !POW && NCH == 1 && QUADS),
+                "no vy stream: the plain ObstaclesCritic rows of whole quads only");
   static_assert(RR || NCH == 1, "parked controls: one chunk of 64 steps");
   static_assert(!POW || (!MANY && !RR && !DEP), "cost powers: the single-context parking form of the five critics");
   // QUADS: T is a multiple of four, so every step of every executed quad is live and the time
@@ -135,7 +144,7 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
       float a = 0.f, b = 0.f, c = 0.f;
       const uint32_t Tn = FULL ? 64u * NCH : (TC ? (uint32_t)TC : p.T);
       for (uint32_t t = (uint32_t)tid; t < Tn; t += WAVE) {
-        const float ux = tk.u[t], uy = tk.u[Tn + t], uz = tk.u[2 * Tn + t];
+        const float ux = tk.u[t], uy = NH ? 0.f : tk.u[Tn + t], uz = tk.u[2 * Tn + t];
         a = fmaf(ux, ux, a);
         b = fmaf(uy, uy, b);
         c = fmaf(uz, uz, c);
@@ -243,10 +252,12 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
     // index with the same scalar q' (the constant 8 i folds into the base register) and can
     // share one s_set_gpr_idx_on/off pair.
     f32x32 PX0, PX1, PY0, PY1;
-    if (!FULL && !RR) PX0 = PX1 = PY0 = PY1 = (f32x32)(0.f);
+    if constexpr (NH) {   // (nothing is parked for vy: PY0 and PY1 are never touched)
+      if (!FULL) PX0 = PX1 = (f32x32)(0.f);
+    } else if (!FULL && !RR) PX0 = PX1 = PY0 = PY1 = (f32x32)(0.f);
 
     // ================= rollout + per-step critics, lane = rollout =====================
-    float cpx = p.svx, cpy = p.svy, cpz = p.swz;   // v[:,0] = measured speed, v[:,t] = c[:,t-1]
+    float cpx = p.svx, cpy = NH ? 0.f : p.svy, cpz = p.swz;   // v[:,0] = measured speed, v[:,t] = c[:,t-1]
     float acc_yaw = 0.f, ax = 0.f, ay = 0.f;
     float cs_prev = p.cos0, sn_prev = p.sin0;
     float x = 0.f, y = 0.f;
@@ -297,17 +308,19 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
                        float& cwz) __attribute__((always_inline)) {
       // NoiseGenerator::setNoisedControls (noise_generator.cpp:65-74)
       cvx = ux + n0;
-      cvy = uy + n1;
+      if constexpr (!NH) cvy = uy + n1;
       cwz = uz + n2;
       const float vx = cpx, vy = cpy, wz = cpz;
       cpx = cvx;
-      cpy = cvy;
+      if constexpr (!NH) cpy = cvy;
       cpz = cwz;
       // integrateStateVelocities (optimizer.cpp:313-343): sequential float cumsums
       acc_yaw = acc_yaw + wz * dt;
       const float yaw = acc_yaw + yaw0;
-      const float dxr = vx * cs_prev - vy * sn_prev;
-      const float dyr = vx * sn_prev + vy * cs_prev;
+      // (NH: vy is +-0 in the other kernels too, and a -+ (+-0) == a but for the sign of a zero,
+      // which the cumulative sums below, starting at +0, do not keep)
+      const float dxr = NH ? vx * cs_prev : vx * cs_prev - vy * sn_prev;
+      const float dyr = NH ? vx * sn_prev : vx * sn_prev + vy * cs_prev;
       ax = ax + dxr * dt;
       ay = ay + dyr * dt;
       if constexpr (DEP) {
@@ -393,7 +406,7 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
       // +35 % at 2 M rollouts.)
       gx = fmaf(ux, cvx, gx);
       gz = fmaf(uz, cwz, gz);
-      gy = fmaf(uy, cvy, gy);
+      if constexpr (!NH) gy = fmaf(uy, cvy, gy);
 
       // PathAlignCritic sample (uniform in t): trajectory points step, 2 step, ...
       // (trajectory_point_step is 4 here, the reference's default — the host sends any other
@@ -464,14 +477,19 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
       return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rn, loff, tensor * noise_bytes + tc * step_bytes, 0));
     };
     auto ldu = [&](uint32_t ctrl, uint32_t t) -> float {return cu[ctrl * T + ((FULL || t < T) ? t : T - 1)];};
-    float nq[12], uq[12];
+    float nq[12], uq[12];   // (NH: the slots 3 i + 1 are never written or read — eight live values each)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       nq[3 * i + 0] = ld(0, i);
-      nq[3 * i + 1] = ld(1, i);
+      if constexpr (!NH) nq[3 * i + 1] = ld(1, i);
       nq[3 * i + 2] = ld(2, i);
 #pragma unroll
-      for (int k = 0; k < 3; ++k) uq[3 * i + k] = ldu(k, i);
+      for (int k = 0; k < 3; ++k) {
+        if constexpr (NH) {
+          if (k == 1) continue;
+        }
+        uq[3 * i + k] = ldu(k, i);
+      }
     }
     uint64_t clk = __builtin_amdgcn_s_memtime();
     // four steps; the quad returns their noised controls in cq[3 i + ctrl] for the caller to park
@@ -497,7 +515,12 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
       }
       float uc[12];
 #pragma unroll
-      for (int j = 0; j < 12; ++j) uc[j] = uq[j];
+      for (int j = 0; j < 12; ++j) {
+        if constexpr (NH) {
+          if (j % 3 == 1) continue;
+        }
+        uc[j] = uq[j];
+      }
       // The next quad's controls and noise are fetched a quad ahead.  Where the trip count is a
       // run-time value (T < 64) the fetch is unconditional — the last quad re-reads the last
       // row: behind a run-time "is there a next quad" the waitcnt pass gives up the prefetch
@@ -507,7 +530,12 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-          for (int k = 0; k < 3; ++k) uq[3 * i + k] = ldu(k, 4 * (q + 1) + i);
+          for (int k = 0; k < 3; ++k) {
+            if constexpr (NH) {
+              if (k == 1) continue;
+            }
+            uq[3 * i + k] = ldu(k, 4 * (q + 1) + i);
+          }
       }
       // kQuadOff (whole quads): one scalar offset per tensor and QUAD — the next quad's first
       // step, clamped to the last quad where the fetch is unconditional — instead of three scalar
@@ -520,7 +548,7 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
       for (int i = 0; i < 4; ++i) {
         const uint32_t t = 4 * q + i;
         // this step's noise; its registers are refilled at once with step t + 4
-        const float n0 = nq[3 * i], n1 = nq[3 * i + 1], n2 = nq[3 * i + 2];
+        const float n0 = nq[3 * i], n1 = NH ? 0.f : nq[3 * i + 1], n2 = nq[3 * i + 2];
         if (kAlwaysAhead || q + 1 < nquad) {
           if constexpr (kQuadOff) {
             const uint32_t tq = (FULL || TC || 4 * (q + 1) < T) ? 4 * (q + 1) : T - 4;
@@ -529,7 +557,7 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
               return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rn, loff + (uint32_t)i * step_bytes, so, 0));
             };
             nq[3 * i + 0] = ldq(so0);
-            nq[3 * i + 1] = ldq(so1);
+            if constexpr (!NH) nq[3 * i + 1] = ldq(so1);
             nq[3 * i + 2] = ldq(so2);
           } else {
             nq[3 * i + 0] = ld(0, t + 4);
@@ -539,7 +567,7 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
         }
         cq[3 * i] = cq[3 * i + 1] = cq[3 * i + 2] = 0.f;
         if (QUADS || t < T)
-          do_step(t, i == 0, uc[3 * i], uc[3 * i + 1], uc[3 * i + 2], n0, n1, n2, cq[3 * i], cq[3 * i + 1],
+          do_step(t, i == 0, uc[3 * i], NH ? 0.f : uc[3 * i + 1], uc[3 * i + 2], n0, n1, n2, cq[3 * i], cq[3 * i + 1],
                   cq[3 * i + 2]);
       }
     };
@@ -555,10 +583,10 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
         _Pragma("unroll") for (int i = 0; i < 4; ++i) { \
           if constexpr (HI) { \
             PX1[8 * i + ((Q) - 8)] = cq[3 * i]; \
-            PY1[8 * i + ((Q) - 8)] = cq[3 * i + 1]; \
+            if constexpr (!NH) PY1[8 * i + ((Q) - 8)] = cq[3 * i + 1]; \
           } else { \
             PX0[8 * i + (Q)] = cq[3 * i]; \
-            PY0[8 * i + (Q)] = cq[3 * i + 1]; \
+            if constexpr (!NH) PY0[8 * i + (Q)] = cq[3 * i + 1]; \
           } \
           park[(4 * (Q) + i) * LANE_PARK_STRIDE + lane] = cq[3 * i + 2]; \
         } \
@@ -723,7 +751,7 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
       if (ga_on) uni += (ga_sum / (float)T) * p.ga_weight;
       lin += p.g_vx * (gx - s_su2[0]);
       lin += p.g_wz * (gz - s_su2[2]);
-      lin += p.g_vy * (gy - s_su2[1]);
+      if constexpr (!NH) lin += p.g_vy * (gy - s_su2[1]);
       cost += uni + lin;
       if (pa_on) {
         const float c_pa = pa_num > 0.f ? pa_sum * fast_rcp(pa_num) : 0.f;
@@ -779,12 +807,14 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
           V[32 + t] = PX1[8 * (t & 3) + (t >> 2)];
         }
         Ux[0] = fmaf(Ux[0], f, lane_reduce64(V, lw, lane));
+        if constexpr (!NH) {   // (NH: Uy stays +0, what the weighted sum of zeros is)
 #pragma unroll
-        for (int t = 0; t < 32; ++t) {
-          V[t] = PY0[8 * (t & 3) + (t >> 2)];
-          V[32 + t] = PY1[8 * (t & 3) + (t >> 2)];
+          for (int t = 0; t < 32; ++t) {
+            V[t] = PY0[8 * (t & 3) + (t >> 2)];
+            V[32 + t] = PY1[8 * (t & 3) + (t >> 2)];
+          }
+          Uy[0] = fmaf(Uy[0], f, lane_reduce64(V, lw, lane));
         }
-        Uy[0] = fmaf(Uy[0], f, lane_reduce64(V, lw, lane));
       }
       {
         // wz from the LDS slot: lane t walks its row of 64 rollouts

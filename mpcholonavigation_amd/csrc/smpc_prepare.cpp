@@ -755,6 +755,22 @@ static int plan_launch(smpc_ctx* c, const smpc_tick_in* in, uint32_t gates, uint
   if (lane_now && !split_now && B < kLaneMinBatch && !c->lane_forced) lane_now = false;
 
   pl.pow = pl.pow && lane_now;   // (a path too long for the lane pass's LDS: the wave pass after all)
+  // DiffDrive and Ackermann: vy is zero at every step, and the Omni-form rows read a zero-filled
+  // noise tensor and carry zeros through the rotation, the gamma sum, 64 parked registers and a
+  // transpose-reduce per group.  A tick that would run a PLAIN lane row anyway — lean MODE 0 with
+  // ObstaclesCritic scored, no GoalAngle term, no deployed-list critic, no cost power, the parking
+  // form in whole quads, one context — runs that row's twin of smpc_pass_lane_nh, which has no vy
+  // (same grid, block, LDS and group order: the geometry planned above; same results, DESIGN.md
+  // 4.2d).  From kLaneMinBatch rollouts up only, also for a context that asks for the lane pass
+  // (SMPC_FLAG_LANE_PER_ROLLOUT, SMPC_PASS=lane): nothing about these rows is measured below it.
+  // Every other tick of such a model keeps the Omni-form instance it had.  SMPC_NONHOLO_PASS=omni:
+  // the Omni-form rows for these ticks too.
+  pl.nh = !c->holonomic && !c->knobs.nonholo_omni && lane_now && !split_now && mode_now == 0 && !pl.pow && !pl.rr &&
+    !c->in_group && step == 4 && T <= 64 && (T & 3u) == 0 && B >= kLaneMinBatch &&
+    [&] {
+      const LaneInst* k = lane_select(gates, T, false, false, c->acker_r, false, true);
+      return k && k->nh;
+    }();
   pl.kind = split_now ? PassPlan::kSplit : (lane_now ? PassPlan::kLane : PassPlan::kWave);
   c->plan = pl;
   mode_out = mode_now;
