@@ -412,7 +412,7 @@ static int launch_draw(smpc_ctx* c, float* nvx, float* nvy, float* nwz, float* t
     if (c->holonomic)
       HIPCK(c, smpc_launch_fill_noise_tm(tvy, B, T, base, c->seed, 2, c->epoch, c->cfg.vy_std, st));
     else
-      HIPCK(c, hipMemsetAsync(tvy, 0, static_cast<size_t>(SMPC_GM_ROLLOUTS(B)) * T * sizeof(float), st));
+      HIPCK(c, hipMemsetAsync(tvy, 0, SMPC_GM_ELEMS(B, T) * sizeof(float), st));
     *rm_valid_out = false;
     return SMPC_OK;
   }
@@ -484,8 +484,9 @@ int redraw_async(smpc_ctx* c)
     HIPCK(c, hipEventCreateWithFlags(&c->ev_fill, hipEventDisableTiming));
   }
   if (c->use_tpr && !c->b_tvx) {
-    const size_t ngm = static_cast<size_t>(SMPC_GM_ROLLOUTS(c->cfg.batch_size)) * c->cfg.time_steps * sizeof(float);
+    const size_t ngm = SMPC_GM_ELEMS(c->cfg.batch_size, c->cfg.time_steps) * sizeof(float);
     HIPCK(c, hipMalloc(&c->b_tvx, 3 * ngm));
+    HIPCK(c, hipMemset(c->b_tvx, 0, 3 * ngm));   // (the padding steps of a ragged horizon: zeros)
     c->b_tvy = c->b_tvx + ngm / sizeof(float);
     c->b_twz = c->b_tvy + ngm / sizeof(float);
   }
@@ -688,7 +689,7 @@ int smpc_create(const smpc_config* cfg, smpc_ctx** out)
     }
     if (cfg->flags & SMPC_FLAG_STORE_TRAJECTORIES) tpr = false;   // visualisation path: wave pass
     // the group-major copies (smpc_dev.h: SMPC_GM_INDEX): the batch padded to whole groups of 64
-    const size_t ngm = static_cast<size_t>(SMPC_GM_ROLLOUTS(cfg->batch_size)) * T * sizeof(float);
+    const size_t ngm = SMPC_GM_ELEMS(cfg->batch_size, T) * sizeof(float);
     if (3ull * ngm >= (1ull << 32)) tpr = false;   // its buffer descriptor spans the three noise tensors
     c->use_tpr = tpr;
     if (tpr) {
@@ -696,7 +697,7 @@ int smpc_create(const smpc_config* cfg, smpc_ctx** out)
       CK(hipMalloc(&c->d_tvx, 3 * ngm));
       c->d_tvy = c->d_tvx + ngm / sizeof(float);
       c->d_twz = c->d_tvy + ngm / sizeof(float);
-      if (!c->holonomic) CK(hipMemset(c->d_tvy, 0, ngm));
+      CK(hipMemset(c->d_tvx, 0, 3 * ngm));   // the padding steps of a ragged horizon, and vy of a non-holonomic model
       CK(lane_set_lds_limit(static_cast<int>(kLdsPerCu)));
       CK(split_set_lds_limit(static_cast<int>(kLdsPerCu)));
     }

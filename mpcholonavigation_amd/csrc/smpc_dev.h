@@ -31,12 +31,18 @@
                           SD_FP_OBSTACLES | SD_FP_COST | SD_PATH_ALIGN_LEGACY)
 
 // Layout of the noise the lane-per-rollout and split passes read ("group-major"): element (b, t) of
-// a [B, T] tensor sits at ((b / 64) T + t) 64 + b % 64 — the 64 rollouts of a wave-group and their T
-// steps are one run of 256 T bytes, where the time-major [T][B] layout of rounds 1-2 put a group's
-// consecutive steps B x 4 bytes (8 MB at the bench size) apart: one page per step and tensor
-// (measured at 2 097 152 x 64: 391 -> 376 us per pass).  B is padded to a multiple of 64.
+// a [B, T] tensor sits at (((b / 64) (T4 / 4) + t / 4) 64 + b % 64) 4 + t % 4, T4 = T rounded up to a
+// multiple of four — the 64 rollouts of a wave-group and their T4 steps are one run of 256 T4 bytes
+// (where the time-major [T][B] layout of rounds 1-2 put a group's consecutive steps B x 4 bytes, 8 MB
+// at the bench size, apart: one page per step and tensor; measured at 2 097 152 x 64: 391 -> 376 us per
+// pass), and inside it the four steps of a quad are 16 contiguous bytes of their lane: a quad of a
+// group is ONE 16-byte load per lane, 1 KB contiguous per wave instruction.  B is padded to a multiple
+// of 64, T to a multiple of four; the padding steps hold zeros and are never consumed.
 #define SMPC_GM_ROLLOUTS(B) ((((B) + 63u) / 64u) * 64u)
-#define SMPC_GM_INDEX(b, t, T) ((((size_t)(b) >> 6) * (T) + (t)) * 64u + ((b) & 63u))
+#define SMPC_GM_STEPS(T) (((T) + 3u) & ~3u)
+#define SMPC_GM_ELEMS(B, T) ((size_t)SMPC_GM_ROLLOUTS(B) * SMPC_GM_STEPS(T))   /* floats of one tensor */
+#define SMPC_GM_INDEX(b, t, T) \
+  (((((size_t)(b) >> 6) * (SMPC_GM_STEPS(T) >> 2) + ((t) >> 2)) * 64u + ((b) & 63u)) * 4u + ((t) & 3u))
 
 #define SMPC_MAX_PATH 1024        // path points staged in LDS
 #define SMPC_MAX_R 4              // time steps per lane (T <= 64 * SMPC_MAX_R)

@@ -10,8 +10,9 @@
 //     the float cumulative sums run in the reference's own sequential order
 //     (optimizer.cpp:313-343);
 //   * everything uniform over the batch (u[t], map geometry, weights) sits in SGPRs;
-//   * noise is read from a group-major copy [B / 64][T][64] (smpc_dev.h): one coalesced 256-B
-//     piece per array and step, a group's steps back to back, prefetched four steps ahead;
+//   * noise is read from a group-major copy [B / 64][T / 4][64][4] (smpc_dev.h): one coalesced 1 KB
+//     piece per array and quad of steps (a 16-byte load per lane), a group's quads back to back,
+//     prefetched a quad ahead;
 //   * the noised controls of the 64 rollouts stay PARKED IN REGISTERS (3 x 64 per lane)
 //     until the rollouts' costs, hence softmax weights, are known; then
 //     U[t] += sum_b w_b c[b][t] is a 64 x 64 transpose-reduce done in registers:
@@ -69,14 +70,16 @@ __global__ void __launch_bounds__(256) smpc_relayout(const float* __restrict__ s
       tile[k][lx] = (b < B && t < T) ? src[(size_t)b * T + t] : 0.f;
     }
     __syncthreads();
-    for (uint32_t k = ly; k < 32; k += 8) {      // 32 rollouts of one group at one step: 128 bytes in a row
-      const uint32_t t = t0 + k, b = b0 + lx;
-      if (b < B && t < T) dst[SMPC_GM_INDEX(b, t, T)] = tile[lx][k];
+    for (uint32_t k = ly; k < 32; k += 8) {      // a quad of steps of 8 rollouts of one group: 128 bytes in a row
+      const uint32_t e = k * 32 + lx, tl = 4 * (e >> 7) + (e & 3), bb = (e >> 2) & 31;
+      const uint32_t t = t0 + tl, b = b0 + bb;
+      if (b < B && t < T) dst[SMPC_GM_INDEX(b, t, T)] = tile[bb][tl];
     }
   } else {
     for (uint32_t k = ly; k < 32; k += 8) {
-      const uint32_t t = t0 + k, b = b0 + lx;
-      tile[lx][k] = (b < B && t < T) ? src[SMPC_GM_INDEX(b, t, T)] : 0.f;
+      const uint32_t e = k * 32 + lx, tl = 4 * (e >> 7) + (e & 3), bb = (e >> 2) & 31;
+      const uint32_t t = t0 + tl, b = b0 + bb;
+      tile[bb][tl] = (b < B && t < T) ? src[SMPC_GM_INDEX(b, t, T)] : 0.f;
     }
     __syncthreads();
     for (uint32_t k = ly; k < 32; k += 8) {

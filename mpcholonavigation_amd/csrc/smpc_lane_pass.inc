@@ -177,12 +177,15 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
   // so that uniform loads stay scalar loads although the kernel also stores to global memory
   const cfloat_p cu = (cfloat_p)(uintptr_t)p.u;
   const uint32_t T = FULL ? 64u * NCH : (TC ? (uint32_t)TC : p.T), B = p.B;
-  // group-major noise through buffer loads: per step one scalar offset (t * 256) serves the
-  // three tensors, the lane's own offset (its group's start + lane * 4) is the vector offset
+  // group-major noise through buffer loads: per QUAD of steps one scalar offset per tensor
+  // (tensor * noise_bytes + quad * 1024), the lane's own offset (its group's start + lane * 16) is the
+  // vector offset and the same for the whole group — a lane's four steps of a quad are 16 contiguous
+  // bytes (smpc_dev.h), one 16-byte load
   // (the host lays the three tensors out back to back: ONE descriptor, four scalar
   // registers instead of twelve — the loop is short of them — and the tensor is part of the
   // scalar offset)
-  const uint32_t noise_bytes = T * SMPC_GM_ROLLOUTS(B) * 4u;   // one tensor, group-major (smpc_dev.h)
+  const uint32_t T4 = SMPC_GM_STEPS(T);
+  const uint32_t noise_bytes = (uint32_t)SMPC_GM_ELEMS(B, T) * 4u;   // one tensor, group-major (smpc_dev.h)
   const __amdgpu_buffer_rsrc_t rn = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.tvx), 0, 3u * noise_bytes, 0x00020000);
   const float dt = p.dt, yaw0 = p.yaw0;
   const double x0 = p.x0, y0 = p.y0;
@@ -299,17 +302,34 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
     // loop constants of the cell index, in scalar registers.  (A scalar operand halves the issue
     // rate of the instruction that reads it, tools/ubench; held in vector registers instead they
     // push the parking form into scratch, 514.5 against 380.0 us at 2 097 152 x 64: DESIGN.md 4.2.)
-    const float k_rinv = p.rinvf, k_cx = p.cxf, k_cy = p.cyf;
+    // kCellVgpr: the two addends of the cell index in vector registers all the same, in the instances
+    // that have the room since the noise arrives in quads (a lane offset per step and tensor is gone):
+    // the fused multiply-add reads one scalar (k_rinv) and needs no v_mov_b32 for a second one, two
+    // instructions less per step.  Per instance, like kPrune: the plain rows of a horizon known at
+    // compile time and their twins without vy, which keep ScratchSize 0 with it; not tried elsewhere.
+    constexpr bool kCellVgpr = OBST && QUADS && (FULL || TC != 0) && !GA && !DEP && !MANY && !RR && !POW;
+    const float k_rinv = p.rinvf, k_cx = kCellVgpr ? in_vgpr(p.cxf) : p.cxf, k_cy = kCellVgpr ? in_vgpr(p.cyf) : p.cyf;
     const float k_edge = 0.5f - p.cell_eps_w;
+    // kAddAtTop: the quad's twelve noised controls are formed at its top — the same additions,
+    // earlier — so that the noise tuples die at once, and the next quad's loads go out later in the
+    // quad, in front of step kFetchAt (run_quad).  Per instance: three rows of T = 64 spill 8-20 bytes
+    // to scratch with both the current and the coming tuples live across the whole quad.  The grouped
+    // deployed-list row fetches behind the quad's first step, PathAlign's sample step, where the
+    // registers are scarcest; the two GoalAngle rows (36 and 20 bytes that way, 36 and 12 a step later)
+    // in front of the last step, where the per-step refill held as many registers as this form does.
+    constexpr bool kAddAtTop = FULL && !RR && (GA || (MANY && DEP));
+    constexpr int kFetchAt = GA ? 3 : 1;
     // one time step for the 64 rollouts of this wave; t, ux, uy, uz are wave-uniform
     // sample_slot: this step is a multiple of four (known at compile time in the unrolled quad)
     auto do_step = [&](const uint32_t t, const bool sample_slot, const float ux, const float uy, const float uz,
                        const float n0, const float n1, const float n2, float& cvx, float& cvy,
                        float& cwz) __attribute__((always_inline)) {
       // NoiseGenerator::setNoisedControls (noise_generator.cpp:65-74)
-      cvx = ux + n0;
-      if constexpr (!NH) cvy = uy + n1;
-      cwz = uz + n2;
+      if constexpr (!kAddAtTop) {
+        cvx = ux + n0;
+        if constexpr (!NH) cvy = uy + n1;
+        cwz = uz + n2;
+      }
       const float vx = cpx, vy = cpy, wz = cpz;
       cpx = cvx;
       if constexpr (!NH) cpy = cvy;
@@ -465,24 +485,25 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
       }
     };
 
-    // noise: step t is a uniform base + this lane's offset; four steps in flight.
+    // noise: a quad of steps is a uniform base + this lane's offset; one quad in flight.
     // The control sequence of the next four steps is fetched (scalar loads) a quad ahead too.
-    // noise, group-major: step t of this wave's 64 rollouts is 256 bytes behind step t - 1
-    const uint32_t loff = ((bl >> 6) * T * 64u + (bl & 63u)) * 4u;   // SMPC_GM_INDEX(bl, 0, T) in 32 bits: the descriptor spans < 4 GB
-    constexpr uint32_t step_bytes = 256u;
-    auto ld = [&](uint32_t tensor, uint32_t t) -> float {
-      // (the whole-quads instances of T < 64 prefetch unconditionally — see run_quad — so their
-      // last quad's prefetch is clamped to the last row; T = 64: never out of range)
-      const uint32_t tc = (FULL || t < T) ? t : T - 1;
-      return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rn, loff, tensor * noise_bytes + tc * step_bytes, 0));
+    // noise, group-major: quad q of this wave's 64 rollouts is 1 KB behind quad q - 1
+    const uint32_t loff = (bl >> 6) * (T4 * 256u) + (bl & 63u) * 16u;   // SMPC_GM_INDEX(bl, 0, T) in bytes, 32 bits: the descriptor spans < 4 GB
+    constexpr uint32_t quad_bytes = 1024u;
+    auto ldq = [&](uint32_t tensor, uint32_t q) -> f32x4 {
+      // (the instances with a run-time trip count prefetch unconditionally — see run_quad — so their
+      // last quad's prefetch is clamped to the last quad; T = 64 or TC: never out of range)
+      const uint32_t qc = (FULL || TC || q < nquad) ? q : nquad - 1;
+      return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rn, loff, tensor * noise_bytes + qc * quad_bytes, 0));
     };
     auto ldu = [&](uint32_t ctrl, uint32_t t) -> float {return cu[ctrl * T + ((FULL || t < T) ? t : T - 1)];};
-    float nq[12], uq[12];   // (NH: the slots 3 i + 1 are never written or read — eight live values each)
+    f32x4 nq0, nq1, nq2;   // the quad's four steps of vx, vy, wz noise (NH: nq1 is never written or read)
+    float uq[12];          // (NH: the slots 3 i + 1 are never written or read — eight live values)
+    nq0 = ldq(0, 0);
+    if constexpr (!NH) nq1 = ldq(1, 0);
+    nq2 = ldq(2, 0);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      nq[3 * i + 0] = ld(0, i);
-      if constexpr (!NH) nq[3 * i + 1] = ld(1, i);
-      nq[3 * i + 2] = ld(2, i);
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         if constexpr (NH) {
@@ -537,35 +558,38 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
             uq[3 * i + k] = ldu(k, 4 * (q + 1) + i);
           }
       }
-      // kQuadOff (whole quads): one scalar offset per tensor and QUAD — the next quad's first
-      // step, clamped to the last quad where the fetch is unconditional — instead of three scalar
-      // instructions per step; the step inside the quad, 0 / 256 / 512 / 768 bytes, is added to the
-      // lane's offset.  (Meant for the load's immediate offset; the compiler hoists the four sums
-      // out of the loop instead, three more vector registers.  The plain instances have them: the
-      // GoalAngle, deployed-list, grouped and cost-power ones spill 12-20 bytes to scratch with it.)
-      constexpr bool kQuadOff = QUADS && !GA && !DEP && !MANY && !POW;
+      // This quad's noise is copied, and the next quad's three 16-byte loads (NH: two) go out at
+      // once: one scalar offset per tensor and quad, the lane's offset is the group's.
+      const f32x4 nc0 = nq0, nc1 = NH ? (f32x4)(0.f) : nq1, nc2 = nq2;
+      if constexpr (kAddAtTop) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          cq[3 * i] = uc[3 * i] + nc0[i];
+          cq[3 * i + 1] = uc[3 * i + 1] + nc1[i];
+          cq[3 * i + 2] = uc[3 * i + 2] + nc2[i];
+        }
+      }
+      auto fetch = [&]() __attribute__((always_inline)) {
+        if (kAlwaysAhead || q + 1 < nquad) {
+          nq0 = ldq(0, q + 1);
+          if constexpr (!NH) nq1 = ldq(1, q + 1);
+          nq2 = ldq(2, q + 1);
+        }
+      };
+      if constexpr (!kAddAtTop) fetch();
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const uint32_t t = 4 * q + i;
-        // this step's noise; its registers are refilled at once with step t + 4
-        const float n0 = nq[3 * i], n1 = NH ? 0.f : nq[3 * i + 1], n2 = nq[3 * i + 2];
-        if (kAlwaysAhead || q + 1 < nquad) {
-          if constexpr (kQuadOff) {
-            const uint32_t tq = (FULL || TC || 4 * (q + 1) < T) ? 4 * (q + 1) : T - 4;
-            const uint32_t so0 = tq * step_bytes, so1 = noise_bytes + so0, so2 = noise_bytes + so1;
-            auto ldq = [&](uint32_t so) -> float {
-              return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rn, loff + (uint32_t)i * step_bytes, so, 0));
-            };
-            nq[3 * i + 0] = ldq(so0);
-            if constexpr (!NH) nq[3 * i + 1] = ldq(so1);
-            nq[3 * i + 2] = ldq(so2);
-          } else {
-            nq[3 * i + 0] = ld(0, t + 4);
-            nq[3 * i + 1] = ld(1, t + 4);
-            nq[3 * i + 2] = ld(2, t + 4);
+        if constexpr (kAddAtTop) {
+          // ... and the loads go out later in the quad (pinned: left alone the scheduler moves them back up)
+          if (i == kFetchAt) {
+            __builtin_amdgcn_sched_barrier(0);
+            fetch();
+            __builtin_amdgcn_sched_barrier(0);
           }
         }
-        cq[3 * i] = cq[3 * i + 1] = cq[3 * i + 2] = 0.f;
+        const float n0 = nc0[i], n1 = nc1[i], n2 = nc2[i];
+        if constexpr (!kAddAtTop) cq[3 * i] = cq[3 * i + 1] = cq[3 * i + 2] = 0.f;
         if (QUADS || t < T)
           do_step(t, i == 0, uc[3 * i], NH ? 0.f : uc[3 * i + 1], uc[3 * i + 2], n0, n1, n2, cq[3 * i], cq[3 * i + 1],
                   cq[3 * i + 2]);
@@ -775,16 +799,21 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
     const LaneW lw = lane_weights(w, lane);
     if constexpr (RR) {
       // the group's noise again (it was read within the last tens of microseconds: served on
-      // die), 64 steps of one control at a time, and c = u + n with the rounding of the step
+      // die), 64 steps of one control at a time in 16 loads of a quad each, and c = u + n with the
+      // rounding of the step
 #pragma unroll
       for (int h = 0; h < NCH; ++h) {
 #pragma unroll
         for (int ctrl = 0; ctrl < 3; ++ctrl) {
-          // all 64 loads go out before the first use (left alone the scheduler pairs every load
-          // with its add and waits for each in turn: 192 memory round trips per group)
+          // all 16 loads go out before the first use (left alone the scheduler pairs every load
+          // with its adds and waits for each in turn: 48 memory round trips per group)
           float V[64];
 #pragma unroll
-          for (int t = 0; t < 64; ++t) V[t] = ld(ctrl, 64u * h + t);
+          for (int j = 0; j < 16; ++j) {
+            const f32x4 v = ldq(ctrl, 16u * h + j);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) V[4 * j + e] = v[e];
+          }
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int t = 0; t < 64; ++t) {

@@ -260,9 +260,9 @@ __global__ void __launch_bounds__(SPLIT_BLOCK, 2) smpc_pass_split(const SmpcDev 
 
   // ---- constants ------------------------------------------------------------------------------
   const uint32_t B = p.B;
-  const uint32_t noise_bytes = T * SMPC_GM_ROLLOUTS(B) * 4u;   // one tensor, group-major (smpc_dev.h)
+  const uint32_t noise_bytes = (uint32_t)SMPC_GM_ELEMS(B, T) * 4u;   // one tensor, group-major (smpc_dev.h); T: whole quads
   const __amdgpu_buffer_rsrc_t rn = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.tvx), 0, 3u * noise_bytes, 0x00020000);
-  constexpr uint32_t row_bytes = 256u;                         // step t + 1 of a 64-rollout group: 256 bytes on
+  constexpr uint32_t quad_bytes = 1024u;                       // the next quad of steps of a 64-rollout group: 1 KB on
   const float dt = p.dt, yaw0 = p.yaw0;
   const double x0 = p.x0, y0 = p.y0;
   uint32_t S = 0;
@@ -303,12 +303,13 @@ __global__ void __launch_bounds__(SPLIT_BLOCK, 2) smpc_pass_split(const SmpcDev 
     const uint32_t b = grp * SPLIT_ROLL + (uint32_t)r;
     const bool live = b < B;
     const uint32_t bl = live ? b : B - 1;
-    // noise row t0 + i of this lane: the lane's own part (rollout, first row of its segment) is the
-    // vector offset, tensor and i the scalar one; the row in front of the segment separately
-    const uint32_t voff = ((bl >> 6) * T * 64u + (bl & 63u)) * 4u + t0 * row_bytes;   // SMPC_GM_INDEX(bl, t0, T) in 32 bits
-    const uint32_t vprev = sg ? voff - row_bytes : voff;   // (segment 0: loaded, not used)
-    auto ld = [&](uint32_t tensor, uint32_t i) -> float {
-      return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rn, voff, tensor * noise_bytes + i * row_bytes, 0));
+    // noise quad t0 / 4 + j of this lane, steps t0 + 4 j .. + 3 in one 16-byte load: the lane's own part
+    // (rollout, first quad of its segment) is the vector offset, tensor and j the scalar one; the step
+    // in front of the segment — the last of the quad before — separately
+    const uint32_t voff = (bl >> 6) * (T * 256u) + (bl & 63u) * 16u + (t0 >> 2) * quad_bytes;   // SMPC_GM_INDEX(bl, t0, T) in bytes, 32 bits
+    const uint32_t vprev = sg ? voff - quad_bytes + 12u : voff;   // (segment 0: loaded, not used)
+    auto ldq = [&](uint32_t tensor, uint32_t j) -> f32x4 {
+      return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rn, voff, tensor * noise_bytes + j * quad_bytes, 0));
     };
     auto ld_prev = [&](uint32_t tensor) -> float {
       return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rn, vprev, tensor * noise_bytes, 0));
@@ -326,7 +327,11 @@ __global__ void __launch_bounds__(SPLIT_BLOCK, 2) smpc_pass_split(const SmpcDev 
       float nz[SPLIT_SEG];
       const float nzp = ld_prev(2);
 #pragma unroll
-      for (int i = 0; i < SPLIT_SEG; ++i) nz[i] = ld(2, i);
+      for (int j = 0; j < SPLIT_SEG / 4; ++j) {
+        const f32x4 v = ldq(2, j);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) nz[4 * j + e] = v[e];
+      }
       const float uzp = s_u[128 + (sg ? t0 - 1 : 0)];
       wprev = sg ? uzp + nzp : p.swz;
       float acc = 0.f, w = wprev;
@@ -354,9 +359,13 @@ __global__ void __launch_bounds__(SPLIT_BLOCK, 2) smpc_pass_split(const SmpcDev 
       const float nxp = ld_prev(0), nyp = ld_prev(1);
       float ny[SPLIT_SEG];
 #pragma unroll
-      for (int i = 0; i < SPLIT_SEG; ++i) {
-        cvx[SLOT(i)] = ld(0, i);
-        ny[i] = ld(1, i);
+      for (int j = 0; j < SPLIT_SEG / 4; ++j) {
+        const f32x4 vx4 = ldq(0, j), vy4 = ldq(1, j);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          cvx[SLOT(4 * j + e)] = vx4[e];
+          ny[4 * j + e] = vy4[e];
+        }
       }
       vxp = sg ? s_u[t0 - 1] + nxp : p.svx;
       vyp = sg ? s_u[64 + t0 - 1] + nyp : p.svy;
