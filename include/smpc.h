@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define SMPC_ABI_VERSION 2
+#define SMPC_ABI_VERSION 3
 
 /* ---- status codes ------------------------------------------------------ */
 #define SMPC_OK 0
@@ -529,21 +529,35 @@ int smpc_shard_combine(smpc_ctx* ctx, const float* d_tuples, uint32_t n_tuples,
 
 /* ---- several planning instances per launch (multi-robot fleets; BASELINE "multi-query") ----
  * Independent contexts (own noise, costmap, critics, control sequence) on one GPU whose
- * ticks are issued together: one upload, one scoring launch with the instance as the second
- * grid dimension, one reduction launch.  Results are exactly those of smpc_optimize on each
- * context; a member that cannot take the batched launch this tick (not on the
- * lane-per-rollout pass — create members with SMPC_FLAG_LANE_PER_ROLLOUT —, first tick without a
- * furthest-point guess, speculation miss, every rollout colliding, iteration_count > 1) is
- * ticked on its own inside the call.  Members must share device and time_steps; while grouped,
- * a context must not be used through smpc_optimize directly; destroy the group before its
- * members.  Replaces N calls of Optimizer::optimize() [ref src/optimizer.cpp:157-164] by
- * N controller instances. */
+ * ticks are issued together: one upload, one scoring launch per scoring instance with the member
+ * as the second grid dimension, one reduction launch.  Results are exactly those of
+ * smpc_optimize on each context, bit for bit.
+ * Which members ride a batched launch:
+ *   - members whose tick takes the lane-per-rollout pass (SMPC_FLAG_LANE_PER_ROLLOUT, or a batch
+ *     large enough for it; the five critics or the deployed list's cruise tick): one launch of a
+ *     grouped lane instance for all of them;
+ *   - members whose tick takes the wave-per-rollout pass with time_steps <= 64 and every
+ *     cost_power == 1 — the deployed critic list with or without consider_footprint, near-goal
+ *     ticks, any context created without the lane flag: one launch of smpc_pass_many per distinct
+ *     instance that at least two members chose.  The lane flag is not required.
+ * Which members are ticked on their own inside the call (smpc_optimize): time_steps > 64, a
+ * cost_power other than 1, SMPC_FLAG_STORE_TRAJECTORIES, path orientations, the critics of the
+ * general pass, the Ackermann model, iteration_count > 1, fail_flag_in, SMPC_FLAG_NO_SPECULATION or
+ * SMPC_FLAG_PROFILE, the only member on its instance; and, for the tick at hand, a member without
+ * a furthest-point guess (its first tick), one whose guess missed, one whose rollouts all collide.
+ * Members must share device and time_steps; while grouped, a context must not be used through
+ * smpc_optimize directly; destroy the group before its members.  Replaces N calls of
+ * Optimizer::optimize() [ref src/optimizer.cpp:157-164] by N controller instances. */
 typedef struct smpc_group smpc_group;
 int smpc_group_create(smpc_ctx* const* ctxs, uint32_t n, smpc_group** out);
 void smpc_group_destroy(smpc_group* group);
 /* ins[n], u_inout[n] (pointers to 3*T floats each), outs[n] (may be NULL) */
 int smpc_group_optimize(smpc_group* group, const smpc_tick_in* ins, float* const* u_inout,
                         smpc_tick_out* outs);
+/* How the group's ticks went so far: *batched_launches counts scoring launches that carried two or
+ * more members, *single_ticks members ticked through smpc_optimize (a re-score after a missed guess
+ * included).  Either pointer may be NULL; a NULL group returns SMPC_ERR_INVALID.  (ABI 3) */
+int smpc_group_stats(const smpc_group* group, uint64_t* batched_launches, uint64_t* single_ticks);
 
 /* ---- the same tick with the exchanges inside the library (RCCL over xGMI) ----
  * One ncclComm per ctx, one call per tick: upload -> score -> ncclAllGather(tuples) ->

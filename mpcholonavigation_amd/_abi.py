@@ -6,7 +6,7 @@ to the CPU oracle, so one set of inputs feeds both.
 """
 import ctypes as C
 
-SMPC_ABI_VERSION = 2
+SMPC_ABI_VERSION = 3
 
 SMPC_OK = 0
 SMPC_ERR_INVALID = -1
@@ -279,6 +279,7 @@ PROTOTYPES = {
     "smpc_group_destroy": (None, [_ctx]),
     "smpc_group_optimize": (C.c_int, [_ctx, C.POINTER(SmpcTickIn), C.POINTER(C.c_void_p),
                                       C.POINTER(SmpcTickOut)]),
+    "smpc_group_stats": (C.c_int, [_ctx, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "smpc_shard_comm_id": (C.c_int, [C.c_void_p, C.c_uint32]),
     "smpc_shard_comm_init": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int]),
     "smpc_shard_p2p_handle": (C.c_int, [_ctx, C.c_void_p, C.c_uint32]),

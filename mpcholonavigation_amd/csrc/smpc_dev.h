@@ -295,4 +295,13 @@ struct SmpcLds {
   uint32_t total;       // bytes
 };
 
+// One planning instance's launch geometry in smpc_pass_many (device memory, next to its SmpcDev):
+// the members of a group differ in path length, costmap window and PathAlign sample count, hence
+// in the carve-up, and in batch size, hence in the blocks they need (a block at or beyond `grid`
+// leaves at once).
+struct SmpcWaveGeom {
+  SmpcLds lds;
+  uint32_t grid;
+};
+
 #endif

@@ -11,11 +11,12 @@ struct smpc_group {
   std::vector<smpc_ctx*> ctxs;
   std::vector<hipStream_t> saved_stream;
   std::vector<uint8_t*> saved_h_tick, saved_d_tick;
-  uint8_t* h_all = nullptr;   // pinned: n tick blocks, then SmpcDev[n], SmpcReduceArgs[n]
+  uint8_t* h_all = nullptr;   // pinned: n tick blocks, then SmpcDev[n], SmpcReduceArgs[n], SmpcWaveGeom[n]
   uint8_t* d_all = nullptr;
-  size_t slot = 0, off_dev = 0, off_red = 0, total = 0;
+  size_t slot = 0, off_dev = 0, off_red = 0, off_geo = 0, total = 0;
   hipStream_t stream = nullptr;
   uint64_t batched_ticks = 0, single_ticks = 0;
+  uint64_t batched_launches = 0;   // scoring launches that carried two or more members (smpc_group_stats)
 };
 
 int smpc_group_create(smpc_ctx* const* ctxs, uint32_t n, smpc_group** out)
@@ -38,7 +39,8 @@ int smpc_group_create(smpc_ctx* const* ctxs, uint32_t n, smpc_group** out)
   g->slot = align_up(static_cast<uint32_t>(c0->tick_cap), 256);
   g->off_dev = g->slot * n;
   g->off_red = g->off_dev + align_up(static_cast<uint32_t>(sizeof(SmpcDev)) * n, 256);
-  g->total = g->off_red + align_up(static_cast<uint32_t>(sizeof(SmpcReduceArgs)) * n, 256);
+  g->off_geo = g->off_red + align_up(static_cast<uint32_t>(sizeof(SmpcReduceArgs)) * n, 256);
+  g->total = g->off_geo + align_up(static_cast<uint32_t>(sizeof(SmpcWaveGeom)) * n, 256);
   if (hipHostMalloc(&g->h_all, g->total, hipHostMallocDefault) != hipSuccess ||
     hipMalloc(&g->d_all, g->total) != hipSuccess)
   {
@@ -82,11 +84,27 @@ void smpc_group_destroy(smpc_group* g)
   delete g;
 }
 
-// One tick of every member.  When every member can take the lane-per-rollout pass with a
-// speculated furthest point (the steady state), the group issues ONE upload, ONE scoring launch
-// (blockIdx.y = member) and ONE reduction launch; a member that misses its speculation, collides
-// everywhere, or is not eligible is ticked on its own with smpc_optimize — results are those of
-// smpc_optimize in every case.
+int smpc_group_stats(const smpc_group* g, uint64_t* batched_launches, uint64_t* single_ticks)
+{
+  if (!g) return SMPC_ERR_INVALID;
+  if (batched_launches) *batched_launches = g->batched_launches;
+  if (single_ticks) *single_ticks = g->single_ticks;
+  return SMPC_OK;
+}
+
+// One tick of every member.  The members that can take a batched launch with a speculated furthest
+// point (the steady state) are partitioned by the scoring instance their own plan chose:
+//   * the members on the lane-per-rollout pass ride ONE launch of a grouped lane instance, as they
+//     always did (they must agree on the window, the block and on whether a costmap lookup is scored;
+//     if they do not, each is ticked on its own);
+//   * the members on the wave-per-rollout pass in MODE 0, 3 or 4 (T <= 64: the deployed critic list
+//     with or without consider_footprint, near-goal ticks, contexts created without the lane flag)
+//     ride one launch of smpc_pass_many per distinct instance, each with the grid, the LDS carve-up
+//     and so the rollout-to-wave assignment and flush group of its own smpc_pass launch; an instance
+//     that only one member chose is not worth a launch of its own kind: that member is ticked alone.
+// The group then issues ONE upload, those scoring launches and ONE reduction + publish launch for all
+// of them.  A member that misses its speculation, collides everywhere, or is not eligible is ticked
+// on its own with smpc_optimize — results are those of smpc_optimize in every case.
 int smpc_group_optimize(smpc_group* g, const smpc_tick_in* ins, float* const* u_inout,
                         smpc_tick_out* outs)
 {
@@ -106,11 +124,16 @@ int smpc_group_optimize(smpc_group* g, const smpc_tick_in* ins, float* const* u_
   auto now = [] {return std::chrono::steady_clock::now();};
   auto us_between = [](auto a, auto b) {return std::chrono::duration<double, std::micro>(b - a).count();};
   const auto t_start = now();
-  // ---- prepare every member; decide whether the batched launch applies -----------------
-  bool batched = true;
-  uint32_t Pmax = 0, window_bytes = 0, gridx = 0;
-  const LaneInst* inst = nullptr;   // the grouped instance: one for all members
+  const uint32_t T = c0->cfg.time_steps;
+  // ---- prepare every member; decide which launch, if any, it rides ------------------------
+  // part[i]: null — ticked alone; the grouped lane instance's address for every lane member; the
+  // member's row of smpc_pass_many for a wave member
+  std::vector<const void*> part(n, nullptr);
   std::vector<uint32_t> flags(n);
+  bool lane_ok = true;
+  uint32_t lane_first = n, Pmax = 0, window_bytes = 0, gridx = 0;
+  const LaneInst* inst = nullptr;   // the grouped lane instance: one for all lane members
+  static const char kLaneTag = 0;   // (stands for "the lane launch" until the instance is known)
   for (uint32_t i = 0; i < n; ++i) {
     smpc_ctx* c = g->ctxs[i];
     if (!u_inout[i]) return fail(c, SMPC_ERR_INVALID, "null control sequence");
@@ -122,71 +145,142 @@ int smpc_group_optimize(smpc_group* g, const smpc_tick_in* ins, float* const* u_
     flags[i] = scoring_flags(c, c->fail_in);
     const bool need_f = (flags[i] & SD_NEED_FURTHEST) != 0;
     if (need_f) flags[i] |= SD_LOCAL_FURTHEST;
+    // what every batched launch asks of a member: one iteration scored once with a predicted
+    // furthest point, the completion polled, no Ackermann launch behind the reduction, one
+    // non-colliding count
+    const bool ok = c->cfg.iteration_count == 1 && !c->fail_in &&
+      !(c->cfg.flags & (SMPC_FLAG_NO_SPECULATION | SMPC_FLAG_PROFILE)) && (!need_f || c->hint_valid) &&
+      c->knobs.poll && c->acker_r < 0.f && !c->two_coll_fp;
+    if (!ok) continue;
     // (a near-goal member scores GoalAngle: instances of the lane pass the batched launch does not
     // have; members with the deployed critic list — Constraint / Cost / Twirling — have theirs, and
     // a member without those critics runs them unchanged; a member that scores with cost powers
     // has no batched instance either and is ticked on its own)
     const LaneInst* k = c->plan.kind == PassPlan::kLane && !c->plan.rr && !c->plan.pow
-      ? lane_select(flags[i], c->cfg.time_steps, false, true, c->acker_r, false) : nullptr;
-    const bool ok = k && c->cfg.iteration_count == 1 && !c->fail_in &&
-      !(c->cfg.flags & (SMPC_FLAG_NO_SPECULATION | SMPC_FLAG_PROFILE)) && (!need_f || c->hint_valid) &&
-      c->knobs.poll && c->acker_r < 0.f && !c->two_coll_fp;
-    if (!ok) batched = false;
-    if (i == 0) window_bytes = c->plan.window_bytes;
-    // the members agree on the window, the block and on whether a costmap lookup is scored
-    else if (c->plan.window_bytes != window_bytes || (k && inst && k->obst != inst->obst) || c->plan.lane.block != c0->plan.lane.block)
-      batched = false;
-    if (k && (!inst || k->dep)) inst = k;
-    Pmax = std::max(Pmax, c->P);
-    gridx = std::max(gridx, c->plan.lane.grid);
+      ? lane_select(flags[i], T, false, true, c->acker_r, false) : nullptr;
+    if (k) {
+      part[i] = &kLaneTag;
+      if (lane_first == n) {
+        lane_first = i;
+        window_bytes = c->plan.window_bytes;
+      }
+      // the lane members agree on the window, the block and on whether a costmap lookup is scored
+      else if (c->plan.window_bytes != window_bytes || (inst && k->obst != inst->obst) ||
+               c->plan.lane.block != g->ctxs[lane_first]->plan.lane.block)
+        lane_ok = false;
+      if (!inst || k->dep) inst = k;
+      Pmax = std::max(Pmax, c->P);
+      gridx = std::max(gridx, c->plan.lane.grid);
+      continue;
+    }
+    // its own plan chose the wave pass: the grouped row of the same <R, MODE, FULL> (R = 1 and the
+    // lean modes only: wave_select has no other grouped row).  The in-launch reduction experiment
+    // waits for the grid's other blocks; smpc_pass_many never does.
+    if (c->plan.kind == PassPlan::kWave && c->R == 1 && !c->knobs.fused_reduce)
+      part[i] = wave_select(c->R, c->score_mode, T, true);
   }
-  const uint32_t T = c0->cfg.time_steps;
-  const SmpcLds L = lane_lds(window_bytes, Pmax, T);
-  if (L.total > kLdsPerCu) batched = false;
-  if (!batched) {
+  SmpcLds L{};
+  if (lane_first != n) {
+    L = lane_lds(window_bytes, Pmax, T);
+    if (L.total > kLdsPerCu) lane_ok = false;
+  }
+  // batched members in launch order: the lane members, then the wave members instance by instance
+  struct Launch { const WaveInst* wave; uint32_t first, count, grid, lds; };   // wave == null: the lane launch
+  std::vector<uint32_t> order;
+  std::vector<Launch> launches;
+  if (lane_first != n && lane_ok) {
+    launches.push_back({nullptr, 0, 0, gridx, L.total});
+    for (uint32_t i = 0; i < n; ++i)
+      if (part[i] == &kLaneTag) order.push_back(i);
+    launches.back().count = static_cast<uint32_t>(order.size());
+  }
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!part[i] || part[i] == &kLaneTag) continue;
+    bool seen = false;
+    for (const Launch& l : launches) seen = seen || l.wave == part[i];
+    if (seen) continue;
+    Launch l{static_cast<const WaveInst*>(part[i]), static_cast<uint32_t>(order.size()), 0, 0, 0};
+    for (uint32_t j = i; j < n; ++j) {
+      if (part[j] != part[i]) continue;
+      order.push_back(j);
+      l.count++;
+      l.grid = std::max(l.grid, g->ctxs[j]->plan.wave.grid);
+      l.lds = std::max(l.lds, g->ctxs[j]->plan.wave.lds.total);
+    }
+    if (l.count >= 2) launches.push_back(l);
+    else order.pop_back();   // alone on its instance: ticked alone
+  }
+  // ---- everybody else is ticked alone, first ------------------------------------------------
+  {
+    std::vector<bool> rides(n, false);
+    for (uint32_t i : order) rides[i] = true;
     for (uint32_t i = 0; i < n; ++i) {
+      if (rides[i]) continue;
       const int rc = single(i);
       if (rc != SMPC_OK) return rc;
     }
-    return SMPC_OK;
   }
+  if (order.empty()) return SMPC_OK;
+  const uint32_t m = static_cast<uint32_t>(order.size());
   const auto t_prep = now();
-  // ---- one upload, one scoring launch, one reduction launch ---------------------------------
+  // ---- one upload, one scoring launch per instance, one reduction launch ---------------------
   SmpcDev* hd = reinterpret_cast<SmpcDev*>(g->h_all + g->off_dev);
   SmpcReduceArgs* hr = reinterpret_cast<SmpcReduceArgs*>(g->h_all + g->off_red);
-  for (uint32_t i = 0; i < n; ++i) {
-    smpc_ctx* c = g->ctxs[i];
-    SmpcFinal fin;
-    fill_score_args(c, flags[i], nullptr, nullptr, c->hint, true, nullptr, hd[i], fin);
-    hr[i].partials = c->d_partials;
-    hr[i].tuple = c->d_tuple;
-    hr[i].nblk = gridx;
-    hr[i].host_out = fin.u_host;
-    hr[i].seq = fin.seq;
-    hr[i].neg_inv_temp = c->dev.neg_inv_temp;   // (its own: the members share the horizon, nothing else)
-    fin.u_host = nullptr;          // one publishing block for the whole group instead
-    fin.done_counter = nullptr;
-    hr[i].fin = fin;
-    c->passes++;
-    c->last_pass_kind = 1;
+  SmpcWaveGeom* hg = reinterpret_cast<SmpcWaveGeom*>(g->h_all + g->off_geo);
+  for (const Launch& l : launches) {
+    for (uint32_t j = l.first; j < l.first + l.count; ++j) {
+      const uint32_t i = order[j];
+      smpc_ctx* c = g->ctxs[i];
+      if (l.wave) {
+        const int rc = ensure_row_major(c);   // the wave-per-rollout pass reads the [B,T] tensors
+        if (rc != SMPC_OK) return rc;
+      }
+      SmpcFinal fin;
+      fill_score_args(c, flags[i], nullptr, nullptr, c->hint, true, nullptr, hd[j], fin);
+      hr[j].partials = c->d_partials;
+      hr[j].tuple = c->d_tuple;
+      // (a wave member: its own grid — the blocks beyond it wrote nothing; the lane launch: every
+      // member's blocks write a partial)
+      hr[j].nblk = l.wave ? c->plan.wave.grid : gridx;
+      hr[j].host_out = fin.u_host;
+      hr[j].seq = fin.seq;
+      hr[j].neg_inv_temp = c->dev.neg_inv_temp;   // (its own: the members share the horizon, nothing else)
+      fin.u_host = nullptr;          // one publishing block for the whole group instead
+      fin.done_counter = nullptr;
+      hr[j].fin = fin;
+      hg[j].lds = c->plan.wave.lds;
+      hg[j].grid = c->plan.wave.grid;
+      c->passes++;
+      c->last_pass_kind = l.wave ? PassPlan::kWave : PassPlan::kLane;
+    }
   }
-  // one hand-over for every member's tick block and parameter block: CPU stores through the BAR
-  // (every member's last tick was fetched: nothing reads the buffer), else a copy on the stream
+  // one hand-over for every riding member's tick block and parameter block: CPU stores through the
+  // BAR (every member's last tick was fetched: nothing reads the buffer), else a copy on the stream
   if (c0->bar_tick) {
     // (only what this tick wrote: a slot is sized for the longest path, 25 KB, a tick fills ~4)
-    for (uint32_t i = 0; i < n; ++i) bar_copy(g->d_all + g->slot * i, g->h_all + g->slot * i, g->ctxs[i]->tick_used);
+    for (uint32_t i : order) bar_copy(g->d_all + g->slot * i, g->h_all + g->slot * i, g->ctxs[i]->tick_used);
     bar_copy(g->d_all + g->off_dev, g->h_all + g->off_dev, g->total - g->off_dev);
     bar_flush(c0);
   }
   else HIPCK(c0, hipMemcpyAsync(g->d_all, g->h_all, g->total, hipMemcpyHostToDevice, g->stream));
-  HIPCK(c0, lane_launch(inst, c0->dev, reinterpret_cast<const SmpcDev*>(g->d_all + g->off_dev), n, L, gridx,
-                        c0->plan.lane.block, g->stream));
-  HIPCK(c0, smpc_launch_reduce_many(reinterpret_cast<const SmpcReduceArgs*>(g->d_all + g->off_red), n,
+  // (the footprint tables of a MODE 4 member and the collision table of any member went out in
+  // prepare_tick on c->stream, which is this stream while the context is grouped: in front of these)
+  for (const Launch& l : launches) {
+    const SmpcDev* d_dev = reinterpret_cast<const SmpcDev*>(g->d_all + g->off_dev) + l.first;
+    if (l.wave) {
+      HIPCK(c0, wave_launch_many(l.wave, d_dev, reinterpret_cast<const SmpcWaveGeom*>(g->d_all + g->off_geo) + l.first,
+                                 l.count, l.grid, l.lds, pass_block(1), g->stream));
+    } else {
+      HIPCK(c0, lane_launch(inst, c0->dev, d_dev, l.count, L, l.grid, g->ctxs[lane_first]->plan.lane.block, g->stream));
+    }
+    if (l.count >= 2) g->batched_launches++;
+  }
+  HIPCK(c0, smpc_launch_reduce_many(reinterpret_cast<const SmpcReduceArgs*>(g->d_all + g->off_red), m,
                                     T, g->stream));
   g->batched_ticks++;
   const auto t_launch = now();
   // ---- per member: wait, verify the speculation and the collision count --------------------
-  for (uint32_t i = 0; i < n; ++i) {
+  for (uint32_t i : order) {
     smpc_ctx* c = g->ctxs[i];
     int rc = fetch_out(c);
     if (rc != SMPC_OK) return rc;
@@ -218,7 +312,7 @@ int smpc_group_optimize(smpc_group* g, const smpc_tick_in* ins, float* const* u_
       o->min_cost = c->h_out[3 * T + 0];
       o->sum_w = c->h_out[3 * T + 1];
       o->passes = c->passes;
-      o->pass_kind = 1;
+      o->pass_kind = c->last_pass_kind;
     }
   }
   if (timing && (g->batched_ticks % 64) == 0)

@@ -13,7 +13,8 @@
 
 #pragma GCC visibility push(hidden)
 
-struct WaveInst { int r, mode; bool full; const void* fn; };                                       // smpc_pass<R, MODE, FULL>
+// many: the instance is smpc_pass_many<...>, the same template arguments with several planning instances per launch
+struct WaveInst { int r, mode; bool full, many; const void* fn; };                                 // smpc_pass<R, MODE, FULL>
 // pow: the instance is smpc_pass_lane_pow<...>, the same template arguments with general cost powers
 // nh: the instance is smpc_pass_lane_nh<...>, the same template arguments without the vy stream
 struct LaneInst { bool full, obst, many; int nch; bool rr, ga, quads; int tc; bool dep; const void* fn; bool pow, nh; };   // smpc_pass_lane<...>
@@ -22,7 +23,8 @@ struct SplitInst { int nseg; bool full; const void* fn; };                      
 // Selectors: the instance that scores these flags at this horizon, or null when there is none.
 // mode: 0 score (all cost_power == 1), 1 furthest only, 3 score (all cost_power == 1, with the
 // additive forms of Cost, Goal, Constraint, Twirling, PathAngle), anything else: the general pass
-const WaveInst* wave_select(int R, int mode, uint32_t T);
+// many: the grouped rows (smpc_group_optimize) — R = 1 and mode 0, 3 or 4 only, null otherwise
+const WaveInst* wave_select(int R, int mode, uint32_t T, bool many = false);
 // rr: the re-read form (no parked controls; required for T > 64); many: the grouped instances
 // (smpc_group_optimize); acker_r: the Ackermann min_turning_r, < 0 for the other models
 // pow: the tick scores with a cost_power other than 1 among the five critics — only then is a row of
@@ -43,6 +45,10 @@ const SplitInst* split_occupancy_row(uint32_t nseg);
 
 // Launch a row; each records the instance's name for smpc_debug_last_pass_kernel().
 hipError_t wave_launch(const WaveInst* k, const SmpcDev& p, const SmpcLds& L, uint32_t grid, uint32_t block, hipStream_t st);
+// a grouped row: n instances in one launch of grid_max x n blocks, their parameter blocks and geometry
+// (each its own LDS carve-up and grid, both in device memory); lds_max: the largest carve-up's total
+hipError_t wave_launch_many(const WaveInst* k, const SmpcDev* d_many, const SmpcWaveGeom* d_geom, uint32_t n, uint32_t grid_max,
+                            uint32_t lds_max, uint32_t block, hipStream_t st);
 // d_many == nullptr: one planning instance, p its parameter block; else n instances in one launch,
 // their parameter blocks in device memory (p is not read)
 hipError_t lane_launch(const LaneInst* k, const SmpcDev& p, const SmpcDev* d_many, uint32_t n, const SmpcLds& L,

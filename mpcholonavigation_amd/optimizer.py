@@ -10,6 +10,7 @@ device half.
 import ctypes as C
 import os
 import sys
+import types
 
 import numpy as np
 
@@ -332,6 +333,15 @@ class SmpcGroup:
             raise SmpcError(rc, msg)
         res = self._bufs.copy()
         return [(res[i], A.SmpcTickOut.from_buffer_copy(self._outs[i])) for i in range(n)]
+
+    def stats(self):
+        """How the group's ticks went so far (smpc_group_stats): batched_launches — scoring launches
+        that carried two or more members; single_ticks — members ticked through smpc_optimize."""
+        launches, singles = C.c_uint64(0), C.c_uint64(0)
+        rc = self.lib.smpc_group_stats(self.h, C.byref(launches), C.byref(singles))
+        if rc != 0:
+            raise SmpcError(rc, "smpc_group_stats")
+        return types.SimpleNamespace(batched_launches=launches.value, single_ticks=singles.value)
 
     def close(self):
         if self.h:
