@@ -547,13 +547,29 @@ int smpc_shard_combine(smpc_ctx* ctx, const float* d_tuples, uint32_t n_tuples,
  * a furthest-point guess (its first tick), one whose guess missed, one whose rollouts all collide.
  * Members must share device and time_steps; while grouped, a context must not be used through
  * smpc_optimize directly; destroy the group before its members.  Replaces N calls of
- * Optimizer::optimize() [ref src/optimizer.cpp:157-164] by N controller instances. */
+ * Optimizer::optimize() [ref src/optimizer.cpp:157-164] by N controller instances.
+ * A round that returns an error may have been abandoned between its launches and the last
+ * member's result: the group remembers that, and the next round waits for the group's stream
+ * before it writes the shared tick blocks and argument arrays again.  The next round is safe. */
 typedef struct smpc_group smpc_group;
 int smpc_group_create(smpc_ctx* const* ctxs, uint32_t n, smpc_group** out);
 void smpc_group_destroy(smpc_group* group);
 /* ins[n], u_inout[n] (pointers to 3*T floats each), outs[n] (may be NULL) */
 int smpc_group_optimize(smpc_group* group, const smpc_tick_in* ins, float* const* u_inout,
                         smpc_tick_out* outs);
+/* The same round over a subset: take[n], one byte per member; take == NULL, or every byte non-zero,
+ * is smpc_group_optimize exactly (which is a call of this).  A member with take[i] == 0 is not
+ * prepared, uploaded, launched or fetched: ins[i], u_inout[i] and outs[i] are neither read nor
+ * written (the pointers may be NULL), its device and host state — furthest-point prediction,
+ * costs, a pending smpc_redraw_noise_async, the tick number — stays as it is, and its next tick is
+ * bit for bit what it would have been without this round: the controller is simply not called
+ * for a robot without a plan [ref src/controller.cpp:80-116].  The rules above on who rides a
+ * batched launch apply to the members taken (an instance needs two riding members).  A round
+ * with nobody taken returns SMPC_OK and does nothing.  An addition under ABI 3: the number is
+ * pinned by the suite and no existing entry point or struct changed; a caller that must run
+ * against an older library looks the symbol up. */
+int smpc_group_optimize_some(smpc_group* group, const smpc_tick_in* ins, float* const* u_inout,
+                             smpc_tick_out* outs, const uint8_t* take);
 /* How the group's ticks went so far: *batched_launches counts scoring launches that carried two or
  * more members, *single_ticks members ticked through smpc_optimize (a re-score after a missed guess
  * included).  Either pointer may be NULL; a NULL group returns SMPC_ERR_INVALID.  (ABI 3) */

@@ -22,7 +22,8 @@ typedef struct sortham_optimizer sortham_optimizer;
 
 typedef struct sortham_optimizer_config {
   smpc_config base;             /* batch/horizon/iterations, dt, temperature, gamma,
-                                   base constraints, sampling std, device          */
+                                   base constraints, sampling std, device; of flags,
+                                   SMPC_FLAG_LANE_PER_ROLLOUT alone is passed on    */
   double controller_frequency;  /* setOffset [ref src/optimizer.cpp:95-114]         */
   uint32_t retry_attempt_limit; /* [ref :82]                                        */
   int32_t regenerate_noises;    /* [ref src/noise_generator.cpp:35]                 */
@@ -66,6 +67,8 @@ int sortham_optimizer_set_noise(sortham_optimizer* o, const float* nvx, const fl
  * twist_out = {linear.x, linear.y, angular.z}. */
 int sortham_optimizer_eval_control(sortham_optimizer* o, const smpc_tick_in* in, double* twist_out,
                                    smpc_tick_out* out);
+/* The smpc_tick_out of the last tick the object ran — the last retry's when eval_control threw. */
+int sortham_optimizer_last_tick(const sortham_optimizer* o, smpc_tick_out* out);
 int sortham_optimizer_set_speed_limit(sortham_optimizer* o, double speed_limit, int percentage);
 int sortham_optimizer_reset(sortham_optimizer* o);
 /* control_sequence_ as {vx[T], vy[T], wz[T]} */
@@ -91,6 +94,48 @@ void sortham_utils_savitsky_golay(float* u, uint32_t T, float* history, int shif
 #define SORTHAM_TICKS_SHARD_SPECULATE 0x8u /* smpc_shard_tick(..., speculate = 1)              */
 int sortham_run_ticks(smpc_ctx* ctx, const smpc_tick_in* in, float* u, uint32_t time_steps, uint32_t n,
                       uint32_t flags, smpc_tick_out* outs, uint32_t* done);
+
+/* ---- Optimizer::evalControl for N robots through one grouped tick (host/fleet.hpp) ----
+ * A fleet over n existing optimizers: the caller keeps them, goes on using them through their own
+ * handles between rounds (set_costmap, set_speed_limit, reset, set_noise, set_control_sequence,
+ * initialize again) and may destroy them and the fleet in any order.  One round ticks the members
+ * taken with ONE smpc_group_optimize_some call and then runs, per member, what
+ * sortham_optimizer_eval_control runs around its own tick: fallback / reset / retry (alone, the
+ * fail flag sticky) / throw, Savitzky-Golay filter, Twist, shift [ref src/optimizer.cpp:134-225].
+ * Every member computes what it computes alone, bit for bit.  Single-threaded.
+ * create: SMPC_ERR_INVALID for a null argument, n = 0, a null member or one listed twice;
+ * SMPC_ERR_STATE for a member without a context or in a fleet already; smpc_group_create's code
+ * for members on different devices or with different time_steps.  The text of a failed create is
+ * sortham_fleet_last_error(NULL). */
+#define SORTHAM_FLEET_NOT_TAKEN 1 /* status of a member the round left out: nothing of its changed */
+typedef struct sortham_fleet sortham_fleet;
+int sortham_fleet_create(sortham_optimizer* const* members, uint32_t n, sortham_fleet** out);
+void sortham_fleet_destroy(sortham_fleet* fleet);
+const char* sortham_fleet_last_error(const sortham_fleet* fleet);
+/* One round.  ins[n] as for sortham_optimizer_eval_control; take[n], one byte per member, NULL =
+ * everybody (a member with take[i] == 0: ins[i] is not read, twists / outs entries not written,
+ * status SORTHAM_FLEET_NOT_TAKEN); twists: n x 3 doubles; outs[n] (may be NULL); status[n]:
+ * SMPC_OK, SORTHAM_FLEET_NOT_TAKEN, or SORTHAM_ERR_THROWN where that member's evalControl would
+ * have thrown — the text is then in that member's sortham_optimizer_last_error, the member is as
+ * evalControl leaves it when it throws, and the other members are not affected.
+ * Returns SMPC_OK, or the SMPC_ERR_* of a round that failed as a whole (sortham_fleet_last_error):
+ * then no member's control sequence, filter history or retry counter moved and the next round is
+ * safe to run.  Taking a member that was shut down or destroyed is SMPC_ERR_STATE. */
+int sortham_fleet_eval_control(sortham_fleet* fleet, const smpc_tick_in* ins, const uint8_t* take,
+                               double* twists, smpc_tick_out* outs, int32_t* status);
+/* smpc_group_stats summed over the groups the fleet has had (it regroups when a member rebuilds its
+ * context), and the retries the fleet ran alone.  Any pointer may be NULL. */
+int sortham_fleet_stats(const sortham_fleet* fleet, uint64_t* batched_launches, uint64_t* single_ticks,
+                        uint64_t* retries);
+/* n_rounds rounds on the same inputs from a compiled caller (host/tick_loop.cpp), the results of
+ * the last one in twists / outs / status (any may be NULL).  alone != 0: instead of the fleet round,
+ * the members' own sortham_optimizer_eval_control one after the other on their ungrouped contexts
+ * (the fleet regroups at its next round) — what a caller without the fleet runs, for timing the
+ * two against each other.  *done (may be NULL) = rounds completed; returns the first SMPC_ERR_* of
+ * a round as a whole. */
+int sortham_fleet_run_rounds(sortham_fleet* fleet, const smpc_tick_in* ins, const uint8_t* take,
+                             uint32_t n_rounds, int alone, double* twists, smpc_tick_out* outs,
+                             int32_t* status, uint32_t* done);
 
 /* ---- PathHandler for plain types [ref src/path_handler.cpp:25-220, tools/path_handler.hpp:46-165]
  * Poses are {x, y, yaw} triples of doubles.  What tf2 supplies in the reference comes in as

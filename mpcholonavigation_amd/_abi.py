@@ -279,6 +279,8 @@ PROTOTYPES = {
     "smpc_group_destroy": (None, [_ctx]),
     "smpc_group_optimize": (C.c_int, [_ctx, C.POINTER(SmpcTickIn), C.POINTER(C.c_void_p),
                                       C.POINTER(SmpcTickOut)]),
+    "smpc_group_optimize_some": (C.c_int, [_ctx, C.POINTER(SmpcTickIn), C.POINTER(C.c_void_p),
+                                           C.POINTER(SmpcTickOut), C.c_void_p]),
     "smpc_group_stats": (C.c_int, [_ctx, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "smpc_shard_comm_id": (C.c_int, [C.c_void_p, C.c_uint32]),
     "smpc_shard_comm_init": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int]),

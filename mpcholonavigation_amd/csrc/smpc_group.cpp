@@ -17,6 +17,10 @@ struct smpc_group {
   hipStream_t stream = nullptr;
   uint64_t batched_ticks = 0, single_ticks = 0;
   uint64_t batched_launches = 0;   // scoring launches that carried two or more members (smpc_group_stats)
+  // a batched launch went out and not every riding member's fetch_out has returned since: a round
+  // abandoned on an error leaves it set, and the next round waits for the stream before it writes
+  // h_all / d_all again
+  bool launched = false;
 };
 
 int smpc_group_create(smpc_ctx* const* ctxs, uint32_t n, smpc_group** out)
@@ -92,7 +96,7 @@ int smpc_group_stats(const smpc_group* g, uint64_t* batched_launches, uint64_t* 
   return SMPC_OK;
 }
 
-// One tick of every member.  The members that can take a batched launch with a speculated furthest
+// One tick of every member taken (take == null: of every member).  The members that can take a batched launch with a speculated furthest
 // point (the steady state) are partitioned by the scoring instance their own plan chose:
 //   * the members on the lane-per-rollout pass ride ONE launch of a grouped lane instance, as they
 //     always did (they must agree on the window, the block and on whether a costmap lookup is scored;
@@ -105,13 +109,25 @@ int smpc_group_stats(const smpc_group* g, uint64_t* batched_launches, uint64_t* 
 // The group then issues ONE upload, those scoring launches and ONE reduction + publish launch for all
 // of them.  A member that misses its speculation, collides everywhere, or is not eligible is ticked
 // on its own with smpc_optimize — results are those of smpc_optimize in every case.
-int smpc_group_optimize(smpc_group* g, const smpc_tick_in* ins, float* const* u_inout,
-                        smpc_tick_out* outs)
+// A member that is not taken is not looked at: no prepare, no upload, no launch, no fetch; the
+// partition above is the partition of the members taken.
+int smpc_group_optimize_some(smpc_group* g, const smpc_tick_in* ins, float* const* u_inout,
+                             smpc_tick_out* outs, const uint8_t* take)
 {
   if (!g || !ins || !u_inout) return fail(nullptr, SMPC_ERR_INVALID, "null argument");
   const uint32_t n = static_cast<uint32_t>(g->ctxs.size());
-  smpc_ctx* c0 = g->ctxs[0];
+  auto taken = [&](uint32_t i) {return !take || take[i] != 0;};
+  uint32_t first = 0;
+  while (first < n && !taken(first)) ++first;
+  if (first == n) return SMPC_OK;   // nobody taken: nothing to do
+  smpc_ctx* c0 = g->ctxs[first];    // (errors of the round as a whole are reported on the first member taken)
   HIPCK(c0, hipSetDevice(c0->device));
+  if (g->launched) {
+    // the round before was abandoned between its launch and its last fetch_out: its kernels may
+    // still read the tick blocks and the argument arrays this round is about to write
+    HIPCK(c0, hipStreamSynchronize(g->stream));
+    g->launched = false;
+  }
   auto single = [&](uint32_t i) -> int {
     smpc_ctx* c = g->ctxs[i];
     c->defer_upload = false;   // its own upload, into its slot of the group's buffers
@@ -135,6 +151,7 @@ int smpc_group_optimize(smpc_group* g, const smpc_tick_in* ins, float* const* u_
   const LaneInst* inst = nullptr;   // the grouped lane instance: one for all lane members
   static const char kLaneTag = 0;   // (stands for "the lane launch" until the instance is known)
   for (uint32_t i = 0; i < n; ++i) {
+    if (!taken(i)) continue;
     smpc_ctx* c = g->ctxs[i];
     if (!u_inout[i]) return fail(c, SMPC_ERR_INVALID, "null control sequence");
     c->passes = 0;
@@ -215,7 +232,7 @@ int smpc_group_optimize(smpc_group* g, const smpc_tick_in* ins, float* const* u_
     std::vector<bool> rides(n, false);
     for (uint32_t i : order) rides[i] = true;
     for (uint32_t i = 0; i < n; ++i) {
-      if (rides[i]) continue;
+      if (rides[i] || !taken(i)) continue;
       const int rc = single(i);
       if (rc != SMPC_OK) return rc;
     }
@@ -273,6 +290,7 @@ int smpc_group_optimize(smpc_group* g, const smpc_tick_in* ins, float* const* u_
     } else {
       HIPCK(c0, lane_launch(inst, c0->dev, d_dev, l.count, L, l.grid, g->ctxs[lane_first]->plan.lane.block, g->stream));
     }
+    g->launched = true;
     if (l.count >= 2) g->batched_launches++;
   }
   HIPCK(c0, smpc_launch_reduce_many(reinterpret_cast<const SmpcReduceArgs*>(g->d_all + g->off_red), m,
@@ -315,11 +333,18 @@ int smpc_group_optimize(smpc_group* g, const smpc_tick_in* ins, float* const* u_
       o->pass_kind = c->last_pass_kind;
     }
   }
+  g->launched = false;   // every riding member's fetch_out has returned
   if (timing && (g->batched_ticks % 64) == 0)
     fprintf(stderr, "[smpc_group] prepare %.1f us, fill+launch %.1f us, wait+collect %.1f us; batched %llu single %llu\n",
             us_between(t_start, t_prep), us_between(t_prep, t_launch), us_between(t_launch, now()),
             (unsigned long long)g->batched_ticks, (unsigned long long)g->single_ticks);
   return SMPC_OK;
+}
+
+int smpc_group_optimize(smpc_group* g, const smpc_tick_in* ins, float* const* u_inout,
+                        smpc_tick_out* outs)
+{
+  return smpc_group_optimize_some(g, ins, u_inout, outs, nullptr);
 }
 
 }  // extern "C"

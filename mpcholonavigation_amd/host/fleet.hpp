@@ -1,0 +1,117 @@
+// fleet.hpp — Optimizer::evalControl for N robots through one grouped tick.
+//
+// A fleet host holds N sortham::Optimizer objects, one per robot.  FleetOptimizer ticks the ones
+// a round takes with ONE smpc_group_optimize_some call (include/smpc.h: one upload, one scoring
+// launch per instance, one reduction for all of them) and then runs, per member, exactly what
+// Optimizer::evalControl runs around its own smpc_optimize call [ref src/optimizer.cpp:134-225]:
+// fallback / reset / retry / throw, the Savitzky-Golay filter, Twist extraction, the shift.  The
+// pieces are the members' own (Optimizer::fillTick / takeTick / fallback / finishTick): a member of
+// a fleet computes what it computes alone, bit for bit.
+//
+// The caller keeps ownership of the optimizers and goes on using them through their own
+// interface between rounds (setCostmap, setSpeedLimit, reset, setNoise, controlSequence(),
+// initialize() again, shutdown()).  Single-threaded: one round, or one member call, at a time.
+// Order of destruction: any; a member that is shut down or destroyed leaves the fleet's group
+// first (smpc.h: the group goes before its contexts), and destroying the fleet hands every
+// context back to its own stream.
+#ifndef SORTHAM_HOST_FLEET_HPP_
+#define SORTHAM_HOST_FLEET_HPP_
+
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "optimizer.hpp"
+
+namespace SORTHAM_HOST_NS
+{
+
+// A member's status after a round: SMPC_OK, FLEET_NOT_TAKEN (positive: nothing of its changed) or
+// FLEET_THROWN where evalControl would have thrown (the text is in MemberResult::error).
+constexpr int FLEET_NOT_TAKEN = 1;
+constexpr int FLEET_THROWN = -10;   // SORTHAM_ERR_THROWN of include/smpc_host.h
+
+struct FleetError : std::runtime_error
+{
+  FleetError(int c, const std::string & what)
+  : std::runtime_error(what), code(c) {}
+  int code;   // SMPC_ERR_*
+};
+
+struct MemberResult
+{
+  Twist2D twist{};
+  smpc_tick_out out{};
+  int status{FLEET_NOT_TAKEN};
+  std::string error;
+};
+
+struct FleetStats
+{
+  uint64_t batched_launches{0};   // smpc_group_stats, summed over the groups the fleet has had
+  uint64_t single_ticks{0};       // (the retries below included: they are ticked alone)
+  uint64_t retries{0};            // optimize() calls of the fallback loop
+};
+
+class FleetOptimizer : public FleetLink
+{
+public:
+  // Throws FleetError: SMPC_ERR_INVALID for no member, a null one or one listed twice,
+  // SMPC_ERR_STATE for one that is not initialised or is in a fleet already; what
+  // smpc_group_create refuses (members on different devices or with different time_steps), with
+  // its message.
+  explicit FleetOptimizer(const std::vector<Optimizer *> & members);
+  ~FleetOptimizer() override;
+  FleetOptimizer(const FleetOptimizer &) = delete;
+  FleetOptimizer & operator=(const FleetOptimizer &) = delete;
+
+  size_t size() const {return members_.size();}
+  // null once the member was destroyed
+  Optimizer * member(size_t i) const {return members_[i];}
+
+  // One round.  Every vector has size() entries; the entries of a member that is not taken are
+  // not looked at.  take: one byte per member, empty = everybody.  Returns SMPC_OK, or the
+  // SMPC_ERR_* of a round that failed as a whole (text in lastError()): then no member's control
+  // sequence, filter history or retry counter has moved, and the next round is safe to run.
+  // A round that takes a member which was shut down or destroyed is SMPC_ERR_STATE.
+  int evalControl(
+    const std::vector<Pose2D> & poses, const std::vector<Twist2D> & speeds,
+    const std::vector<models::Path> & plans, const std::vector<Pose2D> & goals,
+    const std::vector<float> & goal_checker_xy_tolerances, const std::vector<uint8_t> & take,
+    std::vector<MemberResult> & results);
+
+  FleetStats stats() const;
+  const std::string & lastError() const {return err_;}
+
+  // the members' contexts back on their own streams until the next round (which regroups): for a
+  // caller that wants to tick members through their own evalControl on the ungrouped path
+  void ungroup() {dropGroup();}
+
+  // FleetLink
+  void dropGroup() override;
+  void memberDestroyed(Optimizer * member) override;
+  bool grouped(const Optimizer * member) const override;
+  void tickAlone(Optimizer * member, const smpc_tick_in & in, float * u, smpc_tick_out & out) override;
+
+private:
+  int regroup();
+  int fail(int code, const std::string & what);
+
+  std::vector<Optimizer *> members_;
+  smpc_group * group_{nullptr};
+  std::vector<int> slot_;             // member -> index in the group, -1: no context
+  std::vector<size_t> owner_;         // group index -> member
+  // per group slot, one round's arguments
+  std::vector<smpc_tick_in> ins_;
+  std::vector<smpc_tick_out> outs_;
+  std::vector<std::vector<float>> u_;
+  std::vector<float *> u_ptr_;
+  std::vector<uint8_t> take_;
+  std::vector<std::string> errs_before_;
+  FleetStats stats_{};                // of the groups already dropped, and the retries
+  std::string err_;
+};
+
+}  // namespace SORTHAM_HOST_NS
+
+#endif

@@ -1,0 +1,137 @@
+// fleet_c.cpp — extern "C" face of sortham_ns::FleetOptimizer (include/smpc_host.h).
+#include <exception>
+#include <new>
+
+#include "fleet_c.hpp"
+
+namespace
+{
+thread_local std::string g_fleet_err;
+}  // namespace
+
+extern "C" {
+
+int sortham_fleet_create(sortham_optimizer * const * members, uint32_t n, sortham_fleet ** out)
+{
+  if (out) {
+    *out = nullptr;
+  }
+  if (!members || n == 0 || !out) {
+    g_fleet_err = "null argument";
+    return SMPC_ERR_INVALID;
+  }
+  std::vector<sortham_ns::Optimizer *> opts;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!members[i]) {
+      g_fleet_err = "member " + std::to_string(i) + " is null";
+      return SMPC_ERR_INVALID;
+    }
+    opts.push_back(&members[i]->opt);
+  }
+  try {
+    std::unique_ptr<sortham_fleet> f(new sortham_fleet());
+    f->fleet.reset(new sortham_ns::FleetOptimizer(opts));
+    f->handles.assign(members, members + n);
+    f->poses.resize(n);
+    f->goals.resize(n);
+    f->speeds.resize(n);
+    f->plans.resize(n);
+    f->tolerances.assign(n, -1.0f);
+    f->take.assign(n, 1);
+    *out = f.release();
+    return SMPC_OK;
+  } catch (const sortham_ns::FleetError & e) {
+    g_fleet_err = e.what();
+    return e.code;
+  } catch (const std::bad_alloc &) {
+    g_fleet_err = "out of memory";
+    return SMPC_ERR_NOMEM;
+  } catch (const std::exception & e) {
+    g_fleet_err = e.what();
+    return SORTHAM_ERR_THROWN;
+  }
+}
+
+void sortham_fleet_destroy(sortham_fleet * f) {delete f;}
+
+const char * sortham_fleet_last_error(const sortham_fleet * f)
+{
+  return f ? f->err.c_str() : g_fleet_err.c_str();
+}
+
+int sortham_fleet_eval_control(
+  sortham_fleet * f, const smpc_tick_in * ins, const uint8_t * take, double * twists,
+  smpc_tick_out * outs, int32_t * status)
+{
+  if (!f || !ins || !twists || !status) {
+    return SMPC_ERR_INVALID;
+  }
+  const size_t n = f->handles.size();
+  try {
+    for (size_t i = 0; i < n; ++i) {
+      f->take[i] = (!take || take[i]) ? 1 : 0;
+      if (!f->take[i]) {
+        continue;
+      }
+      const smpc_tick_in & in = ins[i];
+      if (in.path_len && (!in.path_x || !in.path_y || !in.path_yaw)) {
+        f->err = "member " + std::to_string(i) + ": null plan";
+        return SMPC_ERR_INVALID;
+      }
+      f->poses[i] = {in.pose_x, in.pose_y, static_cast<double>(in.pose_yaw)};
+      f->goals[i] = {in.goal_x, in.goal_y, 0.0};
+      f->speeds[i] = {in.speed_vx, in.speed_vy, in.speed_wz};
+      f->plans[i].x.assign(in.path_x, in.path_x + in.path_len);
+      f->plans[i].y.assign(in.path_y, in.path_y + in.path_len);
+      f->plans[i].yaws.assign(in.path_yaw, in.path_yaw + in.path_len);
+      f->tolerances[i] = in.goal_checker_xy_tolerance;
+    }
+    const int rc = f->fleet->evalControl(
+      f->poses, f->speeds, f->plans, f->goals, f->tolerances, f->take, f->results);
+    if (rc != SMPC_OK) {
+      f->err = f->fleet->lastError();
+      return rc;
+    }
+  } catch (const std::exception & e) {
+    f->err = e.what();
+    return SORTHAM_ERR_THROWN;
+  }
+  for (size_t i = 0; i < n; ++i) {
+    const sortham_ns::MemberResult & r = f->results[i];
+    status[i] = r.status;
+    if (r.status == sortham_ns::FLEET_NOT_TAKEN) {
+      continue;
+    }
+    twists[3 * i] = r.twist.vx;
+    twists[3 * i + 1] = r.twist.vy;
+    twists[3 * i + 2] = r.twist.wz;
+    if (outs) {
+      outs[i] = r.out;
+    }
+    if (r.status == SORTHAM_ERR_THROWN && f->fleet->member(i)) {
+      f->handles[i]->err = r.error;
+    }
+  }
+  return SMPC_OK;
+}
+
+int sortham_fleet_stats(
+  const sortham_fleet * f, uint64_t * batched_launches, uint64_t * single_ticks, uint64_t * retries)
+{
+  if (!f) {
+    return SMPC_ERR_INVALID;
+  }
+  const sortham_ns::FleetStats s = f->fleet->stats();
+  if (batched_launches) {
+    *batched_launches = s.batched_launches;
+  }
+  if (single_ticks) {
+    *single_ticks = s.single_ticks;
+  }
+  if (retries) {
+    *retries = s.retries;
+  }
+  return SMPC_OK;
+}
+
+}  // extern "C"

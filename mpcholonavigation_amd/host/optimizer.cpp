@@ -19,14 +19,30 @@ void ck(smpc_ctx * ctx, int rc, const char * what)
 }
 }  // namespace
 
-Optimizer::~Optimizer() {shutdown();}
+Optimizer::~Optimizer()
+{
+  shutdown();
+  if (fleet_) {
+    fleet_->memberDestroyed(this);
+  }
+}
 
 void Optimizer::shutdown()
 {
   if (ctx_) {
-    smpc_destroy(ctx_);
+    destroyContext(ctx_);
     ctx_ = nullptr;
   }
+}
+
+void Optimizer::destroyContext(smpc_ctx * ctx)
+{
+  // smpc.h: a group is destroyed before its members.  The fleet drops its group here and forms
+  // a new one, over the contexts its members have by then, before its next round.
+  if (fleet_) {
+    fleet_->dropGroup();
+  }
+  smpc_destroy(ctx);
 }
 
 void Optimizer::setMotionModel(const std::string & model)
@@ -76,9 +92,10 @@ void Optimizer::initialize(
   ctx_ = nullptr;
   struct Guard
   {
+    Optimizer * self;
     smpc_ctx *& k;
-    ~Guard() {if (k) {smpc_destroy(k);}}   // a throwing initialize() leaves no context behind, as before
-  } guard{keep};
+    ~Guard() {if (k) {self->destroyContext(k);}}   // a throwing initialize() leaves no context behind, as before
+  } guard{this, keep};
   settings_ = settings;
   settings_.constraints = settings_.base_constraints;
   setMotionModel(motion_model);
@@ -147,7 +164,7 @@ void Optimizer::initialize(
   cfg.vy_std = settings_.sampling_std.vy;
   cfg.wz_std = settings_.sampling_std.wz;
   cfg.device = device_;
-  cfg.flags = visualize_ ? SMPC_FLAG_STORE_TRAJECTORIES : 0u;
+  cfg.flags = (visualize_ ? SMPC_FLAG_STORE_TRAJECTORIES : 0u) | (lane_per_rollout_ ? SMPC_FLAG_LANE_PER_ROLLOUT : 0u);
   if (keep && have_built_ && std::memcmp(&cfg, &built_cfg_, sizeof(cfg)) == 0 && noise_seed_ == built_seed_) {
     // same shapes, model, sampling and seed: only the critics' parameters can differ.  What the
     // reference's reset() does (src/optimizer.cpp:116-132) is reset() below, noise re-draw included.
@@ -162,7 +179,7 @@ void Optimizer::initialize(
     return;
   }
   if (keep) {
-    smpc_destroy(keep);
+    destroyContext(keep);
     keep = nullptr;
   }
   have_built_ = false;
@@ -233,9 +250,8 @@ void Optimizer::prepare(
   fail_flag_ = false;   // costs_.fill(0) and the CriticData caches are per smpc_optimize call
 }
 
-void Optimizer::optimize()
+void Optimizer::fillTick(smpc_tick_in & in, float * u)
 {
-  smpc_tick_in in;
   std::memset(&in, 0, sizeof(in));
   in.pose_x = pose_.x;
   in.pose_y = pose_.y;
@@ -254,21 +270,41 @@ void Optimizer::optimize()
   in.goal_checker_xy_tolerance = goal_checker_xy_tolerance_;
 
   const unsigned int T = settings_.time_steps;
-  std::vector<float> u(3 * T);
-  std::memcpy(u.data(), control_sequence_.vx.data(), T * sizeof(float));
-  std::memcpy(u.data() + T, control_sequence_.vy.data(), T * sizeof(float));
-  std::memcpy(u.data() + 2 * T, control_sequence_.wz.data(), T * sizeof(float));
+  std::memcpy(u, control_sequence_.vx.data(), T * sizeof(float));
+  std::memcpy(u + T, control_sequence_.vy.data(), T * sizeof(float));
+  std::memcpy(u + 2 * T, control_sequence_.wz.data(), T * sizeof(float));
   pushConstraints();
-  ck(ctx_, smpc_optimize(ctx_, &in, u.data(), &last_out_), "smpc_optimize");
-  std::memcpy(control_sequence_.vx.data(), u.data(), T * sizeof(float));
-  std::memcpy(control_sequence_.vy.data(), u.data() + T, T * sizeof(float));
-  std::memcpy(control_sequence_.wz.data(), u.data() + 2 * T, T * sizeof(float));
+}
+
+void Optimizer::takeTick(const float * u, const smpc_tick_out & out)
+{
+  const unsigned int T = settings_.time_steps;
+  std::memcpy(control_sequence_.vx.data(), u, T * sizeof(float));
+  std::memcpy(control_sequence_.vy.data(), u + T, T * sizeof(float));
+  std::memcpy(control_sequence_.wz.data(), u + 2 * T, T * sizeof(float));
+  last_out_ = out;
   fail_flag_ = last_out_.fail_flag != 0;
   if (regenerate_noises_ && !supplied_noise_) {
     // NoiseGenerator::generateNextNoises (noise_generator.cpp:54-63): next tick's noise, drawn
     // while this tick's result travels on (the reference's noise thread, :97-105)
     ck(ctx_, smpc_redraw_noise_async(ctx_), "smpc_redraw_noise_async");
   }
+}
+
+void Optimizer::optimize()
+{
+  smpc_tick_in in;
+  std::vector<float> u(3 * settings_.time_steps);
+  fillTick(in, u.data());
+  smpc_tick_out out;
+  if (fleet_ && fleet_->grouped(this)) {
+    // a grouped context is not ticked through smpc_optimize directly (smpc.h): the group ticks
+    // this member alone — smpc_optimize on its slot of the group's buffers, the same result
+    fleet_->tickAlone(this, in, u.data(), out);
+  } else {
+    ck(ctx_, smpc_optimize(ctx_, &in, u.data(), &out), "smpc_optimize");
+  }
+  takeTick(u.data(), out);
 }
 
 bool Optimizer::fallback(bool fail)
@@ -294,6 +330,11 @@ Twist2D Optimizer::evalControl(
   do {
     optimize();
   } while (fallback(fail_flag_));
+  return finishTick();
+}
+
+Twist2D Optimizer::finishTick()
+{
   utils::savitskyGolayFilter(control_sequence_, control_history_, settings_);
   auto control = getControlFromSequenceAsTwist();
   if (settings_.shift_control_sequence) {

@@ -122,6 +122,25 @@ void savitskyGolayFilter(
   const models::OptimizerSettings & settings);
 }  // namespace utils
 
+class Optimizer;
+
+// What an Optimizer asks of the fleet it is a member of (fleet.hpp: FleetOptimizer, N optimizers
+// ticked through one smpc_group).  An interface, so that this class links without the fleet.
+class FleetLink
+{
+public:
+  virtual ~FleetLink() = default;
+  // a member's context is about to be destroyed: the group goes first (smpc.h)
+  virtual void dropGroup() = 0;
+  virtual void memberDestroyed(Optimizer * member) = 0;
+  // is this member's context in the fleet's group right now?
+  virtual bool grouped(const Optimizer * member) const = 0;
+  // one tick of this member alone through the group (smpc_optimize on its slot); throws on error
+  virtual void tickAlone(Optimizer * member, const smpc_tick_in & in, float * u, smpc_tick_out & out) = 0;
+};
+
+class FleetOptimizer;
+
 class Optimizer
 {
 public:
@@ -161,12 +180,25 @@ public:
   const models::OptimizerSettings & settings() const {return settings_;}
   const smpc_tick_out & lastTick() const {return last_out_;}
   void setVisualize(bool v) {visualize_ = v;}
+  // SMPC_FLAG_LANE_PER_ROLLOUT for the context initialize() creates (smpc.h); call before it
+  void setLanePerRollout(bool v) {lane_per_rollout_ = v;}
   bool isHolonomic() const {return motion_model_ == SMPC_MODEL_OMNI;}   // ref :235
   // AckermannConstraints.min_turning_r (motion_models.hpp:91-95); call before initialize()
   void setAckermannMinTurningRadius(float r) {ackermann_min_turning_r_ = r;}
 
+  bool initialized() const {return ctx_ != nullptr;}
+
 protected:
+  friend class FleetOptimizer;   // fleet.hpp
   void optimize();                         // ref :157-164 -> smpc_optimize
+  // the three pieces of a tick around the scoring call, shared with FleetOptimizer:
+  // the member's smpc_tick_in and u [3][T] from its state, constraints pushed
+  void fillTick(smpc_tick_in & in, float * u);
+  // a tick's result: u copied back, fail_flag_, last_out_, the regenerate_noises redraw
+  void takeTick(const float * u, const smpc_tick_out & out);
+  // ref :147-154: Savitzky-Golay filter, Twist, shift
+  Twist2D finishTick();
+  void destroyContext(smpc_ctx * ctx);     // tells the fleet first: its group goes before the context
   bool fallback(bool fail);                // ref :166-183 (retry counter per object)
   void prepare(const Pose2D &, const Twist2D &, const models::Path &, const Pose2D &);  // ref :185-204
   void shiftControlSequence();             // ref :206-225
@@ -183,6 +215,7 @@ protected:
   uint32_t motion_model_{SMPC_MODEL_OMNI};
   float ackermann_min_turning_r_{0.2f};
   bool visualize_{false};
+  bool lane_per_rollout_{false};
   uint64_t noise_seed_{0};
   bool supplied_noise_{false};
   int device_{-1};
@@ -199,6 +232,7 @@ protected:
   float goal_checker_xy_tolerance_{-1.0f};
   size_t retry_counter_{0};
   smpc_tick_out last_out_{};
+  FleetLink * fleet_{nullptr};   // set while the object is a fleet's member
 };
 
 }  // namespace SORTHAM_HOST_NS

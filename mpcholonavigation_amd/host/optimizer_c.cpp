@@ -7,34 +7,7 @@
 #include <vector>
 
 #include "../../include/smpc_host.h"
-#include "optimizer.hpp"
-
-namespace sortham_ns = SORTHAM_HOST_NS;
-
-namespace
-{
-// the class plus the one call the C face adds: a footprint handed over on its own, not with a costmap
-struct OptimizerWithFootprint : sortham_ns::Optimizer
-{
-  void applyFootprint(const std::vector<double> & xy, double radius, double layer_scale)
-  {
-    if (!ctx_ || xy.empty()) {return;}
-    if (smpc_set_footprint(ctx_, xy.data(), static_cast<uint32_t>(xy.size() / 2), radius, layer_scale) != SMPC_OK) {
-      throw std::runtime_error(std::string("smpc_set_footprint: ") + smpc_last_error(ctx_));
-    }
-  }
-};
-}  // namespace
-
-struct sortham_optimizer
-{
-  OptimizerWithFootprint opt;
-  std::string err;
-  // sortham_optimizer_set_footprint: kept for the contexts initialize() builds later
-  std::vector<double> footprint_xy;
-  double circumscribed_radius{0};
-  double layer_cost_scaling_factor{-1.0};
-};
+#include "optimizer_c.hpp"
 
 namespace
 {
@@ -80,6 +53,7 @@ void initialize_from(sortham_optimizer * o, const sortham_optimizer_config * cfg
   cc.cost_scaling_factor = cfg->cost_scaling_factor;
   cc.inflation_radius = cfg->inflation_radius;
   o->opt.setVisualize(cfg->visualize != 0);
+  o->opt.setLanePerRollout((b.flags & SMPC_FLAG_LANE_PER_ROLLOUT) != 0);
   o->opt.setAckermannMinTurningRadius(b.ackermann_min_turning_r);
   o->opt.initialize(
     s, cfg->motion_model ? cfg->motion_model : "DiffDrive", cfg->controller_frequency, cc,
@@ -194,6 +168,13 @@ int sortham_optimizer_eval_control(
       twist_out[2] = t.wz;
       if (out) {*out = o->opt.lastTick();}
     });
+}
+
+int sortham_optimizer_last_tick(const sortham_optimizer * o, smpc_tick_out * out)
+{
+  if (!o || !out) {return SMPC_ERR_INVALID;}
+  *out = o->opt.lastTick();
+  return SMPC_OK;
 }
 
 int sortham_optimizer_set_speed_limit(sortham_optimizer * o, double speed_limit, int percentage)

@@ -306,8 +306,10 @@ class SmpcGroup:
             raise SmpcError(rc, self.lib.smpc_last_error(None).decode())
         self.h = h
 
-    def optimize(self, ticks, us):
-        """ticks, us: one per member; returns [(u_new, SmpcTickOut)] in member order."""
+    def optimize(self, ticks, us, take=None):
+        """ticks, us: one per member; returns [(u_new, SmpcTickOut)] in member order.
+        take (smpc_group_optimize_some): one truth value per member; a member left out is not
+        ticked at all — its entries of ticks and us may be None, and its result is None."""
         n = len(self.members)
         if getattr(self, "_ins", None) is None or len(ticks) != n:
             if len(ticks) != n:
@@ -317,7 +319,12 @@ class SmpcGroup:
             self._bufs = np.empty((n, 3, self.members[0].T), np.float32)
             self._ptrs = (C.c_void_p * n)(*[self._bufs[i].ctypes.data for i in range(n)])
             self._outs = (A.SmpcTickOut * n)()
+        if take is not None and len(take) != n:
+            raise ValueError("one take entry per member")
+        on = [True] * n if take is None else [bool(v) for v in take]
         for i, t in enumerate(ticks):
+            if not on[i]:
+                continue
             # Tick.c is rebuilt whenever a field of the tick was assigned: copy it again when
             # it is not the struct object this slot was filled from (an identity check per member)
             c = t.c
@@ -325,14 +332,19 @@ class SmpcGroup:
                 self._ins[i] = c
                 self._src[i] = c
         for i, u in enumerate(us):
-            self._bufs[i] = u
-        rc = self.lib.smpc_group_optimize(self.h, self._ins, self._ptrs, self._outs)
+            if on[i]:
+                self._bufs[i] = u
+        if take is None:
+            rc = self.lib.smpc_group_optimize(self.h, self._ins, self._ptrs, self._outs)
+        else:
+            mask = (C.c_uint8 * n)(*[int(v) for v in on])
+            rc = self.lib.smpc_group_optimize_some(self.h, self._ins, self._ptrs, self._outs, mask)
         if rc != 0:
             msg = next((m.lib.smpc_last_error(m.h).decode() for m in self.members
                         if m.lib.smpc_last_error(m.h)), "")
             raise SmpcError(rc, msg)
         res = self._bufs.copy()
-        return [(res[i], A.SmpcTickOut.from_buffer_copy(self._outs[i])) for i in range(n)]
+        return [(res[i], A.SmpcTickOut.from_buffer_copy(self._outs[i])) if on[i] else None for i in range(n)]
 
     def stats(self):
         """How the group's ticks went so far (smpc_group_stats): batched_launches — scoring launches
