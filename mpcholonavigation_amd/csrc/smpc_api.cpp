@@ -1365,6 +1365,30 @@ int smpc_debug_prune_table(const float* px, const float* py, uint32_t P, uint32_
   return SMPC_OK;
 }
 
+// developer aid, host only (tests/test_lds_layout_cpu.py): the LDS carve-up a scoring pass is
+// launched with — kind 0: the wave pass (make_lds; arg = PathAlign samples per rollout), 1: the lane
+// pass (lane_lds; arg != 0: the re-read form), 2: the split pass (split_lds; arg = segments, 2 or
+// 4) — for a costmap window of window_bytes cells (0: no costmap lookup), P path points and T
+// steps, with the block sizes plan_launch uses.  out: the 16 words of SmpcLds in declaration order.
+int smpc_debug_lds_layout(int kind, uint32_t window_bytes, uint32_t P, uint32_t T, uint32_t arg, uint32_t* out)
+{
+  if (!out || T == 0) return SMPC_ERR_INVALID;
+  SmpcLds L{};
+  if (kind == 0) {
+    const int R = T <= 64 ? 1 : (T <= 128 ? 2 : 4);   // (smpc_create)
+    L = make_lds(window_bytes, P, T, pass_block(R) / 64, window_bytes != 0, arg);
+  } else if (kind == 1) {
+    L = lane_lds(window_bytes, P, T, arg != 0);
+  } else if (kind == 2 && (arg == 2 || arg == 4)) {
+    L = split_lds(window_bytes, P, T, arg);
+  } else {
+    return SMPC_ERR_INVALID;
+  }
+  static_assert(sizeof(SmpcLds) == 16 * sizeof(uint32_t), "SmpcLds: 16 words");
+  memcpy(out, &L, sizeof(L));
+  return SMPC_OK;
+}
+
 // developer aid (bench.py labels its roofline with it): the scoring-pass instance the calling
 // thread launched last, spelled as rocprofv3's kernel trace spells it
 const char* smpc_debug_last_pass_kernel(void) {return smpc_last_pass_kernel;}

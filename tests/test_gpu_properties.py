@@ -159,9 +159,13 @@ def test_fallback_counter_is_per_object():
 
 @pytest.mark.parametrize("P", [1, 2, 3, 64, 65, 300, 1024])
 def test_path_length_edges(P, both_passes):
-    """Plans from a single point to SMPC_MAX_PATH points (argmin over > 64 points, LDS staging)."""
+    """Plans from a single point to SMPC_MAX_PATH points (argmin over > 64 points, LDS staging).
+    Which pass it judged: with SMPC_PASS=lane the lane pass up to the longest plan its LDS layout
+    admits (tests/plan_scenes.py: read through smpc_debug_lds_layout), the wave pass beyond it — and
+    the wave pass for a context that does not ask (512 rollouts)."""
     from mpcholonavigation_amd.optimizer import Smpc
     from oracle.loader import Oracle
+    from tests.plan_scenes import lane_limit
     B, T = 512, 56
     cfg = default_config(batch_size=B, time_steps=T)
     scn = make_scenario(T)
@@ -178,6 +182,9 @@ def test_path_length_edges(P, both_passes):
         configure(x, scn, critics=cr, noise=noise)
     ug, og = g.optimize(tick, scn.u0)
     uo, oo = o.optimize(tick, scn.u0)
+    kind = 1 if both_passes == "lane" and P <= lane_limit(T) else 0
+    print(f"[path length] P={P} ({both_passes}): pass_kind {og.pass_kind}, lane pass up to P = {lane_limit(T)}")
+    assert og.pass_kind == kind, (P, both_passes, og.pass_kind)
     assert_parity(ug, og, uo, oo, g.get_costs(), o.get_costs(), label=f"P={P}", max_flips=1)
 
 
