@@ -142,11 +142,37 @@ int launch_furthest(smpc_ctx* c, float* d_furthest)
   return SMPC_OK;
 }
 
-// one scoring pass + block reduction -> tuple
+int begin_tick(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
+{
+  const int rc = prepare_tick(c, in, u_in);   // (touches none of the three)
+  if (rc != SMPC_OK) return rc;
+  c->passes = 0;
+  c->evp_used = 0;
+  c->costs_cur = 0;
+  return SMPC_OK;
+}
+
+int refuse_sharded(smpc_ctx* c)
+{
+  if (c->two_coll_fp)
+    return fail(c, SMPC_ERR_UNSUPPORTED,
+                "sharded tick: consider_footprint=true with both ObstaclesCritic and CostCritic in the list");
+  if (c->cfg.iteration_count != 1)   // (one exchange = one iteration; never silently fewer than asked for)
+    return fail(c, SMPC_ERR_UNSUPPORTED, "sharded tick: iteration_count must be 1");
+  return SMPC_OK;
+}
+
+uint32_t next_seq(smpc_ctx* c)
+{
+  if (++c->seq == 0) ++c->seq;
+  c->poll_seq = c->seq;
+  return c->seq;
+}
+
+// parameter blocks of one scoring pass + reduction of ctx c (no launch)
 // finish_furthest: when `finish`, the reduction also produces the new control sequence
 // (single-GPU tick) and reports *finish_furthest (or the pass's own value) as the furthest
 // point the critics used
-// parameter blocks of one scoring pass + reduction of ctx c (no launch)
 void fill_score_args(smpc_ctx* c, uint32_t flags, const float* u_dev, const float* d_furthest,
                      uint32_t furthest_hint, bool finish, const float* finish_furthest, SmpcDev& d,
                      SmpcFinal& fin)
@@ -166,10 +192,8 @@ void fill_score_args(smpc_ctx* c, uint32_t flags, const float* u_dev, const floa
   fin.vx_max = c->c_vx_max; fin.vx_min = c->c_vx_min; fin.vy_max = c->c_vy; fin.wz_max = c->c_wz;
   fin.u_dev = c->d_out; fin.u_host = c->h_out_dev; fin.furthest_used = finish_furthest;
   if (finish && c->knobs.poll) {
-    fin.done_counter = reinterpret_cast<uint32_t*>(c->d_furthest) + 2;
-    fin.seq = ++c->seq;
-    if (fin.seq == 0) fin.seq = ++c->seq;
-    c->poll_seq = fin.seq;
+    fin.done_counter = scratch_word(c, SMPC_SCRATCH_REDUCE_COUNTER);
+    fin.seq = next_seq(c);
   }
   if (finish && c->acker_r >= 0.f) {   // the Ackermann launch behind the reduction publishes
     c->acker_seq = fin.seq;
@@ -208,6 +232,7 @@ static PassChoice pass_for(const smpc_ctx* c, uint32_t flags)
   return {PassPlan::kWave, wave_select(c->R, c->score_mode, T), &pl.wave};
 }
 
+// one scoring pass + block reduction -> tuple
 int launch_score(smpc_ctx* c, uint32_t flags, const float* u_dev, const float* d_furthest,
                  uint32_t furthest_hint, float* d_tuple, bool finish, const float* finish_furthest)
 {
@@ -224,17 +249,17 @@ int launch_score(smpc_ctx* c, uint32_t flags, const float* u_dev, const float* d
   const bool tail = pass.kind != PassPlan::kSplit && c->knobs.fused_reduce && nblk <= SMPC_TAIL_MAX_GRID &&
     (pass.kind != PassPlan::kLane || pass.geom->block == smpc_lane_block()) && pass.geom->lds.total >= smpc_tail_lds_bytes(d.T);
   // completion words: one per block of smpc_reduce_partials, or per reducing block of the tail
-  c->poll_words = (fin.enabled && fin.done_counter) ? (4u + 3u * d.T + 31u) / 32u : 0u;
-  static_assert((4u + 3u * 64u * SMPC_MAX_R + 31u) / 32u <= kPollWords, "one completion word per reducing block");
+  const bool polled = fin.enabled && fin.done_counter;
+  c->poll_words = !polled ? 0u : tail ? smpc_tail_reduce_blocks(d.T, nblk) : smpc_reduce_blocks(d.T);
+  static_assert(smpc_reduce_blocks(64u * SMPC_MAX_R) <= kPollWords, "one completion word per reducing block");
   if (tail) {
-    // (every reducing block publishes its own completion word: smpc_tail.h)
-    if (fin.enabled && fin.done_counter) c->poll_words = std::min((4u + 3u * d.T + 63u) / 64u, nblk);
     // the tail's "gave up waiting" mark of an earlier tick must not fail this one (no launch of
     // this ctx is in flight here: every tick ends with fetch_out); the mailbox exchange's mark
     // in the same word is sticky by design and stays
-    if (c->h_out[3 * d.T + 6] == 2.0f) c->h_out[3 * d.T + 6] = 0.0f;
+    float& mark = c->h_out[SMPC_RESULT_AT(d.T) + SMPC_R_MARK];
+    if (mark == SMPC_MARK_TAIL_LATE) mark = SMPC_MARK_NONE;
     d.tail = 1;
-    d.tail_counter = reinterpret_cast<uint32_t*>(c->d_furthest) + 4;
+    d.tail_counter = scratch_word(c, SMPC_SCRATCH_TAIL_COUNTER);
     d.tuple = d_tuple;
     d.fin = fin;
   }
@@ -265,14 +290,12 @@ int launch_combine(smpc_ctx* c, const float* d_tuples, uint32_t n, const float* 
   const uint32_t T = c->cfg.time_steps;
   uint32_t seq = 0;
   if (c->knobs.poll) {
-    seq = ++c->seq;
-    if (seq == 0) seq = ++c->seq;
-    c->poll_seq = seq;
+    seq = next_seq(c);
     c->poll_words = 0;   // (one word, written by the combining block)
   }
   const bool acker = c->acker_r >= 0.f;
   HIPCK(c, smpc_launch_combine(d_tuples, n, T, c->dev.neg_inv_temp, c->c_vx_max, c->c_vx_min,
-                               c->c_vy, c->c_wz, c->d_out, c->d_out + 3 * T, d_furthest_used,
+                               c->c_vy, c->c_wz, c->d_out, c->d_out + SMPC_RESULT_AT(T), d_furthest_used,
                                c->h_out_dev, acker ? 0u : seq, c->stream));
   if (acker) HIPCK(c, smpc_launch_ackermann(c->d_out, c->h_out_dev, T, c->acker_r, seq, c->stream));
   return SMPC_OK;
@@ -297,7 +320,7 @@ static int check_canary(smpc_ctx* c)
 {
   c->launched = false;
   if (!c->canary_expect) return SMPC_OK;
-  const uint32_t got = reinterpret_cast<const volatile uint32_t*>(c->h_out)[3 * c->cfg.time_steps + 5];
+  const uint32_t got = reinterpret_cast<const volatile uint32_t*>(c->h_out)[SMPC_RESULT_AT(c->cfg.time_steps) + SMPC_R_CANARY];
   if (got == c->canary_expect) return SMPC_OK;
   char msg[200];
   snprintf(msg, sizeof(msg), "the scoring pass read tick block %u, not %u: the per-tick upload did not reach the "
@@ -314,10 +337,11 @@ int fetch_out(smpc_ctx* c)
   // runtime's stream wait), and fall back to the stream wait, which also surfaces errors.
   if (c->poll_seq) {
     const volatile uint32_t* flag =
-      reinterpret_cast<const volatile uint32_t*>(c->h_out + 3 * c->cfg.time_steps + 7);
+      reinterpret_cast<const volatile uint32_t*>(c->h_out + SMPC_RESULT_AT(c->cfg.time_steps) + SMPC_R_DONE);
     const uint32_t want = c->poll_seq;
     c->poll_seq = 0;
-    const uint32_t nwords = c->poll_words;   // > 0: one word per reducing block, from flag[1] on
+    const uint32_t nwords = c->poll_words;   // > 0: one word per reducing block, from flag[1] on (SMPC_R_BLOCK_DONE)
+    static_assert(SMPC_R_BLOCK_DONE == SMPC_R_DONE + 1u, "the per-block words follow the completion word");
     c->poll_words = 0;
     auto arrived = [&]() {
       if (nwords == 0) return *flag == want;
@@ -329,7 +353,7 @@ int fetch_out(smpc_ctx* c)
       if (arrived()) {
         __atomic_thread_fence(__ATOMIC_ACQUIRE);
         // smpc_grid_tail's mark: a reducing block gave up waiting for the grid's other blocks
-        if (c->h_out[3 * c->cfg.time_steps + 6] == 2.0f)
+        if (tick_result(c).mark() == SMPC_MARK_TAIL_LATE)
           return fail(c, SMPC_ERR_DEVICE, "the scoring launch's reduction did not see every block's partial");
         return check_canary(c);
       }
@@ -352,6 +376,30 @@ float profile_pass_ms(smpc_ctx* c)
     }
   }
   return n ? sum / n : 0.f;
+}
+
+int fill_tick_out(smpc_ctx* c, smpc_tick_out* out, bool fail_flag, bool furthest_valid, uint32_t furthest,
+                  const float* non_colliding, bool device_ms)
+{
+  if (!out) return SMPC_OK;
+  const TickResult r = tick_result(c);
+  memset(out, 0, sizeof(*out));
+  out->fail_flag = fail_flag ? 1 : 0;
+  out->furthest_valid = furthest_valid ? 1 : 0;
+  out->furthest_reached_path_point = furthest;
+  out->non_colliding = static_cast<uint32_t>(non_colliding ? *non_colliding : r.non_colliding());
+  out->min_cost = r.min_cost();
+  out->sum_w = r.sum_w();
+  out->passes = c->passes;
+  if (device_ms && (c->cfg.flags & SMPC_FLAG_PROFILE)) {
+    // the polled flag can beat the event's completion signal by a few microseconds
+    HIPCK(c, hipEventSynchronize(c->ev1));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) out->device_ms = ms;
+  }
+  out->score_pass_ms = profile_pass_ms(c);
+  out->pass_kind = c->last_pass_kind;
+  return SMPC_OK;
 }
 
 // What the reference had scored when a collision critic found every rollout colliding
@@ -534,6 +582,29 @@ static Knobs read_knobs()
   if (const char* e = getenv("SMPC_FOOTPRINT_PASS")) k.footprint_general = !strcmp(e, "general");
   if (const char* e = getenv("SMPC_NONHOLO_PASS")) k.nonholo_omni = !strcmp(e, "omni");
   return k;
+}
+
+// developer aid (SMPC_TICK_TIMING=1): where the host's share of a tick goes, printed every 1024 ticks
+using clk = std::chrono::steady_clock;
+static void report_tick_timing(clk::time_point t_in, clk::time_point t_prep, clk::time_point t_launch, clk::time_point t_fetch)
+{
+  static thread_local double acc[5] = {0, 0, 0, 0, 0};   // (per calling thread: contexts may tick on several)
+  static thread_local unsigned n = 0;
+  static thread_local clk::time_point t_prev_out;
+  const auto t_out = clk::now();
+  auto us = [](clk::time_point a, clk::time_point b) {return std::chrono::duration<double, std::micro>(b - a).count();};
+  if (n > 0) acc[0] += us(t_prev_out, t_in);   // the caller, between two ticks
+  acc[1] += us(t_in, t_prep);
+  acc[2] += us(t_prep, t_launch);
+  acc[3] += us(t_launch, t_fetch);
+  acc[4] += us(t_fetch, t_out);
+  t_prev_out = t_out;
+  if (++n == 1024) {
+    fprintf(stderr, "[smpc tick timing] caller %.2f us, prepare + upload %.2f, launches %.2f, wait %.2f, collect %.2f (per tick, %u ticks)\n",
+            acc[0] / (n - 1), acc[1] / n, acc[2] / n, acc[3] / n, acc[4] / n, n);
+    n = 0;
+    for (double& a : acc) a = 0;
+  }
 }
 }  // namespace smpc_impl
 
@@ -721,18 +792,18 @@ int smpc_create(const smpc_config* cfg, smpc_ctx** out)
   CK(hipMemset(c->d_lut_fp, 0, 512 * sizeof(SmpcLut)));
   CK(hipHostMalloc(&c->h_lut_fp, 512 * sizeof(SmpcLut), hipHostMallocDefault));
   CK(hipHostMalloc(&c->h_lut, 256 * sizeof(SmpcLut), hipHostMallocDefault));
-  const size_t TL = 4 + 3 * static_cast<size_t>(T);
+  const size_t TL = SMPC_TUPLE_HEADER + 3 * static_cast<size_t>(T);
   CK(hipMalloc(&c->d_partials, (kMaxGrid * TL + 16) * sizeof(float)));   // + the canary's slot (SMPC_CANARY_SLOT)
   CK(hipMemset(c->d_partials, 0, (kMaxGrid * TL + 16) * sizeof(float)));
   CK(hipMalloc(&c->d_tuple, TL * sizeof(float)));
-  CK(hipMalloc(&c->d_out, (3 * T + 8) * sizeof(float)));
+  CK(hipMalloc(&c->d_out, SMPC_RESULT_FLOATS(T) * sizeof(float)));
   CK(hipMalloc(&c->d_u_iter, 3 * T * sizeof(float)));
-  // [3T + 8 ...]: completion words, one per publishing block (at most 13: T = 128)
-  CK(hipHostMalloc(&c->h_out, (3 * T + 8 + kPollWords) * sizeof(float), hipHostMallocMapped));
-  memset(c->h_out, 0, (3 * T + 8 + kPollWords) * sizeof(float));
+  // (the mirror ends in kPollWords completion words, one per publishing block: smpc_reduce_blocks(T), at most 25 at T = 256)
+  CK(hipHostMalloc(&c->h_out, SMPC_RESULT_HOST_FLOATS(T) * sizeof(float), hipHostMallocMapped));
+  memset(c->h_out, 0, SMPC_RESULT_HOST_FLOATS(T) * sizeof(float));
   CK(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->h_out_dev), c->h_out, 0));
-  CK(hipMalloc(&c->d_furthest, 32));
-  CK(hipMemset(c->d_furthest, 0, 32));
+  CK(hipMalloc(&c->d_furthest, SMPC_SCRATCH_WORDS * sizeof(uint32_t)));
+  CK(hipMemset(c->d_furthest, 0, SMPC_SCRATCH_WORDS * sizeof(uint32_t)));
   CK(wave_set_lds_limit(static_cast<int>(kLdsPerCu)));
   // the memsets above went to the default stream; the ctx works on its own non-blocking one
   CK(hipDeviceSynchronize());
@@ -973,23 +1044,32 @@ int smpc_get_noise(smpc_ctx* c, float* nvx, float* nvy, float* nwz)
 int smpc_optimize(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_tick_out* out)
 {
   if (!c || !in || !u_inout) return fail(c, SMPC_ERR_INVALID, "null argument");
-  // developer aid (SMPC_TICK_TIMING=1): where the host's share of a tick goes, printed every 1024 ticks
-  static const bool timing = getenv("SMPC_TICK_TIMING") != nullptr;
-  using clk = std::chrono::steady_clock;
+  static const bool timing = getenv("SMPC_TICK_TIMING") != nullptr;   // (report_tick_timing)
   clk::time_point t_in, t_prep, t_launch, t_fetch;
   if (timing) t_in = clk::now();
   HIPCK(c, hipSetDevice(c->device));
-  int rc = prepare_tick(c, in, u_inout);
+  int rc = begin_tick(c, in, u_inout);
   if (rc != SMPC_OK) return rc;
   if (timing) t_prep = clk::now();
   const uint32_t T = c->cfg.time_steps;
-  const uint32_t iS = 3 * T + 2, iNC = 3 * T + 3, iSused = 3 * T + 4;
-  c->passes = 0;
-  c->evp_used = 0;
-  c->costs_cur = 0;
+  const TickResult res = tick_result(c);
   bool fail_sticky = c->fail_in;
   bool fail_flag = fail_sticky;
   bool fetched = false;
+  // One scoring pass that finishes the control sequence: the launch, the end of the call's GPU
+  // time when profiling (`timed`), and the host round trip for the result (`fetch`).  dF: the
+  // furthest point on the device, for the critics and reported as the one they used.
+  auto score = [&](uint32_t flags, const float* u_dev, const float* dF, uint32_t hintS, bool timed, bool fetch) -> int {
+    int e = launch_score(c, flags, u_dev, dF, hintS, c->d_tuple, true, dF);
+    if (e != SMPC_OK) return e;
+    if (timed && (c->cfg.flags & SMPC_FLAG_PROFILE)) HIPCK(c, hipEventRecord(c->ev1, c->stream));
+    const bool first = c->passes == 1;
+    if (timing && first) t_launch = clk::now();
+    if (fetch) e = fetch_out(c);
+    if (timing && first) t_fetch = clk::now();
+    fetched = fetch;
+    return e;
+  };
   // furthest_reached_path_point of this tick: evaluated once, then cached
   // (setPathFurthestPointIfNotSet, utils.hpp:350-355)
   bool S_known = false, S_on_device = false;
@@ -1000,7 +1080,8 @@ int smpc_optimize(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_tick
   const bool speculate = !(c->cfg.flags & SMPC_FLAG_NO_SPECULATION);
   for (uint32_t it = 0; it < c->cfg.iteration_count; ++it) {
     uint32_t flags = scoring_flags(c, fail_sticky);
-    if (it > 0) flags |= SD_ACCUMULATE;
+    const uint32_t acc = it > 0 ? SD_ACCUMULATE : 0u;
+    flags |= acc;
     have_nc_obstacles = false;   // (the count reported is the LAST iteration's, like every other output)
     // a later iteration starts from what the previous one left in d_out — from a COPY of it: the
     // reduction of this iteration's first pass overwrites d_out, and a second pass of the same
@@ -1033,62 +1114,45 @@ int smpc_optimize(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_tick
         dF = c->d_furthest;
       }
     }
-    rc = launch_score(c, flags, u_dev, dF, hintS, c->d_tuple, true, dF);
-    if (rc != SMPC_OK) return rc;
-    if (c->cfg.flags & SMPC_FLAG_PROFILE) HIPCK(c, hipEventRecord(c->ev1, c->stream));
-    if (timing && it == 0) t_launch = clk::now();
-    fetched = false;
+    // ---- the iteration's first pass.  One host round trip where something hangs on it: fail_flag
+    // (obstacles_critic.cpp:177), the true furthest point, and on the last iteration the result itself
     const bool last = it + 1 == c->cfg.iteration_count;
-    if ((flags & (SD_OBSTACLES | SD_COST)) || spec_try || last) {
-      // one host round trip: it carries fail_flag (obstacles_critic.cpp:177), the true
-      // furthest point, and on the last iteration the result itself
-      rc = fetch_out(c);
-      if (rc != SMPC_OK) return rc;
-      fetched = true;
-    }
-    if (timing && it == 0) t_fetch = clk::now();
+    rc = score(flags, u_dev, dF, hintS, true, (flags & (SD_OBSTACLES | SD_COST)) || spec_try || last);
+    if (rc != SMPC_OK) return rc;
     if (fetched && dF) {
-      F_host = c->h_out[iSused];
+      F_host = res.F_used();
       S_host = smpc_furthest_index(F_host);
       S_known = true;
     }
+    // ---- speculation miss: once more with the true furthest point
     if (spec_try) {
-      F_host = c->h_out[iS];
-      const uint32_t S_true = smpc_furthest_index(F_host);
-      S_host = S_true;
+      F_host = res.F_local();
+      S_host = smpc_furthest_index(F_host);
       S_known = true;
-      if (S_true != hintS) {
+      if (S_host != hintS) {
         c->spec_misses++;
         flags &= ~SD_LOCAL_FURTHEST;
-        rc = launch_score(c, flags, u_dev, nullptr, S_host, c->d_tuple, true, nullptr);
-        if (rc != SMPC_OK) return rc;
-        if (c->cfg.flags & SMPC_FLAG_PROFILE) HIPCK(c, hipEventRecord(c->ev1, c->stream));
-        rc = fetch_out(c);
+        rc = score(flags, u_dev, nullptr, S_host, true, true);
         if (rc != SMPC_OK) return rc;
       }
     }
-    if (c->knobs.repeat_pass) {   // (tests: a second pass of the iteration must see the first one's inputs)
-      rc = launch_score(c, flags & ~SD_LOCAL_FURTHEST, u_dev, nullptr, S_known ? S_host : hintS, c->d_tuple, true, nullptr);
+    // ---- debug repeat (tests: a second pass of the iteration must see the first one's inputs)
+    if (c->knobs.repeat_pass) {
+      rc = score(flags & ~SD_LOCAL_FURTHEST, u_dev, nullptr, S_known ? S_host : hintS, false, true);
       if (rc != SMPC_OK) return rc;
-      rc = fetch_out(c);
-      if (rc != SMPC_OK) return rc;
-      fetched = true;
     }
+    // ---- both collision critics with a footprint: ObstaclesCritic's own count
     bool failed_at_obstacles = false;
-    if (c->two_coll_fp && (flags & SD_OBSTACLES) && (flags & SD_COST) && c->h_out[iNC] != 0.0f) {
+    if (c->two_coll_fp && (flags & SD_OBSTACLES) && (flags & SD_COST) && res.non_colliding() != 0.0f) {
       // CostCritic (scored first, its count is the one the pass reports) let some rollouts
       // through; ObstaclesCritic is scored next and, with a footprint in play, decides on its OWN
       // collisions (obstacles_critic.cpp:177 assigns fail_flag).  One pass that scores it alone
       // counts them; then either the manager stopped behind it (critic_manager.cpp:70-73:
       // Constraint, Cost, Obstacles were scored) or everything is scored again.
-      const uint32_t acc = it > 0 ? SD_ACCUMULATE : 0u;
       const uint32_t keep = SD_STORE_TRAJ | SD_TRACK_UNKNOWN;
-      rc = launch_score(c, (c->gate_flags & (SD_OBSTACLES | SD_FP_OBSTACLES | keep)) | acc, u_dev, nullptr, 0,
-                        c->d_tuple, true, nullptr);
+      rc = score((c->gate_flags & (SD_OBSTACLES | SD_FP_OBSTACLES | keep)) | acc, u_dev, nullptr, 0, false, true);
       if (rc != SMPC_OK) return rc;
-      rc = fetch_out(c);
-      if (rc != SMPC_OK) return rc;
-      nc_obstacles = c->h_out[iNC];
+      nc_obstacles = res.non_colliding();
       uint32_t again = flags & ~SD_LOCAL_FURTHEST;
       if (nc_obstacles == 0.0f) {
         failed_at_obstacles = true;
@@ -1096,26 +1160,18 @@ int smpc_optimize(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_tick
         fail_sticky = true;
         again = (c->gate_flags & (SD_CONSTRAINT | SD_COST | SD_FP_COST | SD_OBSTACLES | SD_FP_OBSTACLES | keep)) | acc;
       }
-      rc = launch_score(c, again, u_dev, nullptr, S_known ? S_host : 0u, c->d_tuple, true, nullptr);
+      rc = score(again, u_dev, nullptr, S_known ? S_host : 0u, true, true);
       if (rc != SMPC_OK) return rc;
-      if (c->cfg.flags & SMPC_FLAG_PROFILE) HIPCK(c, hipEventRecord(c->ev1, c->stream));
-      rc = fetch_out(c);
-      if (rc != SMPC_OK) return rc;
-      fetched = true;
       have_nc_obstacles = true;
     }
-    if (!failed_at_obstacles && (flags & (SD_OBSTACLES | SD_COST)) && c->h_out[iNC] == 0.0f) {
-      // every rollout collides: the critics after Obstacles were not scored in the
-      // reference (critic_manager.cpp:70-73); redo this iteration with Obstacles only
-      // so that costs and u match it exactly
+    // ---- every rollout collides: the critics after Obstacles were not scored in the reference
+    // (critic_manager.cpp:70-73); redo this iteration with Obstacles only so that costs and u
+    // match it exactly
+    if (!failed_at_obstacles && (flags & (SD_OBSTACLES | SD_COST)) && res.non_colliding() == 0.0f) {
       fail_flag = true;
       fail_sticky = true;
-      const uint32_t only = fail_only_flags(c) |
-        (it > 0 ? SD_ACCUMULATE : 0u);
-      rc = launch_score(c, only, u_dev, nullptr, 0, c->d_tuple, true, nullptr);
+      rc = score(fail_only_flags(c) | acc, u_dev, nullptr, 0, true, false);
       if (rc != SMPC_OK) return rc;
-      if (c->cfg.flags & SMPC_FLAG_PROFILE) HIPCK(c, hipEventRecord(c->ev1, c->stream));
-      fetched = false;
     }
   }
   if (!fetched) {
@@ -1124,43 +1180,9 @@ int smpc_optimize(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_tick
   }
   if (S_known) remember_furthest(c, in, F_host);
   store_control_sequence(c, u_inout);
-  if (out) {
-    memset(out, 0, sizeof(*out));
-    out->fail_flag = fail_flag ? 1 : 0;
-    out->furthest_valid = S_known ? 1 : 0;
-    out->furthest_reached_path_point = S_known ? S_host : 0;
-    out->non_colliding = static_cast<uint32_t>(have_nc_obstacles ? nc_obstacles : c->h_out[iNC]);
-    out->min_cost = c->h_out[3 * T + 0];
-    out->sum_w = c->h_out[3 * T + 1];
-    out->passes = c->passes;
-    float ms = 0.f;
-    if (c->cfg.flags & SMPC_FLAG_PROFILE) {
-      // the polled flag can beat the event's completion signal by a few microseconds
-      HIPCK(c, hipEventSynchronize(c->ev1));
-      if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) out->device_ms = ms;
-    }
-    out->score_pass_ms = profile_pass_ms(c);
-    out->pass_kind = c->last_pass_kind;
-  }
-  if (timing) {
-    static thread_local double acc[5] = {0, 0, 0, 0, 0};   // (per calling thread: contexts may tick on several)
-    static thread_local unsigned n = 0;
-    static thread_local clk::time_point t_prev_out;
-    const auto t_out = clk::now();
-    auto us = [](clk::time_point a, clk::time_point b) {return std::chrono::duration<double, std::micro>(b - a).count();};
-    if (n > 0) acc[0] += us(t_prev_out, t_in);   // the caller, between two ticks
-    acc[1] += us(t_in, t_prep);
-    acc[2] += us(t_prep, t_launch);
-    acc[3] += us(t_launch, t_fetch);
-    acc[4] += us(t_fetch, t_out);
-    t_prev_out = t_out;
-    if (++n == 1024) {
-      fprintf(stderr, "[smpc tick timing] caller %.2f us, prepare + upload %.2f, launches %.2f, wait %.2f, collect %.2f (per tick, %u ticks)\n",
-              acc[0] / (n - 1), acc[1] / n, acc[2] / n, acc[3] / n, acc[4] / n, n);
-      n = 0;
-      for (double& a : acc) a = 0;
-    }
-  }
+  rc = fill_tick_out(c, out, fail_flag, S_known, S_known ? S_host : 0u, have_nc_obstacles ? &nc_obstacles : nullptr, true);
+  if (rc != SMPC_OK) return rc;
+  if (timing) report_tick_timing(t_in, t_prep, t_launch, t_fetch);
   return SMPC_OK;
 }
 

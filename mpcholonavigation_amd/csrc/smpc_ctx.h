@@ -91,7 +91,9 @@ constexpr uint32_t kSplitMinBatch = 12u * 1024u;  // smpc_pass_split (T = 64) fr
                                                   // 38.9 -> 36.2 us per tick, 32 768: 44.7 -> 36.7; 4 096: no gain)
 constexpr uint32_t kSplitMinBatchShort = 20000u;  // the same for 36 <= T < 64 (idle step slots are masked, not skipped)
 constexpr uint32_t kLaneMaxT = 128;       // T <= 64: 3 x 64 noised controls parked per lane (or re-read); T <= 128: re-read
-constexpr uint32_t kPollWords = 32;     // completion words behind h_out[3T + 8] (T = 256: 25 blocks of smpc_reduce_partials)
+constexpr uint32_t kPollWords = SMPC_BLOCK_DONE_WORDS;   // completion words from slot SMPC_R_BLOCK_DONE of h_out on: room for
+                                                         // smpc_reduce_blocks(T) of them (T = 64: 7, T = 128: 13, T = 256: 25)
+static_assert(SMPC_TUPLE_HEADER == SMPC_R_F_USED, "the shard tuple's header is the first four result slots, in their order");
 constexpr uint32_t kMaxGrid = SMPC_MAX_GRID;   // smpc_reduce_partials stages this many factors
 constexpr uint32_t kWindowBytes = 96 * 96;  // costmap window staged in LDS: 4.8 m x 4.8 m at
                                            // 0.05 m around the robot; the rest is read from HBM/L2
@@ -248,7 +250,7 @@ struct smpc_ctx {
   // native RCCL exchange of the batch-sharded tick (smpc_shard_tick)
   ncclComm_t comm = nullptr;
   int comm_rank = 0, comm_world = 0;
-  float* d_all = nullptr;     // [world][4 + 3T] gathered shard tuples
+  float* d_all = nullptr;     // [world][SMPC_TUPLE_HEADER + 3T] gathered shard tuples
   // collective-free exchange (smpc_shard_p2p_*): the own mailbox (fine-grained device memory,
   // exported over IPC) and the peers' mailboxes as mapped into this process
   float* p2p_mailbox = nullptr;
@@ -297,13 +299,12 @@ struct smpc_ctx {
   // reductions / outputs
   float* d_partials = nullptr;
   float* d_tuple = nullptr;
-  float* d_out = nullptr;       // [3T u][8 result]
+  float* d_out = nullptr;       // [SMPC_RESULT_FLOATS(T)]: u, then the result slots (smpc_dev.h)
   float* d_u_iter = nullptr;    // [3T] the control sequence iteration it > 0 starts from: a copy of d_out, so that a
                                 // second pass of the same iteration (a re-score) reads what the first one read
-  float* h_out = nullptr;       // pinned, device-mapped: kernels write the result here
+  float* h_out = nullptr;       // [SMPC_RESULT_HOST_FLOATS(T)] pinned, device-mapped: kernels write the result here
   float* h_out_dev = nullptr;   // its device-side address
-  float* d_furthest = nullptr;  // word 0: the furthest point (atomicMax on its bits); 2: smpc_reduce_partials' block count;
-                                // 3: the mailbox exchange's state; 4: smpc_grid_tail's block count
+  float* d_furthest = nullptr;  // the furthest point, and behind it the other device scratch words (smpc_dev.h: SMPC_SCRATCH_*)
   int R = 1;                 // horizon in chunks of 64 steps per wave of the wave-per-rollout pass: 1, 2 or 4
   // per-tick prepared state
   SmpcDev dev{};
@@ -350,7 +351,7 @@ struct smpc_ctx {
   float acker_r = -1.f;      // Ackermann min_turning_r, < 0 for the other models
   uint32_t acker_seq = 0;    // completion word the Ackermann launch publishes this tick
   uint32_t seq = 0, poll_seq = 0;
-  uint32_t poll_words = 0;   // > 0: the tick's completion arrives as this many words (smpc_tail.h), h_out[3T + 8 ...]
+  uint32_t poll_words = 0;   // > 0: the tick's completion arrives as this many words, from slot SMPC_R_BLOCK_DONE of h_out on
   std::string err;
 };
 
@@ -406,6 +407,35 @@ int launch_score(smpc_ctx* c, uint32_t flags, const float* u_dev, const float* d
 int launch_combine(smpc_ctx* c, const float* d_tuples, uint32_t n, const float* d_furthest_used);
 void store_control_sequence(const smpc_ctx* c, float* u_inout);
 int fetch_out(smpc_ctx* c);
+
+// ---- the tick protocol its drivers share (smpc_optimize, smpc_group_optimize_some, smpc_shard_tick,
+// smpc_shard_begin .. smpc_shard_combine) ----
+// a tick starts: the per-tick host work and upload (prepare_tick), then the per-tick counters at zero
+int begin_tick(smpc_ctx* c, const smpc_tick_in* in, const float* u_in);
+// what no sharded tick takes (after begin_tick)
+int refuse_sharded(smpc_ctx* c);
+// the next completion sequence number (never 0), which fetch_out then waits for
+uint32_t next_seq(smpc_ctx* c);
+// device scratch word k of the ctx (smpc_dev.h: SMPC_SCRATCH_*)
+inline uint32_t* scratch_word(const smpc_ctx* c, uint32_t k) {return reinterpret_cast<uint32_t*>(c->d_furthest) + k;}
+// The result block of the tick fetched last, read in place in the host mirror (no copy: a later
+// fetch_out of the same tick shows through the same view).
+struct TickResult {
+  const float* slot;   // h_out + SMPC_RESULT_AT(T)
+  float min_cost() const {return slot[SMPC_R_MIN_COST];}
+  float sum_w() const {return slot[SMPC_R_SUM_W];}
+  float F_local() const {return slot[SMPC_R_F_LOCAL];}
+  float non_colliding() const {return slot[SMPC_R_NON_COLLIDING];}
+  float F_used() const {return slot[SMPC_R_F_USED];}
+  float mark() const {return slot[SMPC_R_MARK];}
+};
+inline TickResult tick_result(const smpc_ctx* c) {return TickResult{c->h_out + SMPC_RESULT_AT(c->cfg.time_steps)};}
+// *out (may be null) of a finished tick.  What differs between the drivers comes in: the fail flag,
+// whether a furthest point was evaluated and the index reported, and a non-colliding count that
+// overrides the block's (null: the block's); device_ms: also the call's GPU time, first upload to
+// last kernel, when profiling (smpc_optimize).  The rest comes from the block and the ctx.
+int fill_tick_out(smpc_ctx* c, smpc_tick_out* out, bool fail_flag, bool furthest_valid, uint32_t furthest,
+                  const float* non_colliding = nullptr, bool device_ms = false);
 float profile_pass_ms(smpc_ctx* c);
 uint32_t fail_only_flags(const smpc_ctx* c);
 uint32_t scoring_flags(const smpc_ctx* c, bool fail_sticky);

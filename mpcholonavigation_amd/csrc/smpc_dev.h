@@ -56,11 +56,11 @@ struct SmpcLut {  // per 8-bit cost: {margin - d | 0, R_infl - d | 0}  (obstacle
 struct SmpcFinal {
   int enabled;
   float vx_max, vx_min, vy_max, wz_max;   // current constraints
-  float* u_dev;                            // [3T + 8] device copy (next iteration reads u here)
-  float* u_host;                           // [3T + 8] host-mapped copy (no D2H memcpy)
+  float* u_dev;                            // [SMPC_RESULT_FLOATS(T)] device copy (next iteration reads u here)
+  float* u_host;                           // [SMPC_RESULT_HOST_FLOATS(T)] host-mapped copy (no D2H memcpy)
   const float* furthest_used;              // device float or null
   uint32_t* done_counter;                  // device word, zero between launches
-  uint32_t seq;                            // tick sequence number published at u_host[3T+7]
+  uint32_t seq;                            // tick sequence number published in slot SMPC_R_DONE of u_host
 };
 
 struct SmpcDev {
@@ -206,6 +206,55 @@ struct SmpcDev {
 // columns, a flag
 static inline uint32_t smpc_tail_lds_bytes(uint32_t T) {return (512u + 64u + ((4u + 3u * T + 63u) / 64u) * 2048u + 4u) * 4u;}
 
+// ---- the tick's result block ---------------------------------------------------------------
+// A scoring tick ends in a block of floats that the finishing kernels (smpc_reduce_partials,
+// smpc_grid_tail, smpc_combine_tuples, smpc_p2p_exchange, smpc_publish_many,
+// smpc_ackermann_constrain) write to the device copy (smpc_ctx::d_out) and to its host-mapped
+// mirror (h_out), which the host polls and reads in place: the control sequence u[3T], then,
+// from SMPC_RESULT_AT(T) on, these slots.
+#define SMPC_R_MIN_COST 0u        /* min over the rollouts' costs */
+#define SMPC_R_SUM_W 1u           /* sum of the softmax weights */
+#define SMPC_R_F_LOCAL 2u         /* the furthest point F the pass itself found (smpc_furthest_index) */
+#define SMPC_R_NON_COLLIDING 3u   /* rollouts that did not collide */
+#define SMPC_R_F_USED 4u          /* the furthest point the critics were scored with */
+#define SMPC_R_CANARY 5u          /* the tick block's number as block 0 of the pass read it (uint32 bits; SMPC_CANARY_SLOT) */
+#define SMPC_R_MARK 6u            /* host mirror only: SMPC_MARK_* */
+#define SMPC_R_DONE 7u            /* host mirror only: the completion word (uint32: the tick's sequence number) */
+#define SMPC_R_BLOCK_DONE 8u      /* host mirror only: one completion word per reducing block, SMPC_BLOCK_DONE_WORDS of them */
+#define SMPC_BLOCK_DONE_WORDS 32u
+#define SMPC_RESULT_AT(T) (3u * (T))
+#define SMPC_RESULT_FLOATS(T) (SMPC_RESULT_AT(T) + SMPC_R_BLOCK_DONE)                   /* the device copy */
+#define SMPC_RESULT_HOST_FLOATS(T) (SMPC_RESULT_FLOATS(T) + SMPC_BLOCK_DONE_WORDS)     /* the host mirror */
+// the finishing kernels write slots 0 .. SMPC_R_F_USED as one run {min, sum w, F, non-colliding, F used},
+// whose first four are the shard tuple's header in its order (include/smpc.h: SMPC_TUPLE_HEADER)
+static_assert(SMPC_R_MIN_COST == 0u && SMPC_R_SUM_W == 1u && SMPC_R_F_LOCAL == 2u && SMPC_R_NON_COLLIDING == 3u &&
+              SMPC_R_F_USED == 4u, "result slots 0-4: the tuple header, then the furthest point used");
+static_assert(SMPC_R_CANARY == 5u && SMPC_R_MARK == 6u && SMPC_R_DONE == 7u && SMPC_R_BLOCK_DONE == 8u,
+              "result slots 5-8: canary echo, mark, completion word, per-block completion words");
+// floats of one shard tuple {min, sum w, F, non-colliding, U[3T]}
+static inline constexpr uint32_t smpc_tuple_floats(uint32_t T) {return SMPC_R_F_USED + 3u * T;}
+// SMPC_R_MARK: why the host must fail the tick whose completion it has just seen
+#define SMPC_MARK_NONE 0.0f
+#define SMPC_MARK_PEER_LATE 1.0f   /* smpc_p2p_exchange: a peer's tuple never came (sticky until smpc_shard_p2p_init) */
+#define SMPC_MARK_TAIL_LATE 2.0f   /* smpc_grid_tail: the in-launch reduction gave up waiting for the grid's blocks */
+// Reducing blocks, each of which publishes its own completion word when it finishes a polled
+// tick: smpc_reduce_partials gives a block 32 tuple columns, smpc_grid_tail gives one of the
+// grid's last blocks 64 (and never uses more blocks than the grid has).
+static inline constexpr uint32_t smpc_reduce_blocks(uint32_t T) {return (smpc_tuple_floats(T) + 31u) / 32u;}
+static inline constexpr uint32_t smpc_tail_reduce_blocks(uint32_t T, uint32_t grid)
+{
+  const uint32_t groups = (smpc_tuple_floats(T) + 63u) / 64u;
+  return groups < grid ? groups : grid;
+}
+
+// The device scratch words of a context (smpc_ctx::d_furthest), zero between launches.
+#define SMPC_SCRATCH_FURTHEST 0u         /* the furthest point F (atomicMax on its float bits) */
+#define SMPC_SCRATCH_REDUCE_COUNTER 2u   /* SmpcFinal::done_counter */
+#define SMPC_SCRATCH_P2P_STATE 3u        /* SmpcP2P::state */
+#define SMPC_SCRATCH_TAIL_COUNTER 4u     /* SmpcDev::tail_counter: two words, tickets taken and reducers finished */
+#define SMPC_SCRATCH_WORDS 8u
+static_assert(SMPC_SCRATCH_TAIL_COUNTER + 2u <= SMPC_SCRATCH_WORDS, "the scratch allocation holds every word");
+
 #if defined(__HIPCC__)
 // where a kernel whose FIRST parameter is the SmpcDev finds the tick block (see tick_inline)
 struct SmpcTickPtrs {
@@ -276,8 +325,8 @@ struct SmpcReduceArgs {
   float* tuple;
   uint32_t nblk;
   SmpcFinal fin;       // u_host and done_counter null: smpc_publish_many reports to the host
-  float* host_out;     // the instance's host-mapped result mirror [3T + 8]
-  uint32_t seq;        // sequence number published at host_out[3T + 7]
+  float* host_out;     // the instance's host-mapped result mirror [SMPC_RESULT_HOST_FLOATS(T)]
+  uint32_t seq;        // sequence number published in slot SMPC_R_DONE of host_out
   float neg_inv_temp;  // -1 / temperature of THIS instance (members of a group may differ)
 };
 

@@ -154,10 +154,7 @@ int smpc_group_optimize_some(smpc_group* g, const smpc_tick_in* ins, float* cons
     if (!taken(i)) continue;
     smpc_ctx* c = g->ctxs[i];
     if (!u_inout[i]) return fail(c, SMPC_ERR_INVALID, "null control sequence");
-    c->passes = 0;
-    c->evp_used = 0;
-    c->costs_cur = 0;
-    int rc = prepare_tick(c, &ins[i], u_inout[i]);
+    int rc = begin_tick(c, &ins[i], u_inout[i]);
     if (rc != SMPC_OK) return rc;
     flags[i] = scoring_flags(c, c->fail_in);
     const bool need_f = (flags[i] & SD_NEED_FURTHEST) != 0;
@@ -303,10 +300,11 @@ int smpc_group_optimize_some(smpc_group* g, const smpc_tick_in* ins, float* cons
     int rc = fetch_out(c);
     if (rc != SMPC_OK) return rc;
     const bool need_f = (flags[i] & SD_NEED_FURTHEST) != 0;
-    const float F_true = c->h_out[3 * T + 2];
+    const TickResult res = tick_result(c);
+    const float F_true = res.F_local();
     const uint32_t S_true = smpc_furthest_index(F_true);
     const bool miss = need_f && S_true != c->hint;
-    const bool all_collide = (flags[i] & (SD_OBSTACLES | SD_COST)) && c->h_out[3 * T + 3] == 0.0f;
+    const bool all_collide = (flags[i] & (SD_OBSTACLES | SD_COST)) && res.non_colliding() == 0.0f;
     if (miss || all_collide) {
       if (miss) {
         c->spec_misses++;
@@ -321,17 +319,9 @@ int smpc_group_optimize_some(smpc_group* g, const smpc_tick_in* ins, float* cons
     }
     if (need_f) remember_furthest(c, &ins[i], F_true);   // as smpc_optimize does: the predictor's state advances every tick
     store_control_sequence(c, u_inout[i]);
-    if (outs) {
-      smpc_tick_out* o = &outs[i];
-      memset(o, 0, sizeof(*o));
-      o->furthest_valid = need_f ? 1 : 0;
-      o->furthest_reached_path_point = need_f ? S_true : 0;
-      o->non_colliding = static_cast<uint32_t>(c->h_out[3 * T + 3]);
-      o->min_cost = c->h_out[3 * T + 0];
-      o->sum_w = c->h_out[3 * T + 1];
-      o->passes = c->passes;
-      o->pass_kind = c->last_pass_kind;
-    }
+    // (no fail flag: such a member was ticked alone; score_pass_ms 0: a profiling member never rides)
+    rc = fill_tick_out(c, outs ? &outs[i] : nullptr, false, need_f, need_f ? S_true : 0u);
+    if (rc != SMPC_OK) return rc;
   }
   g->launched = false;   // every riding member's fetch_out has returned
   if (timing && (g->batched_ticks % 64) == 0)

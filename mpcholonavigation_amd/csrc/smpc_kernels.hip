@@ -187,8 +187,8 @@ __device__ __forceinline__ void reduce_partials_body(const float* __restrict__ p
         const float used = fin.furthest_used ? *fin.furthest_used : fu;
         const float res[5] = {m, sw, fu, nc, used};
         for (int k = 0; k < 5; ++k) {
-          fin.u_dev[3 * T + k] = res[k];
-          if (fin.u_host) fin.u_host[3 * T + k] = res[k];
+          fin.u_dev[SMPC_RESULT_AT(T) + k] = res[k];   // slots SMPC_R_MIN_COST .. SMPC_R_F_USED
+          if (fin.u_host) fin.u_host[SMPC_RESULT_AT(T) + k] = res[k];
         }
       }
     }
@@ -196,19 +196,19 @@ __device__ __forceinline__ void reduce_partials_body(const float* __restrict__ p
     // result (the combine kernels forward it from there) and, when finishing, to the host
     if (col == 0 && fin.u_dev) {
       const float cn = partials[SMPC_CANARY_SLOT(T)];
-      fin.u_dev[3 * T + 5] = cn;
-      if (fin.enabled && fin.u_host) fin.u_host[3 * T + 5] = cn;
+      fin.u_dev[SMPC_RESULT_AT(T) + SMPC_R_CANARY] = cn;
+      if (fin.enabled && fin.u_host) fin.u_host[SMPC_RESULT_AT(T) + SMPC_R_CANARY] = cn;
     }
   }
   // completion for the polling host: every block publishes the tick's sequence number in its
-  // own word (u_host[3T + 8 + block]) behind a system-scope fence over its host stores, and the
+  // own word (slot SMPC_R_BLOCK_DONE + block of u_host) behind a system-scope fence over its host stores, and the
   // host waits for all of them — no counter and no second fence between the last store and the
   // host (the tail timeline of tools/tail_timeline.py prices them at ~2 us)
   if (fin.enabled && fin.done_counter) {
     __threadfence_system();
     __syncthreads();
     if (tid == 0)
-      __hip_atomic_store(reinterpret_cast<uint32_t*>(fin.u_host + 3 * T + 8 + blockIdx.x), fin.seq,
+      __hip_atomic_store(reinterpret_cast<uint32_t*>(fin.u_host + SMPC_RESULT_AT(T) + SMPC_R_BLOCK_DONE + blockIdx.x), fin.seq,
                          __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
@@ -271,16 +271,16 @@ __device__ __forceinline__ void combine_tuples_body(const float* __restrict__ tu
     const float res[5] = {m, sw, fu, nc, furthest_used ? *furthest_used : fu};
     for (int k = 0; k < 5; ++k) {
       result[k] = res[k];
-      if (host_out) host_out[3 * T + k] = res[k];
+      if (host_out) host_out[SMPC_RESULT_AT(T) + k] = res[k];   // slots SMPC_R_MIN_COST .. SMPC_R_F_USED
     }
-    if (host_out) host_out[3 * T + 5] = result[5];   // the pass's echo of the tick block's number (smpc_reduce_partials)
+    if (host_out) host_out[SMPC_RESULT_AT(T) + SMPC_R_CANARY] = result[SMPC_R_CANARY];   // the pass's echo of the tick block's number (smpc_reduce_partials)
   }
   // completion word for the polling host, behind every host store of this (single) block
   if (host_out && seq) {
     __threadfence_system();
     __syncthreads();
     if (threadIdx.x == 0)
-      __hip_atomic_store(reinterpret_cast<uint32_t*>(host_out + 3 * T + 7), seq, __ATOMIC_RELEASE,
+      __hip_atomic_store(reinterpret_cast<uint32_t*>(host_out + SMPC_RESULT_AT(T) + SMPC_R_DONE), seq, __ATOMIC_RELEASE,
                          __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
@@ -310,7 +310,7 @@ __global__ void __launch_bounds__(256) smpc_combine_tuples(const float* __restri
 //
 // The wait is bounded in WALL-CLOCK time (s_memrealtime, a constant 100 MHz counter:
 // x.timeout_ticks of 10 ns each).  On expiry the block sets *x.state (sticky, device memory) and
-// host_out[3T + 6] = 1, publishes the completion word so that the host returns at once, and
+// the host's mark (SMPC_R_MARK) to SMPC_MARK_PEER_LATE, publishes the completion word so that the host returns at once, and
 // publishes nothing else.  Every later exchange of this ctx sees *x.state != 0 on entry and
 // does the same WITHOUT writing to any peer: a rank that failed once stays silent, so its peers
 // fail at their next exchange at the latest instead of consuming tuples of a rank whose own
@@ -359,10 +359,10 @@ __global__ void __launch_bounds__(256) smpc_p2p_exchange(const float* __restrict
     if (tid == 0) {
       __hip_atomic_store(x.state, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (host_out) {
-        host_out[3 * T + 6] = 1.0f;
+        host_out[SMPC_RESULT_AT(T) + SMPC_R_MARK] = SMPC_MARK_PEER_LATE;
         __threadfence_system();
         if (seq)
-          __hip_atomic_store(reinterpret_cast<uint32_t*>(host_out + 3 * T + 7), seq, __ATOMIC_RELEASE,
+          __hip_atomic_store(reinterpret_cast<uint32_t*>(host_out + SMPC_RESULT_AT(T) + SMPC_R_DONE), seq, __ATOMIC_RELEASE,
                              __HIP_MEMORY_SCOPE_SYSTEM);
       }
     }
@@ -404,7 +404,7 @@ __global__ void __launch_bounds__(256) smpc_ackermann_constrain(float* __restric
     __threadfence_system();
     __syncthreads();
     if (threadIdx.x == 0)
-      __hip_atomic_store(reinterpret_cast<uint32_t*>(u_host + 3 * T + 7), seq, __ATOMIC_RELEASE,
+      __hip_atomic_store(reinterpret_cast<uint32_t*>(u_host + SMPC_RESULT_AT(T) + SMPC_R_DONE), seq, __ATOMIC_RELEASE,
                          __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
@@ -624,19 +624,18 @@ hipError_t smpc_launch_reduce(const float* partials, uint32_t nblk, uint32_t T,
                               float neg_inv_temp, float* tuple, const SmpcFinal& fin,
                               hipStream_t st)
 {
-  const uint32_t TL = 4 + 3 * T;
-  hipLaunchKernelGGL(smpc_reduce_partials, dim3((TL + 31) / 32), dim3(1024), 0, st, partials, nblk,
+  hipLaunchKernelGGL(smpc_reduce_partials, dim3(smpc_reduce_blocks(T)), dim3(1024), 0, st, partials, nblk,
                      T, neg_inv_temp, tuple, fin);
   return hipGetLastError();
 }
 
-// After smpc_reduce_partials_many: ONE block copies every instance's result (3T + 8 floats) to its
+// After smpc_reduce_partials_many: ONE block copies every instance's result (u and the slots up to the canary echo) to its
 // host-mapped mirror and publishes the sequence words behind a single system-scope fence
 // (hundreds of blocks fencing PCIe writes one by one cost far more than the reduction itself).
 __global__ void __launch_bounds__(1024) smpc_publish_many(const SmpcReduceArgs* __restrict__ many,
                                                          uint32_t n, uint32_t T)
 {
-  const uint32_t len = 3 * T + 6;   // u, the five results, the tick block's number
+  const uint32_t len = SMPC_RESULT_AT(T) + SMPC_R_CANARY + 1u;   // u, the five results, the tick block's number
   for (uint32_t i = threadIdx.x; i < n * len; i += blockDim.x) {
     const uint32_t q = i / len, k = i - q * len;
     many[q].host_out[k] = many[q].fin.u_dev[k];
@@ -644,14 +643,13 @@ __global__ void __launch_bounds__(1024) smpc_publish_many(const SmpcReduceArgs* 
   __threadfence_system();
   __syncthreads();
   for (uint32_t q = threadIdx.x; q < n; q += blockDim.x)
-    __hip_atomic_store(reinterpret_cast<uint32_t*>(many[q].host_out + 3 * T + 7), many[q].seq,
+    __hip_atomic_store(reinterpret_cast<uint32_t*>(many[q].host_out + SMPC_RESULT_AT(T) + SMPC_R_DONE), many[q].seq,
                        __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 hipError_t smpc_launch_reduce_many(const SmpcReduceArgs* d_many, uint32_t n, uint32_t T, hipStream_t st)
 {
-  const uint32_t TL = 4 + 3 * T;
-  hipLaunchKernelGGL(smpc_reduce_partials_many, dim3((TL + 31) / 32, n), dim3(1024), 0, st, d_many, T);
+  hipLaunchKernelGGL(smpc_reduce_partials_many, dim3(smpc_reduce_blocks(T), n), dim3(1024), 0, st, d_many, T);
   hipLaunchKernelGGL(smpc_publish_many, dim3(1), dim3(1024), 0, st, d_many, n, T);
   return hipGetLastError();
 }

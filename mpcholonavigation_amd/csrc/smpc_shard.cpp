@@ -54,16 +54,9 @@ int smpc_shard_begin(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
 {
   if (!c || !in || !u_in) return fail(c, SMPC_ERR_INVALID, "null argument");
   HIPCK(c, hipSetDevice(c->device));
-  c->passes = 0;
-  c->evp_used = 0;
-  c->costs_cur = 0;
-  const int rc = prepare_tick(c, in, u_in);
+  int rc = begin_tick(c, in, u_in);
+  if (rc == SMPC_OK) rc = refuse_sharded(c);
   if (rc != SMPC_OK) return rc;
-  if (c->two_coll_fp)
-    return fail(c, SMPC_ERR_UNSUPPORTED,
-                "sharded tick: consider_footprint=true with both ObstaclesCritic and CostCritic in the list");
-  if (c->cfg.iteration_count != 1)   // (one exchange = one iteration; never silently fewer than asked for)
-    return fail(c, SMPC_ERR_UNSUPPORTED, "sharded tick: iteration_count must be 1");
   // What smpc_shard_combine hands to the furthest-point predictor, copied: the caller owns *in
   // and its arrays and may free or reuse them as soon as this call returns (include/smpc.h:
   // "the library copies before returning and never retains host pointers").
@@ -122,27 +115,18 @@ int smpc_shard_combine(smpc_ctx* c, const float* d_tuples, uint32_t n_tuples, fl
   if (rc != SMPC_OK) return rc;
   rc = fetch_out(c);
   if (rc != SMPC_OK) return rc;
-  const uint32_t T = c->cfg.time_steps;
-  memcpy(u_out, c->h_out, 3 * T * sizeof(float));
+  const TickResult res = tick_result(c);
+  memcpy(u_out, c->h_out, 3 * c->cfg.time_steps * sizeof(float));
   // the predictor's state advances once per tick (a re-scored tick combines twice: same value)
-  if ((c->gate_flags & SD_NEED_FURTHEST) && !c->step_remembered) {
-    remember_furthest(c, &c->step_in, c->h_out[3 * T + 2]);
+  const bool need_f = (c->gate_flags & SD_NEED_FURTHEST) != 0;
+  if (need_f && !c->step_remembered) {
+    remember_furthest(c, &c->step_in, res.F_local());
     c->step_remembered = true;
   }
-  if (out) {
-    memset(out, 0, sizeof(*out));
-    const bool obstacles_scored = (scoring_flags(c, c->fail_in) & (SD_OBSTACLES | SD_COST)) != 0;
-    out->fail_flag = (c->fail_in || (obstacles_scored && c->h_out[3 * T + 3] == 0.0f)) ? 1 : 0;
-    out->furthest_valid = (c->gate_flags & SD_NEED_FURTHEST) ? 1 : 0;
-    out->furthest_reached_path_point = smpc_furthest_index(c->h_out[3 * T + 2]);
-    out->non_colliding = static_cast<uint32_t>(c->h_out[3 * T + 3]);
-    out->min_cost = c->h_out[3 * T + 0];
-    out->sum_w = c->h_out[3 * T + 1];
-    out->passes = c->passes;
-    out->score_pass_ms = profile_pass_ms(c);
-    out->pass_kind = c->last_pass_kind;
-  }
-  return SMPC_OK;
+  const bool obstacles_scored = (scoring_flags(c, c->fail_in) & (SD_OBSTACLES | SD_COST)) != 0;
+  // (the index is reported whether or not a critic asked for it)
+  return fill_tick_out(c, out, c->fail_in || (obstacles_scored && res.non_colliding() == 0.0f), need_f,
+                       smpc_furthest_index(res.F_local()));
 }
 
 int smpc_shard_comm_id(void* id_out, uint32_t id_bytes)
@@ -183,12 +167,12 @@ int smpc_shard_comm_init(smpc_ctx* c, const void* id_in, int rank, int world)
   c->comm_world = world;
   if (c->d_all) (void)hipFree(c->d_all);
   c->d_all = nullptr;
-  HIPCK(c, hipMalloc(&c->d_all, static_cast<size_t>(world) * (4 + 3 * c->cfg.time_steps) * sizeof(float)));
+  HIPCK(c, hipMalloc(&c->d_all, static_cast<size_t>(world) * smpc_tuple_len(c) * sizeof(float)));
   return SMPC_OK;
 }
 
 // ---- exchange without a collective: mailboxes over IPC / xGMI (smpc_p2p_exchange) ----------
-static uint32_t p2p_slot_floats(uint32_t T) {return align_up(4 + 3 * T + 1, 16);}
+static uint32_t p2p_slot_floats(uint32_t T) {return align_up(smpc_tuple_floats(T) + 1, 16);}   // (the tuple, its sequence word)
 
 int smpc_shard_p2p_set_timeout(smpc_ctx* c, uint32_t milliseconds)
 {
@@ -256,10 +240,10 @@ int smpc_shard_p2p_init(smpc_ctx* c, const void* handles, int rank, int world)
   HIPCK(c, hipMemset(c->p2p_mailbox, 0, 2u * SMPC_P2P_MAX_RANKS * c->p2p.slot_floats * sizeof(float)));
   // the sticky "an exchange timed out" word (device) and its host-visible mark: only this
   // collective set-up clears them
-  c->p2p.state = reinterpret_cast<uint32_t*>(c->d_furthest) + 3;
+  c->p2p.state = scratch_word(c, SMPC_SCRATCH_P2P_STATE);
   HIPCK(c, hipMemset(c->p2p.state, 0, sizeof(uint32_t)));
   HIPCK(c, hipDeviceSynchronize());   // (the ctx's stream is non-blocking: not ordered behind the memsets)
-  c->h_out[3 * c->cfg.time_steps + 6] = 0.0f;
+  c->h_out[SMPC_RESULT_AT(c->cfg.time_steps) + SMPC_R_MARK] = SMPC_MARK_NONE;
   c->p2p_failed = false;
   c->p2p.timeout_ticks = static_cast<unsigned long long>(c->p2p_timeout_ms) * 100000ull;   // 100 MHz
   c->p2p_xseq = 0;
@@ -284,17 +268,11 @@ int smpc_shard_tick(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_ti
                 "next exchange); set the exchange up again on every rank (smpc_shard_p2p_init) and smpc_reset");
   const RcclApi* r = p2p ? nullptr : rccl();
   HIPCK(c, hipSetDevice(c->device));
-  c->passes = 0;
-  c->evp_used = 0;
-  c->costs_cur = 0;
-  int rc = prepare_tick(c, in, u_inout);
+  int rc = begin_tick(c, in, u_inout);
+  if (rc == SMPC_OK) rc = refuse_sharded(c);
   if (rc != SMPC_OK) return rc;
-  if (c->two_coll_fp)
-    return fail(c, SMPC_ERR_UNSUPPORTED,
-                "sharded tick: consider_footprint=true with both ObstaclesCritic and CostCritic in the list");
-  if (c->cfg.iteration_count != 1)   // (one exchange = one iteration; never silently fewer than asked for)
-    return fail(c, SMPC_ERR_UNSUPPORTED, "sharded tick: iteration_count must be 1");
-  const uint32_t T = c->cfg.time_steps, TL = 4 + 3 * T, G = static_cast<uint32_t>(c->comm_world);
+  const uint32_t T = c->cfg.time_steps, TL = smpc_tuple_len(c), G = static_cast<uint32_t>(c->comm_world);
+  const TickResult res = tick_result(c);
   auto nccl_ok = [&](ncclResult_t e, const char* what) {
     if (e == ncclSuccess) return SMPC_OK;
     return fail(c, SMPC_ERR_DEVICE, std::string(what) + ": " + (r->GetErrorString ? r->GetErrorString(e) : "error"));
@@ -303,23 +281,18 @@ int smpc_shard_tick(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_ti
   auto p2p_exchange = [&](int mode, const float* d_used) -> int {
     SmpcP2P x = c->p2p;
     x.xseq = ++c->p2p_xseq;
-    uint32_t seq = 0;
-    if (mode == 0 && c->knobs.poll) {
-      seq = ++c->seq;
-      if (seq == 0) seq = ++c->seq;
-      c->poll_seq = seq;
-    }
-    // (h_out[3T + 6], the kernel's "a peer never answered" mark, is cleared by
+    const uint32_t seq = mode == 0 && c->knobs.poll ? next_seq(c) : 0u;
+    // (SMPC_MARK_PEER_LATE, the kernel's "a peer never answered" mark, is cleared by
     // smpc_shard_p2p_init only: the device may write it at any time after a launch)
     HIPCK(c, smpc_launch_p2p_exchange(c->d_tuple, x, T, mode, c->d_furthest, c->dev.neg_inv_temp, c->c_vx_max,
-                                      c->c_vx_min, c->c_vy, c->c_wz, c->d_out, c->d_out + 3 * T, d_used,
+                                      c->c_vx_min, c->c_vy, c->c_wz, c->d_out, c->d_out + SMPC_RESULT_AT(T), d_used,
                                       c->h_out_dev, seq, c->stream));
     return SMPC_OK;
   };
   // a mode-1 exchange (furthest point) that timed out leaves the device-side state set: the
   // mode-0 exchange of the same tick then publishes nothing and reports here
   auto p2p_check = [&]() -> int {
-    if (c->h_out[3 * T + 6] == 0.0f) return SMPC_OK;
+    if (res.mark() == SMPC_MARK_NONE) return SMPC_OK;
     c->p2p_failed = true;
     c->hint_valid = false;
     char msg[160];
@@ -348,7 +321,7 @@ int smpc_shard_tick(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_ti
     rc = launch_score(c, flags, nullptr, nullptr, c->hint, c->d_tuple);
     if (rc == SMPC_OK) rc = gather_combine_fetch(nullptr);
     if (rc != SMPC_OK) return rc;
-    float F_true = c->h_out[3 * T + 2];
+    float F_true = res.F_local();
     const uint32_t S_true = smpc_furthest_index(F_true);
     if (S_true != c->hint) {
       // miss: the gathered tuples carry the true batch-wide furthest point
@@ -357,7 +330,7 @@ int smpc_shard_tick(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_ti
       rc = launch_score(c, flags, nullptr, nullptr, S_true, c->d_tuple);
       if (rc == SMPC_OK) rc = gather_combine_fetch(nullptr);
       if (rc != SMPC_OK) return rc;
-      F_true = c->h_out[3 * T + 2];
+      F_true = res.F_local();
     }
     remember_furthest(c, in, F_true);
   } else {
@@ -377,11 +350,11 @@ int smpc_shard_tick(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_ti
     rc = launch_score(c, flags, nullptr, need_f ? c->d_furthest : nullptr, 0, c->d_tuple);
     if (rc == SMPC_OK) rc = gather_combine_fetch(need_f ? c->d_furthest : nullptr);
     if (rc != SMPC_OK) return rc;
-    if (need_f) remember_furthest(c, in, c->h_out[3 * T + 2]);
+    if (need_f) remember_furthest(c, in, res.F_local());
   }
   const bool obstacles_scored = (flags & (SD_OBSTACLES | SD_COST)) != 0;
   bool failed = c->fail_in;
-  if (!c->fail_in && obstacles_scored && c->h_out[3 * T + 3] == 0.0f) {
+  if (!c->fail_in && obstacles_scored && res.non_colliding() == 0.0f) {
     // all rollouts of the WHOLE batch collide: the reference scored nothing past Obstacles
     // (critic_manager.cpp:70-73)
     failed = true;
@@ -390,18 +363,6 @@ int smpc_shard_tick(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_ti
     if (rc != SMPC_OK) return rc;
   }
   store_control_sequence(c, u_inout);
-  if (out) {
-    memset(out, 0, sizeof(*out));
-    out->fail_flag = failed ? 1 : 0;
-    out->furthest_valid = need_f ? 1 : 0;
-    out->furthest_reached_path_point = need_f ? c->hint : 0;
-    out->non_colliding = static_cast<uint32_t>(c->h_out[3 * T + 3]);
-    out->min_cost = c->h_out[3 * T + 0];
-    out->sum_w = c->h_out[3 * T + 1];
-    out->passes = c->passes;
-    out->score_pass_ms = profile_pass_ms(c);
-    out->pass_kind = c->last_pass_kind;
-  }
-  return SMPC_OK;
+  return fill_tick_out(c, out, failed, need_f, need_f ? c->hint : 0u);
 }
 }  // extern "C"

@@ -227,33 +227,33 @@ __device__ __forceinline__ void smpc_grid_tail(const SmpcDev& p, unsigned char* 
         if (fin.u_host) fin.u_host[i] = v2;
       } else if (col == 0) {
         const float used = fin.furthest_used ? *fin.furthest_used : fu_;
-        float* outs[2] = {fin.u_dev + 3 * T, fin.u_host ? fin.u_host + 3 * T : nullptr};
+        float* outs[2] = {fin.u_dev + SMPC_RESULT_AT(T), fin.u_host ? fin.u_host + SMPC_RESULT_AT(T) : nullptr};
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
           float* o = outs[k];
           if (!o) continue;
-          o[0] = m_;
-          o[1] = sw;
-          o[2] = fu_;
-          o[3] = nc_;
-          o[4] = used;
+          o[SMPC_R_MIN_COST] = m_;
+          o[SMPC_R_SUM_W] = sw;
+          o[SMPC_R_F_LOCAL] = fu_;
+          o[SMPC_R_NON_COLLIDING] = nc_;
+          o[SMPC_R_F_USED] = used;
         }
       }
     }
   }
-  // ---- every reducer publishes its own completion word (fin.u_host[3T + 8 + role]) behind a
+  // ---- every reducer publishes its own completion word (slot SMPC_R_BLOCK_DONE + role of fin.u_host) behind a
   // system-scope fence over its host stores: the host waits for all nred of them, and no
   // counter sits between the last store and the host.  The reducer that finishes last resets
   // the counters for the next launch, off the critical path.
   const bool publish = fin.enabled && fin.done_counter;
-  if (late && tid == 0 && fin.enabled && fin.u_host) fin.u_host[3 * T + 6] = 2.0f;   // fetch_out fails the tick
+  if (late && tid == 0 && fin.enabled && fin.u_host) fin.u_host[SMPC_RESULT_AT(T) + SMPC_R_MARK] = SMPC_MARK_TAIL_LATE;   // fetch_out fails the tick
   SMPC_TAIL_STAMP(6);
   if (publish) __threadfence_system();
   __syncthreads();
   SMPC_TAIL_STAMP(7);
   if (tid == 0) {
     if (publish)
-      __hip_atomic_store(reinterpret_cast<uint32_t*>(fin.u_host + 3 * T + 8 + role), fin.seq, __ATOMIC_RELEASE,
+      __hip_atomic_store(reinterpret_cast<uint32_t*>(fin.u_host + SMPC_RESULT_AT(T) + SMPC_R_BLOCK_DONE + role), fin.seq, __ATOMIC_RELEASE,
                          __HIP_MEMORY_SCOPE_SYSTEM);
     SMPC_TAIL_STAMP(8);
     if (stamps) {
