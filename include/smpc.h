@@ -449,6 +449,60 @@ int smpc_get_trajectories(smpc_ctx* ctx, float* x, float* y, float* yaws);
  * updateControlSequence) [ref include/.../optimizer.hpp:255]. */
 int smpc_get_costs(smpc_ctx* ctx, float* costs);
 
+/* ---- critic statistics: which critic steers a tick, and how many rollouts carry weight ------
+ * (What upstream Nav2 publishes as `publish_critics_stats`; the reference fork predates it.)
+ * Ids of the registered critics in the scoring order above, and one pseudo-row for the gamma
+ * term of updateControlSequence [ref src/optimizer.cpp:365-380]. */
+#define SMPC_N_CRITICS 12
+#define SMPC_CRITIC_CONSTRAINT 0
+#define SMPC_CRITIC_COST 1
+#define SMPC_CRITIC_OBSTACLES 2
+#define SMPC_CRITIC_PATH_ALIGN 3
+#define SMPC_CRITIC_PATH_ALIGN_LEGACY 4
+#define SMPC_CRITIC_PATH_FOLLOW 5
+#define SMPC_CRITIC_GOAL_ANGLE 6
+#define SMPC_CRITIC_PREFER_FORWARD 7
+#define SMPC_CRITIC_GOAL 8
+#define SMPC_CRITIC_PATH_ANGLE 9
+#define SMPC_CRITIC_TWIRLING 10
+#define SMPC_CRITIC_VELOCITY_DEADBAND 11
+#define SMPC_STATS_CONTROL 12
+#define SMPC_STATS_ROWS 13
+
+/* The critic's class name as nav2_plugin/critics.xml registers it ("ConstraintCritic", ...);
+ * "ControlCost" for SMPC_STATS_CONTROL; NULL for any other id.  Needs no device. */
+const char* smpc_critic_name(uint32_t id);
+
+/* Row k of a rollout is the value CriticManager's k-th critic added to its cost,
+ * (float)pow(v_k, cost_power_k) [ref e.g. src/critics/goal_critic.cpp:44-54]; row 12 the float
+ * sum of the three gamma terms.  The rows of a rollout add up to its entry of smpc_get_costs
+ * to within float rounding. */
+typedef struct smpc_critic_stats {
+  uint32_t scored_mask;              /* bit k: row k was scored on this tick */
+  uint32_t fail_flag;                /* as smpc_tick_out.fail_flag would be */
+  uint32_t batch;                    /* rollouts reduced */
+  uint32_t best_rollout;             /* least total cost, lowest index among ties */
+  float    best_cost, effective_samples; /* (sum w)^2 / sum w^2, w the tick's softmax weights */
+  float    sum[13], min[13], max[13]; /* over the rollouts; rows not in scored_mask hold zeros */
+  float    weighted[13];             /* sum_b w_b t_kb / sum_b w_b */
+  float    at_best[13];              /* the row's value for best_rollout */
+} smpc_critic_stats;
+
+/* Break down the tick smpc_optimize(ctx, in, u_in) would run: what its FIRST iteration scores —
+ * the same noise, the same host gates, the true furthest point (a furthest-point pre-pass, no
+ * speculation), the same all-collide rule: when every rollout collides fail_flag is 1 and mask
+ * and rows are those of the re-score [ref critic_manager.cpp:70-73]; with in->fail_flag_in
+ * nothing is scored and the mask holds only the control row.  Scored by the general pass
+ * whatever pass the tick itself takes.  per_rollout: NULL, or [SMPC_STATS_ROWS][batch_size]
+ * floats, row-major.  Changes nothing a later tick depends on: u_in is read only, costs,
+ * furthest-point prediction and counters of the ctx stay as they are.  Its device buffers
+ * (SMPC_STATS_ROWS + 1 floats per rollout) are allocated at the first call.  A member of an
+ * smpc_group returns SMPC_ERR_STATE; a tick that needs the counting pass of two collision
+ * critics with a footprint returns SMPC_ERR_UNSUPPORTED; on a shard ctx the numbers are the
+ * shard's own.  (An addition under ABI 3, like smpc_group_optimize_some.) */
+int smpc_critic_breakdown(smpc_ctx* ctx, const smpc_tick_in* in, const float* u_in,
+                          smpc_critic_stats* stats, float* per_rollout);
+
 /* Diagnostics: the device sin/cos the rollout uses (integrateStateVelocities,
  * ref src/optimizer.cpp:326-329), evaluated on n host values; tests pin its error. */
 int smpc_selftest_sincos(smpc_ctx* ctx, const float* x, uint32_t n, float* sin_out,

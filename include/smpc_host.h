@@ -67,6 +67,12 @@ int sortham_optimizer_set_noise(sortham_optimizer* o, const float* nvx, const fl
  * twist_out = {linear.x, linear.y, angular.z}. */
 int sortham_optimizer_eval_control(sortham_optimizer* o, const smpc_tick_in* in, double* twist_out,
                                    smpc_tick_out* out);
+/* Optimizer::getCriticStats: per-critic costs and effective samples (smpc.h: smpc_critic_breakdown)
+ * of the tick sortham_optimizer_eval_control(o, in, ...) would run next, from the control sequence
+ * as it stands; in as for eval_control.  Changes nothing: eval_control afterwards returns what it
+ * would have returned without the call.  per_rollout: NULL or [SMPC_STATS_ROWS][batch_size] floats. */
+int sortham_optimizer_critic_stats(sortham_optimizer* o, const smpc_tick_in* in, smpc_critic_stats* stats,
+                                   float* per_rollout);
 /* The smpc_tick_out of the last tick the object ran — the last retry's when eval_control threw. */
 int sortham_optimizer_last_tick(const sortham_optimizer* o, smpc_tick_out* out);
 int sortham_optimizer_set_speed_limit(sortham_optimizer* o, double speed_limit, int percentage);

@@ -232,6 +232,32 @@ class SmpcTickOut(C.Structure):
     ]
 
 
+SMPC_N_CRITICS = 12
+(SMPC_CRITIC_CONSTRAINT, SMPC_CRITIC_COST, SMPC_CRITIC_OBSTACLES, SMPC_CRITIC_PATH_ALIGN,
+ SMPC_CRITIC_PATH_ALIGN_LEGACY, SMPC_CRITIC_PATH_FOLLOW, SMPC_CRITIC_GOAL_ANGLE,
+ SMPC_CRITIC_PREFER_FORWARD, SMPC_CRITIC_GOAL, SMPC_CRITIC_PATH_ANGLE, SMPC_CRITIC_TWIRLING,
+ SMPC_CRITIC_VELOCITY_DEADBAND) = range(SMPC_N_CRITICS)
+SMPC_STATS_CONTROL = 12
+SMPC_STATS_ROWS = 13
+
+
+class SmpcCriticStats(C.Structure):
+    """smpc_critic_stats — per-critic costs and effective samples of a tick (smpc_critic_breakdown)."""
+    _fields_ = [
+        ("scored_mask", C.c_uint32),
+        ("fail_flag", C.c_uint32),
+        ("batch", C.c_uint32),
+        ("best_rollout", C.c_uint32),
+        ("best_cost", C.c_float),
+        ("effective_samples", C.c_float),
+        ("sum", C.c_float * SMPC_STATS_ROWS),
+        ("min", C.c_float * SMPC_STATS_ROWS),
+        ("max", C.c_float * SMPC_STATS_ROWS),
+        ("weighted", C.c_float * SMPC_STATS_ROWS),
+        ("at_best", C.c_float * SMPC_STATS_ROWS),
+    ]
+
+
 # name -> (restype, argtypes) for every symbol include/smpc.h declares.
 _ctx = C.c_void_p
 PROTOTYPES = {
@@ -261,6 +287,9 @@ PROTOTYPES = {
                                 C.POINTER(SmpcTickOut)]),
     "smpc_get_trajectories": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
     "smpc_get_costs": (C.c_int, [_ctx, C.c_void_p]),
+    "smpc_critic_name": (C.c_char_p, [C.c_uint32]),
+    "smpc_critic_breakdown": (C.c_int, [_ctx, C.POINTER(SmpcTickIn), C.c_void_p,
+                                        C.POINTER(SmpcCriticStats), C.c_void_p]),
     "smpc_selftest_sincos": (C.c_int, [_ctx, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "smpc_selftest_philox": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "smpc_selftest_box_muller": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),

@@ -96,6 +96,12 @@ void free_ctx(smpc_ctx* c)
   for (float* p : {c->d_tvx, c->d_nvx, c->d_nvy, c->d_nwz, c->d_costs[0], c->d_costs[1], c->d_traj[0],
          c->d_traj[1], c->d_traj[2], c->d_partials, c->d_tuple, c->d_out, c->d_u_iter, c->d_furthest})
     if (p) (void)hipFree(p);
+  if (c->d_stats || c->d_stats_part) {
+    (void)hipStreamSynchronize(c->stream);   // (a breakdown abandoned on an error may still be writing them)
+    if (c->d_stats) (void)hipFree(c->d_stats);
+    if (c->d_stats_part) (void)hipFree(c->d_stats_part);
+  }
+  for (hipEvent_t e : c->ev_stats) if (e) (void)hipEventDestroy(e);
   if (c->fill_stream) {
     (void)hipStreamSynchronize(c->fill_stream);
     (void)hipStreamDestroy(c->fill_stream);

@@ -5,6 +5,7 @@
 //   smpc_prepare.cpp  per-tick host work: gates, path tables, lookup tables, LDS carve-up
 //   smpc_shard.cpp    batch-sharded tick, RCCL resolved at run time
 //   smpc_group.cpp    several planning instances per launch
+//   smpc_stats.cpp    per-critic breakdown of a tick (smpc_critic_breakdown)
 #ifndef SMPC_CTX_H_
 #define SMPC_CTX_H_
 
@@ -352,6 +353,14 @@ struct smpc_ctx {
   uint32_t acker_seq = 0;    // completion word the Ackermann launch publishes this tick
   uint32_t seq = 0, poll_seq = 0;
   uint32_t poll_words = 0;   // > 0: the tick's completion arrives as this many words, from slot SMPC_R_BLOCK_DONE of h_out on
+  // smpc_critic_breakdown (smpc_stats.cpp): buffers of its own, allocated at the first call — the
+  // 13 rows and the totals [14][stats_ld], the pass's partials, a furthest-point word, the result
+  // (one float allocation), and the reduction's double partials
+  float* d_stats = nullptr;
+  double* d_stats_part = nullptr;
+  uint32_t stats_ld = 0;
+  hipEvent_t ev_stats[4] = {};   // SMPC_FLAG_PROFILE: around the scoring pass and around the reduction
+  float stats_pass_ms = 0.f, stats_reduce_ms = 0.f;
   std::string err;
 };
 

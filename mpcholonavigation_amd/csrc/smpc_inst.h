@@ -1,5 +1,5 @@
 // smpc_inst.h — the scoring-pass instances as data.  Each kernel family keeps ONE table next to its
-// kernel (smpc_kernels.hip, smpc_lane.hip, smpc_split.hip): a row holds the template arguments and
+// kernel (smpc_kernels.hip, smpc_lane.hip, smpc_split.hip, smpc_wave_stats.hip): a row holds the template arguments and
 // the instance's address, written by one macro.  The kernel's name, the LDS limit, occupancy, the
 // selector ("which instance scores these flags?") and the launch all read that table.  Internal:
 // not part of the C-ABI.
@@ -54,6 +54,29 @@ hipError_t wave_launch_many(const WaveInst* k, const SmpcDev* d_many, const Smpc
 hipError_t lane_launch(const LaneInst* k, const SmpcDev& p, const SmpcDev* d_many, uint32_t n, const SmpcLds& L,
                        uint32_t grid, uint32_t block, hipStream_t st);
 hipError_t split_launch(const SplitInst* k, const SmpcDev& p, const SmpcLds& L, uint32_t grid, hipStream_t st);
+
+// ---- smpc_critic_breakdown (smpc_wave_stats.hip): the general wave pass that keeps every critic's term ----
+struct StatsInst { int r; bool full; const void* fn; };                                            // smpc_pass_stats<R, FULL>
+const StatsInst* stats_select(int R, uint32_t T);
+// stats: [SMPC_STATS_ROWS][ld] floats, ld >= p.B; p.costs: the totals; nothing is recorded for
+// smpc_debug_last_pass_kernel (a breakdown leaves no trace in what a tick reports)
+hipError_t stats_launch(const StatsInst* k, const SmpcDev& p, const SmpcLds& L, float* stats, uint32_t ld, uint32_t grid,
+                        uint32_t block, hipStream_t st);
+hipError_t stats_set_lds_limit(int bytes);
+// what the reduction leaves on the device
+struct SmpcStatsOut {
+  uint32_t best_rollout;
+  float best_cost, effective_samples;
+  float non_colliding;   // of the pass whose partials were handed in
+  float sum[13], min[13], max[13], weighted[13], at_best[13];
+};
+// slices of the batch the reduction's first launch works in (and their length, a multiple of four)
+uint32_t stats_reduce_slices(uint32_t B, uint32_t* slice_out);
+// smpc_reduce_stats + smpc_reduce_stats_final over the rows and `costs` (both 16-byte aligned, ld a
+// multiple of four, allocations padded to it); part: (SMPC_STATS_ROWS + 1) x slices x 4 doubles of scratch;
+// pass_partials / nblk: the scoring pass's per-block partials, for its non-colliding count
+hipError_t stats_launch_reduce(const float* stats, uint32_t ld, const float* costs, uint32_t B, float k2, double* part,
+                               const float* pass_partials, uint32_t nblk, uint32_t T, SmpcStatsOut* out, hipStream_t st);
 
 hipError_t wave_set_lds_limit(int bytes);
 hipError_t lane_set_lds_limit(int bytes);

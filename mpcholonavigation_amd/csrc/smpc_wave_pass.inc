@@ -11,7 +11,16 @@
 //                        of more blocks than stay resident just runs in rounds).
 // A second name instead of a fourth template argument: the instances of smpc_pass keep their names
 // and, the text being the same, their registers, scratch and occupancy.
+#if WAVE_PASS_STATS
+//   WAVE_PASS_STATS   1: smpc_pass_stats<R, FULL> (smpc_wave_stats.hip, WAVE_PASS_MANY 0) — the general
+//                        pass (MODE 2) of one planning instance that also KEEPS every critic's term:
+//                        wherever add_cost_pow folds a term into the cost, and at the gamma add, one
+//                        lane stores it to stats[row * stats_ld + rollout] (rows: SMPC_CRITIC_* of
+//                        include/smpc.h).  Undefined or 0: not a line of this text changes.
+template <int R, bool FULL>
+#else
 template <int R, int MODE, bool FULL>
+#endif
 #if WAVE_PASS_MANY
 __global__ void __launch_bounds__((R == 4 ? 512 : 1024), (R == 4 ? 2 : 4))
 WAVE_PASS_KERNEL(const SmpcDev* __restrict__ many, const SmpcWaveGeom* __restrict__ geom)
@@ -25,8 +34,15 @@ WAVE_PASS_KERNEL(const SmpcDev* __restrict__ many, const SmpcWaveGeom* __restric
   const SmpcLds& L = geom[blockIdx.y].lds;
 #define WAVE_PASS_GRID (geom[blockIdx.y].grid)
 #else
+#if WAVE_PASS_STATS
+__global__ void __launch_bounds__((R == 4 ? 512 : 1024), (R == 4 ? 2 : 4))
+WAVE_PASS_KERNEL(const SmpcDev p, const SmpcLds L, float* __restrict__ stats, const uint32_t stats_ld)
+{
+  constexpr int MODE = 2;
+#else
 __global__ void __launch_bounds__((R == 4 ? 512 : 1024), (R == 4 ? 2 : 4)) WAVE_PASS_KERNEL(const SmpcDev p, const SmpcLds L)
 {
+#endif
   constexpr bool MANY = false;
 #define WAVE_PASS_GRID (gridDim.x)
 #endif
@@ -290,6 +306,9 @@ __global__ void __launch_bounds__((R == 4 ? 512 : 1024), (R == 4 ? 2 : 4)) WAVE_
       const float c_pa = num > 0.f ? (GENERIC ? summed / num : summed * fast_rcp(num)) : 0.f;
       if (GENERIC) cost = add_cost_pow(cost, (double)(c_pa * p.pa_weight), p.pa_power);
       else cost += c_pa * pa_w;
+#if WAVE_PASS_STATS
+      stats_put(stats, stats_ld, SMPC_CRITIC_PATH_ALIGN, b_last - (n - 1 - g) * nW, rowon && s == 0, (double)(c_pa * p.pa_weight), p.pa_power);
+#endif
     }
     // ---- PathAlignLegacyCritic (path_align_legacy_critic.cpp:74-129), lane = (rollout g, sample s):
     // every trajectory point step, 2 step, ... against its nearest path point by brute force over
@@ -324,6 +343,9 @@ __global__ void __launch_bounds__((R == 4 ? 512 : 1024), (R == 4 ? 2 : 4)) WAVE_
       const float summed = __shfl(dsum, lane | (int)(SEG - 1), WAVE);
       const float c_pal = summed / p.pal_eval;
       cost = add_cost_pow(cost, (double)(c_pal * p.pal_weight), p.pal_power);
+#if WAVE_PASS_STATS
+      stats_put(stats, stats_ld, SMPC_CRITIC_PATH_ALIGN_LEGACY, b_last - (n - 1 - g) * nW, rowon && s == 0, (double)(c_pal * p.pal_weight), p.pal_power);
+#endif
     }
     // costs_ [B]: one lane per parked rollout
     if (rowon && s == 0) p.costs[b_last - (n - 1 - g) * nW] = cost;
@@ -529,6 +551,9 @@ __global__ void __launch_bounds__((R == 4 ? 512 : 1024), (R == 4 ? 2 : 4)) WAVE_
         }
       }
       cost = add_cost_pow(cost, wave_sum_d(sa) * (double)p.con_weight, p.con_power);
+#if WAVE_PASS_STATS
+      stats_put(stats, stats_ld, SMPC_CRITIC_CONSTRAINT, b, lane == 0, wave_sum_d(sa) * (double)p.con_weight, p.con_power);
+#endif
     }
 
     if (EXTRA && (p.flags & SD_CONSTRAINT)) {
@@ -618,12 +643,18 @@ __global__ void __launch_bounds__((R == 4 ? 512 : 1024), (R == 4 ? 2 : 4)) WAVE_
         const float repulsive = coll_c ? p.cost_collision_cost : wave_sum(crep);
         const float v = p.cost_w254 * repulsive / (float)T;
         cost = add_cost_pow(cost, (double)v, p.cost_power);
+#if WAVE_PASS_STATS
+        stats_put(stats, stats_ld, SMPC_CRITIC_COST, b, lane == 0, (double)v, p.cost_power);
+#endif
       }
       if (p.flags & SD_OBSTACLES) {
         const float rep_sum = wave_sum(rep);
         const float raw = coll_o ? p.obs_collision_cost : wave_sum(crit);
         const float v = (p.obs_critical_w * raw) + (p.obs_repulsion_w * rep_sum / (float)T);
         cost = add_cost_pow(cost, (double)v, p.obs_power);
+#if WAVE_PASS_STATS
+        stats_put(stats, stats_ld, SMPC_CRITIC_OBSTACLES, b, lane == 0, (double)v, p.obs_power);
+#endif
       }
     } else
     // ---- costmap lookups shared by CostCritic and ObstaclesCritic ----------------
@@ -690,6 +721,9 @@ __global__ void __launch_bounds__((R == 4 ? 512 : 1024), (R == 4 ? 2 : 4)) WAVE_
         const float repulsive = collided ? p.cost_collision_cost : wave_sum(crep);
         const float v = p.cost_w254 * repulsive / (float)T;
         cost = add_cost_pow(cost, (double)v, p.cost_power);
+#if WAVE_PASS_STATS
+        stats_put(stats, stats_ld, SMPC_CRITIC_COST, b, lane == 0, (double)v, p.cost_power);
+#endif
       }
       if (EXTRA && (p.flags & SD_COST)) {
         const float k = p.cost_w254 / (float)T;
@@ -702,6 +736,9 @@ __global__ void __launch_bounds__((R == 4 ? 512 : 1024), (R == 4 ? 2 : 4)) WAVE_
           const float raw = collided ? p.obs_collision_cost : wave_sum(crit);
           const float v = (p.obs_critical_w * raw) + (p.obs_repulsion_w * rep_sum / (float)T);
           cost = add_cost_pow(cost, (double)v, p.obs_power);
+#if WAVE_PASS_STATS
+          stats_put(stats, stats_ld, SMPC_CRITIC_OBSTACLES, b, lane == 0, (double)v, p.obs_power);
+#endif
         } else {
           // (added, not assigned: with CostCritic in the list too its terms are already in here)
           lin += (collided ? 0.f : obs_cw * crit) + obs_rt * rep;
@@ -717,6 +754,9 @@ __global__ void __launch_bounds__((R == 4 ? 512 : 1024), (R == 4 ? 2 : 4)) WAVE_
         const double ddx = (double)fdx, ddy = (double)fdy;
         const double dist = sqrt(ddx * ddx + ddy * ddy);
         cost = add_cost_pow(cost, (double)p.pf_weight * dist, p.pf_power);
+#if WAVE_PASS_STATS
+        stats_put(stats, stats_ld, SMPC_CRITIC_PATH_FOLLOW, b, lane == 0, (double)p.pf_weight * dist, p.pf_power);
+#endif
       } else {
         uni += pf_w * fast_sqrt(fdx * fdx + fdy * fdy);
       }
@@ -732,6 +772,9 @@ __global__ void __launch_bounds__((R == 4 ? 512 : 1024), (R == 4 ? 2 : 4)) WAVE_
       const double mean = wave_sum_d(sa) / (double)T;
       if (GENERIC) cost = add_cost_pow(cost, mean * (double)p.ga_weight, p.ga_power);
       else uni += (float)(mean * (double)p.ga_weight);
+#if WAVE_PASS_STATS
+      stats_put(stats, stats_ld, SMPC_CRITIC_GOAL_ANGLE, b, lane == 0, mean * (double)p.ga_weight, p.ga_power);
+#endif
     }
 
     // ---- PreferForwardCritic (prefer_forward_critic.cpp:33-47) ---------------
@@ -741,6 +784,9 @@ __global__ void __launch_bounds__((R == 4 ? 512 : 1024), (R == 4 ? 2 : 4)) WAVE_
       for (int r = 0; r < R; ++r) sb += fmaxf(-vx[r], 0.f) * dt;
       if (GENERIC) cost = add_cost_pow(cost, (double)(wave_sum(sb) * p.pfw_weight), p.pfw_power);
       else lin += sb * pfw_w;
+#if WAVE_PASS_STATS
+      stats_put(stats, stats_ld, SMPC_CRITIC_PREFER_FORWARD, b, lane == 0, (double)(wave_sum(sb) * p.pfw_weight), p.pfw_power);
+#endif
     }
 
     // ---- GoalCritic, PathAngleCritic, TwirlingCritic, VelocityDeadbandCritic: MODE 2 only ----
@@ -755,6 +801,9 @@ __global__ void __launch_bounds__((R == 4 ? 512 : 1024), (R == 4 ? 2 : 4)) WAVE_
         }
       }
       cost = add_cost_pow(cost, wave_sum_d(sa) / (double)T * (double)p.goal_weight, p.goal_power);
+#if WAVE_PASS_STATS
+      stats_put(stats, stats_ld, SMPC_CRITIC_GOAL, b, lane == 0, wave_sum_d(sa) / (double)T * (double)p.goal_weight, p.goal_power);
+#endif
     }
     if (RARE && (p.flags & SD_PATH_ANGLE) && tk.pang_active[S]) {
       // path_angle_critic.cpp:72-100: float atan2, then the double angle arithmetic of
@@ -776,6 +825,9 @@ __global__ void __launch_bounds__((R == 4 ? 512 : 1024), (R == 4 ? 2 : 4)) WAVE_
         }
       }
       cost = add_cost_pow(cost, wave_sum_d(sa) / (double)T * (double)p.pang_weight, p.pang_power);
+#if WAVE_PASS_STATS
+      stats_put(stats, stats_ld, SMPC_CRITIC_PATH_ANGLE, b, lane == 0, wave_sum_d(sa) / (double)T * (double)p.pang_weight, p.pang_power);
+#endif
     }
     if (RARE && (p.flags & SD_TWIRLING)) {
       double sa = 0.0;   // twirling_critic.cpp:40-41
@@ -784,6 +836,9 @@ __global__ void __launch_bounds__((R == 4 ? 512 : 1024), (R == 4 ? 2 : 4)) WAVE_
         if (STEP_OK(r)) sa += (double)fabsf(wz[r]);
       }
       cost = add_cost_pow(cost, wave_sum_d(sa) / (double)T * (double)p.tw_weight, p.tw_power);
+#if WAVE_PASS_STATS
+      stats_put(stats, stats_ld, SMPC_CRITIC_TWIRLING, b, lane == 0, wave_sum_d(sa) / (double)T * (double)p.tw_weight, p.tw_power);
+#endif
     }
     if (RARE && (p.flags & SD_DEADBAND)) {
       double sa = 0.0;   // velocity_deadband_critic.cpp:52-76 (::fabs(double): double arithmetic)
@@ -795,6 +850,9 @@ __global__ void __launch_bounds__((R == 4 ? 512 : 1024), (R == 4 ? 2 : 4)) WAVE_
         }
       }
       cost = add_cost_pow(cost, wave_sum_d(sa) * (double)p.db_weight, p.db_power);
+#if WAVE_PASS_STATS
+      stats_put(stats, stats_ld, SMPC_CRITIC_VELOCITY_DEADBAND, b, lane == 0, wave_sum_d(sa) * (double)p.db_weight, p.db_power);
+#endif
     }
 
     if (EXTRA) {
@@ -859,6 +917,11 @@ __global__ void __launch_bounds__((R == 4 ? 512 : 1024), (R == 4 ? 2 : 4)) WAVE_
       cost += p.g_vx * wave_sum(gx);
       cost += p.g_wz * wave_sum(gz);
       cost += p.g_vy * wave_sum(gy);
+#if WAVE_PASS_STATS
+      // (the control row keeps ONE float: the three gamma terms summed in the order they are added)
+      stats_put(stats, stats_ld, SMPC_STATS_CONTROL, b, lane == 0,
+                (double)(p.g_vx * wave_sum(gx) + p.g_wz * wave_sum(gz) + p.g_vy * wave_sum(gy)), 1u);
+#endif
     } else {
 #pragma unroll
       for (int r = 0; r < R; ++r) {

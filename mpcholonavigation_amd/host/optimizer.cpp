@@ -307,6 +307,36 @@ void Optimizer::optimize()
   takeTick(u.data(), out);
 }
 
+smpc_critic_stats Optimizer::getCriticStats(const TickInput & ti, float * per_rollout)
+{
+  // the smpc_tick_in evalControl's first optimize() would hand over (prepare() clears the fail
+  // flag), without touching the per-tick members
+  smpc_tick_in in;
+  std::memset(&in, 0, sizeof(in));
+  in.pose_x = ti.robot_pose.x;
+  in.pose_y = ti.robot_pose.y;
+  in.pose_yaw = static_cast<float>(ti.robot_pose.yaw);
+  in.speed_vx = ti.robot_speed.vx;
+  in.speed_vy = ti.robot_speed.vy;
+  in.speed_wz = ti.robot_speed.wz;
+  in.path_x = ti.plan.x.data();
+  in.path_y = ti.plan.y.data();
+  in.path_yaw = ti.plan.yaws.data();
+  in.path_len = static_cast<uint32_t>(ti.plan.x.size());
+  in.goal_x = ti.goal.x;
+  in.goal_y = ti.goal.y;
+  in.goal_checker_xy_tolerance = ti.goal_checker_xy_tolerance;
+  const unsigned int T = settings_.time_steps;
+  std::vector<float> u(3 * T);
+  std::memcpy(u.data(), control_sequence_.vx.data(), T * sizeof(float));
+  std::memcpy(u.data() + T, control_sequence_.vy.data(), T * sizeof(float));
+  std::memcpy(u.data() + 2 * T, control_sequence_.wz.data(), T * sizeof(float));
+  pushConstraints();   // (what the tick pushes too: the same values)
+  smpc_critic_stats stats;
+  ck(ctx_, smpc_critic_breakdown(ctx_, &in, u.data(), &stats, per_rollout), "smpc_critic_breakdown");
+  return stats;
+}
+
 bool Optimizer::fallback(bool fail)
 {
   if (!fail) {

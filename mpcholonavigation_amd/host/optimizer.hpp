@@ -124,6 +124,16 @@ void savitskyGolayFilter(
 
 class Optimizer;
 
+// the arguments of Optimizer::evalControl as one value (getCriticStats)
+struct TickInput
+{
+  Pose2D robot_pose;
+  Twist2D robot_speed;
+  models::Path plan;
+  Pose2D goal;
+  float goal_checker_xy_tolerance{-1.0f};
+};
+
 // What an Optimizer asks of the fleet it is a member of (fleet.hpp: FleetOptimizer, N optimizers
 // ticked through one smpc_group).  An interface, so that this class links without the fleet.
 class FleetLink
@@ -167,6 +177,13 @@ public:
   Twist2D evalControl(
     const Pose2D & robot_pose, const Twist2D & robot_speed, const models::Path & plan,
     const Pose2D & goal, float goal_checker_xy_tolerance = -1.0f);
+
+  // Per-critic costs and effective samples (smpc_critic_breakdown) of the tick evalControl(in)
+  // would run next: its first scoring pass, from the control sequence as it stands.  Changes
+  // nothing: evalControl afterwards returns what it would have returned without the call.
+  // per_rollout: null, or [SMPC_STATS_ROWS][batch_size] floats.  Throws for a fleet member whose
+  // context is grouped (SMPC_ERR_STATE).
+  smpc_critic_stats getCriticStats(const TickInput & in, float * per_rollout = nullptr);
 
   void setSpeedLimit(double speed_limit, bool percentage);  // ref :428-453
   void reset();                                             // ref :116-132

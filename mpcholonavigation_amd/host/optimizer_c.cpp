@@ -170,6 +170,24 @@ int sortham_optimizer_eval_control(
     });
 }
 
+int sortham_optimizer_critic_stats(
+  sortham_optimizer * o, const smpc_tick_in * in, smpc_critic_stats * stats, float * per_rollout)
+{
+  if (!o || !in || !stats) {return SMPC_ERR_INVALID;}
+  return guarded(
+    o, [&]() {
+      sortham_ns::TickInput ti;
+      ti.robot_pose = {in->pose_x, in->pose_y, static_cast<double>(in->pose_yaw)};
+      ti.goal = {in->goal_x, in->goal_y, 0.0};
+      ti.robot_speed = {in->speed_vx, in->speed_vy, in->speed_wz};
+      ti.plan.x.assign(in->path_x, in->path_x + in->path_len);
+      ti.plan.y.assign(in->path_y, in->path_y + in->path_len);
+      ti.plan.yaws.assign(in->path_yaw, in->path_yaw + in->path_len);
+      ti.goal_checker_xy_tolerance = in->goal_checker_xy_tolerance;
+      *stats = o->opt.getCriticStats(ti, per_rollout);
+    });
+}
+
 int sortham_optimizer_last_tick(const sortham_optimizer * o, smpc_tick_out * out)
 {
   if (!o || !out) {return SMPC_ERR_INVALID;}

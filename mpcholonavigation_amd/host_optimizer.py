@@ -51,6 +51,8 @@ PROTOTYPES = {
     "sortham_optimizer_set_noise": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sortham_optimizer_eval_control": (C.c_int, [_ctx, C.POINTER(A.SmpcTickIn), C.c_void_p,
                                                  C.POINTER(A.SmpcTickOut)]),
+    "sortham_optimizer_critic_stats": (C.c_int, [_ctx, C.POINTER(A.SmpcTickIn),
+                                                 C.POINTER(A.SmpcCriticStats), C.c_void_p]),
     "sortham_optimizer_last_tick": (C.c_int, [_ctx, C.POINTER(A.SmpcTickOut)]),
     "sortham_optimizer_set_speed_limit": (C.c_int, [_ctx, C.c_double, C.c_int]),
     "sortham_optimizer_reset": (C.c_int, [_ctx]),
@@ -210,6 +212,18 @@ class Optimizer:
         self._ck(self.lib.sortham_optimizer_eval_control(self.h, C.byref(tick.c), _ptr(tw),
                                                          C.byref(out)))
         return tw, out
+
+    def critic_stats(self, tick, per_rollout=False):
+        """Optimizer::getCriticStats: the per-critic breakdown (optimizer.CriticStats) of the tick
+        eval_control(tick) would run next; eval_control afterwards is unaffected."""
+        from .optimizer import critic_names, critic_stats_from_c, load_library as load_smpc
+        st = A.SmpcCriticStats()
+        rows = None
+        if per_rollout:
+            rows = np.empty((A.SMPC_STATS_ROWS, self.B), np.float32)
+        self._ck(self.lib.sortham_optimizer_critic_stats(self.h, C.byref(tick.c), C.byref(st),
+                                                         _ptr(rows) if rows is not None else None))
+        return critic_stats_from_c(st, critic_names(load_smpc()), rows)
 
     def last_tick(self):
         """The SmpcTickOut of the last tick the object ran (the last retry's when eval_control raised)."""

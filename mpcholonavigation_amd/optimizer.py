@@ -8,9 +8,11 @@ Optimizer::getGeneratedTrajectories, `reset` is Optimizer::reset's
 device half.
 """
 import ctypes as C
+import dataclasses
 import os
 import sys
 import types
+from typing import Optional
 
 import numpy as np
 
@@ -49,6 +51,49 @@ def load_library():
         if _lib.smpc_abi_version() != A.SMPC_ABI_VERSION:
             raise ImportError("libsmpc.so ABI version mismatch")
     return _lib
+
+
+@dataclasses.dataclass
+class CriticStats:
+    """smpc_critic_stats with the names attached (Smpc.critic_stats).  The arrays have one entry per
+    row of `names`: the twelve critics in scoring order, then "ControlCost" (the gamma term)."""
+    names: tuple
+    scored_mask: int
+    fail_flag: bool
+    batch: int
+    best_rollout: int
+    best_cost: float
+    effective_samples: float
+    sum: np.ndarray
+    min: np.ndarray
+    max: np.ndarray
+    weighted: np.ndarray
+    at_best: np.ndarray
+    per_rollout: Optional[np.ndarray] = None   # [13, B] float32 when asked for
+
+    def scored(self, name):
+        """Whether the row called `name` ("PathAlignCritic", ...) was scored on this tick."""
+        return bool(self.scored_mask >> self.names.index(name) & 1)
+
+    def as_dict(self):
+        """{name: {"sum", "min", "max", "mean", "weighted", "at_best"}} of the scored rows."""
+        return {n: {"sum": float(self.sum[k]), "min": float(self.min[k]), "max": float(self.max[k]),
+                    "mean": float(self.sum[k]) / max(self.batch, 1), "weighted": float(self.weighted[k]),
+                    "at_best": float(self.at_best[k])}
+                for k, n in enumerate(self.names) if self.scored_mask >> k & 1}
+
+
+def critic_names(lib=None):
+    """The rows of a breakdown: smpc_critic_name(0 .. SMPC_STATS_ROWS - 1)."""
+    lib = lib or load_library()
+    return tuple(lib.smpc_critic_name(k).decode() for k in range(A.SMPC_STATS_ROWS))
+
+
+def critic_stats_from_c(st, names, per_rollout=None):
+    rows = {f: np.array(getattr(st, f), np.float32) for f in ("sum", "min", "max", "weighted", "at_best")}
+    return CriticStats(names=names, scored_mask=int(st.scored_mask), fail_flag=bool(st.fail_flag),
+                       batch=int(st.batch), best_rollout=int(st.best_rollout), best_cost=float(st.best_cost),
+                       effective_samples=float(st.effective_samples), per_rollout=per_rollout, **rows)
 
 
 def _ptr(a):
@@ -171,6 +216,18 @@ class Smpc:
         c = np.empty(self.B, np.float32)
         self._ck(self.lib.smpc_get_costs(self.h, _ptr(c)))
         return c
+
+    def critic_stats(self, tick, u, per_rollout=False):
+        """Per-critic costs and effective samples of the tick optimize(tick, u) would run next
+        (smpc_critic_breakdown): its first iteration, scored without changing anything the next
+        tick depends on.  per_rollout: also every rollout's rows, float32 [13, B]."""
+        u = np.ascontiguousarray(u, dtype=np.float32)
+        if u.shape != (3, self.T):
+            raise ValueError(f"u must be [3, {self.T}]")
+        st = A.SmpcCriticStats()
+        rows = np.empty((A.SMPC_STATS_ROWS, self.B), np.float32) if per_rollout else None
+        self._ck(self.lib.smpc_critic_breakdown(self.h, C.byref(tick.c), _ptr(u), C.byref(st), _ptr(rows)))
+        return critic_stats_from_c(st, critic_names(self.lib), rows)
 
     def selftest_sincos(self, x):
         x = np.ascontiguousarray(x, dtype=np.float32)

@@ -321,6 +321,60 @@ def run(case):
     return d, kinds, notes
 
 
+def critic_difference(case):
+    """Developer aid for a failing case: the breakdown of its FIRST tick (Smpc.critic_stats) against the
+    oracle critic by critic — the oracle scoring each critic of the list alone with gamma = 0, so that its
+    costs are that critic's term — one line per row: where the totals differ, which critic does."""
+    d = draw(case)
+    cfg, scn, tick, u0, cr, noise = build(d)
+    if d["rng"]:
+        print("    (device noise: no per-critic comparison)")
+        return
+    fp = np.array([[0.25, 0.15], [0.25, -0.15], [-0.2, -0.15], [-0.2, 0.15]])
+
+    def setup(obj, critics):
+        if cr.obstacles.consider_footprint or cr.cost.consider_footprint:
+            obj.set_footprint(fp, 0.3)
+        configure(obj, scn, critics=critics, noise=noise, track_unknown=d["track_unknown"])
+    g = Smpc(cfg)
+    try:
+        setup(g, cr)
+        st = g.critic_stats(tick, u0, per_rollout=True)
+    finally:
+        g.close()
+    cfg0 = default_config(batch_size=d["B"], time_steps=d["T"], iteration_count=1, motion_model=d["model"], model_dt=d["dt"],
+                          temperature=d["temperature"], gamma=0.0, vy_max=cfg.vy_max, vy_std=cfg.vy_std)
+    print(f"    first tick by critic (fail_flag {int(st.fail_flag)}, effective samples {st.effective_samples:.1f} of {st.batch}, "
+          f"best rollout {st.best_rollout} at {st.best_cost:.6g}):")
+    if st.fail_flag:
+        print("      (every rollout collides: the rows are the re-score's, nothing behind the first collision critic is scored; "
+              "the oracle's single-critic terms below are)")
+    for k, name in enumerate(CRITICS_IN_SCORING_ORDER):
+        sub = getattr(cr, name)
+        if not sub.enabled:
+            continue
+        one = type(cr).from_buffer_copy(cr)
+        for other in CRITICS_IN_SCORING_ORDER:
+            getattr(one, other).enabled = 1 if other == name else 0
+        o = Oracle(cfg0)
+        try:
+            setup(o, one)
+            o.optimize(tick, u0)
+            ref = o.get_costs().astype(np.float64)
+        finally:
+            o.close()
+        row = st.per_rollout[k].astype(np.float64)
+        dd = np.abs(row - ref)
+        i = int(np.argmax(dd))
+        off = int(np.sum(dd > 2e-4 * np.maximum(np.abs(ref), 1.0)))
+        print(f"      {st.names[k]:24s} {'scored' if st.scored_mask >> k & 1 else 'gated '}  weighted {st.weighted[k]:12.6g}  "
+              f"max |d| {dd[i]:.4g} at rollout {i} ({row[i]:.6g} vs {ref[i]:.6g}); beyond 2e-4 relative: {off}")
+
+
+CRITICS_IN_SCORING_ORDER = ("constraint", "cost", "obstacles", "path_align", "path_align_legacy", "path_follow", "goal_angle",
+                            "prefer_forward", "goal", "path_angle", "twirling", "velocity_deadband")
+
+
 def main():
     first, count = int(sys.argv[1]), int(sys.argv[2])
     only = [int(a.split("=")[1]) for a in sys.argv[3:] if a.startswith("only=")]
@@ -343,6 +397,11 @@ def main():
                 continue
             bad += 1
             print(f"case {case}: FAILED  {type(e).__name__}: {msg[:300]}\n    draw: {draw(case)}", flush=True)
+            if isinstance(e, Mismatch):
+                try:
+                    critic_difference(case)
+                except Exception as e2:      # (the aid must not hide the finding)
+                    print(f"    (no per-critic difference: {type(e2).__name__}: {e2})")
             if only:
                 traceback.print_exc()
     print(f"{bad} of {len(list(cases))} cases failed", flush=True)
