@@ -4,7 +4,9 @@ effect on the ticks around a call, the mask, the host face.
 
 Shapes (one per instance of smpc_pass_stats and the partial PathAlign flush): 400 x 15 (the reference
 smoke fixture's shape: R = 1, ragged), 192 x 64 (R = 1, whole), 2 000 x 56 (the deployed nine),
-200 x 128 (R = 2, whole), 130 x 200 (R = 4, ragged; 130 is no multiple of the flush group)."""
+200 x 128 (R = 2, whole), 130 x 200 (R = 4, ragged; 130 is no multiple of the flush group).
+What lies beyond one slice of the reduction (B > 16 384), a footprint, a non-holonomic model and a lane
+context's device noise is in test_gpu_critic_stats_reach.py."""
 import ctypes as C
 import math
 
@@ -202,6 +204,53 @@ def check_statistics(st, costs, cfg):
         if not st.scored_mask >> k & 1:
             assert st.sum[k] == st.min[k] == st.max[k] == st.weighted[k] == st.at_best[k] == 0.0
     return ess
+
+
+def slices_of(B):
+    """(number of slices, slice length) of the reduction, as stats_reduce_slices cuts the batch:
+    16 384 rollouts a slice, doubled until at most 1024 slices remain."""
+    n = 16384
+    while -(-B // n) > 1024:
+        n *= 2
+    return -(-B // n), n
+
+
+def sliced_float32_statistics(rows, costs, cfg):
+    """The reduction's arithmetic restated in NumPy, slice by slice: the weights 2^(k2 (c - m_s))
+    against the SLICE's least cost m_s, the argument and the weight in float32 (exp2 correctly
+    rounded, which the hardware's v_exp_f32 is not), the sums in double, every slice multiplied by
+    the float32 factor 2^(k2 (m_s - m)) in slice order.  -> (weighted float64 [13],
+    effective_samples).  What a result beyond check_statistics' bar is compared with to tell a
+    defect of the kernels from the error of the device's exponent (test_gpu_critic_stats_reach.py)."""
+    c32 = np.asarray(costs, np.float32)
+    k2, m = k2_of(cfg), c32.min()
+    S, n = slices_of(len(c32))
+    W = W2 = 0.0
+    Aw = np.zeros(rows.shape[0])
+    for s in range(S):
+        c = c32[s * n:(s + 1) * n]
+        ms = c.min()
+        w = np.exp2((k2 * (c - ms)).astype(np.float64)).astype(np.float32).astype(np.float64)
+        f = float(np.float32(np.exp2(np.float64(k2 * (ms - m)))))
+        W += f * w.sum()
+        W2 += f * f * (w * w).sum()
+        Aw += f * (rows[:, s * n:(s + 1) * n].astype(np.float64) @ w)
+    return Aw / W, W * W / W2
+
+
+def statistics_ratios(st, costs, cfg, other=None):
+    """Error / bar of `weighted` (the largest over the rows) and of `effective_samples` under
+    check_statistics' model and bar, log2(B) 2^-24 relative to the absolute sums.  other:
+    (weighted, effective_samples) to judge in place of the device's (the float32 restatement)."""
+    rows = st.per_rollout.astype(np.float64)
+    c32 = costs.astype(np.float32)
+    w = np.exp2((k2_of(cfg) * (c32 - c32.min())).astype(np.float64))
+    tol = math.log2(st.batch) * EPS
+    weighted, ess_dev = (st.weighted, st.effective_samples) if other is None else other
+    bar = tol * (np.abs(rows) @ w / w.sum())
+    err = np.abs(np.asarray(weighted, np.float64) - rows @ w / w.sum())
+    ess = w.sum() ** 2 / (w * w).sum()
+    return float((err[bar > 0] / bar[bar > 0]).max()), float(abs(ess_dev - ess) / (tol * ess))
 
 
 @pytest.mark.parametrize("B,T,names", SHAPES, ids=[f"{b}x{t}" for b, t, _ in SHAPES])
