@@ -150,7 +150,7 @@ int launch_furthest(smpc_ctx* c, float* d_furthest)
 
 int begin_tick(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
 {
-  const int rc = prepare_tick(c, in, u_in);   // (touches none of the three)
+  const int rc = prepare_tick(c, in, u_in);   // (touches none of the three; the predictor it advances is c->pred)
   if (rc != SMPC_OK) return rc;
   c->passes = 0;
   c->evp_used = 0;
@@ -831,10 +831,7 @@ int smpc_reset(smpc_ctx* c)
   HIPCK(c, hipMemsetAsync(c->d_costs[0], 0, c->cfg.batch_size * sizeof(float), c->stream));
   HIPCK(c, hipMemsetAsync(c->d_costs[1], 0, c->cfg.batch_size * sizeof(float), c->stream));
   c->tick_ready = false;
-  c->hint_valid = false;
-  c->hint_Fp_valid = false;
-  c->hint_is_this_ticks = false;
-  c->hint_drift = 0.f;
+  c->pred.forget();
   if (c->rng_mode) {
     c->epoch++;
     return draw_noise(c);
@@ -1107,11 +1104,11 @@ int smpc_optimize(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_tick
         hintS = S_host;
       } else if (S_on_device) {
         dF = c->d_furthest;
-      } else if (speculate && c->hint_valid) {
+      } else if (speculate && c->pred.hint_valid) {
         // score with the previous tick's furthest point; the pass reports the true
         // one and a miss is re-scored below, so the result is exact either way
         spec_try = true;
-        hintS = c->hint;
+        hintS = c->pred.hint;
         flags |= SD_LOCAL_FURTHEST;
       } else {
         rc = launch_furthest(c, c->d_furthest);
@@ -1379,8 +1376,8 @@ int smpc_debug_lane_scan_count(smpc_ctx* c, unsigned long long* scanned, uint32_
 // itself while the stored noise stays the same from tick to tick
 int smpc_debug_furthest_f(const smpc_ctx* c, float* F)
 {
-  if (!c || !F || !c->hint_valid) return SMPC_ERR_INVALID;
-  *F = c->hint_F;
+  if (!c || !F || !c->pred.hint_valid) return SMPC_ERR_INVALID;
+  *F = c->pred.hint_F;
   return SMPC_OK;
 }
 

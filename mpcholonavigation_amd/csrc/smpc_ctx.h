@@ -198,6 +198,43 @@ struct PassPlan {
   uint32_t window_bytes = 0;  // first LDS region of the lane pass
 };
 
+// The furthest-point predictor: everything remember_furthest and predict_hint (smpc_prepare.cpp) own.
+// Who else writes it: smpc_reset (forget), a sharded tick whose exchange timed out (drop_hint), the
+// sharded tick and the group after a miss (hint, hint_F, hint_is_this_ticks); smpc_critic_breakdown
+// saves and restores it whole.
+struct FurthestPredictor {
+  // the index this tick is scored with first (predict_hint: last tick's value carried forward by the
+  // robot's motion and the plan's shift)
+  bool hint_valid = false;
+  uint32_t hint = 0;
+  // what the prediction starts from: the last known F = index + fraction (smpc_dev.h) and the
+  // tick inputs it was measured on
+  float hint_F = 0.f;
+  float hint_Fp = 0.f;       // the last prediction, unrounded; valid when hint_Fp_valid
+  bool hint_Fp_valid = false;
+  bool hint_is_this_ticks = false;   // set by the group's re-run of a missed member (predict_hint)
+  float hint_drift = 0.f;    // last tick's (true - predicted): how fast the endpoints drift relative to the robot
+  bool anchor_valid = false;
+  double anchor_x = 0, anchor_y = 0;
+  // endpoint of the NOMINAL rollout (the control sequence a tick starts from, no noise) of the last
+  // remembered tick and of the tick at hand: what carries the furthest point from tick to tick
+  double anchor_ex = 0, anchor_ey = 0, cur_ex = 0, cur_ey = 0;
+  bool anchor_e_valid = false, cur_e_valid = false;
+  std::vector<float> anchor_px, anchor_py;
+  uint32_t noise_gen_remembered = 0;   // smpc_ctx::noise_gen as of the last remember_furthest
+  // smpc_reset: no prediction and no drift; the anchor stays (unread while hint_valid is false, and
+  // the next remember_furthest overwrites it)
+  void forget()
+  {
+    hint_valid = false;
+    hint_Fp_valid = false;
+    hint_is_this_ticks = false;
+    hint_drift = 0.f;
+  }
+  // the tick's furthest point never became known: the next tick does not speculate
+  void drop_hint() {hint_valid = false;}
+};
+
 }  // namespace smpc_impl
 
 struct smpc_ctx {
@@ -229,8 +266,8 @@ struct smpc_ctx {
   hipStream_t fill_stream = nullptr;
   hipEvent_t ev_fill = nullptr;
   bool redraw_pending = false, redraw_rm_valid = true;
-  uint32_t noise_gen = 0;              // counts changes of the noise the ticks score with
-  uint32_t noise_gen_remembered = 0;   // ... as of the last remember_furthest
+  uint32_t noise_gen = 0;              // counts changes of the noise the ticks score with (pred.noise_gen_remembered:
+                                       // as of the last remember_furthest)
   bool use_tpr = false;      // group-major noise kept: the lane-per-rollout pass may run
   bool rm_valid = true;      // the [B,T] tensors hold the current noise (a device-RNG draw fills the
                              // group-major copy only; ensure_row_major() makes the other on demand)
@@ -259,7 +296,8 @@ struct smpc_ctx {
   uint32_t p2p_xseq = 0;
   uint32_t p2p_timeout_ms = 10000;   // bound of the in-kernel wait for the peers (smpc_shard_p2p_set_timeout)
   bool p2p_failed = false;           // an exchange timed out: no further mailbox tick until re-init
-  bool pang_any = false;        // this tick: PathAngleCritic is live for some candidate furthest point (prepare_tick)
+  bool pang_any = false;        // this tick: PathAngleCritic is live for some candidate furthest point (prepare_tick, from
+                                // path_angle_gates; plan_launch reads it)
   // the lane pass's prune table as last built, and what it was built for (prepare_tick)
   float prune_table[SMPC_PRUNE_FLOATS] = {};
   std::vector<float> prune_px, prune_py;
@@ -310,7 +348,7 @@ struct smpc_ctx {
   // per-tick prepared state
   SmpcDev dev{};
   uint32_t gate_flags = 0;   // critics past their host-side gates this tick
-  int score_mode = 0;        // this tick's wave-pass MODE (plan_launch): 0, 3, 4 lean (every cost_power == 1), 2 general
+  int score_mode = 0;        // this tick's wave-pass MODE (wave_mode in plan_launch): 0, 3, 4 lean (every cost_power == 1), 2 general
   static int score_mode_for(const smpc_critic_params& cr)
   {
     return (cr.obstacles.cost_power == 1 && cr.path_align.cost_power == 1 &&
@@ -321,28 +359,12 @@ struct smpc_ctx {
   bool fail_in = false;
   uint32_t P = 0;
   uint32_t passes = 0;
-  // speculation on furthest_reached_path_point: the index this tick is scored with first
-  // (predict_hint: last tick's value carried forward by the robot's motion and the plan's shift)
-  bool hint_valid = false;
-  uint32_t hint = 0;
+  // speculation on furthest_reached_path_point: the index this tick is scored with first is pred.hint
+  smpc_impl::FurthestPredictor pred;
   uint64_t spec_misses = 0;
-  // what the prediction starts from: the last known F = index + fraction (smpc_dev.h) and the
-  // tick inputs it was measured on
-  float hint_F = 0.f;
-  float hint_Fp = 0.f;       // the last prediction, unrounded; valid when hint_Fp_valid
-  bool hint_Fp_valid = false;
   smpc_tick_in step_in{};       // step-wise sharded API: this tick's inputs (smpc_shard_begin .. smpc_shard_combine),
   std::vector<float> step_px, step_py;   // with the path it points at copied here
   bool step_remembered = false;
-  bool hint_is_this_ticks = false;   // set by the group's re-run of a missed member (predict_hint)
-  float hint_drift = 0.f;    // last tick's (true - predicted): how fast the endpoints drift relative to the robot
-  bool anchor_valid = false;
-  double anchor_x = 0, anchor_y = 0;
-  // endpoint of the NOMINAL rollout (the control sequence a tick starts from, no noise) of the last
-  // remembered tick and of the tick at hand: what carries the furthest point from tick to tick
-  double anchor_ex = 0, anchor_ey = 0, cur_ex = 0, cur_ey = 0;
-  bool anchor_e_valid = false, cur_e_valid = false;
-  std::vector<float> anchor_px, anchor_py;
   // Optimizer::isHolonomic (optimizer.cpp:235).  A non-holonomic model is the Omni data path
   // with the vy noise, control_sequence.vy and state.vy[:,0] all zero: then state.vy = 0,
   // dx = vx cos - 0 sin, the vy gamma term and the weighted vy update are exactly 0 — what the

@@ -163,7 +163,7 @@ int smpc_group_optimize_some(smpc_group* g, const smpc_tick_in* ins, float* cons
     // furthest point, the completion polled, no Ackermann launch behind the reduction, one
     // non-colliding count
     const bool ok = c->cfg.iteration_count == 1 && !c->fail_in &&
-      !(c->cfg.flags & (SMPC_FLAG_NO_SPECULATION | SMPC_FLAG_PROFILE)) && (!need_f || c->hint_valid) &&
+      !(c->cfg.flags & (SMPC_FLAG_NO_SPECULATION | SMPC_FLAG_PROFILE)) && (!need_f || c->pred.hint_valid) &&
       c->knobs.poll && c->acker_r < 0.f && !c->two_coll_fp;
     if (!ok) continue;
     // (a near-goal member scores GoalAngle: instances of the lane pass the batched launch does not
@@ -250,7 +250,7 @@ int smpc_group_optimize_some(smpc_group* g, const smpc_tick_in* ins, float* cons
         if (rc != SMPC_OK) return rc;
       }
       SmpcFinal fin;
-      fill_score_args(c, flags[i], nullptr, nullptr, c->hint, true, nullptr, hd[j], fin);
+      fill_score_args(c, flags[i], nullptr, nullptr, c->pred.hint, true, nullptr, hd[j], fin);
       hr[j].partials = c->d_partials;
       hr[j].tuple = c->d_tuple;
       // (a wave member: its own grid — the blocks beyond it wrote nothing; the lane launch: every
@@ -303,14 +303,14 @@ int smpc_group_optimize_some(smpc_group* g, const smpc_tick_in* ins, float* cons
     const TickResult res = tick_result(c);
     const float F_true = res.F_local();
     const uint32_t S_true = smpc_furthest_index(F_true);
-    const bool miss = need_f && S_true != c->hint;
+    const bool miss = need_f && S_true != c->pred.hint;
     const bool all_collide = (flags[i] & (SD_OBSTACLES | SD_COST)) && res.non_colliding() == 0.0f;
     if (miss || all_collide) {
       if (miss) {
         c->spec_misses++;
         remember_furthest(c, &ins[i], F_true);   // smpc_optimize speculates with the true value now: one pass
-        c->hint_F = F_true;                      // (not the smoothed estimate a fresh-noise tick leaves)
-        c->hint_is_this_ticks = true;
+        c->pred.hint_F = F_true;                      // (not the smoothed estimate a fresh-noise tick leaves)
+        c->pred.hint_is_this_ticks = true;
       }
       rc = single(i);
       if (rc != SMPC_OK) return rc;

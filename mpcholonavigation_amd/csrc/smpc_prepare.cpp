@@ -110,11 +110,9 @@ static float distance_to_obstacle(const HostCostmap& m, float cost, bool using_f
 // CostCritic's per-cost term (cost_critic.cpp:141-155) instead of ObstaclesCritic's repulsion — the
 // first field keeps the shared collision marker and is otherwise zero — so that the lane pass's
 // lookup pipeline scores CostCritic as it stands; the wave pass reads only the marker then
-static void build_lut(const smpc_ctx* c, bool near_goal, SmpcLut* lut, bool consider_fp = false,
-               bool using_fp = false, const float* cost_terms = nullptr)
+static void build_lut(const HostCostmap& m, const smpc_obstacles_params& p, bool near_goal, SmpcLut* lut,
+                      bool consider_fp = false, bool using_fp = false, const float* cost_terms = nullptr)
 {
-  const auto& m = c->map;
-  const auto& p = c->critics.obstacles;
   for (int v = 0; v < 256; ++v) {
     lut[v].crit = 0.f;
     lut[v].rep = 0.f;
@@ -261,40 +259,40 @@ void remember_furthest(smpc_ctx* c, const smpc_tick_in* in, float F)
   static const bool trace = getenv("SMPC_TRACE_FURTHEST") != nullptr;
   if (trace)
     fprintf(stderr, "[smpc furthest] true %.3f predicted %.3f (geometry %.3f, valid %d, drift %.3f)\n", F,
-            c->hint_Fp + c->hint_drift, c->hint_Fp, (int)c->hint_Fp_valid, c->hint_drift);
+            c->pred.hint_Fp + c->pred.hint_drift, c->pred.hint_Fp, (int)c->pred.hint_Fp_valid, c->pred.hint_drift);
   // A tick scored with NEW noise (regenerate_noises = true) moves the extreme rollout by itself:
   // at 2 097 152 rollouts the true value jitters by +-0.5 of an index from epoch to epoch.  What
   // the last prediction missed is then mostly that jitter, not a trend: carrying it forward as
   // drift doubles it (observed: 1.55 scoring passes per tick).  Such ticks update a smoothed
   // estimate instead — the next prediction starts from F' + 0.4 (F - F'), F' the geometric
   // prediction of this tick — and leave the drift alone.
-  const bool fresh_noise = c->noise_gen != c->noise_gen_remembered;
-  c->noise_gen_remembered = c->noise_gen;
+  const bool fresh_noise = c->noise_gen != c->pred.noise_gen_remembered;
+  c->pred.noise_gen_remembered = c->noise_gen;
   float F_next = F;
-  if (c->hint_Fp_valid) {
-    const float d = F - c->hint_Fp;
+  if (c->pred.hint_Fp_valid) {
+    const float d = F - c->pred.hint_Fp;
     if (fresh_noise && std::fabs(d) < 2.f) {
-      F_next = c->hint_Fp + c->hint_drift + 0.4f * (F - (c->hint_Fp + c->hint_drift));
-      c->hint_drift *= 0.5f;
+      F_next = c->pred.hint_Fp + c->pred.hint_drift + 0.4f * (F - (c->pred.hint_Fp + c->pred.hint_drift));
+      c->pred.hint_drift *= 0.5f;
     } else {
-      c->hint_drift = std::fabs(d) < 2.f ? d : 0.f;
+      c->pred.hint_drift = std::fabs(d) < 2.f ? d : 0.f;
     }
   } else {
-    c->hint_drift = 0.f;
+    c->pred.hint_drift = 0.f;
   }
-  c->hint_Fp_valid = false;
-  c->hint_F = F_next;
-  c->hint = smpc_furthest_index(F_next);
-  c->hint_valid = true;
-  c->anchor_x = in->pose_x;
-  c->anchor_y = in->pose_y;
-  c->anchor_ex = c->cur_ex;
-  c->anchor_ey = c->cur_ey;
-  c->anchor_e_valid = c->cur_e_valid;
-  c->cur_e_valid = false;
-  c->anchor_px.assign(in->path_x, in->path_x + in->path_len);
-  c->anchor_py.assign(in->path_y, in->path_y + in->path_len);
-  c->anchor_valid = true;
+  c->pred.hint_Fp_valid = false;
+  c->pred.hint_F = F_next;
+  c->pred.hint = smpc_furthest_index(F_next);
+  c->pred.hint_valid = true;
+  c->pred.anchor_x = in->pose_x;
+  c->pred.anchor_y = in->pose_y;
+  c->pred.anchor_ex = c->pred.cur_ex;
+  c->pred.anchor_ey = c->pred.cur_ey;
+  c->pred.anchor_e_valid = c->pred.cur_e_valid;
+  c->pred.cur_e_valid = false;
+  c->pred.anchor_px.assign(in->path_x, in->path_x + in->path_len);
+  c->pred.anchor_py.assign(in->path_y, in->path_y + in->path_len);
+  c->pred.anchor_valid = true;
 }
 
 // The index a tick is first scored with.  Between two ticks the robot advances and the plan
@@ -338,26 +336,26 @@ void predict_hint(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
   // moves with the nominal endpoint — the robot's motion and the change of the control sequence
   // (a sequence still accelerating reaches further every tick, and stops doing so where it meets
   // the constraints: the kink a tick-to-tick drift estimate overshoots).
-  c->cur_e_valid = false;
+  c->pred.cur_e_valid = false;
   if (u_in) {
-    nominal_endpoint(c, in, u_in, c->cur_ex, c->cur_ey);
-    c->cur_e_valid = true;
+    nominal_endpoint(c, in, u_in, c->pred.cur_ex, c->pred.cur_ey);
+    c->pred.cur_e_valid = true;
   }
-  if (!c->hint_valid || !c->anchor_valid) return;
-  const uint32_t P0 = static_cast<uint32_t>(c->anchor_px.size()), P = in->path_len;
-  c->hint = smpc_furthest_index(c->hint_F);
-  if (c->hint_is_this_ticks) {
+  if (!c->pred.hint_valid || !c->pred.anchor_valid) return;
+  const uint32_t P0 = static_cast<uint32_t>(c->pred.anchor_px.size()), P = in->path_len;
+  c->pred.hint = smpc_furthest_index(c->pred.hint_F);
+  if (c->pred.hint_is_this_ticks) {
     // smpc_group_optimize re-runs a member whose prediction missed: hint_F is this very tick's
     // true value.  Score with it, and leave the drift as remember_furthest measured it.
-    c->hint_is_this_ticks = false;
-    c->hint_Fp = c->hint_F - c->hint_drift;
-    c->hint_Fp_valid = true;
+    c->pred.hint_is_this_ticks = false;
+    c->pred.hint_Fp = c->pred.hint_F - c->pred.hint_drift;
+    c->pred.hint_Fp_valid = true;
     return;
   }
-  c->hint_Fp_valid = false;
+  c->pred.hint_Fp_valid = false;
   if (P0 < 2 || P < 1) return;
-  const float* ox = c->anchor_px.data();
-  const float* oy = c->anchor_py.data();
+  const float* ox = c->pred.anchor_px.data();
+  const float* oy = c->pred.anchor_py.data();
   auto d2 = [](float ax, float ay, float bx, float by) {return (ax - bx) * (ax - bx) + (ay - by) * (ay - by);};
   // the old point the new plan starts at
   uint32_t k = 0;
@@ -372,7 +370,7 @@ void predict_hint(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
   const uint32_t kn = k + 1 < P0 ? k + 1 : k - 1;
   const float seg_k = d2(ox[k], oy[k], ox[kn], oy[kn]);
   if (!(best <= 0.0625f * seg_k)) return;   // not a pruned copy of the old plan: nothing to carry over
-  uint32_t S0 = c->hint;
+  uint32_t S0 = c->pred.hint;
   if (S0 >= P0) S0 = P0 - 1;
   const uint32_t Sn = S0 + 1 < P0 ? S0 + 1 : S0 - 1;
   const float sx = (S0 + 1 < P0 ? 1.f : -1.f) * (ox[Sn] - ox[S0]), sy = (S0 + 1 < P0 ? 1.f : -1.f) * (oy[Sn] - oy[S0]);
@@ -380,19 +378,19 @@ void predict_hint(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
   if (!(seg2 > 0.f)) return;
   // displacement along the plan at the furthest point, in segment lengths: of the nominal endpoint
   // when both ticks have one, else of the pose alone
-  const bool by_endpoint = c->cur_e_valid && c->anchor_e_valid;
-  const double dx = by_endpoint ? c->cur_ex - c->anchor_ex : in->pose_x - c->anchor_x;
-  const double dy = by_endpoint ? c->cur_ey - c->anchor_ey : in->pose_y - c->anchor_y;
+  const bool by_endpoint = c->pred.cur_e_valid && c->pred.anchor_e_valid;
+  const double dx = by_endpoint ? c->pred.cur_ex - c->pred.anchor_ex : in->pose_x - c->pred.anchor_x;
+  const double dy = by_endpoint ? c->pred.cur_ey - c->pred.anchor_ey : in->pose_y - c->pred.anchor_y;
   const float disp = static_cast<float>(dx * sx + dy * sy) / seg2;
   if (!(std::fabs(disp) < (by_endpoint ? 8.f : 4.f))) return;     // a jump, not a controller period's motion
-  const float Fp0 = c->hint_F + disp - static_cast<float>(k);   // carried by the geometry alone
-  const float Fp = Fp0 + c->hint_drift;                          // ... and by last tick's drift
-  c->hint_Fp = Fp0;
-  c->hint_Fp_valid = true;
+  const float Fp0 = c->pred.hint_F + disp - static_cast<float>(k);   // carried by the geometry alone
+  const float Fp = Fp0 + c->pred.hint_drift;                          // ... and by last tick's drift
+  c->pred.hint_Fp = Fp0;
+  c->pred.hint_Fp_valid = true;
   long h = std::lround(Fp);
   if (h < 0) h = 0;
   if (h > static_cast<long>(P) - 1) h = static_cast<long>(P) - 1;
-  c->hint = static_cast<uint32_t>(h);
+  c->pred.hint = static_cast<uint32_t>(h);
 }
 
 int check_tick(smpc_ctx* c, const smpc_tick_in* in)
@@ -411,8 +409,6 @@ int check_tick(smpc_ctx* c, const smpc_tick_in* in)
   return SMPC_OK;
 }
 
-// Everything the reference's critics decide once per tick on the host, plus the
-// upload of the tick block.  Leaves c->dev ready for the launches.
 // Which critics score this tick: membership in the critics list, and for the gated ones the
 // reference's withinPositionGoalTolerance test at the top of score().  Also the
 // number of PathAlign samples per trajectory.
@@ -495,7 +491,7 @@ static int tick_gates(smpc_ctx* c, const smpc_tick_in* in, uint32_t& gates_out, 
 
 // Path validity (utils::findPathCosts) and PathAlign's cumulative path lengths, into the tick
 // block: pvalid[P-1], D[P-1].
-static void path_tables(const smpc_ctx* c, const smpc_tick_in* in, uint32_t gates, const float* px,
+static void path_tables(const HostCostmap& map, const smpc_tick_in* in, uint32_t gates, const float* px,
                         const float* py, uint8_t* pvalid, float* D)
 {
   const uint32_t P = in->path_len;
@@ -507,12 +503,12 @@ static void path_tables(const smpc_ctx* c, const smpc_tick_in* in, uint32_t gate
     for (uint32_t i = 0; i < nseg; ++i) {
       unsigned mx, my;
       uint8_t v = 1;
-      if (!world_to_map(c->map, px[i], py[i], mx, my)) {
+      if (!world_to_map(map, px[i], py[i], mx, my)) {
         v = 0;
       } else {
-        const uint8_t cost = c->map.cells[static_cast<size_t>(my) * c->map.W + mx];
+        const uint8_t cost = map.cells[static_cast<size_t>(my) * map.W + mx];
         if (cost == SMPC_COST_LETHAL || cost == SMPC_COST_INSCRIBED) v = 0;
-        else if (cost == SMPC_COST_NO_INFORMATION) v = c->map.track_unknown ? 1 : 0;
+        else if (cost == SMPC_COST_NO_INFORMATION) v = map.track_unknown ? 1 : 0;
       }
       pvalid[i] = v;
     }
@@ -532,15 +528,13 @@ static void path_tables(const smpc_ctx* c, const smpc_tick_in* in, uint32_t gate
 
 }
 
-// Launch geometry of the tick: the costmap window staged in LDS (centred on the robot), the LDS
-// carve-up and persistent grid of the wave-per-rollout pass, which scoring mode the enabled
-// critics need, and whether — and how — the lane-per-rollout pass takes the tick.
-static int plan_launch(smpc_ctx* c, const smpc_tick_in* in, uint32_t gates, uint32_t nsamp, int& mode_out)
+// ---- the stages of plan_launch ---------------------------------------------------------------
+
+// The costmap window staged in LDS, centred on the robot: its corner and size into d, its bytes
+// returned (0: no collision critic scored, or no map).
+static uint32_t plan_window(const smpc_ctx* c, const smpc_tick_in* in, uint32_t gates, SmpcDev& d)
 {
-  const uint32_t T = c->cfg.time_steps, B = c->cfg.batch_size, P = in->path_len;
-  const auto& cr = c->critics;
-  const uint32_t step = cr.path_align.trajectory_point_step;
-  SmpcDev& d = c->dev;
+  const uint32_t T = c->cfg.time_steps;
   uint32_t window_bytes = 0;
   if (c->map.set && (gates & (SD_OBSTACLES | SD_COST))) {
     uint32_t side = 4;
@@ -573,18 +567,13 @@ static int plan_launch(smpc_ctx* c, const smpc_tick_in* in, uint32_t gates, uint
     d.win_w = static_cast<int32_t>(ww); d.win_h = static_cast<int32_t>(wh);
     window_bytes = ww * wh;
   }
-  PassPlan pl;
-  pl.wave.block = pass_block(c->R);
-  pl.wave.lds = make_lds(window_bytes, P, T, (pass_block(c->R) / 64), window_bytes != 0, nsamp);
-  if (pl.wave.lds.total > kLdsPerCu) return fail(c, SMPC_ERR_UNSUPPORTED, "LDS budget exceeded");
-  // room for the reduction inside the scoring launch (smpc_tail.h works in the launch's LDS) —
-  // only for contexts that run that experiment: for 128 < T <= 256 the padding would halve the
-  // wave pass's blocks per CU
-  if (c->knobs.fused_reduce) pl.wave.lds.total = std::max(pl.wave.lds.total, smpc_tail_lds_bytes(T));
+  return window_bytes;
+}
 
-  // persistent grid: as many blocks as stay resident, never more than the work
-  const uint32_t waves_per_block = (pass_block(c->R) / 64);
-  int mode_now = c->score_mode_for(cr);
+// The wave-pass MODE the tick's critics need.  Decides and writes nothing.
+static int wave_mode(uint32_t gates, const smpc_critic_params& cr, const Knobs& knobs)
+{
+  int mode_now = smpc_ctx::score_mode_for(cr);
   // the lean kernels: MODE 0 scores the north star's five away from the goal, MODE 3 also the
   // additive forms of Cost, Goal, Constraint, Twirling, PathAngle (the deployed list) and of the
   // near-goal GoalAngle term; MODE 4 is MODE 3 with the footprint check of the list's one collision
@@ -596,7 +585,7 @@ static int plan_launch(smpc_ctx* c, const smpc_tick_in* in, uint32_t gates, uint
   // batch.  SMPC_FOOTPRINT_PASS=general keeps footprint ticks on the general pass.
   const uint32_t fp_gates = SD_FP_OBSTACLES | SD_FP_COST;
   const uint32_t lean_extra = SD_CONSTRAINT | SD_COST | SD_GOAL | SD_TWIRLING | SD_PATH_ANGLE | SD_GOAL_ANGLE;
-  const bool fp_general = c->knobs.footprint_general || ((gates & SD_OBSTACLES) && (gates & SD_COST));
+  const bool fp_general = knobs.footprint_general || ((gates & SD_OBSTACLES) && (gates & SD_COST));
   if (gates & (SD_STORE_TRAJ | SD_USE_PATH_YAW | (SD_EXTRA_CRITICS & ~(lean_extra | fp_gates)))) {
     mode_now = 2;
   } else if ((gates & fp_gates) && fp_general) {
@@ -608,6 +597,23 @@ static int plan_launch(smpc_ctx* c, const smpc_tick_in* in, uint32_t gates, uint
       (!(gates & SD_GOAL_ANGLE) || cr.goal_angle.cost_power == 1);
     mode_now = (mode_now == 0 && unit_powers) ? ((gates & fp_gates) ? 4 : 3) : 2;
   }
+  return mode_now;
+}
+
+// The wave-per-rollout pass: planned for every tick.  Its LDS carve-up and persistent grid.
+static int plan_wave(smpc_ctx* c, uint32_t window_bytes, uint32_t P, uint32_t nsamp, int mode_now, PassPlan& pl)
+{
+  const uint32_t T = c->cfg.time_steps, B = c->cfg.batch_size;
+  pl.wave.block = pass_block(c->R);
+  pl.wave.lds = make_lds(window_bytes, P, T, (pass_block(c->R) / 64), window_bytes != 0, nsamp);
+  if (pl.wave.lds.total > kLdsPerCu) return fail(c, SMPC_ERR_UNSUPPORTED, "LDS budget exceeded");
+  // room for the reduction inside the scoring launch (smpc_tail.h works in the launch's LDS) —
+  // only for contexts that run that experiment: for 128 < T <= 256 the padding would halve the
+  // wave pass's blocks per CU
+  if (c->knobs.fused_reduce) pl.wave.lds.total = std::max(pl.wave.lds.total, smpc_tail_lds_bytes(T));
+
+  // persistent grid: as many blocks as stay resident, never more than the work
+  const uint32_t waves_per_block = (pass_block(c->R) / 64);
   const WaveInst* wave = wave_select(c->R, mode_now, T);
   if (!wave) return fail(c, SMPC_ERR_UNSUPPORTED, "no instance of the wave-per-rollout pass for this horizon");
   uint32_t per_cu = std::min(c->occ_wave.get(wave->fn, pl.wave.block, pl.wave.lds.total), 32u / waves_per_block);
@@ -615,107 +621,139 @@ static int plan_launch(smpc_ctx* c, const smpc_tick_in* in, uint32_t gates, uint
   uint32_t grid = std::min((B + waves_per_block - 1) / waves_per_block,
                            static_cast<uint32_t>(c->num_cu) * per_cu);
   pl.wave.grid = std::max(1u, std::min(grid, kMaxGrid));
+  return SMPC_OK;
+}
 
-  // The lane-per-rollout pass takes the tick when the kernels score with unit cost powers (MODE 0
-  // or 3) and lane_select has an instance for the gates: the north star's five, with the near-goal
-  // GoalAngle term (ObstaclesCritic scored, T <= 64), or with the deployed list's Constraint / Cost /
-  // Twirling on a cruise tick (T = 64 or the default 56).  Known to the host only: PathAngle must
-  // be inside its angle for every candidate furthest point (it then adds nothing), and the lane
-  // pass samples PathAlign's trajectory points at the first step of every quad
-  // (trajectory_point_step = 4, the reference's default: path_align_critic.cpp:36).
-  // The re-read form (no parked controls) is the only one for T > 64; SMPC_LANE_REREAD=1 selects
-  // it for T <= 64 too (experiments) where it has an instance.
-  pl.rr = (T > 64 || c->knobs.lane_reread) && lane_select(gates, T, true, false, c->acker_r, false) != nullptr;
-  bool lane_now = c->use_tpr && (mode_now == 0 || mode_now == 3) && T <= kLaneMaxT &&
+// The lane-per-rollout pass takes the tick when the kernels score with unit cost powers (MODE 0
+// or 3) and lane_select has an instance for the gates: the north star's five, with the near-goal
+// GoalAngle term (ObstaclesCritic scored, T <= 64), or with the deployed list's Constraint / Cost /
+// Twirling on a cruise tick (T = 64 or the default 56).  Known to the host only: PathAngle must
+// be inside its angle for every candidate furthest point (it then adds nothing), and the lane
+// pass samples PathAlign's trajectory points at the first step of every quad
+// (trajectory_point_step = 4, the reference's default: path_align_critic.cpp:36).
+static bool lane_eligible(const smpc_ctx* c, uint32_t gates, int mode_now, uint32_t step)
+{
+  const uint32_t T = c->cfg.time_steps;
+  return c->use_tpr && (mode_now == 0 || mode_now == 3) && T <= kLaneMaxT &&
     lane_select(gates, T, T > 64, false, c->acker_r, false) != nullptr &&
     !((gates & SD_PATH_ANGLE) && c->pang_any) && !((gates & SD_PATH_ALIGN) && step != 4);
-  // A cost_power other than 1 among the five critics (near the goal: GoalAngle's too) puts the tick
-  // in MODE 2.  When that power is the ONLY reason — no trajectory write-out, no path orientations,
-  // no critic beyond the five — the tick still takes the lane pass, on the rows of
-  // smpc_pass_lane_pow (parking form: T <= 64, trajectory_point_step 4), which apply each power to
-  // its critic's per-rollout total in the epilogue.  From kLaneMinBatch rollouts up only, also for
-  // a context that asks for the lane pass (SMPC_FLAG_LANE_PER_ROLLOUT, SMPC_PASS=lane): that is the
-  // crossover below which the lane pass loses to the wave pass, and the power rows have not been
-  // measured below it.  Never the split or the re-read form.
-  pl.pow = mode_now == 2 && c->score_mode_for(cr) == 2 && c->use_tpr && !pl.rr && T <= 64 && step == 4 &&
+}
+
+// The re-read form (no parked controls) is the only one for T > 64; SMPC_LANE_REREAD=1 selects
+// it for T <= 64 too (experiments) where it has an instance.
+static bool lane_reread_form(const smpc_ctx* c, uint32_t gates)
+{
+  const uint32_t T = c->cfg.time_steps;
+  return (T > 64 || c->knobs.lane_reread) && lane_select(gates, T, true, false, c->acker_r, false) != nullptr;
+}
+
+// A cost_power other than 1 among the five critics (near the goal: GoalAngle's too) puts the tick
+// in MODE 2.  When that power is the ONLY reason — no trajectory write-out, no path orientations,
+// no critic beyond the five — the tick still takes the lane pass, on the rows of
+// smpc_pass_lane_pow (parking form: T <= 64, trajectory_point_step 4), which apply each power to
+// its critic's per-rollout total in the epilogue.  From kLaneMinBatch rollouts up only, also for
+// a context that asks for the lane pass (SMPC_FLAG_LANE_PER_ROLLOUT, SMPC_PASS=lane): that is the
+// crossover below which the lane pass loses to the wave pass, and the power rows have not been
+// measured below it.  Never the split or the re-read form.
+static bool lane_power_rows(const smpc_ctx* c, uint32_t gates, int mode_now, uint32_t step, bool rr)
+{
+  const uint32_t T = c->cfg.time_steps, B = c->cfg.batch_size;
+  return mode_now == 2 && c->score_mode_for(c->critics) == 2 && c->use_tpr && !rr && T <= 64 && step == 4 &&
     B >= kLaneMinBatch && !(gates & (SD_STORE_TRAJ | SD_USE_PATH_YAW | SD_EXTRA_CRITICS)) &&
     lane_select(gates, T, false, false, c->acker_r, true) != nullptr;
-  if (pl.pow) lane_now = true;
-  if (lane_now) {
-    pl.window_bytes = window_bytes;
-    pl.lane.lds = lane_lds(window_bytes, P, T, pl.rr);
-    if (pl.lane.lds.total > kLdsPerCu) lane_now = false;   // long paths: the parked wz no longer fits
-    // (the re-read form: no in-launch reduction, smpc_lane.hip)
-    if (!pl.rr && c->knobs.fused_reduce) pl.lane.lds.total = std::max(pl.lane.lds.total, smpc_tail_lds_bytes(T));
-  }
-  if (lane_now) {
-    const uint32_t lblock = pl.rr ? smpc_lane_block_rr() : smpc_lane_block();
-    uint32_t occ_blocks = c->occ_lane.get(lane_occupancy_row(T, pl.rr)->fn, lblock, pl.lane.lds.total);
-    if (pl.rr) occ_blocks = std::min(occ_blocks, 3u);   // (four-wave blocks: launch bounds of three waves per SIMD)
-    const uint32_t groups = (B + 63) / 64;
-    uint32_t wpb = lblock / 64;
-    pl.lane.block = lblock;
-    // Small batches: when every group can have a SIMD to itself (at most four groups per CU),
-    // blocks of four waves, one per CU.  Two waves on a SIMD share its VALU and each runs its
-    // group in 22.5 us; a wave alone runs it in 20.5 (tools/lane_timeline.py) — and a batch
-    // this small is one group per wave anyway: -2 us per tick at 65 536 x 64.
-    if (!pl.rr && c->knobs.half_blocks && !c->in_group && groups <= static_cast<uint32_t>(c->num_cu) * 4u) {
-      wpb = 4;
-      pl.lane.block = 256;
-    }
-    uint32_t g = std::min((groups + wpb - 1) / wpb, static_cast<uint32_t>(c->num_cu) * occ_blocks);
-    g = std::max(1u, std::min(g, kMaxGrid));
-    // Every wave takes whole groups, so a launch lasts ceil(groups / waves) group-times whatever
-    // the remainder: launch only the waves that fill every round, and — where several blocks fit
-    // a CU — pad the launch's LDS so that the dispatcher cannot stack them unevenly.  (Built for
-    // the re-read form's first shape, four-wave blocks at three per CU: 4096 groups on 3072 waves;
-    // with the eight-wave blocks it has now the grid is one block per CU and this trims nothing
-    // at the benchmarked sizes.  SMPC_NO_BALANCED_GRID=1: off.)
-    if (pl.rr && c->knobs.balanced_grid) {
-      const uint32_t waves = g * wpb;
-      const uint32_t rounds = (groups + waves - 1) / waves;
-      const uint32_t need = (groups + rounds - 1) / rounds;
-      const uint32_t g2 = (need + wpb - 1) / wpb;
-      const uint32_t per_cu = (g2 + c->num_cu - 1) / static_cast<uint32_t>(c->num_cu);
-      if (g2 < g && per_cu < occ_blocks) {
-        g = g2;
-        const uint32_t pad = align_up(kLdsPerCu / (per_cu + 1) + 1024u, 16);
-        if (pad <= kLdsPerCu / per_cu) pl.lane.lds.total = std::max(pl.lane.lds.total, pad);
-      }
-    }
-    pl.lane.grid = g;
-    // window-relative float cell index and its guard band.  The pass forms
-    //   q~ = fma(ax, (1/res)_f, cxf),   cxf = ((x0 - window corner) / res)_f
-    // from the accumulated displacement ax; the reference truncates
-    //   Q = ((double)x - origin) / res - win_x0,   x = (float)(x0 + (double)ax).
-    // |q~ - Q| is at most: the rounding of x to float, (1/2) ulp(|x|) / res with |x| inside the
-    // window (lanes outside it never take the fast path); three float roundings of quantities
-    // no larger than the window (the two constants' images and the fma's own); and the rounding
-    // of the window corner origin + win0 * res in double.
-    const double rinv = 1.0 / c->map.res;
-    const double wx = c->map.ox + static_cast<double>(d.win_x0) * c->map.res;
-    const double wy = c->map.oy + static_cast<double>(d.win_y0) * c->map.res;
-    d.wxf = static_cast<float>(wx);
-    d.wyf = static_cast<float>(wy);
-    d.cxf = static_cast<float>((in->pose_x - wx) * rinv);
-    d.cyf = static_cast<float>((in->pose_y - wy) * rinv);
-    const double ext_x = static_cast<double>(d.win_w + 1) * c->map.res, ext_y = static_cast<double>(d.win_h + 1) * c->map.res;
-    const double xmax = std::max(std::max(std::fabs(wx - c->map.res), std::fabs(wx + ext_x)),
-                                 std::max(std::fabs(wy - c->map.res), std::fabs(wy + ext_y)));
-    const double u24 = 5.9604644775390625e-08;   // 2^-24
-    const double e_c = 2.3e-16 * (std::fabs(wx) + std::fabs(wy) + 1.0);
-    const double qmax = static_cast<double>(std::max(d.win_w, d.win_h)) + 2.0;
-    const double eps = 2.0 * (u24 * xmax * rinv + 3.0 * u24 * qmax + e_c * rinv) + 1e-7;
-    d.cell_eps_w = static_cast<float>(std::min(eps, 0.5));
-  }
+}
 
-  // Small batches at T = 64: while the waves of smpc_pass_split (16 rollouts, four lanes each) have
-  // at most two groups each, the horizon split over four lanes runs the tick's one scoring pass in
-  // a fraction of a 64-step chain (65 536 x 64: one wave per SIMD on the lane pass).  The plain five
-  // critics only; the geometry above (window, cell index constants) is shared.
+// The lane pass's cell lookup: window-relative float cell index and its guard band, into d (the
+// window itself is plan_window's).  The pass forms
+//   q~ = fma(ax, (1/res)_f, cxf),   cxf = ((x0 - window corner) / res)_f
+// from the accumulated displacement ax; the reference truncates
+//   Q = ((double)x - origin) / res - win_x0,   x = (float)(x0 + (double)ax).
+// |q~ - Q| is at most: the rounding of x to float, (1/2) ulp(|x|) / res with |x| inside the
+// window (lanes outside it never take the fast path); three float roundings of quantities
+// no larger than the window (the two constants' images and the fma's own); and the rounding
+// of the window corner origin + win0 * res in double.
+// (cell_eps_w; the wave pass's guard band cell_eps has other terms: fill_dev_state)
+static void lane_cell_constants(const HostCostmap& map, const smpc_tick_in* in, SmpcDev& d)
+{
+  const double rinv = 1.0 / map.res;
+  const double wx = map.ox + static_cast<double>(d.win_x0) * map.res;
+  const double wy = map.oy + static_cast<double>(d.win_y0) * map.res;
+  d.wxf = static_cast<float>(wx);
+  d.wyf = static_cast<float>(wy);
+  d.cxf = static_cast<float>((in->pose_x - wx) * rinv);
+  d.cyf = static_cast<float>((in->pose_y - wy) * rinv);
+  const double ext_x = static_cast<double>(d.win_w + 1) * map.res, ext_y = static_cast<double>(d.win_h + 1) * map.res;
+  const double xmax = std::max(std::max(std::fabs(wx - map.res), std::fabs(wx + ext_x)),
+                               std::max(std::fabs(wy - map.res), std::fabs(wy + ext_y)));
+  const double u24 = 5.9604644775390625e-08;   // 2^-24
+  const double e_c = 2.3e-16 * (std::fabs(wx) + std::fabs(wy) + 1.0);
+  const double qmax = static_cast<double>(std::max(d.win_w, d.win_h)) + 2.0;
+  const double eps = 2.0 * (u24 * xmax * rinv + 3.0 * u24 * qmax + e_c * rinv) + 1e-7;
+  d.cell_eps_w = static_cast<float>(std::min(eps, 0.5));
+}
+
+// The lane pass's LDS, block and grid into pl, its cell-index constants into c->dev.  False: the
+// pass does not fit (long paths: the parked wz no longer fits) and the tick takes the wave pass.
+static bool plan_lane(smpc_ctx* c, const smpc_tick_in* in, uint32_t window_bytes, PassPlan& pl)
+{
+  const uint32_t T = c->cfg.time_steps, B = c->cfg.batch_size, P = in->path_len;
+  pl.window_bytes = window_bytes;
+  pl.lane.lds = lane_lds(window_bytes, P, T, pl.rr);
+  const bool fits = pl.lane.lds.total <= kLdsPerCu;
+  // (the re-read form: no in-launch reduction, smpc_lane.hip)
+  if (!pl.rr && c->knobs.fused_reduce) pl.lane.lds.total = std::max(pl.lane.lds.total, smpc_tail_lds_bytes(T));
+  if (!fits) return false;
+  const uint32_t lblock = pl.rr ? smpc_lane_block_rr() : smpc_lane_block();
+  uint32_t occ_blocks = c->occ_lane.get(lane_occupancy_row(T, pl.rr)->fn, lblock, pl.lane.lds.total);
+  if (pl.rr) occ_blocks = std::min(occ_blocks, 3u);   // (four-wave blocks: launch bounds of three waves per SIMD)
+  const uint32_t groups = (B + 63) / 64;
+  uint32_t wpb = lblock / 64;
+  pl.lane.block = lblock;
+  // Small batches: when every group can have a SIMD to itself (at most four groups per CU),
+  // blocks of four waves, one per CU.  Two waves on a SIMD share its VALU and each runs its
+  // group in 22.5 us; a wave alone runs it in 20.5 (tools/lane_timeline.py) — and a batch
+  // this small is one group per wave anyway: -2 us per tick at 65 536 x 64.
+  if (!pl.rr && c->knobs.half_blocks && !c->in_group && groups <= static_cast<uint32_t>(c->num_cu) * 4u) {
+    wpb = 4;
+    pl.lane.block = 256;
+  }
+  uint32_t g = std::min((groups + wpb - 1) / wpb, static_cast<uint32_t>(c->num_cu) * occ_blocks);
+  g = std::max(1u, std::min(g, kMaxGrid));
+  // Every wave takes whole groups, so a launch lasts ceil(groups / waves) group-times whatever
+  // the remainder: launch only the waves that fill every round, and — where several blocks fit
+  // a CU — pad the launch's LDS so that the dispatcher cannot stack them unevenly.  (Built for
+  // the re-read form's first shape, four-wave blocks at three per CU: 4096 groups on 3072 waves;
+  // with the eight-wave blocks it has now the grid is one block per CU and this trims nothing
+  // at the benchmarked sizes.  SMPC_NO_BALANCED_GRID=1: off.)
+  if (pl.rr && c->knobs.balanced_grid) {
+    const uint32_t waves = g * wpb;
+    const uint32_t rounds = (groups + waves - 1) / waves;
+    const uint32_t need = (groups + rounds - 1) / rounds;
+    const uint32_t g2 = (need + wpb - 1) / wpb;
+    const uint32_t per_cu = (g2 + c->num_cu - 1) / static_cast<uint32_t>(c->num_cu);
+    if (g2 < g && per_cu < occ_blocks) {
+      g = g2;
+      const uint32_t pad = align_up(kLdsPerCu / (per_cu + 1) + 1024u, 16);
+      if (pad <= kLdsPerCu / per_cu) pl.lane.lds.total = std::max(pl.lane.lds.total, pad);
+    }
+  }
+  pl.lane.grid = g;
+  lane_cell_constants(c->map, in, c->dev);
+  return true;
+}
+
+// Small batches at T = 64: while the waves of smpc_pass_split (16 rollouts, four lanes each) have
+// at most two groups each, the horizon split over four lanes runs the tick's one scoring pass in
+// a fraction of a 64-step chain (65 536 x 64: one wave per SIMD on the lane pass).  The plain five
+// critics only; the lane pass's geometry (window, cell index constants) is shared.  For a tick
+// the lane pass takes; true: the split pass takes it instead, its LDS, block and grid in pl.
+static bool plan_split(smpc_ctx* c, uint32_t gates, int mode_now, uint32_t step, uint32_t window_bytes, uint32_t P,
+                       PassPlan& pl)
+{
+  const uint32_t T = c->cfg.time_steps, B = c->cfg.batch_size;
   const bool force_split = c->knobs.pass == Knobs::kSplit;
   bool split_now = false;
-  if (lane_now && !pl.rr && mode_now == 0 && T >= 36 && !c->in_group && !c->knobs.no_split && !c->knobs.fused_reduce &&
+  if (!pl.rr && mode_now == 0 && T >= 36 && !c->in_group && !c->knobs.no_split && !c->knobs.fused_reduce &&
       (!c->lane_forced || force_split)) {
     // (a context that ASKS for the lane pass — SMPC_FLAG_LANE_PER_ROLLOUT, SMPC_PASS=lane — gets it)
     // one block per CU (two waves per SIMD: the kernel's registers), and ONE group per wave: four
@@ -748,6 +786,53 @@ static int plan_launch(smpc_ctx* c, const smpc_tick_in* in, uint32_t gates, uint
       }
     }
   }
+  return split_now;
+}
+
+// DiffDrive and Ackermann: vy is zero at every step, and the Omni-form rows read a zero-filled
+// noise tensor and carry zeros through the rotation, the gamma sum, 64 parked registers and a
+// transpose-reduce per group.  A tick that would run a PLAIN lane row anyway — lean MODE 0 with
+// ObstaclesCritic scored, no GoalAngle term, no deployed-list critic, no cost power, the parking
+// form in whole quads, one context — runs that row's twin of smpc_pass_lane_nh, which has no vy
+// (same grid, block, LDS and group order: the geometry planned above; same results, DESIGN.md
+// 4.2d).  From kLaneMinBatch rollouts up only, also for a context that asks for the lane pass
+// (SMPC_FLAG_LANE_PER_ROLLOUT, SMPC_PASS=lane): nothing about these rows is measured below it.
+// Every other tick of such a model keeps the Omni-form instance it had.  SMPC_NONHOLO_PASS=omni:
+// the Omni-form rows for these ticks too.
+static bool lane_nonholonomic_rows(const smpc_ctx* c, uint32_t gates, int mode_now, uint32_t step, const PassPlan& pl,
+                                   bool lane_now, bool split_now)
+{
+  const uint32_t T = c->cfg.time_steps, B = c->cfg.batch_size;
+  return !c->holonomic && !c->knobs.nonholo_omni && lane_now && !split_now && mode_now == 0 && !pl.pow && !pl.rr &&
+    !c->in_group && step == 4 && T <= 64 && (T & 3u) == 0 && B >= kLaneMinBatch &&
+    [&] {
+      const LaneInst* k = lane_select(gates, T, false, false, c->acker_r, false, true);
+      return k && k->nh;
+    }();
+}
+
+// Launch geometry of the tick: the costmap window staged in LDS (centred on the robot), the LDS
+// carve-up and persistent grid of the wave-per-rollout pass, which scoring mode the enabled
+// critics need, and whether — and how — the lane-per-rollout pass takes the tick.  Reads
+// c->pang_any (prepare_tick's PathAngle gates) and writes, into the c->dev prepare_tick has filled,
+// the window (plan_window) and wxf / cxf / cell_eps_w (lane_cell_constants).  c->plan, which the
+// NEXT tick's prune-table decision reads, is written only when everything succeeded.
+static int plan_launch(smpc_ctx* c, const smpc_tick_in* in, uint32_t gates, uint32_t nsamp, int& mode_out)
+{
+  const uint32_t B = c->cfg.batch_size, P = in->path_len;
+  const uint32_t step = c->critics.path_align.trajectory_point_step;
+  const uint32_t window_bytes = plan_window(c, in, gates, c->dev);
+  const int mode_now = wave_mode(gates, c->critics, c->knobs);
+  PassPlan pl;
+  const int rc = plan_wave(c, window_bytes, P, nsamp, mode_now, pl);
+  if (rc != SMPC_OK) return rc;
+
+  pl.rr = lane_reread_form(c, gates);
+  bool lane_now = lane_eligible(c, gates, mode_now, step);
+  pl.pow = lane_power_rows(c, gates, mode_now, step, pl.rr);
+  if (pl.pow) lane_now = true;
+  if (lane_now) lane_now = plan_lane(c, in, window_bytes, pl);
+  const bool split_now = lane_now && plan_split(c, gates, mode_now, step, window_bytes, P, pl);
 
   // below kLaneMinBatch the lane pass itself loses to the wave pass (one group per CU's worth of
   // waves: crossover measured at ~50 k rollouts); such contexts keep the group-major noise only
@@ -755,74 +840,71 @@ static int plan_launch(smpc_ctx* c, const smpc_tick_in* in, uint32_t gates, uint
   if (lane_now && !split_now && B < kLaneMinBatch && !c->lane_forced) lane_now = false;
 
   pl.pow = pl.pow && lane_now;   // (a path too long for the lane pass's LDS: the wave pass after all)
-  // DiffDrive and Ackermann: vy is zero at every step, and the Omni-form rows read a zero-filled
-  // noise tensor and carry zeros through the rotation, the gamma sum, 64 parked registers and a
-  // transpose-reduce per group.  A tick that would run a PLAIN lane row anyway — lean MODE 0 with
-  // ObstaclesCritic scored, no GoalAngle term, no deployed-list critic, no cost power, the parking
-  // form in whole quads, one context — runs that row's twin of smpc_pass_lane_nh, which has no vy
-  // (same grid, block, LDS and group order: the geometry planned above; same results, DESIGN.md
-  // 4.2d).  From kLaneMinBatch rollouts up only, also for a context that asks for the lane pass
-  // (SMPC_FLAG_LANE_PER_ROLLOUT, SMPC_PASS=lane): nothing about these rows is measured below it.
-  // Every other tick of such a model keeps the Omni-form instance it had.  SMPC_NONHOLO_PASS=omni:
-  // the Omni-form rows for these ticks too.
-  pl.nh = !c->holonomic && !c->knobs.nonholo_omni && lane_now && !split_now && mode_now == 0 && !pl.pow && !pl.rr &&
-    !c->in_group && step == 4 && T <= 64 && (T & 3u) == 0 && B >= kLaneMinBatch &&
-    [&] {
-      const LaneInst* k = lane_select(gates, T, false, false, c->acker_r, false, true);
-      return k && k->nh;
-    }();
+  pl.nh = lane_nonholonomic_rows(c, gates, mode_now, step, pl, lane_now, split_now);
   pl.kind = split_now ? PassPlan::kSplit : (lane_now ? PassPlan::kLane : PassPlan::kWave);
   c->plan = pl;
   mode_out = mode_now;
   return SMPC_OK;
 }
 
-int prepare_tick(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
+// ---- the stages of prepare_tick --------------------------------------------------------------
+// The table builders among them take plain arrays, a critic's parameters and the costmap, never
+// the context.
+
+// the tick block's regions in its host copy (TickLayout's offsets as typed pointers)
+struct TickBlock {
+  uint8_t* h;
+  float *px, *py, *pyaw, *D;
+  uint32_t* pf_idx;
+  uint8_t *pvalid, *pa_active, *pang_active, *pal_active;
+  float *lut_cost, *prune;
+};
+static TickBlock tick_block(uint8_t* h, const TickLayout& tl)
 {
-  int rc = check_tick(c, in);
-  if (rc != SMPC_OK) return rc;
-  if (!u_in) return fail(c, SMPC_ERR_INVALID, "control sequence missing");
-  rc = absorb_redraw(c);   // noise drawn in the background since the last tick, if any
-  if (rc != SMPC_OK) return rc;
-  const uint32_t T = c->cfg.time_steps, B = c->cfg.batch_size, P = in->path_len;
-  const auto& cr = c->critics;
-  HIPCK(c, hipSetDevice(c->device));
+  TickBlock b{};
+  b.h = h;
+  b.px = reinterpret_cast<float*>(h + tl.px);
+  b.py = reinterpret_cast<float*>(h + tl.py);
+  b.pyaw = reinterpret_cast<float*>(h + tl.pyaw);
+  b.D = reinterpret_cast<float*>(h + tl.D);
+  b.pf_idx = reinterpret_cast<uint32_t*>(h + tl.pf_idx);
+  b.pvalid = h + tl.pvalid;
+  b.pa_active = h + tl.pa_active;
+  b.pang_active = h + tl.pang_active;
+  b.pal_active = h + tl.pal_active;
+  b.lut_cost = reinterpret_cast<float*>(h + tl.lut_cost);
+  b.prune = reinterpret_cast<float*>(h + tl.prune);
+  return b;
+}
 
-  const TickLayout tl = tick_layout(T, std::max(P, 1u));
-  if (tl.total > c->tick_cap) return fail(c, SMPC_ERR_INVALID, "tick block overflow");
-  uint8_t* h = c->h_tick;
+// the control sequence (vy row zeroed for a non-holonomic model) and the plan into the tick block
+static void copy_plan(const TickBlock& b, const TickLayout& tl, const smpc_tick_in* in, const float* u_in, uint32_t T,
+                      bool holonomic)
+{
+  const uint32_t P = in->path_len;
+  uint8_t* h = b.h;
   memcpy(h + tl.u, u_in, 3 * T * sizeof(float));
-  if (!c->holonomic) memset(h + tl.u + T * sizeof(float), 0, T * sizeof(float));
-  float* px = reinterpret_cast<float*>(h + tl.px);
-  float* py = reinterpret_cast<float*>(h + tl.py);
-  float* pyaw = reinterpret_cast<float*>(h + tl.pyaw);
-  float* D = reinterpret_cast<float*>(h + tl.D);
-  uint32_t* pf_idx = reinterpret_cast<uint32_t*>(h + tl.pf_idx);
-  uint8_t* pvalid = h + tl.pvalid;
-  uint8_t* pa_active = h + tl.pa_active;
+  if (!holonomic) memset(h + tl.u + T * sizeof(float), 0, T * sizeof(float));
   if (P) {
-    memcpy(px, in->path_x, P * 4);
-    memcpy(py, in->path_y, P * 4);
-    memcpy(pyaw, in->path_yaw, P * 4);
+    memcpy(b.px, in->path_x, P * 4);
+    memcpy(b.py, in->path_y, P * 4);
+    memcpy(b.pyaw, in->path_yaw, P * 4);
   }
+}
 
-  uint32_t gates = 0, nsamp = 0;
-  rc = tick_gates(c, in, gates, nsamp);
-  if (rc != SMPC_OK) return rc;
-  const double rx = in->pose_x, ry = in->pose_y, gx = in->goal_x, gy = in->goal_y;
-  // (PathAlignLegacy alone: its own step — tick_gates refuses two different ones)
-  const uint32_t step = (gates & SD_PATH_ALIGN) || !(gates & SD_PATH_ALIGN_LEGACY) ? cr.path_align.trajectory_point_step
-                                                                                    : cr.path_align_legacy.trajectory_point_step;
-  path_tables(c, in, gates, px, py, pvalid, D);
-
-  // ---- per-candidate-furthest-point tables -------------------------------------
+// the robot's state as the kernels take it, the first rollout point and the cost under it
+struct FirstPoint {
+  float yaw0, cos0, sin0, svx, svy, swz, x00, y00;
+  uint32_t cost_t0;
+};
+static FirstPoint first_point(const smpc_tick_in* in, bool holonomic, float dt, const HostCostmap& map)
+{
   const float yaw0 = in->pose_yaw;
   const float cos0 = cosf(yaw0), sin0 = sinf(yaw0);
   const float svx = static_cast<float>(in->speed_vx);
   // state.vy[:,0] = speed.linear.y only if holonomic (optimizer.cpp:264-266)
-  const float svy = c->holonomic ? static_cast<float>(in->speed_vy) : 0.f;
+  const float svy = holonomic ? static_cast<float>(in->speed_vy) : 0.f;
   const float swz = static_cast<float>(in->speed_wz);
-  const float dt = c->cfg.model_dt;
   // trajectories(0,0): first rollout point, identical for every rollout because
   // v[:,0] is the measured speed (optimizer.cpp:258-267,331-342)
   const float dx0 = svx * cos0 - svy * sin0;
@@ -830,128 +912,161 @@ int prepare_tick(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
   const float x00 = static_cast<float>(in->pose_x + static_cast<double>(dx0 * dt));
   const float y00 = static_cast<float>(in->pose_y + static_cast<double>(dy0 * dt));
   uint32_t cost_t0 = SMPC_COST_NO_INFORMATION;   // costAtPose of that point (obstacles_critic.cpp:203-212)
-  if (c->map.set) {
+  if (map.set) {
     unsigned mx, my;
-    if (world_to_map(c->map, x00, y00, mx, my))
-      cost_t0 = c->map.cells[static_cast<size_t>(my) * c->map.W + mx];
+    if (world_to_map(map, x00, y00, mx, my))
+      cost_t0 = map.cells[static_cast<size_t>(my) * map.W + mx];
   }
-  // PathAlignCritic's and PathAlignLegacyCritic's gate per candidate furthest point S
-  // (path_align_critic.cpp:58-74, path_align_legacy_critic.cpp:56-72: the same code)
-  auto occupancy_gate = [&](const smpc_path_align_params& q, uint8_t* active) {
-    // utils::findPathTrajectoryInitialPoint (tools/utils.hpp:327-344)
-    size_t init = 0;
-    float best = std::numeric_limits<float>::max();
-    for (uint32_t j = 0; j < P; ++j) {
-      const float ddx = px[j] - x00, ddy = py[j] - y00;
-      const float d = ddx * ddx + ddy * ddy;
-      if (d < best) {
-        best = d;
-        init = j;
-      }
-    }
-    // occupancy of the path between the initial and the furthest point.  The reference
-    // walks i = init..S-1 with a running count of invalid points and stops at the first i where
-    // count / range > ratio and count > 2; the count only grows and range is fixed per S, so
-    // that happens iff it holds for the final count: prefix sums, O(P).
-    std::vector<uint32_t> inval(P + 1, 0);
-    for (uint32_t i = 0; i < P; ++i) inval[i + 1] = inval[i] + ((i + 1 < P && !pvalid[i]) ? 1u : 0u);
-    for (uint32_t S = 0; S < P; ++S) {
-      bool on = S >= q.offset_from_furthest;
-      if (on && S > init) {
-        const unsigned int invalid_ctr = inval[S] - inval[init];
-        const float range = static_cast<float>(static_cast<size_t>(S) - init);
-        if (static_cast<float>(invalid_ctr) / range > q.max_path_occupancy_ratio && invalid_ctr > 2) on = false;
-      }
-      active[S] = on ? 1 : 0;
-    }
-  };
-  if (gates & SD_PATH_ALIGN) occupancy_gate(cr.path_align, pa_active);
-  else memset(pa_active, 0, std::max(P, 1u));
-  uint8_t* pal_active = h + tl.pal_active;
-  if (gates & SD_PATH_ALIGN_LEGACY) occupancy_gate(cr.path_align_legacy, pal_active);
-  else memset(pal_active, 0, std::max(P, 1u));
-  if (gates & SD_PATH_FOLLOW) {
-    // path_follow_critic.cpp:46-57
-    const size_t path_size = P - 1;
-    for (uint32_t S = 0; S < P; ++S) {
-      size_t idx = std::min(static_cast<size_t>(S) + cr.path_follow.offset_from_furthest, path_size);
-      bool valid = false;
-      while (!valid && idx < path_size - 1) {
-        valid = pvalid[idx];
-        if (!valid) idx++;
-      }
-      pf_idx[S] = static_cast<uint32_t>(idx);
-    }
-  } else {
-    memset(pf_idx, 0, std::max(P, 1u) * 4);
-  }
+  return FirstPoint{yaw0, cos0, sin0, svx, svy, swz, x00, y00, cost_t0};
+}
 
-  uint8_t* pang_active = h + tl.pang_active;
-  bool pang_correct = false;
-  c->pang_any = false;     // PathAngleCritic live for some candidate furthest point this tick
-  if (gates & SD_PATH_ANGLE) {
-    // path_angle_critic.cpp:24-31,52-54: reversing / forward preference
-    bool reversing_allowed = true;
-    if (std::fabs(cr.path_angle.vx_min) < 1e-6) reversing_allowed = false;
-    else if (cr.path_angle.vx_min < 0.0f) reversing_allowed = true;
-    bool forward_preference = cr.path_angle.forward_preference != 0;
-    if (!reversing_allowed) forward_preference = true;
-    pang_correct = reversing_allowed && !forward_preference;
-    for (uint32_t S = 0; S < P; ++S) {
-      // :73-83 utils::posePointAngle (tools/utils.hpp:417-434) against the offset point
-      const size_t idx = std::min(static_cast<size_t>(S) + cr.path_angle.offset_from_furthest,
-                                  static_cast<size_t>(P) - 1);
-      const float pose_x = static_cast<float>(rx), pose_y = static_cast<float>(ry);
-      const double point_x = px[idx], point_y = py[idx];
-      const float yaw = atan2f(static_cast<float>(point_y - static_cast<double>(pose_y)),
-                               static_cast<float>(point_x - static_cast<double>(pose_x)));
-      auto norm = [](double a) {
-        const double theta = std::fmod(a + M_PI, 2.0 * M_PI);
-        return theta <= 0.0 ? theta + M_PI : theta - M_PI;
-      };
-      const double pyaw0 = static_cast<double>(in->pose_yaw);
-      float ang = static_cast<float>(std::fabs(norm(pyaw0 - static_cast<double>(yaw))));
-      if (!forward_preference) {
-        const double b = std::fabs(norm(norm(pyaw0 + M_PI) - static_cast<double>(yaw)));
-        ang = static_cast<float>(std::min(std::fabs(norm(pyaw0 - static_cast<double>(yaw))), b));
-      }
-      pang_active[S] = ang < cr.path_angle.max_angle_to_furthest ? 0 : 1;
-      if (pang_active[S]) c->pang_any = true;
-    }
-  } else {
-    memset(pang_active, 0, std::max(P, 1u));
-  }
-  float* lut_cost = reinterpret_cast<float*>(h + tl.lut_cost);
-  bool near_goal_cost = false;
-  if (gates & SD_COST) {
-    // cost_critic.cpp:120-124,141-155 per 8-bit cost (collisions are marked in the shared LUT)
-    const bool near_goal_c = within_tol(cr.cost.near_goal_distance, rx, ry, gx, gy);
-    near_goal_cost = near_goal_c;
-    for (int v = 0; v < 256; ++v) {
-      float t = 0.0f;
-      if (v >= 1) {
-        if (static_cast<float>(v) >= static_cast<float>(SMPC_COST_INSCRIBED)) t = cr.cost.critical_cost;
-        else if (!near_goal_c) t = static_cast<float>(v);
-      }
-      lut_cost[v] = t;
-    }
-  } else {
-    memset(lut_cost, 0, 256 * 4);
-  }
+// ---- per-candidate-furthest-point tables -------------------------------------
 
-  // ---- Obstacles LUT: rebuilt and uploaded only when its inputs changed -----------
+// PathAlignCritic's and PathAlignLegacyCritic's gate per candidate furthest point S
+// (path_align_critic.cpp:58-74, path_align_legacy_critic.cpp:56-72: the same code)
+static void occupancy_gate(const float* px, const float* py, const uint8_t* pvalid, uint32_t P, float x00, float y00,
+                           const smpc_path_align_params& q, uint8_t* active)
+{
+  // utils::findPathTrajectoryInitialPoint (tools/utils.hpp:327-344)
+  size_t init = 0;
+  float best = std::numeric_limits<float>::max();
+  for (uint32_t j = 0; j < P; ++j) {
+    const float ddx = px[j] - x00, ddy = py[j] - y00;
+    const float d = ddx * ddx + ddy * ddy;
+    if (d < best) {
+      best = d;
+      init = j;
+    }
+  }
+  // occupancy of the path between the initial and the furthest point.  The reference
+  // walks i = init..S-1 with a running count of invalid points and stops at the first i where
+  // count / range > ratio and count > 2; the count only grows and range is fixed per S, so
+  // that happens iff it holds for the final count: prefix sums, O(P).
+  std::vector<uint32_t> inval(P + 1, 0);
+  for (uint32_t i = 0; i < P; ++i) inval[i + 1] = inval[i] + ((i + 1 < P && !pvalid[i]) ? 1u : 0u);
+  for (uint32_t S = 0; S < P; ++S) {
+    bool on = S >= q.offset_from_furthest;
+    if (on && S > init) {
+      const unsigned int invalid_ctr = inval[S] - inval[init];
+      const float range = static_cast<float>(static_cast<size_t>(S) - init);
+      if (static_cast<float>(invalid_ctr) / range > q.max_path_occupancy_ratio && invalid_ctr > 2) on = false;
+    }
+    active[S] = on ? 1 : 0;
+  }
+}
+
+// PathFollowCritic's target point per candidate furthest point S
+static void path_follow_targets(const uint8_t* pvalid, uint32_t P, uint32_t offset_from_furthest, uint32_t* pf_idx)
+{
+  // path_follow_critic.cpp:46-57
+  const size_t path_size = P - 1;
+  for (uint32_t S = 0; S < P; ++S) {
+    size_t idx = std::min(static_cast<size_t>(S) + offset_from_furthest, path_size);
+    bool valid = false;
+    while (!valid && idx < path_size - 1) {
+      valid = pvalid[idx];
+      if (!valid) idx++;
+    }
+    pf_idx[S] = static_cast<uint32_t>(idx);
+  }
+}
+
+// PathAngleCritic per candidate furthest point S: pang_active[S] = 1 where the critic is live (the
+// angle to the offset point is not inside max_angle_to_furthest)
+struct PathAngleGates {
+  bool any_live;   // live for some S: the lane pass cannot take the tick (lane_eligible)
+  bool correct;    // SmpcDev::pang_correct
+};
+static PathAngleGates path_angle_gates(const float* px, const float* py, uint32_t P, const smpc_tick_in* in,
+                                       const smpc_path_angle_params& q, uint8_t* pang_active)
+{
+  const double rx = in->pose_x, ry = in->pose_y;
+  bool pang_correct = false, pang_any = false;
+  // path_angle_critic.cpp:24-31,52-54: reversing / forward preference
+  bool reversing_allowed = true;
+  if (std::fabs(q.vx_min) < 1e-6) reversing_allowed = false;
+  else if (q.vx_min < 0.0f) reversing_allowed = true;
+  bool forward_preference = q.forward_preference != 0;
+  if (!reversing_allowed) forward_preference = true;
+  pang_correct = reversing_allowed && !forward_preference;
+  for (uint32_t S = 0; S < P; ++S) {
+    // :73-83 utils::posePointAngle (tools/utils.hpp:417-434) against the offset point
+    const size_t idx = std::min(static_cast<size_t>(S) + q.offset_from_furthest,
+                                static_cast<size_t>(P) - 1);
+    const float pose_x = static_cast<float>(rx), pose_y = static_cast<float>(ry);
+    const double point_x = px[idx], point_y = py[idx];
+    const float yaw = atan2f(static_cast<float>(point_y - static_cast<double>(pose_y)),
+                             static_cast<float>(point_x - static_cast<double>(pose_x)));
+    auto norm = [](double a) {
+      const double theta = std::fmod(a + M_PI, 2.0 * M_PI);
+      return theta <= 0.0 ? theta + M_PI : theta - M_PI;
+    };
+    const double pyaw0 = static_cast<double>(in->pose_yaw);
+    float ang = static_cast<float>(std::fabs(norm(pyaw0 - static_cast<double>(yaw))));
+    if (!forward_preference) {
+      const double b = std::fabs(norm(norm(pyaw0 + M_PI) - static_cast<double>(yaw)));
+      ang = static_cast<float>(std::min(std::fabs(norm(pyaw0 - static_cast<double>(yaw))), b));
+    }
+    pang_active[S] = ang < q.max_angle_to_furthest ? 0 : 1;
+    if (pang_active[S]) pang_any = true;
+  }
+  return PathAngleGates{pang_any, pang_correct};
+}
+
+// CostCritic's term per 8-bit cost
+static void cost_lut(const smpc_cost_params& q, bool near_goal_c, float* lut_cost)
+{
+  // cost_critic.cpp:120-124,141-155 per 8-bit cost (collisions are marked in the shared LUT)
+  for (int v = 0; v < 256; ++v) {
+    float t = 0.0f;
+    if (v >= 1) {
+      if (static_cast<float>(v) >= static_cast<float>(SMPC_COST_INSCRIBED)) t = q.critical_cost;
+      else if (!near_goal_c) t = static_cast<float>(v);
+    }
+    lut_cost[v] = t;
+  }
+}
+
+// {Obstacles,Cost}Critic::findCircumscribedCost with InflationLayer::computeCost
+// (nav2_costmap_2d, Humble): the cost at the circumscribed radius, -1 without a layer
+static float circumscribed_cost(const HostCostmap& map, double fp_circumscribed_radius, double fp_layer_scale)
+{
+  double result = -1.0;
+  if (fp_layer_scale >= 0.0) {
+    const double distance = fp_circumscribed_radius / map.res;
+    unsigned char cost = 0;
+    if (distance == 0) {
+      cost = SMPC_COST_LETHAL;
+    } else if (distance * map.res <= static_cast<double>(map.inscribed_radius)) {
+      cost = SMPC_COST_INSCRIBED;
+    } else {
+      const double factor = std::exp(-1.0 * fp_layer_scale *
+                                     (distance * map.res - static_cast<double>(map.inscribed_radius)));
+      cost = static_cast<unsigned char>((SMPC_COST_INSCRIBED - 1) * factor);
+    }
+    result = cost;
+  }
+  return static_cast<float>(result);
+}
+
+// ---- Obstacles LUT: rebuilt and uploaded only when its inputs changed -----------
+static int upload_collision_luts(smpc_ctx* c, const smpc_tick_in* in, uint32_t gates, bool near_goal_cost,
+                                 const float* lut_cost)
+{
+  const auto& cr = c->critics;
+  const double rx = in->pose_x, ry = in->pose_y, gx = in->goal_x, gy = in->goal_y;
   if (gates & (SD_OBSTACLES | SD_COST)) {
     const bool near_goal = within_tol(cr.obstacles.near_goal_distance, rx, ry, gx, gy);  // :124-127
     const bool cost_only = (gates & SD_COST) && !(gates & SD_OBSTACLES) && !(gates & (SD_FP_OBSTACLES | SD_FP_COST));
     const uint64_t key = (c->map_version << 20) ^ (c->critics_version << 4) ^ (near_goal ? 1u : 0u) ^
       ((gates & (SD_FP_OBSTACLES | SD_FP_COST)) ? 2u : 0u) ^ (cost_only ? 4u : 0u) ^ (near_goal_cost ? 8u : 0u);
     if (!c->lut_valid || key != c->lut_key) {
-      build_lut(c, near_goal, c->h_lut, false, false, cost_only ? lut_cost : nullptr);
+      build_lut(c->map, cr.obstacles, near_goal, c->h_lut, false, false, cost_only ? lut_cost : nullptr);
       HIPCK(c, hipMemcpyAsync(c->d_lut, c->h_lut, 256 * sizeof(SmpcLut), hipMemcpyHostToDevice,
                               c->stream));
       if (gates & (SD_FP_OBSTACLES | SD_FP_COST)) {
-        build_lut(c, near_goal, c->h_lut_fp, true, false);
-        build_lut(c, near_goal, c->h_lut_fp + 256, true, true);
+        build_lut(c->map, cr.obstacles, near_goal, c->h_lut_fp, true, false);
+        build_lut(c->map, cr.obstacles, near_goal, c->h_lut_fp + 256, true, true);
         HIPCK(c, hipMemcpyAsync(c->d_lut_fp, c->h_lut_fp, 512 * sizeof(SmpcLut), hipMemcpyHostToDevice,
                                 c->stream));
       }
@@ -959,48 +1074,64 @@ int prepare_tick(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
       c->lut_valid = true;
     }
   }
+  return SMPC_OK;
+}
 
-  {
-    const int rc_map = wait_map_upload(c);
-    if (rc_map != SMPC_OK) return rc_map;
-  }
-  // The index this tick is first scored with (it does not depend on the launch plan), and the lane
-  // pass's prune table for the 16 indices around it: the batch's furthest point — what the table is
-  // indexed with — lands within one or two of the prediction.  O(16 P), ~0.5 us for 60 points, so:
-  // only where it is read — a speculating tick of a context whose LAST tick took the parking form of
-  // the lane pass on its own (this tick's plan is made after the block has gone to the device; a
-  // wrong guess costs scans or a table nobody reads, never a result) — once per plan and first index
-  // (a plan is handed over unchanged for several ticks), and not beyond kPruneMaxPath points.
-  // SMPC_FURTHEST_PRUNE=0 gets the empty table, every entry "never prune" (the same work in the
-  // kernel: the A/B switch); a tick that does not read the table gets only its header with no
-  // entries (a pass that reads it after all scans every group), and the block handed to the device
-  // ends behind that header: 512 bytes less through the BAR on every small tick.
-  predict_hint(c, in, u_in);
+// The index this tick is first scored with (it does not depend on the launch plan), and the lane
+// pass's prune table for the 16 indices around it: the batch's furthest point — what the table is
+// indexed with — lands within one or two of the prediction.  O(16 P), ~0.5 us for 60 points, so:
+// only where it is read — a speculating tick of a context whose LAST tick took the parking form of
+// the lane pass on its own (this tick's plan is made after the block has gone to the device; a
+// wrong guess costs scans or a table nobody reads, never a result) — once per plan and first index
+// (a plan is handed over unchanged for several ticks), and not beyond kPruneMaxPath points.
+// SMPC_FURTHEST_PRUNE=0 gets the empty table, every entry "never prune" (the same work in the
+// kernel: the A/B switch); a tick that does not read the table gets only its header with no
+// entries (a pass that reads it after all scans every group), and the block handed to the device
+// ends behind that header: 512 bytes less through the BAR on every small tick.
+// Runs after predict_hint (it reads the hint) and before plan_launch: c->plan is still the
+// PREVIOUS tick's.  Returns the bytes of the block to hand over.
+static size_t prune_table_for_tick(smpc_ctx* c, const TickBlock& b, const TickLayout& tl, uint32_t P)
+{
+  const float* px = b.px;
+  const float* py = b.py;
   size_t tick_bytes = tl.total;
-  {
-    constexpr uint32_t kPruneMaxPath = 256;
-    float* table = reinterpret_cast<float*>(h + tl.prune);
-    uint32_t k0 = (c->hint_valid && c->hint > SMPC_PRUNE_ENTRIES / 2) ? c->hint - SMPC_PRUNE_ENTRIES / 2 : 0u;
-    k0 = std::min(k0, P > SMPC_PRUNE_ENTRIES ? P - SMPC_PRUNE_ENTRIES : 0u);
-    const bool read = c->plan.kind == PassPlan::kLane && !c->plan.rr && !c->plan.pow && !c->in_group && c->hint_valid &&
-      !(c->cfg.flags & SMPC_FLAG_NO_SPECULATION);
-    if (!read || P > kPruneMaxPath) {
-      memset(table, 0, 16);
-      tick_bytes = tl.prune + 16;
-    } else if (!c->knobs.furthest_prune) {
-      build_prune_table(px, py, P, k0, false, table);
-    } else if (c->prune_k0 == k0 && c->prune_px.size() == P && !memcmp(c->prune_px.data(), px, P * 4) &&
-               !memcmp(c->prune_py.data(), py, P * 4)) {
-      memcpy(table, c->prune_table, sizeof(c->prune_table));
-    } else {
-      build_prune_table(px, py, P, k0, true, table);
-      memcpy(c->prune_table, table, sizeof(c->prune_table));
-      c->prune_px.assign(px, px + P);
-      c->prune_py.assign(py, py + P);
-      c->prune_k0 = k0;
-    }
+  constexpr uint32_t kPruneMaxPath = 256;
+  float* table = b.prune;
+  uint32_t k0 = (c->pred.hint_valid && c->pred.hint > SMPC_PRUNE_ENTRIES / 2) ? c->pred.hint - SMPC_PRUNE_ENTRIES / 2 : 0u;
+  k0 = std::min(k0, P > SMPC_PRUNE_ENTRIES ? P - SMPC_PRUNE_ENTRIES : 0u);
+  const bool read = c->plan.kind == PassPlan::kLane && !c->plan.rr && !c->plan.pow && !c->in_group && c->pred.hint_valid &&
+    !(c->cfg.flags & SMPC_FLAG_NO_SPECULATION);
+  if (!read || P > kPruneMaxPath) {
+    memset(table, 0, 16);
+    tick_bytes = tl.prune + 16;
+  } else if (!c->knobs.furthest_prune) {
+    build_prune_table(px, py, P, k0, false, table);
+  } else if (c->prune_k0 == k0 && c->prune_px.size() == P && !memcmp(c->prune_px.data(), px, P * 4) &&
+             !memcmp(c->prune_py.data(), py, P * 4)) {
+    memcpy(table, c->prune_table, sizeof(c->prune_table));
+  } else {
+    build_prune_table(px, py, P, k0, true, table);
+    memcpy(c->prune_table, table, sizeof(c->prune_table));
+    c->prune_px.assign(px, px + P);
+    c->prune_py.assign(py, py + P);
+    c->prune_k0 = k0;
   }
-  if (c->cfg.flags & SMPC_FLAG_PROFILE) HIPCK(c, hipEventRecord(c->ev0, c->stream));
+  return tick_bytes;
+}
+
+// how the kernels get the tick block: the base address they read it from, or inside their arguments
+struct HandOver {
+  const uint8_t* base;   // pinned host memory (SMPC_PINNED_TICK=1) or c->d_tick
+  bool inline_tick;
+};
+// The tick's number and canary, then the block to the device: CPU stores through the BAR, a copy
+// on the stream, inside the kernel arguments (fill_dev_footprint_inline), read in place from pinned
+// memory, or left to the group (defer_upload).  tick_no advances here, so also for a tick whose
+// planning fails afterwards.
+static int hand_over_tick_block(smpc_ctx* c, uint32_t gates, const TickLayout& tl, size_t tick_bytes, HandOver& ho)
+{
+  const uint32_t T = c->cfg.time_steps;
+  uint8_t* h = c->h_tick;
   // small ticks travel inside the kernel arguments (SmpcDev::tick_bytes) instead of a copy of
   // their own; the CostCritic table (general pass only) is not part of that
   // (contexts of the wave-per-rollout pass only: see smpc_lane.hip for why not the other)
@@ -1040,22 +1171,33 @@ int prepare_tick(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
       HIPCK(c, hipMemcpyAsync(c->d_tick + tl.lut_cost, h + tl.lut_cost, 256 * sizeof(float), hipMemcpyHostToDevice,
                               c->stream));
   }
+  ho.base = tb;
+  ho.inline_tick = inline_tick;
+  return SMPC_OK;
+}
 
-  // ---- kernel parameter block ------------------------------------------------------
+// ---- kernel parameter block ------------------------------------------------------
+
+// c->dev zeroed, then the tick's sizes, the robot's state, the tensors, the costmap with the wave
+// pass's cell-index guard band, and the tick block's regions at the base the kernels read
+static void fill_dev_state(smpc_ctx* c, const smpc_tick_in* in, uint32_t nsamp, uint32_t step, const FirstPoint& fp,
+                           const TickLayout& tl, const uint8_t* tb)
+{
+  const uint32_t T = c->cfg.time_steps, B = c->cfg.batch_size, P = in->path_len;
   SmpcDev& d = c->dev;
   memset(&d, 0, sizeof(d));
   d.B = B; d.T = T; d.P = P; d.nsamp = nsamp; d.step = step;
   d.x0 = in->pose_x; d.y0 = in->pose_y;
-  d.yaw0 = yaw0; d.cos0 = cos0; d.sin0 = sin0;
-  d.svx = svx; d.svy = svy; d.swz = swz; d.dt = dt;
+  d.yaw0 = fp.yaw0; d.cos0 = fp.cos0; d.sin0 = fp.sin0;
+  d.svx = fp.svx; d.svy = fp.svy; d.swz = fp.swz; d.dt = c->cfg.model_dt;
   d.nvx = c->d_nvx; d.nvy = c->d_nvy; d.nwz = c->d_nwz;
   d.tvx = c->d_tvx; d.tvy = c->d_tvy; d.twz = c->d_twz;
   d.u = reinterpret_cast<const float*>(tb + tl.u);
   d.traj_x = c->d_traj[0]; d.traj_y = c->d_traj[1]; d.traj_yaw = c->d_traj[2];
   d.map = c->d_map; d.W = c->map.W; d.H = c->map.H;
   d.ox = c->map.ox; d.oy = c->map.oy; d.res = c->map.res;
-  d.cost_t0 = cost_t0;
-  d.x00f = x00; d.y00f = y00;
+  d.cost_t0 = fp.cost_t0;
+  d.x00f = fp.x00; d.y00f = fp.y00;
   {
     // fast cell index: float quotient + guard band (see cost_at in smpc_kernels.hip)
     const double rinv = 1.0 / c->map.res;
@@ -1077,6 +1219,22 @@ int prepare_tick(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
   d.pa_active = tb + tl.pa_active;
   d.pf_idx = reinterpret_cast<const uint32_t*>(tb + tl.pf_idx);
   d.prune = reinterpret_cast<const float*>(tb + tl.prune);
+  d.lut_cost = reinterpret_cast<const float*>(tb + tl.lut_cost);
+  d.pang_active = tb + tl.pang_active;
+  d.pal_active = tb + tl.pal_active;
+  d.timeline = c->d_timeline;
+  d.canary_echo = c->canary_expect ? 1u : 0u;
+  d.partials = c->d_partials;
+  d.furthest_out = reinterpret_cast<uint32_t*>(c->d_furthest);
+}
+
+// the critics' parameters as the kernels take them, and the optimizer's (gamma terms, temperature)
+static void fill_dev_critics(smpc_ctx* c, const smpc_tick_in* in, const float* pyaw, bool near_goal_cost,
+                             bool pang_correct)
+{
+  const uint32_t T = c->cfg.time_steps, P = in->path_len;
+  const auto& cr = c->critics;
+  SmpcDev& d = c->dev;
   d.obs_critical_w = cr.obstacles.critical_weight;
   d.obs_repulsion_w = cr.obstacles.repulsion_weight;
   d.obs_collision_cost = cr.obstacles.collision_cost;
@@ -1095,7 +1253,6 @@ int prepare_tick(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
     d.con_min_vel = min_sgn * sqrtf(cr.constraint.vx_min * cr.constraint.vx_min + cr.constraint.vy_max * cr.constraint.vy_max);
     d.con_acker_r = c->acker_r;
   }
-  d.lut_cost = reinterpret_cast<const float*>(tb + tl.lut_cost);
   d.cost_w254 = cr.cost.cost_weight / 254.0f;   // cost_critic.cpp:34
   d.cost_collision_cost = cr.cost.collision_cost; d.cost_power = cr.cost.cost_power;
   d.cost_critical = cr.cost.critical_cost;
@@ -1103,8 +1260,6 @@ int prepare_tick(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
   d.goal_x = in->goal_x; d.goal_y = in->goal_y;
   d.goal_weight = cr.goal.cost_weight; d.goal_power = cr.goal.cost_power;
   d.tw_weight = cr.twirling.cost_weight; d.tw_power = cr.twirling.cost_power;
-  d.pang_active = tb + tl.pang_active;
-  d.pal_active = tb + tl.pal_active;
   d.pal_weight = cr.path_align_legacy.cost_weight;
   d.pal_power = cr.path_align_legacy.cost_power;
   {
@@ -1119,6 +1274,20 @@ int prepare_tick(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
   d.db_vy = c->holonomic ? std::fabs(static_cast<double>(cr.velocity_deadband.deadband_velocities[1])) : 0.0;
   d.db_wz = std::fabs(static_cast<double>(cr.velocity_deadband.deadband_velocities[2]));
   d.db_weight = cr.velocity_deadband.cost_weight; d.db_power = cr.velocity_deadband.cost_power;
+  d.g_vx = c->cfg.gamma / powf(c->cfg.vx_std, 2);
+  d.g_vy = c->holonomic ? c->cfg.gamma / powf(c->cfg.vy_std, 2) : 0.f;   // optimizer.cpp:374-380
+  d.g_wz = c->cfg.gamma / powf(c->cfg.wz_std, 2);
+  d.neg_inv_temp = -1 / c->cfg.temperature;
+  d.k2 = d.neg_inv_temp * 1.4426950408889634f;
+}
+
+// the footprint and its circumscribed cost; for an inline tick the control sequence and the path
+// block inside the arguments
+static void fill_dev_footprint_inline(smpc_ctx* c, uint32_t gates, const TickLayout& tl, bool inline_tick)
+{
+  const uint32_t T = c->cfg.time_steps;
+  const uint8_t* h = c->h_tick;
+  SmpcDev& d = c->dev;
   d.lut_fp = c->d_lut_fp;
   d.fp_n = static_cast<uint32_t>(c->fp_x.size());
   for (uint32_t i = 0; i < d.fp_n; ++i) {
@@ -1126,33 +1295,9 @@ int prepare_tick(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
     d.fp_y[i] = c->fp_y[i];
   }
   d.fp_pic = 0.0f;
-  if (gates & (SD_FP_OBSTACLES | SD_FP_COST)) {
-    // {Obstacles,Cost}Critic::findCircumscribedCost with InflationLayer::computeCost
-    // (nav2_costmap_2d, Humble): the cost at the circumscribed radius, -1 without a layer
-    double result = -1.0;
-    if (c->fp_layer_scale >= 0.0) {
-      const double distance = c->fp_circumscribed_radius / c->map.res;
-      unsigned char cost = 0;
-      if (distance == 0) {
-        cost = SMPC_COST_LETHAL;
-      } else if (distance * c->map.res <= static_cast<double>(c->map.inscribed_radius)) {
-        cost = SMPC_COST_INSCRIBED;
-      } else {
-        const double factor = std::exp(-1.0 * c->fp_layer_scale *
-                                       (distance * c->map.res - static_cast<double>(c->map.inscribed_radius)));
-        cost = static_cast<unsigned char>((SMPC_COST_INSCRIBED - 1) * factor);
-      }
-      result = cost;
-    }
-    d.fp_pic = static_cast<float>(result);
-  }
-  d.g_vx = c->cfg.gamma / powf(c->cfg.vx_std, 2);
-  d.g_vy = c->holonomic ? c->cfg.gamma / powf(c->cfg.vy_std, 2) : 0.f;   // optimizer.cpp:374-380
-  d.g_wz = c->cfg.gamma / powf(c->cfg.wz_std, 2);
-  d.neg_inv_temp = -1 / c->cfg.temperature;
-  d.k2 = d.neg_inv_temp * 1.4426950408889634f;
-  d.timeline = c->d_timeline;
-  d.canary_echo = c->canary_expect ? 1u : 0u;
+  if (gates & (SD_FP_OBSTACLES | SD_FP_COST))
+    d.fp_pic = circumscribed_cost(c->map, c->fp_circumscribed_radius, c->fp_layer_scale);
+  // (u_arg: copied from the block, after copy_plan zeroed the vy row of a non-holonomic model)
   if (inline_tick) memcpy(d.u_arg, h + tl.u, 3 * T * sizeof(float));
   if (inline_tick) {
     d.tick_inline = 1;
@@ -1165,13 +1310,78 @@ int prepare_tick(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
     d.io_pal_active = static_cast<uint16_t>(tl.pal_active - o);
     memcpy(d.tick_bytes, h + o, tl.lut_cost - o);
   }
-  d.partials = c->d_partials;
-  d.furthest_out = reinterpret_cast<uint32_t*>(c->d_furthest);
+}
 
+// Everything the reference's critics decide once per tick on the host, plus the
+// upload of the tick block.  Leaves c->dev ready for the launches.
+int prepare_tick(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
+{
+  int rc = check_tick(c, in);
+  if (rc != SMPC_OK) return rc;
+  if (!u_in) return fail(c, SMPC_ERR_INVALID, "control sequence missing");
+  rc = absorb_redraw(c);   // noise drawn in the background since the last tick, if any
+  if (rc != SMPC_OK) return rc;
+  const uint32_t T = c->cfg.time_steps, P = in->path_len;
+  const auto& cr = c->critics;
+  HIPCK(c, hipSetDevice(c->device));
+
+  const TickLayout tl = tick_layout(T, std::max(P, 1u));
+  if (tl.total > c->tick_cap) return fail(c, SMPC_ERR_INVALID, "tick block overflow");
+  const TickBlock b = tick_block(c->h_tick, tl);
+  copy_plan(b, tl, in, u_in, T, c->holonomic);
+
+  uint32_t gates = 0, nsamp = 0;
+  rc = tick_gates(c, in, gates, nsamp);
+  if (rc != SMPC_OK) return rc;
+  const double rx = in->pose_x, ry = in->pose_y, gx = in->goal_x, gy = in->goal_y;
+  // (PathAlignLegacy alone: its own step — tick_gates refuses two different ones)
+  const uint32_t step = (gates & SD_PATH_ALIGN) || !(gates & SD_PATH_ALIGN_LEGACY) ? cr.path_align.trajectory_point_step
+                                                                                    : cr.path_align_legacy.trajectory_point_step;
+  path_tables(c->map, in, gates, b.px, b.py, b.pvalid, b.D);
+  const FirstPoint fp = first_point(in, c->holonomic, c->cfg.model_dt, c->map);
+
+  // the per-candidate-furthest-point tables; a critic past its gate gets its table, the others zeros
+  const uint32_t P1 = std::max(P, 1u);
+  if (gates & SD_PATH_ALIGN) occupancy_gate(b.px, b.py, b.pvalid, P, fp.x00, fp.y00, cr.path_align, b.pa_active);
+  else memset(b.pa_active, 0, P1);
+  if (gates & SD_PATH_ALIGN_LEGACY) occupancy_gate(b.px, b.py, b.pvalid, P, fp.x00, fp.y00, cr.path_align_legacy, b.pal_active);
+  else memset(b.pal_active, 0, P1);
+  if (gates & SD_PATH_FOLLOW) path_follow_targets(b.pvalid, P, cr.path_follow.offset_from_furthest, b.pf_idx);
+  else memset(b.pf_idx, 0, P1 * 4);
+  // (c->pang_any: cleared here for every tick, read by plan_launch below)
+  PathAngleGates pang{false, false};
+  if (gates & SD_PATH_ANGLE) pang = path_angle_gates(b.px, b.py, P, in, cr.path_angle, b.pang_active);
+  else memset(b.pang_active, 0, P1);
+  c->pang_any = pang.any_live;
+  const bool near_goal_cost = (gates & SD_COST) && within_tol(cr.cost.near_goal_distance, rx, ry, gx, gy);
+  if (gates & SD_COST) cost_lut(cr.cost, near_goal_cost, b.lut_cost);
+  else memset(b.lut_cost, 0, 256 * 4);
+
+  // the LUT upload is enqueued before the wait on the map upload
+  rc = upload_collision_luts(c, in, gates, near_goal_cost, b.lut_cost);
+  if (rc != SMPC_OK) return rc;
+  rc = wait_map_upload(c);
+  if (rc != SMPC_OK) return rc;
+  // after wait_map_upload and before the prune table, which is indexed around the hint; the prune
+  // table before plan_launch, which overwrites the c->plan of the previous tick it looks at
+  predict_hint(c, in, u_in);
+  const size_t tick_bytes = prune_table_for_tick(c, b, tl, P);
+  // (the profile's first event: between the prune table and the hand-over)
+  if (c->cfg.flags & SMPC_FLAG_PROFILE) HIPCK(c, hipEventRecord(c->ev0, c->stream));
+  HandOver ho{};
+  rc = hand_over_tick_block(c, gates, tl, tick_bytes, ho);
+  if (rc != SMPC_OK) return rc;
+
+  // c->dev is zeroed and filled before plan_launch, which writes the window, wxf / cxf and
+  // cell_eps_w into it
+  fill_dev_state(c, in, nsamp, step, fp, tl, ho.base);
+  fill_dev_critics(c, in, b.pyaw, near_goal_cost, pang.correct);
+  fill_dev_footprint_inline(c, gates, tl, ho.inline_tick);
   int mode_now = 0;
   rc = plan_launch(c, in, gates, nsamp, mode_now);
   if (rc != SMPC_OK) return rc;
 
+  // written only after everything succeeded
   c->gate_flags = gates;
   // with a footprint the two collision critics no longer see the same set of colliding rollouts,
   // and a pass reports one non-colliding count (CostCritic's, scored first): smpc_optimize counts

@@ -74,8 +74,8 @@ int smpc_shard_begin(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
 int smpc_shard_predicted_furthest(smpc_ctx* c, uint32_t* hint)
 {
   if (!c || !hint) return 0;
-  if (!c->tick_ready || !c->hint_valid || !(c->gate_flags & SD_NEED_FURTHEST)) return 0;
-  *hint = c->hint;
+  if (!c->tick_ready || !c->pred.hint_valid || !(c->gate_flags & SD_NEED_FURTHEST)) return 0;
+  *hint = c->pred.hint;
   return 1;
 }
 
@@ -294,7 +294,7 @@ int smpc_shard_tick(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_ti
   auto p2p_check = [&]() -> int {
     if (res.mark() == SMPC_MARK_NONE) return SMPC_OK;
     c->p2p_failed = true;
-    c->hint_valid = false;
+    c->pred.drop_hint();
     char msg[160];
     snprintf(msg, sizeof(msg), "shard exchange %u: a peer's tuple did not arrive within %u ms", c->p2p_xseq,
              c->p2p_timeout_ms);
@@ -317,16 +317,16 @@ int smpc_shard_tick(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_ti
   uint32_t flags = scoring_flags(c, c->fail_in);
   const bool need_f = (flags & SD_NEED_FURTHEST) != 0;
   if (need_f) flags |= SD_LOCAL_FURTHEST;   // the tuple carries the true local value
-  if (speculate && need_f && c->hint_valid) {
-    rc = launch_score(c, flags, nullptr, nullptr, c->hint, c->d_tuple);
+  if (speculate && need_f && c->pred.hint_valid) {
+    rc = launch_score(c, flags, nullptr, nullptr, c->pred.hint, c->d_tuple);
     if (rc == SMPC_OK) rc = gather_combine_fetch(nullptr);
     if (rc != SMPC_OK) return rc;
     float F_true = res.F_local();
     const uint32_t S_true = smpc_furthest_index(F_true);
-    if (S_true != c->hint) {
+    if (S_true != c->pred.hint) {
       // miss: the gathered tuples carry the true batch-wide furthest point
       c->spec_misses++;
-      c->hint = S_true;
+      c->pred.hint = S_true;
       rc = launch_score(c, flags, nullptr, nullptr, S_true, c->d_tuple);
       if (rc == SMPC_OK) rc = gather_combine_fetch(nullptr);
       if (rc != SMPC_OK) return rc;
@@ -363,6 +363,6 @@ int smpc_shard_tick(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_ti
     if (rc != SMPC_OK) return rc;
   }
   store_control_sequence(c, u_inout);
-  return fill_tick_out(c, out, failed, need_f, need_f ? c->hint : 0u);
+  return fill_tick_out(c, out, failed, need_f, need_f ? c->pred.hint : 0u);
 }
 }  // extern "C"

@@ -17,28 +17,30 @@ static const char* const kCriticNames[SMPC_STATS_ROWS] = {
   "GoalAngleCritic", "PreferForwardCritic", "GoalCritic", "PathAngleCritic", "TwirlingCritic", "VelocityDeadbandCritic",
   "ControlCost"};
 
-// what prepare_tick and the furthest-point pre-pass change and a later tick would see
+// What prepare_tick and the furthest-point pre-pass change and a later tick would see: the predictor
+// as a whole (the breakdown runs predict_hint — the hint, the last prediction, the nominal endpoint of
+// the tick at hand — and never remember_furthest, so the anchor and the drift come back as they
+// were: a field added to the predictor is carried without being named here), the launch plan
+// (plan_launch; the next tick's prune_table_for_tick reads it), the last kernel's name (the
+// pre-pass and the stats pass write it) and the pass counters.
 struct Carried {
-  bool hint_valid, hint_Fp_valid, hint_is_this_ticks, cur_e_valid;
-  uint32_t hint, passes, last_pass_kind;
-  float hint_F, hint_Fp, hint_drift;
-  double cur_ex, cur_ey;
+  FurthestPredictor pred;
   PassPlan plan;
+  uint32_t passes, last_pass_kind;
   char last_kernel[sizeof(smpc_last_pass_kernel)];
 };
 static Carried save_carried(const smpc_ctx* c)
 {
-  Carried s{c->hint_valid, c->hint_Fp_valid, c->hint_is_this_ticks, c->cur_e_valid, c->hint, c->passes, c->last_pass_kind,
-            c->hint_F, c->hint_Fp, c->hint_drift, c->cur_ex, c->cur_ey, c->plan, {}};
+  Carried s{c->pred, c->plan, c->passes, c->last_pass_kind, {}};
   memcpy(s.last_kernel, smpc_last_pass_kernel, sizeof(s.last_kernel));
   return s;
 }
-static void restore_carried(smpc_ctx* c, const Carried& s)
+static void restore_carried(smpc_ctx* c, Carried& s)
 {
-  c->hint_valid = s.hint_valid; c->hint_Fp_valid = s.hint_Fp_valid; c->hint_is_this_ticks = s.hint_is_this_ticks;
-  c->cur_e_valid = s.cur_e_valid; c->hint = s.hint; c->passes = s.passes; c->last_pass_kind = s.last_pass_kind;
-  c->hint_F = s.hint_F; c->hint_Fp = s.hint_Fp; c->hint_drift = s.hint_drift; c->cur_ex = s.cur_ex; c->cur_ey = s.cur_ey;
+  c->pred = std::move(s.pred);
   c->plan = s.plan;
+  c->passes = s.passes;
+  c->last_pass_kind = s.last_pass_kind;
   memcpy(smpc_last_pass_kernel, s.last_kernel, sizeof(s.last_kernel));
 }
 
@@ -217,7 +219,7 @@ int smpc_critic_breakdown(smpc_ctx* c, const smpc_tick_in* in, const float* u_in
   if (c->in_group || c->defer_upload)
     return fail(c, SMPC_ERR_STATE, "critic breakdown: the ctx is a member of a group (its tick block is the group's)");
   HIPCK(c, hipSetDevice(c->device));
-  const Carried carried = save_carried(c);
+  Carried carried = save_carried(c);
   const int rc = breakdown(c, in, u_in, stats, per_rollout);
   if (rc != SMPC_OK && c->launched) {
     (void)hipStreamSynchronize(c->stream);   // nothing of an abandoned breakdown may run into the next tick
