@@ -360,6 +360,28 @@ int smpc_reset(smpc_ctx* ctx);
 int smpc_set_constraints(smpc_ctx* ctx, float vx_max, float vx_min, float vy_max,
                          float wz_max);
 
+/* Acceleration limits on the sampled controls (nav2_mppi_controller's ax_max, ax_min, ay_max,
+ * az_max; m/s^2 on vx, on vy — symmetric — and rad/s^2 on wz — symmetric).  With
+ *   dhi = model_dt * {ax_max, ay_max, az_max},  dlo = model_dt * {ax_min, -ay_max, -az_max}
+ * (products formed once, in float), every iteration turns the stored noise N into the LIMITED
+ * noise N' it scores with: per rollout b and control k, sequentially over t, all in float,
+ *   last = (float) speed_k
+ *   c  = u_k[t] + N_k[b][t];   ct = min(max(c, last + dlo_k), last + dhi_k)
+ *   N'_k[b][t] = (ct == c) ? N_k[b][t] : ct - u_k[t];   last = u_k[t] + N'_k[b][t]
+ * Every pass of the iteration (furthest-point pre-pass, scoring passes, the critic breakdown)
+ * reads N' where it read N: rollout velocities, the gamma term and the weighted update use the
+ * limited controls.  Where no limit binds N' == N bit for bit.  vy of a DiffDrive or Ackermann
+ * model is not touched.  The stored noise itself is never modified (smpc_get_noise).
+ * All four zero: off (the default; nothing is allocated or launched).  Otherwise ax_max > 0,
+ * ax_min < 0, ay_max > 0, az_max > 0, all finite; anything else is SMPC_ERR_INVALID.  The limits
+ * survive smpc_reset.  (Additions under ABI 3.) */
+int smpc_set_acceleration_limits(smpc_ctx* ctx, float ax_max, float ax_min, float ay_max,
+                                 float az_max);
+int smpc_get_acceleration_limits(const smpc_ctx* ctx, float out[4]);
+/* The N' the last tick's last iteration scored with, [B,T] each; any pointer may be NULL (vy of a
+ * non-holonomic model: zeros).  SMPC_ERR_STATE when the limits are off or no tick has run. */
+int smpc_get_limited_noise(smpc_ctx* ctx, float* noise_vx, float* noise_vy, float* noise_wz);
+
 int smpc_set_critics(smpc_ctx* ctx, const smpc_critic_params* p);
 
 /* Replaces the Costmap2D* the critics hold

@@ -76,6 +76,10 @@ int sortham_optimizer_critic_stats(sortham_optimizer* o, const smpc_tick_in* in,
 /* The smpc_tick_out of the last tick the object ran — the last retry's when eval_control threw. */
 int sortham_optimizer_last_tick(const sortham_optimizer* o, smpc_tick_out* out);
 int sortham_optimizer_set_speed_limit(sortham_optimizer* o, double speed_limit, int percentage);
+/* Optimizer::setAccelerationLimits: the limits of smpc_set_acceleration_limits (all zero: off).
+ * Before or after initialize; kept across reset and across a re-initialize. */
+int sortham_optimizer_set_acceleration_limits(sortham_optimizer* o, float ax_max, float ax_min,
+                                              float ay_max, float az_max);
 int sortham_optimizer_reset(sortham_optimizer* o);
 /* control_sequence_ as {vx[T], vy[T], wz[T]} */
 int sortham_optimizer_get_control_sequence(sortham_optimizer* o, float* u);

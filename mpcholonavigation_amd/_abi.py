@@ -270,6 +270,9 @@ PROTOTYPES = {
     "smpc_build_info": (C.c_char_p, []),
     "smpc_reset": (C.c_int, [_ctx]),
     "smpc_set_constraints": (C.c_int, [_ctx, C.c_float, C.c_float, C.c_float, C.c_float]),
+    "smpc_set_acceleration_limits": (C.c_int, [_ctx, C.c_float, C.c_float, C.c_float, C.c_float]),
+    "smpc_get_acceleration_limits": (C.c_int, [_ctx, C.POINTER(C.c_float)]),
+    "smpc_get_limited_noise": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
     "smpc_set_critics": (C.c_int, [_ctx, C.POINTER(SmpcCriticParams)]),
     "smpc_set_costmap": (C.c_int, [_ctx, C.c_void_p, C.c_uint32, C.c_uint32, C.c_double,
                                    C.c_double, C.c_double, C.c_int, C.c_float, C.c_float,

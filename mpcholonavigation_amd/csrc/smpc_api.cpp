@@ -102,6 +102,12 @@ void free_ctx(smpc_ctx* c)
     if (c->d_stats_part) (void)hipFree(c->d_stats_part);
   }
   for (hipEvent_t e : c->ev_stats) if (e) (void)hipEventDestroy(e);
+  if (c->l_gm || c->l_rm[0] || c->l_rm[1] || c->l_rm[2]) {
+    (void)hipStreamSynchronize(c->stream);
+    for (float* p : {c->l_gm, c->l_rm[0], c->l_rm[1], c->l_rm[2]})
+      if (p) (void)hipFree(p);
+  }
+  for (hipEvent_t e : c->ev_lim) if (e) (void)hipEventDestroy(e);
   if (c->fill_stream) {
     (void)hipStreamSynchronize(c->fill_stream);
     (void)hipStreamDestroy(c->fill_stream);
@@ -132,6 +138,78 @@ void free_ctx(smpc_ctx* c)
   delete c;
 }
 
+void begin_limit_iteration(smpc_ctx* c, const float* u_dev)
+{
+  c->lim_u_dev = u_dev;
+  if (++c->lim_iter == 0) ++c->lim_iter;
+}
+
+// The limiter's launch for one layout.  The buffers of that layout are allocated here, at the
+// first tick that reads it.
+static int limit_noise(smpc_ctx* c, bool group_major)
+{
+  const uint32_t B = c->cfg.batch_size, T = c->cfg.time_steps;
+  SmpcLimitArgs a{};
+  if (group_major) {
+    const size_t ngm = SMPC_GM_ELEMS(B, T);
+    if (!c->l_gm) {
+      HIPCK(c, hipMalloc(&c->l_gm, 3 * ngm * sizeof(float)));
+      HIPCK(c, hipMemsetAsync(c->l_gm, 0, 3 * ngm * sizeof(float), c->stream));   // (vy of a non-holonomic model stays zero)
+    }
+    a.src[0] = c->d_tvx; a.src[1] = c->holonomic ? c->d_tvy : nullptr; a.src[2] = c->d_twz;
+    a.dst[0] = c->l_gm; a.dst[1] = c->holonomic ? c->l_gm + ngm : nullptr; a.dst[2] = c->l_gm + 2 * ngm;
+  } else {
+    const int rc = ensure_row_major(c);
+    if (rc != SMPC_OK) return rc;
+    for (int k = 0; k < 3; ++k)
+      if (!c->l_rm[k] && (k != 1 || c->holonomic)) HIPCK(c, hipMalloc(&c->l_rm[k], static_cast<size_t>(B) * T * sizeof(float)));
+    a.src[0] = c->d_nvx; a.src[1] = c->holonomic ? c->d_nvy : nullptr; a.src[2] = c->d_nwz;
+    for (int k = 0; k < 3; ++k) a.dst[k] = c->l_rm[k];
+  }
+  a.B = B; a.T = T;
+  a.u_dev = c->lim_u_dev;
+  if (!a.u_dev) {
+    // iteration 0: the control sequence as prepare_tick put it into the tick block's host copy
+    // (vy row zeroed for a non-holonomic model), whichever way the block itself travels
+    const TickLayout tl = tick_layout(T, std::max(c->P, 1u));
+    memcpy(a.u_arg, c->h_tick + tl.u, 3 * T * sizeof(float));
+  }
+  a.v0[0] = c->dev.svx; a.v0[1] = c->dev.svy; a.v0[2] = c->dev.swz;
+  const float dt = c->cfg.model_dt;
+  a.dhi[0] = dt * c->lim[0]; a.dhi[1] = dt * c->lim[2]; a.dhi[2] = dt * c->lim[3];
+  a.dlo[0] = dt * c->lim[1]; a.dlo[1] = -a.dhi[1]; a.dlo[2] = -a.dhi[2];
+  const bool prof = (c->cfg.flags & SMPC_FLAG_PROFILE) != 0;
+  if (prof) {
+    for (hipEvent_t& e : c->ev_lim)
+      if (!e) HIPCK(c, hipEventCreate(&e));
+    HIPCK(c, hipEventRecord(c->ev_lim[0], c->stream));
+  }
+  c->launched = true;
+  HIPCK(c, smpc_launch_limit_noise(a, group_major, c->stream));
+  if (prof) HIPCK(c, hipEventRecord(c->ev_lim[1], c->stream));
+  return SMPC_OK;
+}
+
+int use_limited_noise(smpc_ctx* c, SmpcDev& d, bool group_major)
+{
+  if (!c->lim_on) return SMPC_OK;
+  uint32_t& have = group_major ? c->lim_gm_iter : c->lim_rm_iter;
+  if (have != c->lim_iter || c->lim_iter == 0) {
+    if (c->lim_iter == 0) begin_limit_iteration(c, nullptr);
+    const int rc = limit_noise(c, group_major);
+    if (rc != SMPC_OK) return rc;
+    have = c->lim_iter;
+  }
+  if (group_major) {
+    const size_t ngm = SMPC_GM_ELEMS(c->cfg.batch_size, c->cfg.time_steps);
+    d.tvx = c->l_gm; d.tvy = c->l_gm + ngm; d.twz = c->l_gm + 2 * ngm;
+  } else {
+    d.nvx = c->l_rm[0]; d.nwz = c->l_rm[2];
+    if (c->holonomic) d.nvy = c->l_rm[1];   // (else: the stored zeros, untouched)
+  }
+  return SMPC_OK;
+}
+
 int launch_furthest(smpc_ctx* c, float* d_furthest)
 {
   {
@@ -140,6 +218,10 @@ int launch_furthest(smpc_ctx* c, float* d_furthest)
   }
   HIPCK(c, hipMemsetAsync(d_furthest, 0, sizeof(float), c->stream));
   SmpcDev d = c->dev;
+  {
+    const int rc = use_limited_noise(c, d, false);
+    if (rc != SMPC_OK) return rc;
+  }
   d.flags = c->gate_flags & SD_NEED_FURTHEST;
   d.furthest_out = reinterpret_cast<uint32_t*>(d_furthest);
   SmpcLds L = make_lds(0, c->P, d.T, (pass_block(c->R) / 64), false);
@@ -245,9 +327,15 @@ int launch_score(smpc_ctx* c, uint32_t flags, const float* u_dev, const float* d
   SmpcDev d;
   SmpcFinal fin;
   fill_score_args(c, flags, u_dev, d_furthest, furthest_hint, finish, finish_furthest, d, fin);
+  const PassChoice pass = pass_for(c, flags);
+  {
+    // acceleration limits: the iteration's limited noise in the layout this pass reads (made here if
+    // this is the first pass of the iteration to read it), in front of the pass's profile events
+    const int rc = use_limited_noise(c, d, pass.kind != PassPlan::kWave);
+    if (rc != SMPC_OK) return rc;
+  }
   const bool prof = (c->cfg.flags & SMPC_FLAG_PROFILE) && c->evp_used + 2 <= 8;
   if (prof) HIPCK(c, hipEventRecord(c->evp[c->evp_used], c->stream));
-  const PassChoice pass = pass_for(c, flags);
   const uint32_t nblk = pass.geom->grid;
   // The block that finishes last reduces the partials inside the scoring launch (smpc_tail.h);
   // larger grids, and launches whose LDS was not sized for it, take the separate reduction.
@@ -847,6 +935,70 @@ int smpc_set_constraints(smpc_ctx* c, float vx_max, float vx_min, float vy_max, 
   return SMPC_OK;
 }
 
+int smpc_set_acceleration_limits(smpc_ctx* c, float ax_max, float ax_min, float ay_max, float az_max)
+{
+  if (!c) return SMPC_ERR_INVALID;
+  const bool off = ax_max == 0.f && ax_min == 0.f && ay_max == 0.f && az_max == 0.f;
+  if (!off) {
+    if (!std::isfinite(ax_max) || !std::isfinite(ax_min) || !std::isfinite(ay_max) || !std::isfinite(az_max))
+      return fail(c, SMPC_ERR_INVALID, "acceleration limits must be finite");
+    if (!(ax_max > 0.f) || !(ax_min < 0.f) || !(ay_max > 0.f) || !(az_max > 0.f))
+      return fail(c, SMPC_ERR_INVALID, "acceleration limits: ax_max > 0, ax_min < 0, ay_max > 0, az_max > 0 (all four 0: off)");
+  }
+  c->lim_on = !off;
+  c->lim[0] = ax_max; c->lim[1] = ax_min; c->lim[2] = ay_max; c->lim[3] = az_max;
+  // what the buffers hold was made with the limits as they were: nothing to hand out until a tick ran
+  c->lim_rm_iter = c->lim_gm_iter = 0;
+  return SMPC_OK;
+}
+
+int smpc_get_acceleration_limits(const smpc_ctx* c, float out[4])
+{
+  if (!c || !out) return SMPC_ERR_INVALID;
+  memcpy(out, c->lim, sizeof(c->lim));
+  return SMPC_OK;
+}
+
+int smpc_get_limited_noise(smpc_ctx* c, float* nvx, float* nvy, float* nwz)
+{
+  if (!c) return SMPC_ERR_INVALID;
+  if (!c->lim_on) return fail(c, SMPC_ERR_STATE, "no limited noise: the acceleration limits are off");
+  const bool rm = c->lim_iter != 0 && c->lim_rm_iter == c->lim_iter;
+  const bool gm = c->lim_iter != 0 && c->lim_gm_iter == c->lim_iter;
+  if (!rm && !gm) return fail(c, SMPC_ERR_STATE, "no limited noise: no tick has run with these acceleration limits");
+  HIPCK(c, hipSetDevice(c->device));
+  const uint32_t B = c->cfg.batch_size, T = c->cfg.time_steps;
+  const size_t n = static_cast<size_t>(B) * T * sizeof(float);
+  if (!rm) {
+    // the last iteration's passes read the group-major layout only: the [B,T] form is made from it
+    const size_t ngm = SMPC_GM_ELEMS(B, T);
+    for (int k = 0; k < 3; ++k) {
+      if (k == 1 && !c->holonomic) continue;
+      if (!c->l_rm[k]) HIPCK(c, hipMalloc(&c->l_rm[k], n));
+      HIPCK(c, smpc_launch_relayout(c->l_gm + k * ngm, c->l_rm[k], B, T, false, c->stream));
+    }
+    c->lim_rm_iter = c->lim_iter;
+  }
+  HIPCK(c, hipStreamSynchronize(c->stream));
+  if (nvx) HIPCK(c, hipMemcpy(nvx, c->l_rm[0], n, hipMemcpyDeviceToHost));
+  if (nvy) {
+    if (c->holonomic) HIPCK(c, hipMemcpy(nvy, c->l_rm[1], n, hipMemcpyDeviceToHost));
+    else memset(nvy, 0, n);
+  }
+  if (nwz) HIPCK(c, hipMemcpy(nwz, c->l_rm[2], n, hipMemcpyDeviceToHost));
+  return SMPC_OK;
+}
+
+// developer aid (SMPC_FLAG_PROFILE): GPU time of the last smpc_limit_noise launch, by HIP events
+int smpc_debug_limit_ms(smpc_ctx* c, float* ms)
+{
+  if (!c || !ms || !c->ev_lim[0] || !c->ev_lim[1]) return SMPC_ERR_INVALID;
+  HIPCK(c, hipSetDevice(c->device));
+  HIPCK(c, hipEventSynchronize(c->ev_lim[1]));
+  HIPCK(c, hipEventElapsedTime(ms, c->ev_lim[0], c->ev_lim[1]));
+  return SMPC_OK;
+}
+
 int smpc_set_footprint(smpc_ctx* c, const double* xy, uint32_t n_points, double circumscribed_radius,
                        double layer_cost_scaling_factor)
 {
@@ -1094,6 +1246,7 @@ int smpc_optimize(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_tick
     if (it > 0) {
       HIPCK(c, hipMemcpyAsync(c->d_u_iter, c->d_out, 3 * T * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
       u_dev = c->d_u_iter;
+      begin_limit_iteration(c, u_dev);   // this iteration limits the stored noise afresh, against its own u
     }
     c->costs_cur = it & 1;
     const float* dF = nullptr;

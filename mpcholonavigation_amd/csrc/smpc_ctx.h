@@ -27,6 +27,7 @@
 #include "../../include/smpc.h"
 #include "smpc_dev.h"
 #include "smpc_inst.h"   // the scoring-pass instances: tables, selectors, launch
+#include "smpc_limit.h"  // smpc_limit_noise: its arguments
 
 // nothing below is part of the C-ABI: keep it out of the dynamic symbol table
 #pragma GCC visibility push(hidden)
@@ -64,6 +65,9 @@ hipError_t smpc_launch_philox(const uint32_t* ctr, uint32_t k0, uint32_t k1, uin
                               hipStream_t st);
 hipError_t smpc_launch_box_muller(const uint32_t* r0, const uint32_t* r1, uint32_t n, float* z0, float* z1,
                                   hipStream_t st);
+
+// smpc_limit.hip: the stored noise of an iteration into its limited noise, in either layout
+hipError_t smpc_launch_limit_noise(const SmpcLimitArgs& a, bool group_major, hipStream_t st);
 
 namespace smpc_impl {
 
@@ -381,6 +385,18 @@ struct smpc_ctx {
   float* d_stats = nullptr;
   double* d_stats_part = nullptr;
   uint32_t stats_ld = 0;
+  // Acceleration limits (smpc_set_acceleration_limits).  While lim_on, every pass
+  // reads the LIMITED noise of its iteration in place of the stored noise: use_limited_noise
+  // (smpc_api.cpp) makes it, once per iteration and layout, in front of the first pass that reads
+  // that layout.  Buffers: allocated at the first tick that reads their layout.
+  bool lim_on = false;
+  float lim[4] = {0.f, 0.f, 0.f, 0.f};   // ax_max, ax_min, ay_max, az_max
+  float* l_rm[3] = {nullptr, nullptr, nullptr};   // [B,T] each (vy: holonomic models only)
+  float* l_gm = nullptr;                 // group-major, vx | vy | wz back to back like d_tvx (vy of a non-holonomic model: zeros)
+  const float* lim_u_dev = nullptr;      // the iteration's u on the device; null: the tick block's host copy (iteration 0)
+  uint32_t lim_iter = 0;                 // counts iterations (begin_limit_iteration); never 0 once a tick ran
+  uint32_t lim_rm_iter = 0, lim_gm_iter = 0;   // the iteration each layout's buffer holds (0: none)
+  hipEvent_t ev_lim[2] = {};             // SMPC_FLAG_PROFILE: around the last limiter launch
   hipEvent_t ev_stats[4] = {};   // SMPC_FLAG_PROFILE: around the scoring pass and around the reduction
   float stats_pass_ms = 0.f, stats_reduce_ms = 0.f;
   std::string err;
@@ -470,6 +486,14 @@ int fill_tick_out(smpc_ctx* c, smpc_tick_out* out, bool fail_flag, bool furthest
 float profile_pass_ms(smpc_ctx* c);
 uint32_t fail_only_flags(const smpc_ctx* c);
 uint32_t scoring_flags(const smpc_ctx* c, bool fail_sticky);
+// ---- acceleration limits ----
+// a tick (u_dev null: u is the tick block's) or a later iteration starts: the limited noise of the
+// iteration before is stale
+void begin_limit_iteration(smpc_ctx* c, const float* u_dev);
+// d's noise pointers at the limited noise of the iteration at hand, in the layout the pass about to
+// be launched with d reads; made first (one launch on c->stream) if no pass of the iteration read
+// that layout yet.  Limits off: nothing.
+int use_limited_noise(smpc_ctx* c, SmpcDev& d, bool group_major);
 int update_time_major(smpc_ctx* c);
 int ensure_row_major(smpc_ctx* c);
 int draw_noise(smpc_ctx* c);

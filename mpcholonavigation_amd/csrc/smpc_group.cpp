@@ -251,6 +251,12 @@ int smpc_group_optimize_some(smpc_group* g, const smpc_tick_in* ins, float* cons
       }
       SmpcFinal fin;
       fill_score_args(c, flags[i], nullptr, nullptr, c->pred.hint, true, nullptr, hd[j], fin);
+      {
+        // a member with acceleration limits: its limiter goes out here, on the group's stream (c->stream
+        // while grouped) ahead of the grouped pass, and its parameter block points at the limited noise
+        const int rc = use_limited_noise(c, hd[j], !l.wave);
+        if (rc != SMPC_OK) return rc;
+      }
       hr[j].partials = c->d_partials;
       hr[j].tuple = c->d_tuple;
       // (a wave member: its own grid — the blocks beyond it wrote nothing; the lane launch: every

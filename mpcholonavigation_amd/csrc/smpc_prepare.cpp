@@ -1391,6 +1391,7 @@ int prepare_tick(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
   c->fail_in = in->fail_flag_in != 0;
   c->P = P;
   c->tick_ready = true;
+  begin_limit_iteration(c, nullptr);   // iteration 0 limits against the uploaded u
   return SMPC_OK;
 }
 

@@ -125,7 +125,10 @@ static int score_rows(smpc_ctx* c, uint32_t flags, const float* d_furthest, Smpc
   if (!k) return fail(c, SMPC_ERR_UNSUPPORTED, "no instance of the stats pass for this horizon");
   const PassGeom& g = c->plan.wave;   // planned for every tick, whatever pass the tick itself takes
   {
-    const int rc = ensure_row_major(c);
+    int rc = ensure_row_major(c);
+    if (rc != SMPC_OK) return rc;
+    // acceleration limits: the [B,T] limited noise (a lane context has it only because of this call)
+    rc = use_limited_noise(c, d, false);
     if (rc != SMPC_OK) return rc;
   }
   c->launched = true;

@@ -171,6 +171,7 @@ void Optimizer::initialize(
     ctx_ = keep;
     keep = nullptr;
     ck(ctx_, smpc_set_critics(ctx_, &critics_.params), "smpc_set_critics");
+    pushAccelerationLimits();
     // as a fresh context: noise supplied through setNoise() does not survive initialize(), and the
     // draw starts from the seed's first epoch again (same seed, same noise as a new object)
     supplied_noise_ = false;
@@ -192,6 +193,7 @@ void Optimizer::initialize(
   built_seed_ = noise_seed_;
   have_built_ = true;
   ck(ctx_, smpc_set_critics(ctx_, &critics_.params), "smpc_set_critics");
+  pushAccelerationLimits();
   // NoiseGenerator::initialize draws once (noise_generator.cpp:26-42) ...
   ck(ctx_, smpc_seed(ctx_, noise_seed_), "smpc_seed");
   // ... and Optimizer::initialize ends in reset(), which draws again (H7)
@@ -202,6 +204,36 @@ void Optimizer::pushConstraints()
 {
   const auto & c = settings_.constraints;
   ck(ctx_, smpc_set_constraints(ctx_, c.vx_max, c.vx_min, c.vy, c.wz), "smpc_set_constraints");
+}
+
+void Optimizer::pushAccelerationLimits()
+{
+  const auto & a = accel_limits_;
+  ck(ctx_, smpc_set_acceleration_limits(ctx_, a[0], a[1], a[2], a[3]), "smpc_set_acceleration_limits");
+}
+
+void Optimizer::setAccelerationLimits(float ax_max, float ax_min, float ay_max, float az_max)
+{
+  const std::array<float, 4> before = accel_limits_;
+  if (!ctx_) {
+    // no context yet to refuse them: the library's rule (smpc_set_acceleration_limits), so that
+    // initialize() never meets values it cannot hand on
+    const bool off = ax_max == 0.0f && ax_min == 0.0f && ay_max == 0.0f && az_max == 0.0f;
+    const bool finite = std::isfinite(ax_max) && std::isfinite(ax_min) && std::isfinite(ay_max) && std::isfinite(az_max);
+    if (!off && !(finite && ax_max > 0.0f && ax_min < 0.0f && ay_max > 0.0f && az_max > 0.0f)) {
+      throw std::runtime_error(
+              "setAccelerationLimits: ax_max > 0, ax_min < 0, ay_max > 0, az_max > 0, all finite (all four 0: off)");
+    }
+    accel_limits_ = {{ax_max, ax_min, ay_max, az_max}};
+    return;   // initialize() hands them to the context it creates
+  }
+  accel_limits_ = {{ax_max, ax_min, ay_max, az_max}};
+  try {
+    pushAccelerationLimits();
+  } catch (...) {
+    accel_limits_ = before;   // refused: the context keeps what it had
+    throw;
+  }
 }
 
 void Optimizer::reset()

@@ -186,6 +186,10 @@ public:
   smpc_critic_stats getCriticStats(const TickInput & in, float * per_rollout = nullptr);
 
   void setSpeedLimit(double speed_limit, bool percentage);  // ref :428-453
+  // Acceleration limits on the sampled controls (smpc_set_acceleration_limits: ax_max > 0, ax_min < 0,
+  // ay_max > 0, az_max > 0; all zero: off, the default).  Before or after initialize(); kept across
+  // reset() and across whatever recreates the context.  Throws where the library refuses the values.
+  void setAccelerationLimits(float ax_max, float ax_min, float ay_max, float az_max);
   void reset();                                             // ref :116-132
 
   // ref :345-360: [T][3] x, y, yaw of the optimal sequence
@@ -223,6 +227,7 @@ protected:
   void setOffset(double controller_frequency);  // ref :95-114
   void setMotionModel(const std::string & model);  // ref :412-426
   void pushConstraints();
+  void pushAccelerationLimits();
 
   models::OptimizerSettings settings_{};
   models::ControlSequence control_sequence_{};
@@ -233,6 +238,7 @@ protected:
   float ackermann_min_turning_r_{0.2f};
   bool visualize_{false};
   bool lane_per_rollout_{false};
+  std::array<float, 4> accel_limits_{{0.0f, 0.0f, 0.0f, 0.0f}};   // ax_max, ax_min, ay_max, az_max; all zero: off
   uint64_t noise_seed_{0};
   bool supplied_noise_{false};
   int device_{-1};

@@ -195,6 +195,13 @@ int sortham_optimizer_last_tick(const sortham_optimizer * o, smpc_tick_out * out
   return SMPC_OK;
 }
 
+int sortham_optimizer_set_acceleration_limits(
+  sortham_optimizer * o, float ax_max, float ax_min, float ay_max, float az_max)
+{
+  if (!o) {return SMPC_ERR_INVALID;}
+  return guarded(o, [&]() {o->opt.setAccelerationLimits(ax_max, ax_min, ay_max, az_max);});
+}
+
 int sortham_optimizer_set_speed_limit(sortham_optimizer * o, double speed_limit, int percentage)
 {
   if (!o) {return SMPC_ERR_INVALID;}

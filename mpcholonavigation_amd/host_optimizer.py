@@ -55,6 +55,7 @@ PROTOTYPES = {
                                                  C.POINTER(A.SmpcCriticStats), C.c_void_p]),
     "sortham_optimizer_last_tick": (C.c_int, [_ctx, C.POINTER(A.SmpcTickOut)]),
     "sortham_optimizer_set_speed_limit": (C.c_int, [_ctx, C.c_double, C.c_int]),
+    "sortham_optimizer_set_acceleration_limits": (C.c_int, [_ctx, C.c_float, C.c_float, C.c_float, C.c_float]),
     "sortham_optimizer_reset": (C.c_int, [_ctx]),
     "sortham_optimizer_get_control_sequence": (C.c_int, [_ctx, C.c_void_p]),
     "sortham_optimizer_set_control_sequence": (C.c_int, [_ctx, C.c_void_p]),
@@ -230,6 +231,10 @@ class Optimizer:
         out = A.SmpcTickOut()
         self._ck(self.lib.sortham_optimizer_last_tick(self.h, C.byref(out)))
         return out
+
+    def set_acceleration_limits(self, ax_max, ax_min, ay_max, az_max):
+        """Bounds on how fast a sampled control may change (all zero: off); kept across reset()."""
+        self._ck(self.lib.sortham_optimizer_set_acceleration_limits(self.h, ax_max, ax_min, ay_max, az_max))
 
     def set_speed_limit(self, speed_limit, percentage):
         self._ck(self.lib.sortham_optimizer_set_speed_limit(self.h, speed_limit, int(percentage)))

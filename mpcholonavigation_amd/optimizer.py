@@ -138,6 +138,21 @@ class Smpc:
     def set_constraints(self, vx_max, vx_min, vy_max, wz_max):
         self._ck(self.lib.smpc_set_constraints(self.h, vx_max, vx_min, vy_max, wz_max))
 
+    def set_acceleration_limits(self, ax_max, ax_min, ay_max, az_max):
+        """Bounds on how fast a sampled control may change (m/s^2, m/s^2, rad/s^2); all zero: off."""
+        self._ck(self.lib.smpc_set_acceleration_limits(self.h, ax_max, ax_min, ay_max, az_max))
+
+    def get_acceleration_limits(self):
+        out = (C.c_float * 4)()
+        self._ck(self.lib.smpc_get_acceleration_limits(self.h, out))
+        return tuple(float(v) for v in out)
+
+    def get_limited_noise(self):
+        """The limited noise [B, T] x 3 the last tick's last iteration scored with."""
+        out = [np.empty((self.B, self.T), np.float32) for _ in range(3)]
+        self._ck(self.lib.smpc_get_limited_noise(self.h, _ptr(out[0]), _ptr(out[1]), _ptr(out[2])))
+        return out
+
     def set_critics(self, p: A.SmpcCriticParams):
         self._ck(self.lib.smpc_set_critics(self.h, C.byref(p)))
 

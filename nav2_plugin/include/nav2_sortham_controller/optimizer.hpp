@@ -67,6 +67,8 @@ protected:
   double controller_frequency_{0.0};
   bool regenerate_noises_{false};
   bool visualize_{false};
+  // acceleration limits on the sampled controls (upstream nav2_mppi_controller's names); 0: off
+  float ax_max_{0.0f}, ax_min_{0.0f}, ay_max_{0.0f}, az_max_{0.0f};
   models::Trajectories generated_trajectories_;
   rclcpp::Logger logger_{rclcpp::get_logger("SORTHAMController")};
 };

@@ -44,6 +44,11 @@ void Optimizer::getParams()
   getParam(s.base_constraints.vx_min, "vx_min", -0.35);
   getParam(s.base_constraints.vy, "vy_max", 0.5);
   getParam(s.base_constraints.wz, "wz_max", 1.9);
+  // acceleration limits: off unless set (upstream's defaults are 3.0 / -3.0 / 3.0 / 3.5)
+  getParam(ax_max_, "ax_max", 0.0);
+  getParam(ax_min_, "ax_min", 0.0);
+  getParam(ay_max_, "ay_max", 0.0);
+  getParam(az_max_, "az_max", 0.0);
   getParam(s.sampling_std.vx, "vx_std", 0.2);
   getParam(s.sampling_std.vy, "vy_std", 0.2);
   getParam(s.sampling_std.wz, "wz_std", 0.4);
@@ -77,6 +82,7 @@ void Optimizer::reset()
     getAcker(min_turning_r, "min_turning_r", 0.2);
     host_.setAckermannMinTurningRadius(min_turning_r);
   }
+  host_.setAccelerationLimits(ax_max_, ax_min_, ay_max_, az_max_);
   host_.initialize(settings_, motion_model_name_, controller_frequency_, cc, regenerate_noises_);
   generated_trajectories_.reset(settings_.batch_size, settings_.time_steps);
   RCLCPP_INFO(logger_, "Optimizer reset");
