@@ -651,6 +651,41 @@ int smpc_group_optimize_some(smpc_group* group, const smpc_tick_in* ins, float* 
  * included).  Either pointer may be NULL; a NULL group returns SMPC_ERR_INVALID.  (ABI 3) */
 int smpc_group_stats(const smpc_group* group, uint64_t* batched_launches, uint64_t* single_ticks);
 
+/* smpc_critic_breakdown for the members of a group, the group staying a group: ins[n], u_ins[n]
+ * (3*T floats each, read only), take[n] as in smpc_group_optimize_some (NULL: every member),
+ * stats[n], per_rollout (NULL, or n pointers of which any may be NULL; else
+ * [SMPC_STATS_ROWS][batch_size] floats of that member), status[n].
+ * For every member taken, stats[i] and per_rollout[i] are bit for bit what smpc_critic_breakdown
+ * returns on an identical context that is in no group — the first iteration's flags, the same
+ * noise (limited, where the member has acceleration limits) and host gates, the true furthest
+ * point, the all-collide re-score, fail_flag_in — and status[i] is SMPC_OK or the code that call
+ * would have returned (SMPC_ERR_UNSUPPORTED for both collision critics with a footprint, a refused
+ * plan, ...), the message in that member's smpc_last_error.  A member that fails this way does not
+ * fail the others.  stats[i], per_rollout[i] and status[i] of a member that is not taken are
+ * neither read nor written, and nothing of it is prepared.
+ * With time_steps <= 64 the members taken ride ONE furthest-point pre-pass (those whose critics
+ * need it), ONE launch of smpc_pass_stats_many and ONE pair of reduction launches, behind one
+ * memset and one upload, in front of one copy back and one wait: their number does not depend on
+ * n.  A member whose rollouts all collide is re-scored behind that, on its own.  Members of a
+ * group with time_steps > 64 are scored one by one inside the call, with the same results (as
+ * smpc_pass_many has no instance for them either).
+ * Changes nothing a later round depends on, for any member: control sequences, costs, result
+ * blocks, furthest-point prediction, launch plan and counters stay, and so do the two counters of
+ * smpc_group_stats.  The float regions live in one allocation of the group's, sized at the first
+ * call and again when the members taken or their batch sizes need more.
+ * Returns an error only for NULL arguments (before any member is touched), when no member is
+ * taken, or for a device error; a call that follows an abandoned round waits for the group's
+ * stream first, as a round does.  (An addition under ABI 3, like smpc_group_optimize_some.) */
+int smpc_group_critic_breakdown(smpc_group* group, const smpc_tick_in* ins,
+                                const float* const* u_ins, const uint8_t* take,
+                                smpc_critic_stats* stats, float* const* per_rollout,
+                                int32_t* status);
+/* Which way the member-breakdowns of smpc_group_critic_breakdown went so far: *batched_members
+ * counts those that rode a grouped stats launch, *single_members those scored one by one
+ * (time_steps > 64).  Either pointer may be NULL; a NULL group returns SMPC_ERR_INVALID.  (ABI 3) */
+int smpc_group_breakdown_counts(const smpc_group* group, uint64_t* batched_members,
+                                uint64_t* single_members);
+
 /* ---- the same tick with the exchanges inside the library (RCCL over xGMI) ----
  * One ncclComm per ctx, one call per tick: upload -> score -> ncclAllGather(tuples) ->
  * combine -> wait, all on the ctx's stream (speculate != 0: the furthest point of the

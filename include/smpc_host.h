@@ -137,6 +137,17 @@ int sortham_fleet_eval_control(sortham_fleet* fleet, const smpc_tick_in* ins, co
  * context), and the retries the fleet ran alone.  Any pointer may be NULL. */
 int sortham_fleet_stats(const sortham_fleet* fleet, uint64_t* batched_launches, uint64_t* single_ticks,
                         uint64_t* retries);
+/* FleetOptimizer::getCriticStats: sortham_optimizer_critic_stats for the members taken, the fleet
+ * staying grouped (smpc.h: smpc_group_critic_breakdown).  ins[n], take[n] as for
+ * sortham_fleet_eval_control; stats[n]; per_rollout: NULL, or n pointers of which any may be NULL,
+ * else [SMPC_STATS_ROWS][batch_size] floats of that member; status[n]: SMPC_OK,
+ * SORTHAM_FLEET_NOT_TAKEN (the member's entries are not written), or the SMPC_ERR_* that member's
+ * sortham_optimizer_critic_stats would have returned — SMPC_ERR_STATE for a member that was shut
+ * down or destroyed — with the text in that member's sortham_optimizer_last_error.  Changes
+ * nothing: the next round returns what it would have returned without the call.  Returns SMPC_OK,
+ * or the SMPC_ERR_* of a call that failed as a whole (sortham_fleet_last_error). */
+int sortham_fleet_critic_stats(sortham_fleet* fleet, const smpc_tick_in* ins, const uint8_t* take,
+                               smpc_critic_stats* stats, float* const* per_rollout, int32_t* status);
 /* n_rounds rounds on the same inputs from a compiled caller (host/tick_loop.cpp), the results of
  * the last one in twists / outs / status (any may be NULL).  alone != 0: instead of the fleet round,
  * the members' own sortham_optimizer_eval_control one after the other on their ungrouped contexts

@@ -314,6 +314,10 @@ PROTOTYPES = {
     "smpc_group_optimize_some": (C.c_int, [_ctx, C.POINTER(SmpcTickIn), C.POINTER(C.c_void_p),
                                            C.POINTER(SmpcTickOut), C.c_void_p]),
     "smpc_group_stats": (C.c_int, [_ctx, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "smpc_group_critic_breakdown": (C.c_int, [_ctx, C.POINTER(SmpcTickIn), C.POINTER(C.c_void_p), C.c_void_p,
+                                              C.POINTER(SmpcCriticStats), C.POINTER(C.c_void_p),
+                                              C.POINTER(C.c_int32)]),
+    "smpc_group_breakdown_counts": (C.c_int, [_ctx, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "smpc_shard_comm_id": (C.c_int, [C.c_void_p, C.c_uint32]),
     "smpc_shard_comm_init": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int]),
     "smpc_shard_p2p_handle": (C.c_int, [_ctx, C.c_void_p, C.c_uint32]),

@@ -4,8 +4,9 @@
 //   smpc_api.cpp      lifecycle, setters, the single-GPU tick (smpc_optimize), launch helpers
 //   smpc_prepare.cpp  per-tick host work: gates, path tables, lookup tables, LDS carve-up
 //   smpc_shard.cpp    batch-sharded tick, RCCL resolved at run time
-//   smpc_group.cpp    several planning instances per launch
-//   smpc_stats.cpp    per-critic breakdown of a tick (smpc_critic_breakdown)
+//   smpc_group.cpp    several planning instances per launch (the group object: smpc_group.h)
+//   smpc_stats.cpp    per-critic breakdown of a tick (smpc_critic_breakdown) and of a group's
+//                     members (smpc_group_critic_breakdown)
 #ifndef SMPC_CTX_H_
 #define SMPC_CTX_H_
 

@@ -353,4 +353,11 @@ struct SmpcWaveGeom {
   uint32_t grid;
 };
 
+// One member's rows in smpc_pass_stats_many (smpc_group_critic_breakdown): [SMPC_STATS_ROWS][ld]
+// floats, as smpc_pass_stats takes them in its arguments
+struct SmpcStatsDst {
+  float* stats;
+  uint32_t ld;
+};
+
 #endif

@@ -2,26 +2,11 @@
 // BASELINE configs[4]: multi-robot fleets): one upload, one scoring launch, one reduction for a
 // set of contexts.
 #include "smpc_ctx.h"
+#include "smpc_group.h"
 
 using namespace smpc_impl;
 
 extern "C" {
-
-struct smpc_group {
-  std::vector<smpc_ctx*> ctxs;
-  std::vector<hipStream_t> saved_stream;
-  std::vector<uint8_t*> saved_h_tick, saved_d_tick;
-  uint8_t* h_all = nullptr;   // pinned: n tick blocks, then SmpcDev[n], SmpcReduceArgs[n], SmpcWaveGeom[n]
-  uint8_t* d_all = nullptr;
-  size_t slot = 0, off_dev = 0, off_red = 0, off_geo = 0, total = 0;
-  hipStream_t stream = nullptr;
-  uint64_t batched_ticks = 0, single_ticks = 0;
-  uint64_t batched_launches = 0;   // scoring launches that carried two or more members (smpc_group_stats)
-  // a batched launch went out and not every riding member's fetch_out has returned since: a round
-  // abandoned on an error leaves it set, and the next round waits for the stream before it writes
-  // h_all / d_all again
-  bool launched = false;
-};
 
 int smpc_group_create(smpc_ctx* const* ctxs, uint32_t n, smpc_group** out)
 {
@@ -45,8 +30,14 @@ int smpc_group_create(smpc_ctx* const* ctxs, uint32_t n, smpc_group** out)
   g->off_red = g->off_dev + align_up(static_cast<uint32_t>(sizeof(SmpcDev)) * n, 256);
   g->off_geo = g->off_red + align_up(static_cast<uint32_t>(sizeof(SmpcReduceArgs)) * n, 256);
   g->total = g->off_geo + align_up(static_cast<uint32_t>(sizeof(SmpcWaveGeom)) * n, 256);
-  if (hipHostMalloc(&g->h_all, g->total, hipHostMallocDefault) != hipSuccess ||
-    hipMalloc(&g->d_all, g->total) != hipSuccess)
+  // behind what a round hands over: the further argument arrays of smpc_group_critic_breakdown
+  g->off_fdev = g->total;
+  g->off_fgeo = g->off_fdev + align_up(static_cast<uint32_t>(sizeof(SmpcDev)) * n, 256);
+  g->off_sdst = g->off_fgeo + align_up(static_cast<uint32_t>(sizeof(SmpcWaveGeom)) * n, 256);
+  g->off_sred = g->off_sdst + align_up(static_cast<uint32_t>(sizeof(SmpcStatsDst)) * n, 256);
+  g->total_stats = g->off_sred + align_up(static_cast<uint32_t>(sizeof(SmpcStatsReduceArgs)) * n, 256);
+  if (hipHostMalloc(&g->h_all, g->total_stats, hipHostMallocDefault) != hipSuccess ||
+    hipMalloc(&g->d_all, g->total_stats) != hipSuccess)
   {
     if (g->h_all) (void)hipHostFree(g->h_all);
     delete g;
@@ -85,6 +76,9 @@ void smpc_group_destroy(smpc_group* g)
   }
   if (g->h_all) (void)hipHostFree(g->h_all);
   if (g->d_all) (void)hipFree(g->d_all);
+  if (g->d_stats) (void)hipFree(g->d_stats);
+  if (g->d_stats_part) (void)hipFree(g->d_stats_part);
+  if (g->h_stats_out) (void)hipHostFree(g->h_stats_out);
   delete g;
 }
 

@@ -1,0 +1,48 @@
+// smpc_group.h — the group object behind smpc_group_* (include/smpc.h), shared by smpc_group.cpp
+// (rounds of ticks) and smpc_stats.cpp (smpc_group_critic_breakdown).  Internal: not part of the
+// C-ABI.
+#ifndef SMPC_GROUP_H_
+#define SMPC_GROUP_H_
+
+#include "smpc_ctx.h"
+
+#pragma GCC visibility push(hidden)
+
+extern "C" {
+
+struct smpc_group {
+  std::vector<smpc_ctx*> ctxs;
+  std::vector<hipStream_t> saved_stream;
+  std::vector<uint8_t*> saved_h_tick, saved_d_tick;
+  uint8_t* h_all = nullptr;   // pinned: n tick blocks, then SmpcDev[n], SmpcReduceArgs[n], SmpcWaveGeom[n]
+  uint8_t* d_all = nullptr;
+  size_t slot = 0, off_dev = 0, off_red = 0, off_geo = 0, total = 0;
+  hipStream_t stream = nullptr;
+  uint64_t batched_ticks = 0, single_ticks = 0;
+  uint64_t batched_launches = 0;   // scoring launches that carried two or more members (smpc_group_stats)
+  // a batched launch went out and not every riding member's fetch_out has returned since: a round
+  // abandoned on an error leaves it set, and the next round waits for the stream before it writes
+  // h_all / d_all again
+  bool launched = false;
+  // ---- smpc_group_critic_breakdown (smpc_stats.cpp) ----
+  // further argument arrays in h_all / d_all, behind `total` (a round never uploads them): the
+  // pre-pass's parameter blocks and geometry, the members' rows, the reduction's arguments
+  size_t off_fdev = 0, off_fgeo = 0, off_sdst = 0, off_sred = 0, total_stats = 0;
+  // the members' float regions in ONE allocation (GroupStatsArena in smpc_stats.cpp), sized at the
+  // first grouped breakdown and again when the members taken or their batch sizes ask for more; the
+  // reduction's double partials likewise; the results' pinned landing place
+  float* d_stats = nullptr;
+  size_t stats_cap = 0;        // floats
+  double* d_stats_part = nullptr;
+  size_t stats_part_cap = 0;   // doubles
+  float* h_stats_out = nullptr;
+  size_t stats_out_cap = 0;    // floats
+  bool stats_lds_set = false;
+  uint64_t breakdown_batched = 0, breakdown_single = 0;   // member-breakdowns by route (smpc_group_breakdown_counts)
+};
+
+}  // extern "C"
+
+#pragma GCC visibility pop
+
+#endif  // SMPC_GROUP_H_

@@ -78,6 +78,32 @@ uint32_t stats_reduce_slices(uint32_t B, uint32_t* slice_out);
 hipError_t stats_launch_reduce(const float* stats, uint32_t ld, const float* costs, uint32_t B, float k2, double* part,
                                const float* pass_partials, uint32_t nblk, uint32_t T, SmpcStatsOut* out, hipStream_t st);
 
+// ---- smpc_group_critic_breakdown (smpc_wave_stats_many.hip): the breakdown of a group's members per launch ----
+// fn: smpc_pass_stats_many<R, FULL>; fn_furthest: smpc_furthest_many<R, 1, FULL>, the pre-pass.  R = 1 only.
+struct StatsManyInst { int r; bool full; const void* fn; const void* fn_furthest; };
+const StatsManyInst* stats_many_select(int R, uint32_t T);
+hipError_t stats_many_set_lds_limit(int bytes);
+// one member's arguments of the two reduction kernels (device memory): those of stats_launch_reduce
+struct SmpcStatsReduceArgs {
+  const float* stats;
+  const float* costs;
+  double* part;
+  const float* pass_partials;
+  SmpcStatsOut* out;
+  uint32_t ld, B, slice, S;   // S: this member's slices, of `slice` rollouts
+  uint32_t nblk, TL;          // the scoring pass's blocks and the floats of one of its partials
+  float k2;
+};
+// n members in one launch of grid_max x n blocks: parameter blocks, geometry and (the stats pass) rows
+// per member in device memory; lds_max: the largest carve-up's total.  Nothing is recorded for
+// smpc_debug_last_pass_kernel.
+hipError_t stats_launch_furthest_many(const StatsManyInst* k, const SmpcDev* d_many, const SmpcWaveGeom* d_geom, uint32_t n,
+                                      uint32_t grid_max, uint32_t lds_max, uint32_t block, hipStream_t st);
+hipError_t stats_launch_many(const StatsManyInst* k, const SmpcDev* d_many, const SmpcWaveGeom* d_geom, const SmpcStatsDst* d_dst,
+                             uint32_t n, uint32_t grid_max, uint32_t lds_max, uint32_t block, hipStream_t st);
+// smpc_reduce_stats_many + smpc_reduce_stats_final_many; slices_max: the most slices any member has
+hipError_t stats_launch_reduce_many(const SmpcStatsReduceArgs* d_many, uint32_t n, uint32_t slices_max, hipStream_t st);
+
 hipError_t wave_set_lds_limit(int bytes);
 hipError_t lane_set_lds_limit(int bytes);
 hipError_t split_set_lds_limit(int bytes);

@@ -1,5 +1,6 @@
-// smpc_wave_pass.inc — the wave-per-rollout pass: ONE text, compiled under two kernel names
-// (smpc_kernels.hip and smpc_wave_many.hip include it, as smpc_lane.hip does smpc_lane_pass.inc).
+// smpc_wave_pass.inc — the wave-per-rollout pass: ONE text, compiled under several kernel names
+// (smpc_kernels.hip, smpc_wave_many.hip, smpc_wave_stats.hip and smpc_wave_stats_many.hip include it,
+// as smpc_lane.hip does smpc_lane_pass.inc).
 //   WAVE_PASS_KERNEL  names the kernel
 //   WAVE_PASS_MANY    0: smpc_pass — one planning instance, parameter block and LDS carve-up in the
 //                        kernel arguments
@@ -17,21 +18,40 @@
 //                        wherever add_cost_pow folds a term into the cost, and at the gamma add, one
 //                        lane stores it to stats[row * stats_ld + rollout] (rows: SMPC_CRITIC_* of
 //                        include/smpc.h).  Undefined or 0: not a line of this text changes.
+//                        With WAVE_PASS_MANY 1: smpc_pass_stats_many<R, FULL> (smpc_wave_stats_many.hip,
+//                        smpc_group_critic_breakdown) — blockIdx.y picks the member, whose rows and their
+//                        leading dimension (SmpcStatsDst) come from device memory like its parameter block.
 template <int R, bool FULL>
 #else
 template <int R, int MODE, bool FULL>
 #endif
 #if WAVE_PASS_MANY
 __global__ void __launch_bounds__((R == 4 ? 512 : 1024), (R == 4 ? 2 : 4))
+#if WAVE_PASS_STATS
+WAVE_PASS_KERNEL(const SmpcDev* __restrict__ many, const SmpcWaveGeom* __restrict__ geom, const SmpcStatsDst* __restrict__ dst)
+{
+  constexpr int MODE = 2;
+  static_assert(R == 1, "the grouped rows: T <= 64");
+#else
 WAVE_PASS_KERNEL(const SmpcDev* __restrict__ many, const SmpcWaveGeom* __restrict__ geom)
 {
+#if WAVE_PASS_MANY_FURTHEST
+  // (smpc_wave_stats_many.hip: the furthest-point pre-pass of smpc_group_critic_breakdown)
+  static_assert(R == 1 && MODE == 1, "the grouped pre-pass: T <= 64, furthest point only");
+#else
   static_assert(R == 1 && (MODE == 0 || MODE == 3 || MODE == 4), "the grouped rows: T <= 64, the lean scoring modes");
+#endif
+#endif
   constexpr bool MANY = true;
   // Members differ in batch size, hence in the blocks they need: a block beyond its member's own
   // grid leaves before the first barrier, having written nothing (uniform over the block)
   if (blockIdx.x >= geom[blockIdx.y].grid) return;
   const SmpcDev& p = many[blockIdx.y];
   const SmpcLds& L = geom[blockIdx.y].lds;
+#if WAVE_PASS_STATS
+  float* __restrict__ const stats = dst[blockIdx.y].stats;
+  const uint32_t stats_ld = dst[blockIdx.y].ld;
+#endif
 #define WAVE_PASS_GRID (geom[blockIdx.y].grid)
 #else
 #if WAVE_PASS_STATS

@@ -2,6 +2,7 @@
 #include "fleet.hpp"
 
 #include <algorithm>
+#include <cstring>
 #include <exception>
 
 namespace SORTHAM_HOST_NS
@@ -243,6 +244,121 @@ int FleetOptimizer::evalControl(
       r.error = e.what();
     }
     r.out = m->last_out_;
+  }
+  return SMPC_OK;
+}
+
+int FleetOptimizer::getCriticStats(
+  const std::vector<Pose2D> & poses, const std::vector<Twist2D> & speeds,
+  const std::vector<models::Path> & plans, const std::vector<Pose2D> & goals,
+  const std::vector<float> & goal_checker_xy_tolerances, const std::vector<uint8_t> & take,
+  std::vector<MemberCriticStats> & out, const std::vector<float *> & per_rollout)
+{
+  const size_t n = members_.size();
+  out.assign(n, MemberCriticStats{});
+  if (poses.size() < n || speeds.size() < n || plans.size() < n || goals.size() < n ||
+    goal_checker_xy_tolerances.size() < n || (!take.empty() && take.size() < n) ||
+    (!per_rollout.empty() && per_rollout.size() < n))
+  {
+    return fail(SMPC_ERR_INVALID, "one pose, speed, plan, goal and tolerance per member");
+  }
+  auto taken = [&](size_t i) {return take.empty() || take[i] != 0;};
+  bool any = false;
+  for (size_t i = 0; i < n; ++i) {
+    if (!taken(i)) {
+      continue;
+    }
+    if (!members_[i] || !members_[i]->ctx_) {
+      out[i].status = SMPC_ERR_STATE;
+      out[i].error = "member " + std::to_string(i) + " was shut down or destroyed: it has no context";
+      continue;
+    }
+    any = true;
+  }
+  if (!any) {
+    return SMPC_OK;
+  }
+  // (as a round: no group, or a member taken that got its context after the group was formed)
+  bool stale = !group_;
+  for (size_t i = 0; i < n && !stale; ++i) {
+    stale = taken(i) && out[i].status != SMPC_ERR_STATE && slot_[i] < 0;
+  }
+  if (stale) {
+    const int rc = regroup();
+    if (rc != SMPC_OK) {
+      return rc;
+    }
+  }
+  // the smpc_tick_in evalControl's first optimize() would hand over (prepare() clears the fail
+  // flag), without touching the members' per-tick state: Optimizer::getCriticStats, per slot
+  const size_t g = owner_.size();
+  std::vector<smpc_tick_in> ins(g);
+  std::vector<std::vector<float>> u(g);
+  std::vector<const float *> u_ptr(g, nullptr);
+  std::vector<uint8_t> tk(g, 0);
+  std::vector<smpc_critic_stats> st(g);
+  std::vector<float *> rows(g, nullptr);
+  std::vector<int32_t> status(g, SMPC_OK);
+  for (size_t i = 0; i < n; ++i) {
+    if (!taken(i) || out[i].status == SMPC_ERR_STATE) {
+      continue;
+    }
+    Optimizer * m = members_[i];
+    const size_t s = static_cast<size_t>(slot_[i]);
+    smpc_tick_in & in = ins[s];
+    std::memset(&in, 0, sizeof(in));
+    in.pose_x = poses[i].x;
+    in.pose_y = poses[i].y;
+    in.pose_yaw = static_cast<float>(poses[i].yaw);
+    in.speed_vx = speeds[i].vx;
+    in.speed_vy = speeds[i].vy;
+    in.speed_wz = speeds[i].wz;
+    in.path_x = plans[i].x.data();
+    in.path_y = plans[i].y.data();
+    in.path_yaw = plans[i].yaws.data();
+    in.path_len = static_cast<uint32_t>(plans[i].x.size());
+    in.goal_x = goals[i].x;
+    in.goal_y = goals[i].y;
+    in.goal_checker_xy_tolerance = goal_checker_xy_tolerances[i];
+    const unsigned int T = m->settings_.time_steps;
+    u[s].resize(3 * static_cast<size_t>(T));
+    std::memcpy(u[s].data(), m->control_sequence_.vx.data(), T * sizeof(float));
+    std::memcpy(u[s].data() + T, m->control_sequence_.vy.data(), T * sizeof(float));
+    std::memcpy(u[s].data() + 2 * T, m->control_sequence_.wz.data(), T * sizeof(float));
+    u_ptr[s] = u[s].data();
+    try {
+      m->pushConstraints();   // (what the tick pushes too: the same values)
+    } catch (const std::exception & e) {
+      return fail(SMPC_ERR_STATE, "member " + std::to_string(i) + ": " + e.what());
+    }
+    tk[s] = 1;
+    rows[s] = per_rollout.empty() ? nullptr : per_rollout[i];
+  }
+  const int rc = smpc_group_critic_breakdown(
+    group_, ins.data(), u_ptr.data(), tk.data(), st.data(), per_rollout.empty() ? nullptr : rows.data(),
+    status.data());
+  if (rc != SMPC_OK) {
+    std::string what = smpc_last_error(nullptr);
+    for (size_t s = 0; s < g && rc == SMPC_ERR_DEVICE; ++s) {
+      const std::string now = tk[s] ? smpc_last_error(members_[owner_[s]]->ctx_) : "";
+      if (!now.empty()) {
+        what = "member " + std::to_string(owner_[s]) + ": " + now;
+        break;
+      }
+    }
+    return fail(rc, "smpc_group_critic_breakdown: " + what);
+  }
+  for (size_t s = 0; s < g; ++s) {
+    if (!tk[s]) {
+      continue;
+    }
+    MemberCriticStats & r = out[owner_[s]];
+    r.status = status[s];
+    if (status[s] == SMPC_OK) {
+      r.stats = st[s];
+    } else {
+      r.error = std::string("smpc_critic_breakdown: ") + smpc_last_error(members_[owner_[s]]->ctx_);
+    }
   }
   return SMPC_OK;
 }

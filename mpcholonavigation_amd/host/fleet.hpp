@@ -46,6 +46,16 @@ struct MemberResult
   std::string error;
 };
 
+// A member's entry of FleetOptimizer::getCriticStats: status SMPC_OK with the statistics,
+// FLEET_NOT_TAKEN (nothing written), or the SMPC_ERR_* Optimizer::getCriticStats would have thrown
+// with (the text in error); SMPC_ERR_STATE for a member without a context.
+struct MemberCriticStats
+{
+  smpc_critic_stats stats{};
+  int status{FLEET_NOT_TAKEN};
+  std::string error;
+};
+
 struct FleetStats
 {
   uint64_t batched_launches{0};   // smpc_group_stats, summed over the groups the fleet has had
@@ -79,6 +89,20 @@ public:
     const std::vector<models::Path> & plans, const std::vector<Pose2D> & goals,
     const std::vector<float> & goal_checker_xy_tolerances, const std::vector<uint8_t> & take,
     std::vector<MemberResult> & results);
+
+  // Optimizer::getCriticStats for the members taken, the fleet staying grouped (smpc.h:
+  // smpc_group_critic_breakdown — launches whose number does not depend on the fleet's size): per
+  // member the statistics of the tick the next evalControl round would run first, from its control
+  // sequence as it stands, its constraints pushed as getCriticStats pushes them.  Arguments as
+  // evalControl's; per_rollout: empty, or one pointer per member (null, or
+  // [SMPC_STATS_ROWS][batch_size] floats).  Regroups first if the fleet is ungrouped.  Changes
+  // nothing: the next round returns what it would have returned without the call.  Returns SMPC_OK,
+  // or the SMPC_ERR_* of a call that failed as a whole (text in lastError()).
+  int getCriticStats(
+    const std::vector<Pose2D> & poses, const std::vector<Twist2D> & speeds,
+    const std::vector<models::Path> & plans, const std::vector<Pose2D> & goals,
+    const std::vector<float> & goal_checker_xy_tolerances, const std::vector<uint8_t> & take,
+    std::vector<MemberCriticStats> & out, const std::vector<float *> & per_rollout = {});
 
   FleetStats stats() const;
   const std::string & lastError() const {return err_;}

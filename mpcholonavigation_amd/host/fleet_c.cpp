@@ -115,6 +115,59 @@ int sortham_fleet_eval_control(
   return SMPC_OK;
 }
 
+int sortham_fleet_critic_stats(
+  sortham_fleet * f, const smpc_tick_in * ins, const uint8_t * take, smpc_critic_stats * stats,
+  float * const * per_rollout, int32_t * status)
+{
+  if (!f || !ins || !stats || !status) {
+    return SMPC_ERR_INVALID;
+  }
+  const size_t n = f->handles.size();
+  std::vector<sortham_ns::MemberCriticStats> res;
+  try {
+    for (size_t i = 0; i < n; ++i) {
+      f->take[i] = (!take || take[i]) ? 1 : 0;
+      if (!f->take[i]) {
+        continue;
+      }
+      const smpc_tick_in & in = ins[i];
+      if (in.path_len && (!in.path_x || !in.path_y || !in.path_yaw)) {
+        f->err = "member " + std::to_string(i) + ": null plan";
+        return SMPC_ERR_INVALID;
+      }
+      f->poses[i] = {in.pose_x, in.pose_y, static_cast<double>(in.pose_yaw)};
+      f->goals[i] = {in.goal_x, in.goal_y, 0.0};
+      f->speeds[i] = {in.speed_vx, in.speed_vy, in.speed_wz};
+      f->plans[i].x.assign(in.path_x, in.path_x + in.path_len);
+      f->plans[i].y.assign(in.path_y, in.path_y + in.path_len);
+      f->plans[i].yaws.assign(in.path_yaw, in.path_yaw + in.path_len);
+      f->tolerances[i] = in.goal_checker_xy_tolerance;
+    }
+    std::vector<float *> rows;
+    if (per_rollout) {
+      rows.assign(per_rollout, per_rollout + n);
+    }
+    const int rc = f->fleet->getCriticStats(
+      f->poses, f->speeds, f->plans, f->goals, f->tolerances, f->take, res, rows);
+    if (rc != SMPC_OK) {
+      f->err = f->fleet->lastError();
+      return rc;
+    }
+  } catch (const std::exception & e) {
+    f->err = e.what();
+    return SORTHAM_ERR_THROWN;
+  }
+  for (size_t i = 0; i < n; ++i) {
+    status[i] = res[i].status;
+    if (res[i].status == SMPC_OK) {
+      stats[i] = res[i].stats;
+    } else if (res[i].status != sortham_ns::FLEET_NOT_TAKEN && f->fleet->member(i)) {
+      f->handles[i]->err = res[i].error;
+    }
+  }
+  return SMPC_OK;
+}
+
 int sortham_fleet_stats(
   const sortham_fleet * f, uint64_t * batched_launches, uint64_t * single_ticks, uint64_t * retries)
 {

@@ -80,6 +80,12 @@ FLEET_PROTOTYPES = {
                                            C.POINTER(C.c_uint32)]),
 }
 
+# the fleet's critic statistics (FleetOptimizer::getCriticStats): bound with the fleet's entry points
+FLEET_STATS_PROTOTYPES = {
+    "sortham_fleet_critic_stats": (C.c_int, [_ctx, C.POINTER(A.SmpcTickIn), C.c_void_p,
+                                             C.POINTER(A.SmpcCriticStats), C.POINTER(C.c_void_p), C.c_void_p]),
+}
+
 TICKS_SHIFT, TICKS_REDRAW_ASYNC, TICKS_SHARD, TICKS_SHARD_SPECULATE = 1, 2, 4, 8
 
 DEFAULT_CRITICS = ["ObstaclesCritic", "PathAlignCritic", "PathFollowCritic", "GoalAngleCritic",
@@ -100,6 +106,7 @@ def load_fleet_library():
     lib = load_library()
     if not _fleet_bound:
         A.bind(lib, FLEET_PROTOTYPES)
+        A.bind(lib, FLEET_STATS_PROTOTYPES)
         _fleet_bound = True
     return lib
 
@@ -339,6 +346,35 @@ class FleetOptimizer:
         if rc != 0:
             raise FleetError(rc, self.lib.sortham_fleet_last_error(self.h).decode())
         return self._results(on)
+
+    def critic_stats(self, ticks, take=None, per_rollout=False):
+        """FleetOptimizer::getCriticStats: Optimizer.critic_stats for the members taken, the fleet staying
+        grouped.  -> per member what Optimizer.critic_stats returns (optimizer.CriticStats) for the tick
+        the next eval_control round would run first; None for a member that is not taken; the
+        FleetError (not raised) with that member's code and text where its own call would have failed.
+        The next round is unaffected.  Raises FleetError when the call failed as a whole."""
+        from .optimizer import critic_names, critic_stats_from_c, load_library as load_smpc
+        on, mask = self._fill(ticks, take)
+        n = len(self.members)
+        st = (A.SmpcCriticStats * n)()
+        status = np.zeros(n, np.int32)
+        rows = [np.empty((A.SMPC_STATS_ROWS, m.B), np.float32) if per_rollout and on[i] else None
+                for i, m in enumerate(self.members)]
+        rptr = (C.c_void_p * n)(*[r.ctypes.data if r is not None else None for r in rows])
+        rc = self.lib.sortham_fleet_critic_stats(self.h, self._ins, None if mask is None else _ptr(mask), st,
+                                                 rptr if per_rollout else None, _ptr(status))
+        if rc != 0:
+            raise FleetError(rc, self.lib.sortham_fleet_last_error(self.h).decode())
+        names = critic_names(load_smpc())
+        res = []
+        for i, m in enumerate(self.members):
+            if not on[i] or status[i] == SORTHAM_FLEET_NOT_TAKEN:
+                res.append(None)
+            elif status[i] != 0:
+                res.append(FleetError(int(status[i]), m.lib.sortham_optimizer_last_error(m.h).decode()))
+            else:
+                res.append(critic_stats_from_c(A.SmpcCriticStats.from_buffer_copy(st[i]), names, rows[i]))
+        return res
 
     def run_rounds(self, ticks, n_rounds, take=None, alone=False):
         """sortham_fleet_run_rounds: n_rounds rounds on the same inputs from the compiled loop of

@@ -427,6 +427,61 @@ class SmpcGroup:
             raise SmpcError(rc, "smpc_group_stats")
         return types.SimpleNamespace(batched_launches=launches.value, single_ticks=singles.value)
 
+    def critic_stats(self, ticks, us, take=None, per_rollout=False):
+        """Smpc.critic_stats for the members, the group staying a group (smpc_group_critic_breakdown):
+        ticks, us — one per member, as optimize takes them, us read only.  Returns one entry per
+        member: what Smpc.critic_stats returns on an identical context outside any group, bit for
+        bit; None for a member left out by take; the SmpcError (not raised: the others have their
+        statistics) for a member the call refused on its own, e.g. both collision critics with a
+        footprint.  Changes nothing the next optimize depends on."""
+        n = len(self.members)
+        if len(ticks) != n or len(us) != n:
+            raise ValueError("one tick and one control sequence per member")
+        if take is not None and len(take) != n:
+            raise ValueError("one take entry per member")
+        on = [True] * n if take is None else [bool(v) for v in take]
+        ins = (A.SmpcTickIn * n)()
+        T = self.members[0].T
+        ubuf = np.zeros((n, 3, T), np.float32)
+        rows = [np.empty((A.SMPC_STATS_ROWS, m.B), np.float32) if per_rollout and on[i] else None
+                for i, m in enumerate(self.members)]
+        for i in range(n):
+            if on[i]:
+                ins[i] = ticks[i].c
+                u = np.asarray(us[i], dtype=np.float32)
+                if u.shape != (3, T):
+                    raise ValueError(f"u must be [3, {T}]")
+                ubuf[i] = u
+        uptr = (C.c_void_p * n)(*[ubuf[i].ctypes.data for i in range(n)])
+        rptr = (C.c_void_p * n)(*[r.ctypes.data if r is not None else None for r in rows])
+        st = (A.SmpcCriticStats * n)()
+        status = (C.c_int32 * n)()
+        mask = None if take is None else (C.c_uint8 * n)(*[int(v) for v in on])
+        rc = self.lib.smpc_group_critic_breakdown(self.h, ins, uptr, mask, st, rptr if per_rollout else None, status)
+        if rc != 0:
+            msg = next((m.lib.smpc_last_error(m.h).decode() for m in self.members
+                        if m.lib.smpc_last_error(m.h)), "") or self.lib.smpc_last_error(None).decode()
+            raise SmpcError(rc, msg)
+        names = critic_names(self.lib)
+        res = []
+        for i, m in enumerate(self.members):
+            if not on[i]:
+                res.append(None)
+            elif status[i] != 0:
+                res.append(SmpcError(int(status[i]), m.lib.smpc_last_error(m.h).decode()))
+            else:
+                res.append(critic_stats_from_c(A.SmpcCriticStats.from_buffer_copy(st[i]), names, rows[i]))
+        return res
+
+    def breakdown_counts(self):
+        """Which way the member-breakdowns of critic_stats went so far (smpc_group_breakdown_counts):
+        batched_members rode a grouped stats launch, single_members were scored one by one."""
+        b, s = C.c_uint64(0), C.c_uint64(0)
+        rc = self.lib.smpc_group_breakdown_counts(self.h, C.byref(b), C.byref(s))
+        if rc != 0:
+            raise SmpcError(rc, "smpc_group_breakdown_counts")
+        return types.SimpleNamespace(batched_members=b.value, single_members=s.value)
+
     def close(self):
         if self.h:
             self.lib.smpc_group_destroy(self.h)
