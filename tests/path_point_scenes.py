@@ -1,0 +1,886 @@
+"""Scenes that aim PathAlignCritic's path-point choice at its ties, equalities, stalls and overruns,
+and a float64 judge for them.
+
+PathAlignCritic picks one path point per trajectory sample (utils::findClosestPathPt,
+tools/utils.hpp:665-675): a lower_bound over the plan's integrated distances that starts at the
+previous sample's point, a strict `<` that sends an exact tie to the upper point, `iter == begin +
+init -> return 0`, which throws a stalled rollout back to point 0 every other sample, and a
+dereferenced end() that the oracle and the kernels define as size - 1.  The furthest reached path
+point (utils.hpp:292-319: first minimum wins, then the maximum over the batch) has the same
+structure.  The kernels restate the rule three times, each parallelised differently, and the parity
+tests forgive a budget of "soft flips" that a rare wrong choice hides in.  On the scenes here every
+quantity that enters a decision is exact in float32, whatever the summation order, so that ANY
+flip is a defect:
+
+  * the construction of tests/edge_scenes.py: yaw 0, speed 0, warm start 0, no wz noise,
+    model_dt = 2^-4, stored noise = diff(a) / dt for accumulated displacements a on the grid
+    q = max(2^-20 m, one float ulp of the map's coordinates), |a| < 8 m, pose and plan on that grid;
+  * a rollout moves once per sample window (at its first step) and then holds, either along one
+    axis (chord |dx|: sqrt(fl(dx^2)) is |dx| under a correctly rounded root) or, for the holonomic
+    forms, by (3u, 4u) with 25 u^2 exact in float32 (chord 5u): a root that is not exact on a
+    perfect square shows;
+  * the costmap is blank: ObstaclesCritic adds exactly 0 and nobody collides;
+  * the plan runs along +x from the pose; the integrated distance LEADS the x progress by a fixed
+    offset (a first lateral jog of h/4, h the plan's least spacing; back-then-forward by h/8 for
+    DiffDrive), so the two candidates of a tie lie at different distances from the trajectory
+    point and a wrong pick moves the cost.
+
+Not a conftest: plain helpers, imported by tests/test_path_point_cpu.py (which pins the premise on
+the oracle alone and checks that the scenes are adversarial) and tests/test_gpu_path_point.py.
+"""
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from mpcholonavigation_amd import _abi as A
+from mpcholonavigation_amd.tick import Tick, default_config
+from tests import edge_scenes as E
+
+U = 1 << 20                   # integer units per metre: every coordinate below is an int of 2^-20 m
+MODEL_DT = E.MODEL_DT
+MAX_DISPLACEMENT = E.MAX_DISPLACEMENT
+G_FURTHEST = 44               # the furthest reached path point every scene is built for
+PLAN_POINTS = 60
+INVALID_POINTS = (0, 9, 23)   # the variant: point 0 and two interior ones (3 / 44 < 0.07: still scored)
+OUTLIER = 3                   # metres: the last sample's move back in the invalid variant
+MIN_COUNT = 32                # every admitted category of adversarial_stats, per scene
+# u of the (3u, 4u, 5u) moves: 25 u^2 has at most 11 bits, and 4u is a multiple of every plan's g
+TRIPLE_UNITS = (U >> 7, 5 * (U >> 7), 7 * (U >> 7), 9 * (U >> 7))
+
+
+def plan_gaps(name):
+    """Spacing of the plan's 60 points, in units."""
+    h3, h4, h6, h8 = U >> 3, U >> 4, U >> 6, U >> 8
+    gaps = {
+        "uniform": [h4] * 59,                                   # (a)
+        "alt": ([h6, 7 * h6] * 30)[:59],                        # (b)
+        "cluster": [h3] * 10 + [h8] * 15 + [h3] * 34,           # (c) 16 points 2^-8 apart, points 10..25
+        "repeat": [0 if i % 4 == 2 else h4 for i in range(59)],  # (d) D[k] == D[k+1] for k = 2 mod 4
+    }[name]
+    assert len(gaps) == PLAN_POINTS - 1
+    return np.asarray(gaps, np.int64)
+
+
+@dataclass
+class PathScene:
+    plan: str
+    m: str
+    B: int
+    T: int
+    step: int
+    holonomic: bool
+    invalid: bool
+    q: int                       # the grid, in units
+    N: int                       # samples per rollout
+    Nt: int                      # ... of which the table aims (the invalid variant: N - 1)
+    K: int                       # the longest stall run aimed at
+    free_end: bool               # the endpoint is no sample
+    tick: Tick
+    u0: np.ndarray
+    noise: tuple
+    x: np.ndarray                # float32 [B, T] intended trajectory points
+    y: np.ndarray
+    cells: np.ndarray
+    origin_x: float
+    origin_y: float
+    resolution: float
+    family: np.ndarray           # [B] index into FAMILIES
+    label: str = ""
+    extra: dict = field(default_factory=dict)
+
+    def config(self, **kw):
+        mm = A.SMPC_MODEL_OMNI if self.holonomic else A.SMPC_MODEL_DIFF_DRIVE
+        return default_config(batch_size=self.B, time_steps=self.T, model_dt=MODEL_DT, motion_model=mm, **kw)
+
+    def configure(self, obj, critics):
+        obj.set_critics(critics)
+        obj.set_costmap(self.cells, self.origin_x, self.origin_y, self.resolution)
+        obj.set_noise(*self.noise)
+
+
+FIVE = E.FIVE
+NO_OBST = FIVE[1:]
+ONLY = ("path_align",)
+
+
+def critics_of(names, step=4, pa_power=1):
+    cr = E.critics_of(names)
+    cr.path_align.trajectory_point_step = step
+    cr.path_align.cost_power = pa_power
+    return cr
+
+
+FAMILIES = ("filler", "full_stall", "runs", "ties", "equalities", "quirk", "overrun", "back_forth", "scout")
+
+
+class _Table:
+    """The rollouts of one scene at the sample level, in integer units relative to the pose:
+    sx, sy [N + 1] per rollout (sample 0 is the pose) and the endpoint (ex, ey)."""
+
+    def __init__(self, D, P, N, q, hol, free_end, rng, invalid=False):
+        self.D, self.P, self.N, self.q, self.hol, self.free_end, self.rng = D, P, N, q, hol, free_end, rng
+        self.S = len(D)
+        gaps = np.diff(P)
+        self.smin = int(gaps[gaps > 0].min())
+        self.o = self.smin // 4              # the decoupling offset h/4
+        self.g = self.smin // 2              # the step of everything that is not aimed
+        assert self.o % (2 * q) == 0
+        self.cap_x = int(P[G_FURTHEST])      # no endpoint passes the scouts' point
+        self.rows = []
+
+    # -- one rollout that only moves forward after its prefix ---------------------------------
+    def prefix(self, u345=0):
+        """(sx, sy, d) up to sample j0, lead = d - x afterwards."""
+        o = self.o
+        if not self.hol:
+            return [0, -o // 2, 0], [0, 0, 0], [0, o // 2, o], o
+        if u345:
+            return [0, 0, 3 * u345, 6 * u345], [0, o, o + 4 * u345, o], [0, o, o + 5 * u345, o + 10 * u345], o + 4 * u345
+        return [0, 0], [0, o], [0, o], o
+
+    def forward(self, targets, inc=None, u345=0, fam=0, past_cap=False):
+        """targets: [(sample, d)], samples increasing, d non-decreasing.  Between targets equal
+        parts rounded down to a multiple of g; after the last one +inc per sample up to the cap.
+        (Distances that are multiples of g = h/2 put x = d - h/4 off every midpoint of two path
+        points: no unaimed sample is as far from the point it takes as from a candidate.)"""
+        N, g = self.N, self.g
+        sx, sy, d, lead = self.prefix(u345)
+        j0 = len(d) - 1
+        if targets and (targets[0][0] <= j0 or targets[0][1] < d[-1]) and u345:
+            return self.forward(targets, inc, 0, fam, past_cap)
+        capd = self.cap_x + lead
+        if past_cap:                         # (the scouts alone end past the cap)
+            capd = max(capd, targets[-1][1])
+        ja, da = j0, d[-1]
+        for jb, db in targets:
+            assert ja < jb <= N and da <= db <= capd, (targets, ja, da, capd)
+            n = jb - ja
+            for i in range(1, n):
+                d.append(max(da, (da + (db - da) * i // n) // g * g))
+            d.append(db)
+            ja, da = jb, db
+        inc = g if inc is None else inc
+        while len(d) <= N:
+            d.append(min(d[-1] + inc, capd) if d[-1] < capd else d[-1])
+        y = sy[-1]
+        sx += [v - lead for v in d[len(sx):]]
+        sy += [y] * (N + 1 - len(sy))
+        return self.add(sx, sy, fam)
+
+    def add(self, sx, sy, fam, end=None):
+        assert len(sx) == len(sy) == self.N + 1
+        ex, ey = (sx[-1], sy[-1]) if end is None or not self.free_end else end
+        self.rows.append((np.asarray(sx, np.int64), np.asarray(sy, np.int64), int(ex), int(ey), fam))
+        return len(self.rows) - 1
+
+    # -- what the aimed families aim at -------------------------------------------------------
+    def aim(self, k, v):
+        """v 0: the tie of (k, k + 1) (upper point); 1: one grid step below it (lower point);
+        2: D[k] itself (lower_bound lands on k, picked as the upper point); 3: one step above."""
+        D, q = self.D, self.q
+        mid = int(D[k] + D[k + 1]) // 2
+        return (mid, mid - q, int(D[k]), int(D[k]) + q)[v]
+
+    def j_first(self):
+        return 2 if self.hol else 3
+
+    def spread(self, m, r):
+        """m strictly increasing path points in 1 .. S - 2, rotated by the rollout's number."""
+        S = self.S
+        w = max((S - 2) // m, 1)
+        return [1 + (i * (S - 2)) // m + (r % w) for i in range(m)]
+
+    def events(self, r, m, j1):
+        """m sample slots for aimed events from sample j1 + 1 on, two apart at least, rotated by r."""
+        stride = (self.N - j1 + 1) // m
+        assert stride >= 2
+        ph = r % (stride - 1)
+        return [j1 + 1 + ph + i * stride for i in range(m)]
+
+
+def _rollouts(D, P, N, q, hol, free_end, B, K, seed, invalid=False):
+    """The table of one scene: (sx, sy [B, N + 1], ex, ey, family [B])."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    t = _Table(D, P, N, q, hol, free_end, rng, invalid)
+    S, g, o = t.S, t.g, t.o
+    j1 = t.j_first()
+    n_small = max(36, B // 96)
+    quarter = []                          # the full-length stalls, placed at b = 0 mod 4
+    special = []                          # every other aimed rollout
+
+    if N == 1:
+        # one sample: its move is the lateral one (x stays 0, the distance is |dy|), or along x
+        def single(dx, dy, fam):
+            return t.add([0, dx], [0, dy], fam)
+        for r in range(6 * n_small):
+            k = 1 + r % (S - 2)
+            special.append(single(0, t.aim(k, 0) + (r % 3 - 1) * q, 3))
+            special.append(single(0, int(D[k]) + (r % 3 - 1) * q, 4))
+        for r in range(n_small):
+            special.append(single(0, int(D[S - 1]) + (1 + r) * q, 6))
+            special.append(single(int(D[S - 1]) + (1 + r % 4) * q, 0, 6))
+    else:
+        u_of = (lambda r: TRIPLE_UNITS[(r // 2) % 4] if (hol and N >= 6 and r % 2) else 0)
+        # full-length stalls: arrive at sample ja, stay K samples
+        n_quarter = (B + 3) // 4
+        for r in range(n_quarter + (128 if B >= 4096 else 0)):   # (and one contiguous block)
+            ja = j1 + (r % (N - K - j1 + 1))
+            d = t.aim(1 + (r // 4) % (S - 2), r % 4)
+            (quarter if r < n_quarter else special).append(
+                t.forward([(ja, d), (ja + K, d)], inc=g * (1 + r % 3), fam=1))
+        # runs of every other length, packed: each run is an arrival and L stalled samples
+        need = [L for L in range(1, K) for _ in range(MIN_COUNT + 1)]
+        need = sorted(need, key=lambda L: (min(L, K - L), L))          # (long with short)
+        order, lo, hi = [], 0, len(need) - 1
+        while lo <= hi:
+            order.append(need[hi]); hi -= 1
+            if lo <= hi:
+                order.append(need[lo]); lo += 1
+        r = 0
+        while order:
+            room, picked = N - j1 + 1, []
+            for L in list(order):
+                if L + 1 <= room and len(picked) < 8:
+                    picked.append(L); order.remove(L); room -= L + 1
+                    if room < 2:
+                        break
+            ks = t.spread(len(picked), r)
+            j, targets = j1 + (r % (room + 1)), []
+            for i, L in enumerate(picked):
+                d = t.aim(ks[i], (r + i) % 4)
+                targets += [(j, d), (j + L, d)]
+                j += L + 1
+            special.append(t.forward(targets, fam=2))
+            r += 1
+        # ties and equalities and one grid step either side of both
+        def slots_of(r, u, per):
+            jj = 4 if u else j1              # (a 3-4-5 pair takes samples 2 and 3)
+            m = max(1, min(4 if per == 2 else 3, (N - jj + 1) // per))
+            return t.events(r, m, jj), t.spread(m, r)
+        for r in range(-(-3 * (MIN_COUNT + 4) // max(1, min(4, (N - 3) // 2)))):
+            for fam, u in ((3, u_of(r)), (4, u_of(r + 1))):
+                js, ks = slots_of(r, u, 2)
+                at = (lambda k: t.aim(k, 0)) if fam == 3 else (lambda k: int(D[k]))
+                special.append(t.forward([(j, at(k) + ((r + i) % 3 - 1) * q) for i, (j, k) in enumerate(zip(js, ks))],
+                                         u345=u, fam=fam))
+        # an equality at the previous sample's point: arrive where k is picked, then land on D[k]
+        for r in range(-(-8 * (MIN_COUNT + 4) // max(1, min(3, (N - 3) // 3)))):
+            js, ks = slots_of(r, u_of(r), 3)
+            targets = []
+            for i, (j, k) in enumerate(zip(js, ks)):
+                k = max(k, 2)
+                before = t.aim(k - 1, 0) if (r + i) % 2 and D[k] > D[k - 1] else int(D[k]) - 2 * q
+                targets += [(j - 1, before), (j, int(D[k]) + ((r + i) % 3 - 1) * q)]
+            special.append(t.forward(targets, u345=u_of(r), fam=5))
+        # overruns: past D[S - 1] and on to the cap, where the rollout stays
+        for r in range(n_small):
+            j = j1 + r % max(1, N - j1 - 1)
+            special.append(t.forward([(j, int(D[S - 1]) + (r % 3 - 1) * q)], inc=g * (1 + r % 4), fam=6))
+        # ... and by going back and forth: the endpoint never passes the plan's first points
+        half = max(1, (N - j1 + 1) // 2)
+        A0 = -(-(int(D[S - 1]) + q) // half // g) * g
+        for r in range(0 if invalid else n_small):
+            sx, sy, d, _ = t.prefix()
+            a = min(A0 + (r % 8) * g, t.cap_x) - o
+            while len(sx) <= N:
+                sx.append(a if sx[-1] == 0 else 0)
+                sy.append(sy[-1])
+            special.append(t.add(sx, sy, 7))
+
+    # scouts: the endpoints that fix the furthest point G
+    Gp = G_FURTHEST
+    mid_a, mid_b = int(P[Gp - 1] + P[Gp]) // 2, int(P[Gp] + P[Gp + 1]) // 2
+    ends = [mid_a + q, mid_a, mid_a - q, mid_b, mid_b - q]
+    scouts = []
+    for r in range(6 * (MIN_COUNT + 1)):
+        kind = r % 6
+        if kind == 5 and (not hol or N == 1):
+            continue
+        lateral = (U >> 2) + (r % 5) * (U >> 5)
+        if kind < 5:
+            scouts.append((ends[kind], None))
+        else:
+            scouts.append((int(P[Gp]) + (r % 3) * q * 2, lateral if r % 12 == 5 else -lateral))
+    overlay = {}
+    if free_end and quarter:
+        # the endpoint is no sample: any rollout can carry a scout's endpoint
+        hosts = quarter + [i for i in special if t.rows[i][4] in (2, 3, 4, 5)]
+        for i, sc in enumerate(scouts):
+            overlay[hosts[i]] = sc
+    else:
+        for i, (ex, ey) in enumerate(scouts):
+            if N == 1:
+                special.append(t.add([0, ex], [0, 0], 8))
+                continue
+            if free_end:
+                idx = t.forward([], fam=8)
+                overlay[idx] = (ex, ey)
+            elif ey is None:
+                lead = t.prefix()[3]
+                special.append(t.forward([(N, ex + lead)], fam=8, past_cap=True))
+                continue
+            else:
+                lead = t.prefix()[3]
+                idx = t.forward([(N - 1, ex + lead)], inc=0, fam=8, past_cap=True)
+                sx, sy, _, _, _ = t.rows[idx]
+                sx[N] = sx[N - 1]
+                sy[N] = sy[N - 1] + ey
+                t.rows[idx] = (sx, sy, int(sx[N]), int(sy[N]), 8)
+            special.append(idx)
+    for idx, (ex, ey) in overlay.items():
+        sx, sy, _, _, fam = t.rows[idx]
+        t.rows[idx] = (sx, sy, ex, int(sy[-1]) + (ey or 0), fam)
+
+    # place: full-length stalls at b = 0 mod 4 (rollouts that share a wave), the rest in order
+    slots = [None] * B
+    qi = iter(quarter)
+    for b in range(0, B, 4):
+        slots[b] = next(qi, None)
+    free = [b for b in range(B) if slots[b] is None]
+    assert len(special) <= len(free), f"{len(special)} aimed rollouts for {len(free)} places"
+    stride = len(free) / max(len(special), 1)
+    for i, idx in enumerate(special):
+        b = free[int(i * stride)]
+        slots[b] = idx
+    # filler: seeded random walks on the grid, forward mostly, capped like everyone
+    for b in range(B):
+        if slots[b] is not None:
+            continue
+        if N == 1:
+            dx = int(rng.integers(1, t.cap_x // g + 1)) * g - o
+            slots[b] = t.add([0, dx], [0, 0], 0)
+            continue
+        sx, sy, d, lead = t.prefix()
+        unit = max(g, t.cap_x // (4 * N) // g * g)
+        steps = rng.integers(0 if invalid else -2, 9, size=N + 1) * unit * int(rng.integers(1, 3))
+        while len(sx) <= N:
+            cur = sx[-1] if len(sx) > len(d) else -o          # (x = -h/4 modulo g from the first move on)
+            sx.append(int(np.clip(cur + steps[len(sx)], -U - o, t.cap_x - o)))
+            sy.append(sy[-1])
+        slots[b] = t.add(sx, sy, 0)
+    rows = [t.rows[i] for i in slots]
+    return (np.stack([r[0] for r in rows]), np.stack([r[1] for r in rows]),
+            np.array([r[2] for r in rows]), np.array([r[3] for r in rows]), np.array([r[4] for r in rows]))
+
+
+def stall_length(B, N, hol):
+    """K: the longest stall run a scene aims at, and the length of the runs a quarter of the batch
+    carries.  All the samples after the prefix and the arrival, where the batch has room for 34
+    runs of every shorter length as well; else what has room (34 sum(L + 1) is about 17 K^2 samples,
+    under a third of the batch's B (N - 2))."""
+    free = N - (2 if hol else 3)
+    return max(0, min(free, int(np.sqrt(B * max(free, 0) / 56.0))))
+
+
+def build_scene(plan="uniform", m="o0", B=4096, T=64, step=4, holonomic=True, invalid=False, seed=11, label=""):
+    origin, res = E.MAPS[m]
+    ox, oy = float(origin[0]), float(origin[1])
+    W = H = 200
+    cells = np.zeros((H, W), np.uint8)
+    span = max(abs(ox), abs(ox + W * res), abs(oy), abs(oy + H * res))
+    q = max(1, int(round(float(np.spacing(np.float32(span))) * U)))
+    qm = q / U
+    pose_x = float(np.rint((ox + 0.5 * W * res) / qm) * qm)
+    pose_y = float(np.rint((oy + 0.5 * H * res) / qm) * qm)
+    N = (T - 1) // step
+    free_end = N * step < T - 1
+    base = min(B, 4096)
+    assert B % base == 0
+    # the invalid variant: the table has one sample less, and every rollout's last sample is a
+    # move of OUTLIER metres back along the plan (see below)
+    Nt = N - 1 if invalid else N
+    assert holonomic or not invalid
+    K = stall_length(base, Nt, holonomic)
+
+    P = np.concatenate([[0], np.cumsum(plan_gaps(plan))])
+    assert P[G_FURTHEST] > P[G_FURTHEST - 1] and P[G_FURTHEST + 1] > P[G_FURTHEST]
+    D = P[:G_FURTHEST]                         # the plan is straight: integrated distance = x offset
+    sx, sy, ex, ey, fam = _rollouts(D, P, Nt, q, holonomic, free_end, base, K, seed, invalid)
+    if invalid:
+        # Where a candidate swap turns a counted sample into a skipped one, or back (point 0 is
+        # invalid, and `return 0` lands there), the cost moves by |distance - mean of the others| / n,
+        # which is as small as chance makes it among thousands of samples.  One sample far from
+        # the plan bounds it from below: with OUTLIER above (n - 1) times any other distance, every
+        # other sample lies below every mean it is compared with.  (Forward-only rollouts keep
+        # those distances small: this variant has no back-and-forth family and its filler only
+        # advances.)  The outlier's chord overruns the plan: the sample takes S - 1.
+        assert Nt <= 14 and N >= 2
+        # It moves back along the plan, not sideways: from the side, S - 1 and S - 2 would be all
+        # but equally far.  The endpoint is no sample in this variant and jumps forward again.
+        assert free_end
+        sx = np.concatenate([sx, sx[:, -1:] - OUTLIER * U], axis=1)
+        sy = np.concatenate([sy, sy[:, -1:]], axis=1)
+    # steps: the sample's move happens at the first step of its window, then the point holds
+    tt = np.arange(T)
+    j = np.minimum(-(-tt // step), N)
+    ax = sx[:, j].astype(np.float64)
+    ay = sy[:, j].astype(np.float64)
+    if free_end:
+        ax[:, N * step + 1:] = ex[:, None]
+        ay[:, N * step + 1:] = ey[:, None]
+    reps = B // base
+    ax, ay, fam = np.tile(ax, (reps, 1)) / U, np.tile(ay, (reps, 1)) / U, np.tile(fam, reps)
+    assert max(np.abs(ax).max(), np.abs(ay).max()) < MAX_DISPLACEMENT
+    assert holonomic or not ay.any()
+
+    def noise_of(a):
+        n = np.zeros((B, T), np.float64)
+        n[:, :-1] = np.diff(a, axis=1) / MODEL_DT
+        return n
+    n64 = (noise_of(ax), noise_of(ay))
+    nvx, nvy = (n.astype(np.float32) for n in n64)
+    exact = all(np.array_equal(n32.astype(np.float64), n) for n32, n in zip((nvx, nvy), n64))
+    x = (pose_x + ax).astype(np.float32)
+    y = (pose_y + ay).astype(np.float32)
+    exact = exact and np.array_equal(x.astype(np.float64), pose_x + ax) and np.array_equal(y.astype(np.float64), pose_y + ay)
+
+    path_x = (pose_x + P / U).astype(np.float32)
+    assert np.array_equal(path_x.astype(np.float64), pose_x + P / U)
+    path_y = np.full(PLAN_POINTS, pose_y, np.float32)
+    valid = np.ones(PLAN_POINTS - 1, np.uint8)
+    if invalid:
+        valid[list(INVALID_POINTS)] = 0
+    tick = Tick(pose_x=pose_x, pose_y=pose_y, pose_yaw=0.0, speed=(0.0, 0.0, 0.0), path_x=path_x, path_y=path_y,
+                path_yaw=np.zeros(PLAN_POINTS, np.float32), goal_x=float(path_x[-1]), goal_y=float(path_y[-1]),
+                path_pts_valid=valid)
+    return PathScene(plan=plan, m=m, B=B, T=T, step=step, holonomic=holonomic, invalid=invalid, q=q, N=N, Nt=Nt, K=K,
+                     free_end=free_end, tick=tick, u0=np.zeros((3, T), np.float32),
+                     noise=(nvx, nvy, np.zeros((B, T), np.float32)), x=x, y=y, cells=cells, origin_x=ox,
+                     origin_y=oy, resolution=res, family=fam, label=label, extra={"noise_exact": exact})
+
+
+# ---- the judge: float64 / NumPy, from the reference's lines -----------------------------------
+
+def find_closest_path_pt(D, dist, init):
+    """utils.hpp:665-675 for arrays of (dist, init); end() as size - 1.  Returns (point, iter).
+    std::lower_bound over [begin + init, end): D is sorted, so that is the later of init and the
+    lower bound over the whole of D."""
+    D = np.asarray(D, np.float64)
+    dist = np.asarray(dist, np.float64)
+    n = len(D)
+    it = np.maximum(np.searchsorted(D, dist, side="left"), init)          # :667
+    at_end = it >= n
+    i = np.clip(it, 1, n - 1)
+    lower = dist - D[i - 1] < D[i] - dist                                # :671 (strict)
+    pt = np.where(lower, i - 1, i)
+    pt = np.where(at_end, n - 1, pt)                                     # *end(): size - 1
+    pt = np.where(it == init, 0, pt)                                     # :668-670
+    return pt, it
+
+
+def furthest_point(px, py, ex, ey):
+    """utils.hpp:292-319: per rollout the FIRST minimum over the path points, then the maximum."""
+    d = (px[None, :] - ex[:, None]) ** 2 + (py[None, :] - ey[:, None]) ** 2
+    per = d.argmin(axis=1)                                               # (argmin: first minimum)
+    return int(per.max()), per, d
+
+
+def model(scn, critics):
+    """The judge.  Returns dict(x, y, furthest, scored, pa [B] PathAlign alone, five [B] the default
+    five together, pt, it, init, dist, chord [B, N], cand [B, N, 4] the candidates the rule weighs
+    (-1: none), sums and counts for min_single_choice_shift)."""
+    f8 = np.float64
+    x32, y32 = E.trajectories(scn)
+    x, y = x32.astype(f8), y32.astype(f8)
+    B, T = scn.B, scn.T
+    tk = scn.tick
+    px, py = tk.path_x.astype(f8), tk.path_y.astype(f8)
+    valid_all = tk.path_pts_valid.astype(bool)
+    p = critics.path_align
+    F, per_rollout, d_end = furthest_point(px, py, x[:, -1], y[:, -1])
+    goal_d2 = (tk.goal_x - tk.pose_x) ** 2 + (tk.goal_y - tk.pose_y) ** 2
+    out = dict(x=x32, y=y32, furthest=F, furthest_per_rollout=per_rollout, end_d2=d_end)
+
+    # path_align_critic.cpp:46-72
+    scored = bool(p.enabled) and not goal_d2 < f8(np.float32(p.threshold_to_consider)) ** 2
+    scored = scored and F >= p.offset_from_furthest
+    if scored:
+        d0 = (px - x[0, 0]) ** 2 + (py - y[0, 0]) ** 2                   # utils.hpp:327-344
+        first = int(d0.argmin())
+        ctr, rng_ = 0, np.float32(F - first)
+        for i in range(first, F):
+            ctr += 0 if valid_all[i] else 1
+            if np.float32(ctr) / rng_ > np.float32(p.max_path_occupancy_ratio) and ctr > 2:
+                scored = False
+                break
+    out["scored"] = scored
+    step = int(p.trajectory_point_step)
+    N = len(range(step, T, step))
+    S = F
+    # :74-90 (the views drop the plan's last point: S <= P - 1 always)
+    D = np.zeros(max(S, 1))
+    for i in range(1, S):
+        D[i] = D[i - 1] + np.sqrt((px[i] - px[i - 1]) ** 2 + (py[i] - py[i - 1]) ** 2)
+    out["D"] = D
+    pts = np.zeros((B, N), np.int64)
+    its = np.zeros((B, N), np.int64)
+    inits = np.zeros((B, N), np.int64)
+    dists = np.zeros((B, N))
+    chords = np.zeros((B, N))
+    diag = np.zeros((B, N), bool)
+    gap = np.zeros((B, N, max(S, 1)))         # distance from the sample's point to every path point < S
+    summed, num, path_pt, acc = np.zeros(B), np.zeros(B), np.zeros(B, np.int64), np.zeros(B)
+    if scored:
+        for n_, q_ in enumerate(range(step, T, step)):                   # :104-127
+            dx, dy = x[:, q_] - x[:, q_ - step], y[:, q_] - y[:, q_ - step]
+            chords[:, n_] = np.sqrt(dx * dx + dy * dy)
+            diag[:, n_] = (dx != 0) & (dy != 0)
+            acc = acc + chords[:, n_]
+            inits[:, n_] = path_pt
+            path_pt, its[:, n_] = find_closest_path_pt(D, acc, path_pt)
+            pts[:, n_], dists[:, n_] = path_pt, acc
+            gap[:, n_, :] = np.sqrt((px[None, :S] - x[:, q_, None]) ** 2 + (py[None, :S] - y[:, q_, None]) ** 2)
+            ok = valid_all[path_pt]
+            summed += np.where(ok, gap[np.arange(B), n_, path_pt], 0.0)
+            num += ok
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = np.where(num > 0, summed / np.where(num > 0, num, 1.0), 0.0)   # :128-132
+    w = f8(np.float32(p.cost_weight))
+    pa = (mean * w) ** int(p.cost_power) if scored else np.zeros(B)      # :135
+    out.update(pa=pa, pt=pts, it=its, init=inits, dist=dists, chord=chords, diag=diag, gap=gap,
+               summed=summed, num=num, S=S, N=N)
+
+    # the default five: ObstaclesCritic adds 0 on a blank map, GoalAngle nothing away from the goal
+    five = pa.copy()
+    f = critics.path_follow                                              # path_follow_critic.cpp:35-71
+    if f.enabled and len(px) >= 2 and not goal_d2 < f8(np.float32(f.threshold_to_consider)) ** 2:
+        size = len(px) - 1
+        idx = min(F + int(f.offset_from_furthest), size)
+        ok = False
+        while not ok and idx < size - 1:
+            ok = bool(valid_all[idx])
+            if not ok:
+                idx += 1
+        dd = np.sqrt((x[:, -1] - px[idx]) ** 2 + (y[:, -1] - py[idx]) ** 2)
+        five = five + (f8(np.float32(f.cost_weight)) * dd) ** int(f.cost_power)
+    g = critics.prefer_forward                                           # prefer_forward_critic.cpp:33-47
+    if g.enabled and not goal_d2 < f8(np.float32(g.threshold_to_consider)) ** 2:
+        vx = np.zeros((B, T))
+        vx[:, 1:] = scn.noise[0][:, :-1].astype(f8)
+        back = (np.maximum(-vx, 0.0) * MODEL_DT).sum(axis=1)
+        five = five + (back * f8(np.float32(g.cost_weight))) ** int(g.cost_power)
+    ga = critics.goal_angle
+    assert not (ga.enabled and goal_d2 < f8(np.float32(ga.threshold_to_consider)) ** 2)
+    out["five"] = five
+    return out
+
+
+def candidates(m):
+    """Per sample, the points the rule weighs besides the one it takes ([B, N, 4], -1: none): the
+    other neighbour of the lower bound; point 0 where the `return 0` quirk applies (the other
+    candidate is then what the rule picks without it) or is one slip from applying (the lower
+    bound is the previous point or the one after it, the rollout stalls, or the previous sample
+    took the quirk); S - 1 and S - 2 at end()."""
+    pt, it, init, S = m["pt"], m["it"], m["init"], m["S"]
+    D, dist = m["D"], m["dist"]
+    B, N = pt.shape
+    i = np.clip(it, 1, S - 1)
+    regular = np.where(dist - D[i - 1] < D[i] - dist, i - 1, i)
+    regular = np.where(it >= S, S - 1, regular)
+    other = np.where(regular == i, i - 1, i)
+    quirk = it == init
+    prev_quirk = np.zeros_like(quirk)
+    prev_quirk[:, 1:] = quirk[:, :-1]
+    near_quirk = quirk | (it == init + 1) | (m["chord"] == 0) | prev_quirk
+    c = np.full((B, N, 4), -1, np.int64)
+    c[:, :, 0] = np.where(quirk, regular, other)
+    c[:, :, 1] = np.where(near_quirk, np.where(quirk, other, 0), -1)
+    c[:, :, 2] = np.where(it >= S - 1, S - 1, -1)
+    c[:, :, 3] = np.where(it >= S, S - 2, -1)
+    c[(c == pt[:, :, None]) | (c >= S)] = -1
+    return c
+
+
+def min_single_choice_shift(scn, critics, m=None):
+    """The least any rollout's PathAlign cost moves when ONE of its samples takes another of its
+    candidates(); pairs of which both points are invalid are left out (the critic skips either:
+    path_align_critic.cpp:115), and pairs that are one place (a plan with repeated points).  From the model; strictly positive by assertion."""
+    m = m or model(scn, critics)
+    assert m["scored"]
+    valid = scn.tick.path_pts_valid.astype(bool)
+    p = critics.path_align
+    w, power = np.float64(np.float32(p.cost_weight)), int(p.cost_power)
+    pt, gap = m["pt"], m["gap"]
+    px, py = scn.tick.path_x, scn.tick.path_y
+    B, N = pt.shape
+    rows = np.arange(B)[:, None], np.arange(N)[None, :]
+    v_ch = valid[pt]
+    g_ch = gap[rows[0], rows[1], pt]
+    least = np.inf
+    cand = candidates(m)
+    for a in range(4):
+        alt = cand[:, :, a]
+        on = alt >= 0
+        al = np.where(on, alt, 0)
+        v_al = valid[al]
+        on &= (v_ch | v_al) & ((px[al] != px[pt]) | (py[al] != py[pt]))
+        s2 = m["summed"][:, None] - np.where(v_ch, g_ch, 0.0) + np.where(v_al, gap[rows[0], rows[1], al], 0.0)
+        n2 = m["num"][:, None] - v_ch + v_al
+        c2 = (np.where(n2 > 0, s2 / np.where(n2 > 0, n2, 1.0), 0.0) * w) ** power
+        shift = np.abs(c2 - m["pa"][:, None])
+        if on.any():
+            least = min(least, float(shift[on].min()))
+    assert np.isfinite(least) and least > 0.0, "a candidate swap that moves no cost"
+    return least
+
+
+def adversarial_stats(scn, m):
+    """How adversarial the scene is: counts over the samples (and endpoints) of the model's run."""
+    D, S, q = m["D"], m["S"], scn.q / U
+    dist, it, init, pt, chord = m["dist"], m["it"], m["init"], m["pt"], m["chord"]
+    inside = (it > 0) & (it < S)
+    i = np.clip(it, 1, S - 1)
+
+    def tie(d):
+        j = np.clip(np.searchsorted(D, d, side="left"), 1, S - 1)
+        return (d > D[0]) & (d < D[S - 1]) & (D[j] > D[j - 1]) & (d - D[j - 1] == D[j] - d)
+
+    def on_point(d):
+        j = np.clip(np.searchsorted(D, d, side="left"), 1, S - 1)
+        return d == D[j]
+    st = {"ties": int(tie(dist).sum()), "tie_minus": int(tie(dist + q).sum()), "tie_plus": int(tie(dist - q).sum()),
+          "equalities": int(on_point(dist).sum()), "eq_minus": int(on_point(dist + q).sum()),
+          "eq_plus": int(on_point(dist - q).sum())}
+    quirk = (it == init) & (it > 0)
+    st["quirk_returns"] = int(quirk.sum())
+    st["eq_at_previous_point"] = int((quirk & on_point(dist) & (chord > 0)).sum())
+    st["eq_plus_at_previous_point"] = int(((it == init + 1) & on_point(dist - q) & (chord > 0) & (init > 0)).sum())
+    # stall runs by length, and whether the point before the run was the upper or the lower pick
+    runs, upper, lower = {}, 0, 0
+    z = chord == 0
+    B, N = z.shape
+    for b in np.nonzero(z.any(axis=1))[0]:
+        n = 0
+        while n < N:
+            if z[b, n] and n > 0:
+                e = n
+                while e < N and z[b, e]:
+                    e += 1
+                runs[e - n] = runs.get(e - n, 0) + 1
+                if inside[b, n - 1] and init[b, n - 1] != it[b, n - 1]:
+                    upper += pt[b, n - 1] == it[b, n - 1]
+                    lower += pt[b, n - 1] == it[b, n - 1] - 1
+                n = e
+            else:
+                n += 1
+    st["stall_runs"] = dict(sorted(runs.items()))
+    st["stall_after_upper"], st["stall_after_lower"] = int(upper), int(lower)
+    full = np.zeros(B, bool)
+    if scn.K > 0:
+        zz = np.concatenate([np.zeros((B, 1), bool), z, np.zeros((B, 1), bool)], axis=1).astype(np.int8)
+        edges = np.diff(zz, axis=1)
+        for b in range(B):
+            s_, e_ = np.nonzero(edges[b] == 1)[0], np.nonzero(edges[b] == -1)[0]
+            full[b] = len(s_) > 0 and (e_ - s_).max() >= scn.K
+    st["full_length_rollouts"] = int(full.sum())
+    over = it >= S
+    st["overruns"] = int(over.sum())
+    st["overrun_again"] = int((over[:, 1:] & over[:, :-1]).sum())
+    px = scn.tick.path_x.astype(np.float64)
+    st["overrun_back_and_forth"] = int((over.any(axis=1) & (m["x"][:, -1].astype(np.float64) < px[S - 1])).sum())
+    st["invalid_samples"] = int((~scn.tick.path_pts_valid.astype(bool)[pt]).sum())
+    st["chords_345"] = int(m["diag"].sum())
+    guess = np.minimum((dist * ((S - 1) / D[S - 1])).astype(np.int64), S - 1)
+    st["guess_off_by_more_than_one"] = int(((it < guess) | (it > guess + 1)).sum())
+    # scouts: endpoints at the furthest point's ties
+    F = m["furthest"]
+    ex = m["x"][:, -1].astype(np.float64)
+    ey = m["y"][:, -1].astype(np.float64)
+
+    def end_tie(k, e):        # endpoints midway between points k and k + 1, e grid steps further
+        return int(((ex - e * q) * 2 == px[k] + px[k + 1]).sum())
+    st["scouts_at_tie"] = end_tie(F, 0)
+    st["scouts_below_tie"] = end_tie(F, -1)
+    st["scouts_at_lower_tie"] = end_tie(F - 1, 0)
+    st["scouts_either_side_of_lower_tie"] = min(end_tie(F - 1, -1), end_tie(F - 1, 1))
+    st["scouts_lateral"] = int(((np.abs(ey - np.median(ey)) >= 0.125) & (m["furthest_per_rollout"] == F)).sum())
+    st["endpoints_past"] = int((m["furthest_per_rollout"] > F).sum())
+    return st
+
+
+def admitted(scn):
+    """The counts that this scene's plan and tick shape admit: each must reach MIN_COUNT."""
+    keys = ["ties", "tie_minus", "tie_plus", "equalities", "eq_minus", "eq_plus", "overruns",
+            "scouts_at_tie", "scouts_below_tie", "scouts_at_lower_tie", "scouts_either_side_of_lower_tie"]
+    if scn.holonomic and scn.Nt > 1:
+        keys.append("scouts_lateral")
+    if scn.Nt >= 2:
+        keys += ["overrun_again"]
+    if scn.Nt >= 4:
+        keys += ["quirk_returns", "eq_at_previous_point", "eq_plus_at_previous_point", "stall_after_upper",
+                 "stall_after_lower"] + ([] if scn.invalid else ["overrun_back_and_forth"])
+    if scn.Nt >= 6 and scn.holonomic:
+        keys.append("chords_345")
+    if scn.invalid:
+        keys.append("invalid_samples")
+    if scn.plan == "cluster":
+        keys.append("guess_off_by_more_than_one")
+    return keys
+
+
+# ---- the scenes and the kernel forms that score them ------------------------------------------
+
+def scene_key(plan="uniform", m="o0", B=4096, T=64, step=4, holonomic=True, invalid=False):
+    return (plan, m, B, T, step, bool(holonomic), bool(invalid))
+
+
+def scene_name(key):
+    plan, m, B, T, step, hol, invalid = key
+    return (f"{plan}-{m}-{B}x{T}" + (f"-step{step}" if step != 4 else "") + ("" if hol else "-diff")
+            + ("-invalid" if invalid else ""))
+
+
+_scene_cache = {}
+
+
+def scene(key):
+    if key not in _scene_cache:
+        while len(_scene_cache) >= 3:
+            _scene_cache.pop(next(iter(_scene_cache)))
+        plan, m, B, T, step, hol, invalid = key
+        _scene_cache[key] = build_scene(plan, m, B, T, step, hol, invalid, label=scene_name(key))
+    return _scene_cache[key]
+
+
+def primary(B, T, **kw):
+    """The five plans of the issue, (e) being the uniform plan far from the frame origin, and the
+    invalid variant on two of them."""
+    assert (T - 1) // kw.get("step", 4) <= 15
+    return [scene_key("uniform", B=B, T=T, **kw), scene_key("alt", B=B, T=T, **kw),
+            scene_key("cluster", B=B, T=T, **kw), scene_key("repeat", B=B, T=T, **kw),
+            scene_key("uniform", "o2", B=B, T=T, **kw), scene_key("uniform", B=B, T=T, invalid=True, **kw),
+            scene_key("cluster", "o2", B=B, T=T, invalid=True, **kw)]
+
+
+def squared(B, T):
+    """For a cost_power of 2 on PathAlign.  Squaring widens the spread: the least single-choice
+    shift comes from the cheapest rollouts, 2 c dc with c small, and the oracle's float32 error from
+    the dearest.  The plans with the larger offset h/4 = 2^-6 m keep the two a factor 100 apart; the
+    cluster's 2^-10 m and the invalid variant's far sample do not."""
+    return [scene_key("repeat", B=B, T=T), scene_key("uniform", "o2", B=B, T=T)]
+
+
+def subset(B, T, **kw):
+    """The plan with repeated points, and the cluster far from the frame origin: in its invalid
+    variant where that exists (a holonomic model, 2 to 15 samples, the endpoint no sample)."""
+    n = (T - 1) // kw.get("step", 4)
+    invalid = kw.get("holonomic", True) and 2 <= n <= 15 and n * kw.get("step", 4) < T - 1
+    return [scene_key("repeat", B=B, T=T, **kw), scene_key("cluster", "o2", B=B, T=T, invalid=invalid, **kw)]
+
+
+WAVE, LANE = E.WAVE, E.LANE
+_T, _F = True, False
+_lane, _wave = E._lane, E._wave
+
+
+def _spell(name, args):
+    return name + "<" + ", ".join(str(v).lower() if isinstance(v, bool) else str(v) for v in args) + ">"
+
+
+@dataclass
+class Form:
+    """One kernel family and form: tick shape, flags and knobs that select it, the critics scored,
+    pass_kind and the instance's name (the spelling of tests/test_gpu_pass_selection.py), the
+    scenes it runs.  stats: the costs are row SMPC_CRITIC_PATH_ALIGN of Smpc.critic_stats."""
+    B: int
+    T: int
+    flags: int
+    env: dict
+    critics: tuple
+    kind: int
+    kernel: str
+    scenes: list
+    step: int = 4
+    pa_power: int = 1
+    stats: bool = False
+
+
+_SPLIT = {"SMPC_PASS": "split"}
+FORMS = {
+    # wave per rollout, PathAlign alone
+    "wave-64": Form(4096, 64, WAVE, {}, ONLY, 0, _wave(1, 0, _T), primary(4096, 64)),
+    "wave-30": Form(4096, 30, WAVE, {}, ONLY, 0, _wave(1, 0, _F), subset(4096, 30)),
+    "wave-100": Form(2048, 100, WAVE, {}, ONLY, 0, _wave(2, 0, _F), subset(2048, 100)),
+    "wave-128": Form(2048, 128, WAVE, {}, ONLY, 0, _wave(2, 0, _T), subset(2048, 128)),
+    "wave-200": Form(512, 200, WAVE, {}, ONLY, 0, _wave(4, 0, _F), subset(512, 200)),
+    # the general pass: sqrtf
+    "wave-64-pow2": Form(4096, 64, WAVE, {}, ONLY, 0, _wave(1, 2, _T), squared(4096, 64), pa_power=2),
+    # trajectory_point_step 1: 63 samples, one segment per wave, the << 32 step of the chain
+    "wave-64-step1": Form(1024, 64, WAVE, {}, ONLY, 0, _wave(1, 0, _T), subset(1024, 64, step=1), step=1),
+    "wave-64-step2": Form(2048, 64, WAVE, {}, ONLY, 0, _wave(1, 0, _T), subset(2048, 64, step=2), step=2),
+    "wave-64-step7": Form(4096, 64, WAVE, {}, ONLY, 0, _wave(1, 0, _T), subset(4096, 64, step=7), step=7),
+    "wave-30-step29": Form(4096, 30, WAVE, {}, ONLY, 0, _wave(1, 0, _F), subset(4096, 30, step=29), step=29),
+    # lane per rollout: the five critics, and the list without ObstaclesCritic
+    "lane-64": Form(4096, 64, LANE, {}, FIVE, 1, _lane(_T, _T, _F, 1, _F, _F, _T, 0, _F), primary(4096, 64)),
+    "lane-56": Form(4096, 56, LANE, {}, FIVE, 1, _lane(_F, _T, _F, 1, _F, _F, _T, 56, _F), subset(4096, 56)),
+    "lane-40": Form(4096, 40, LANE, {}, FIVE, 1, _lane(_F, _T, _F, 1, _F, _F, _T, 0, _F), subset(4096, 40)),
+    "lane-rr-128": Form(4096, 128, LANE, {}, FIVE, 1, _lane(_T, _T, _F, 2, _T, _F, _T, 0, _F), subset(4096, 128)),
+    "lane-rr-64": Form(4096, 64, LANE, {"SMPC_LANE_REREAD": "1"}, FIVE, 1, _lane(_T, _T, _F, 1, _T, _F, _T, 0, _F),
+                       subset(4096, 64)),
+    "lane-64-no-obst": Form(4096, 64, LANE, {}, NO_OBST, 1, _lane(_T, _F, _F, 1, _F, _F, _T, 0, _F), primary(4096, 64)),
+    "lane-56-no-obst": Form(4096, 56, LANE, {}, NO_OBST, 1, _lane(_F, _F, _F, 1, _F, _F, _F, 0, _F), subset(4096, 56)),
+    "lane-40-no-obst": Form(4096, 40, LANE, {}, NO_OBST, 1, _lane(_F, _F, _F, 1, _F, _F, _F, 0, _F), subset(4096, 40)),
+    # the power rows and the rows without a vy stream: from 61 440 rollouts up (the table tiled)
+    "lane-pow-64": Form(61440, 64, 0, {}, FIVE, 1, _spell("smpc_pass_lane_pow", (_T, _T, _F, 1, _F, _F, _T, 0, _F)),
+                        squared(61440, 64), pa_power=2),
+    "lane-nh-64": Form(61440, 64, 0, {}, FIVE, 1, _spell("smpc_pass_lane_nh", (_T, _T, _F, 1, _F, _F, _T, 0, _F)),
+                       subset(61440, 64, holonomic=False)),
+    # split horizon
+    "split-4-64": Form(16384, 64, 0, _SPLIT, FIVE, 2, "smpc_pass_split<4, true>", subset(16384, 64)),
+    "split-4-48": Form(16384, 48, 0, _SPLIT, FIVE, 2, "smpc_pass_split<4, false>", subset(16384, 48)),
+    "split-2-64": Form(4096, 64, 0, {"SMPC_PASS": "split", "SMPC_SPLIT_NSEG": "2"}, FIVE, 2, "smpc_pass_split<2, true>",
+                       subset(4096, 64)),
+    # the stats pass: the PathAlign row of the per-rollout breakdown
+    "stats-64": Form(4096, 64, WAVE, {}, FIVE, 0, "", subset(4096, 64), stats=True),
+    "stats-200": Form(512, 200, WAVE, {}, FIVE, 0, "", subset(512, 200), stats=True),
+}
+# grouped launches: three members on different plans
+GROUP_SCENES = [scene_key("alt"), scene_key("cluster", "o2", invalid=True), scene_key("repeat")]
+GROUP_LANE_KERNEL = _lane(_T, _T, _T, 1, _F, _F, _T, 0, _F)
+GROUP_WAVE_KERNEL = "smpc_pass_many<1, 0, true>"
+
+
+def all_scene_keys():
+    keys = list(GROUP_SCENES)
+    for f in FORMS.values():
+        keys += f.scenes
+    return sorted(set(keys), key=scene_name)
+
+
+_judged_cache = {}
+
+
+def judged(key, pa_power=1):
+    """What the tests need of the model on a scene, for PathAlign's cost_power: dict(furthest,
+    scored, pa, five [B], x, y, shift = min_single_choice_shift, stats = adversarial_stats).  A tiled
+    scene (more than 4096 rollouts) is judged on its 4096-rollout table, after checking that its
+    noise is that table repeated."""
+    k = (key, pa_power)
+    if k in _judged_cache:
+        return _judged_cache[k]
+    scn = scene(key)
+    cr = critics_of(FIVE, scn.step, pa_power)
+    if scn.B > 4096:
+        base_key = key[:2] + (4096,) + key[3:]
+        j0 = judged(base_key, pa_power)
+        base, reps = scene(base_key), scn.B // 4096
+        assert all(np.array_equal(a, np.tile(b, (reps, 1))) for a, b in zip(scn.noise, base.noise))
+        assert np.array_equal(scn.tick.path_x, base.tick.path_x) and scn.tick.pose_x == base.tick.pose_x
+        j = dict(j0, pa=np.tile(j0["pa"], reps), five=np.tile(j0["five"], reps), x=np.tile(j0["x"], (reps, 1)),
+                 y=np.tile(j0["y"], (reps, 1)))
+    else:
+        m = model(scn, cr)
+        j = dict(furthest=m["furthest"], scored=m["scored"], pa=m["pa"], five=m["five"], x=m["x"], y=m["y"],
+                 shift=min_single_choice_shift(scn, cr, m), stats=adversarial_stats(scn, m))
+    while len(_judged_cache) >= 4:
+        _judged_cache.pop(next(iter(_judged_cache)))
+    _judged_cache[k] = j
+    return j
+
+
+def judged_cases():
+    """Every (scene, PathAlign cost_power) that a form or a grouped launch scores."""
+    cases = {(k, 1) for k in GROUP_SCENES}
+    for f in FORMS.values():
+        cases |= {(k, f.pa_power) for k in f.scenes}
+    return sorted(cases, key=lambda c: (scene_name(c[0]), c[1]))

@@ -1,0 +1,167 @@
+"""PathAlign's path point at ties, equalities, stalls and overruns: every kernel family, zero flips.
+
+utils::findClosestPathPt (tools/utils.hpp:665-675) is written three times in the kernels: sequential
+with a guessed index in smpc_lane_pass.inc, from a segmented scan with the `return 0` chain resolved
+by a ballot in smpc_wave_pass.inc (included again by the stats pass and by smpc_pass_many), and
+carried from horizon quarter to quarter in smpc_split.hip; all three feed it the 1-ulp hardware
+square root.  The parity tests forgive a budget of soft flips, and one wrong path point in one
+rollout is exactly that.  On the scenes of tests/path_point_scenes.py every quantity that enters
+the choice is exact in float32 (tests/test_path_point_cpu.py pins that premise, and that the scenes
+are adversarial, on the oracle alone), so here, for both ticks of every (form, scene) pair,
+
+  * pass_kind and the instance's name are the form's,
+  * fail_flag == 0, furthest_valid, furthest_reached_path_point == the float64 model's (and
+    non_colliding == B where a collision critic counts it),
+  * EVERY rollout's cost is within tol of the oracle's for the same critic list: no flip allowance,
+    nothing skipped; tol = 0.25 * min_single_choice_shift, asserted to exceed ten times the oracle's
+    own distance from the float64 model,
+  * the second tick (speculated: the lane pass's furthest-point prune runs) repeats the first's
+    costs bit for bit.
+
+With findClosestPathPt broken three ways in one kernel family at a time this file fails in that
+family: DESIGN.md section 7 has the counts.
+"""
+import ctypes
+
+import numpy as np
+import pytest
+
+from tests import path_point_scenes as S
+
+pytestmark = pytest.mark.gpu
+
+CASES = sorted(((name, key) for name, f in S.FORMS.items() for key in f.scenes),
+               key=lambda c: (S.scene_name(c[1]), c[0]))
+
+
+@pytest.fixture(scope="module")
+def Smpc():
+    from mpcholonavigation_amd.optimizer import Smpc as Cls
+    return Cls
+
+
+def last_kernel(g):
+    f = g.lib.smpc_debug_last_pass_kernel
+    f.restype, f.argtypes = ctypes.c_char_p, []
+    return f().decode()
+
+
+_oracle_cache = {}
+
+
+def oracle_run(oracle_lib, key, names, step, power):
+    """(tick out, per-rollout costs) of the oracle on a scene; the last few kept."""
+    from oracle.loader import Oracle
+    k = (key, tuple(names), step, power)
+    if k not in _oracle_cache:
+        while len(_oracle_cache) >= 6:
+            _oracle_cache.pop(next(iter(_oracle_cache)))
+        scn = S.scene(key)
+        o = Oracle(scn.config())
+        scn.configure(o, S.critics_of(names, step, power))
+        _, out = o.optimize(scn.tick, scn.u0)
+        _oracle_cache[k] = (out, o.get_costs())
+        o.close()
+    return _oracle_cache[k]
+
+
+def tolerance(oracle_lib, key, step, power):
+    """tol = a quarter of the least one other choice moves a cost; it must stand ten times clear of
+    what separates the oracle's float32 PathAlign cost from the float64 model's."""
+    j = S.judged(key, power)
+    tol = 0.25 * j["shift"]
+    _, c_only = oracle_run(oracle_lib, key, S.ONLY, step, power)
+    d = float(np.abs(c_only.astype(np.float64) - j["pa"]).max())
+    assert tol > 10.0 * d, f"tol {tol:.3e} against oracle-vs-model {d:.3e}"
+    return tol, d, j
+
+
+def check(label, out, costs, j, out_ref, c_ref, tol, obstacles, B):
+    d = np.abs(costs.astype(np.float64) - c_ref.astype(np.float64))
+    bad = int(np.sum(~(d <= tol)))
+    print(f"[path point] {label}: max |cost - oracle| {d.max():.3e} (tol {tol:.3e}), rollouts beyond it {bad} of {d.size}; "
+          f"furthest {out.furthest_reached_path_point} / {j['furthest']}")
+    assert out.fail_flag == 0 == out_ref.fail_flag, label
+    if obstacles:          # (counted by the collision critic: out_ref has it where its list has the critic)
+        assert out.non_colliding == B and out_ref.non_colliding in (0, B), label
+    assert out.furthest_valid and out_ref.furthest_valid, label
+    assert out.furthest_reached_path_point == j["furthest"] == out_ref.furthest_reached_path_point, label
+    assert bad == 0, f"{label}: {bad} rollouts took another path point (worst {d.max():.3e} at rollout {int(d.argmax())})"
+
+
+def make_ctx(Smpc, monkeypatch, scn, flags, env, critics):
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)          # (the knobs are read when the context is created)
+    g = Smpc(scn.config(flags=flags))
+    for k in env:
+        monkeypatch.delenv(k)
+    scn.configure(g, critics)
+    return g
+
+
+@pytest.mark.parametrize("case", CASES, ids=[f"{c[0]}/{S.scene_name(c[1])}" for c in CASES])
+def test_every_sample_takes_the_reference_path_point(Smpc, oracle_lib, monkeypatch, case):
+    name, key = case
+    form = S.FORMS[name]
+    scn = S.scene(key)
+    assert (scn.B, scn.T, scn.step) == (form.B, form.T, form.step)
+    label = f"{name}/{scn.label}"
+    tol, d_om, j = tolerance(oracle_lib, key, form.step, form.pa_power)
+    stats = {k: v for k, v in j["stats"].items() if k != "stall_runs"}
+    print(f"[path point] {label}: oracle vs float64 model {d_om:.2e}; {stats}")
+    # a stats form is judged on the PathAlign row: the oracle scoring PathAlign alone
+    out_ref, c_ref = oracle_run(oracle_lib, key, S.ONLY if form.stats else form.critics, form.step, form.pa_power)
+    g = make_ctx(Smpc, monkeypatch, scn, form.flags, form.env, S.critics_of(form.critics, form.step, form.pa_power))
+    try:
+        first = None
+        for tick in range(2):       # the first without a furthest-point prediction, the second speculated
+            if form.stats:
+                st = g.critic_stats(scn.tick, scn.u0, per_rollout=True)
+                assert st.scored("PathAlignCritic") and not st.fail_flag, label
+                costs = st.per_rollout[st.names.index("PathAlignCritic")].copy()
+            _, out = g.optimize(scn.tick, scn.u0)
+            kernel = last_kernel(g)
+            print(f"[path point] {label} tick {tick}: pass_kind {out.pass_kind} kernel {kernel}")
+            assert out.pass_kind == form.kind and (form.stats or kernel == form.kernel), (label, tick)
+            if not form.stats:
+                costs = g.get_costs()
+            check(f"{label} tick {tick}", out, costs, j, out_ref, c_ref, tol, "obstacles" in form.critics, scn.B)
+            if first is None:
+                first = costs.copy()
+            assert np.array_equal(costs, first), f"{label}: the second tick's costs differ from the first's"
+    finally:
+        g.close()
+
+
+@pytest.mark.parametrize("flags,kernel", [(S.LANE, S.GROUP_LANE_KERNEL), (0, S.GROUP_WAVE_KERNEL)], ids=["lane", "wave"])
+def test_grouped_launch_takes_the_reference_path_point(Smpc, oracle_lib, flags, kernel):
+    """smpc_group_optimize, three members on different plans: the `many` rows of the lane pass and
+    of the wave pass.  The default five critics; the first tick has no furthest-point prediction
+    and scores each member alone, the later ones in one launch: every tick is checked."""
+    from mpcholonavigation_amd.optimizer import SmpcGroup
+    scns = [S.scene(k) for k in S.GROUP_SCENES]
+    members = []
+    for scn in scns:
+        g = Smpc(scn.config(flags=flags))
+        scn.configure(g, S.critics_of(S.FIVE))
+        members.append(g)
+    grp = SmpcGroup(members)
+    seen, firsts = [], [None] * len(scns)
+    try:
+        for tick in range(4):
+            res = grp.optimize([s.tick for s in scns], [s.u0 for s in scns])
+            seen.append(last_kernel(members[0]))
+            for i, (key, scn) in enumerate(zip(S.GROUP_SCENES, scns)):
+                tol, _, j = tolerance(oracle_lib, key, 4, 1)
+                out_ref, c_ref = oracle_run(oracle_lib, key, S.FIVE, 4, 1)
+                assert res[i][1].pass_kind == (1 if flags else 0)
+                costs = members[i].get_costs()
+                check(f"group tick {tick} member {i} {scn.label}", res[i][1], costs, j, out_ref, c_ref, tol, True, scn.B)
+                firsts[i] = costs.copy() if firsts[i] is None else firsts[i]
+                assert np.array_equal(costs, firsts[i]), (tick, i)
+        print(f"[path point] group: kernel launched last, per tick: {seen}")
+        assert kernel in seen, seen
+    finally:
+        grp.close()
+        for g in members:
+            g.close()
