@@ -329,6 +329,22 @@ PROTOTYPES = {
 SMPC_COMM_ID_BYTES = 128
 SMPC_MAX_FOOTPRINT = 16
 
+# The developer entry points of include/smpc_debug.h: aids for tests, tools and the benchmark, no
+# part of the ABI above.  Kept apart so that PROTOTYPES stays the mirror of smpc.h alone.
+DEBUG_PROTOTYPES = {
+    "smpc_debug_last_pass_kernel": (C.c_char_p, []),
+    "smpc_debug_bar_tick": (C.c_int, [_ctx]),
+    "smpc_debug_limit_ms": (C.c_int, [_ctx, C.POINTER(C.c_float)]),
+    "smpc_debug_stats_ms": (C.c_int, [_ctx, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "smpc_debug_furthest_f": (C.c_int, [_ctx, C.POINTER(C.c_float)]),
+    "smpc_debug_tail_timeline": (C.c_int, [_ctx, C.POINTER(C.c_ulonglong)]),
+    "smpc_debug_lane_timeline": (C.c_int, [_ctx, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
+    "smpc_debug_lane_scan_count": (C.c_int, [_ctx, C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint32)]),
+    "smpc_debug_prune_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
+    "smpc_debug_lds_layout": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "smpc_selftest_row_reduce": (C.c_int, [_ctx, C.c_void_p, C.c_uint32, C.c_void_p]),
+}
+
 
 def bind(lib, prototypes=None):
     """Attach restype/argtypes to every prototype; raises AttributeError on a

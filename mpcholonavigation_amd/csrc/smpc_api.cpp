@@ -8,6 +8,7 @@
 // smpc_create() fails.
 
 #include "smpc_ctx.h"
+#include "../../include/smpc_debug.h"   // the developer entry points defined below
 
 #include <emmintrin.h>
 

@@ -13,6 +13,7 @@
 
 #include "smpc_ctx.h"
 #include "smpc_group.h"
+#include "../../include/smpc_debug.h"   // smpc_debug_stats_ms
 
 namespace smpc_impl {
 

@@ -31,8 +31,8 @@ class SmpcError(RuntimeError):
 
 
 def load_library():
-    """dlopen libsmpc.so and bind every prototype of include/smpc.h.
-    Raises if the library was not built (no silent fallback)."""
+    """dlopen libsmpc.so and bind every prototype of include/smpc.h and of the developer entry
+    points (include/smpc_debug.h).  Raises if the library was not built (no silent fallback)."""
     global _lib
     if _lib is None:
         # libsmpc and PyTorch-ROCm both link libamdhip64.so.7 and the first copy loaded serves
@@ -47,7 +47,7 @@ def load_library():
             raise ImportError(
                 f"{LIB_PATH} not found: build it with `make -C mpcholonavigation_amd/csrc` "
                 "(or __graft_entry__.build()); the sampling-MPC path has no CPU fallback")
-        _lib = A.bind(C.CDLL(LIB_PATH))
+        _lib = A.bind(A.bind(C.CDLL(LIB_PATH)), A.DEBUG_PROTOTYPES)
         if _lib.smpc_abi_version() != A.SMPC_ABI_VERSION:
             raise ImportError("libsmpc.so ABI version mismatch")
     return _lib
@@ -281,11 +281,13 @@ class Smpc:
         """smpc_split.hip's N x N transpose-reduce per group of N lanes: v [64 lanes][N] -> [64], N = 16 or 32."""
         v = np.ascontiguousarray(v, dtype=np.float32)
         out = np.empty(64, np.float32)
-        f = self.lib.smpc_selftest_row_reduce
-        f.restype = C.c_int
-        f.argtypes = [A._ctx, C.c_void_p, C.c_uint32, C.c_void_p]
-        self._ck(f(self.h, _ptr(v), v.shape[1], _ptr(out)))
+        self._ck(self.lib.smpc_selftest_row_reduce(self.h, _ptr(v), v.shape[1], _ptr(out)))
         return out
+
+    def last_pass_kernel(self) -> str:
+        """The scoring-pass instance this thread launched last, as a kernel trace spells it
+        (smpc_debug_last_pass_kernel: a developer aid, include/smpc_debug.h)."""
+        return self.lib.smpc_debug_last_pass_kernel().decode()
 
     def set_stream(self, hip_stream):
         self._ck(self.lib.smpc_set_stream(self.h, C.c_void_p(hip_stream)))

@@ -25,7 +25,9 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from mpcholonavigation_amd import _abi as A
-from mpcholonavigation_amd.tick import Tick, default_config, default_critics
+from mpcholonavigation_amd.tick import Tick, default_config
+from tests import harness as H
+from tests.kernel_names import lane, wave
 
 QUANTUM = 2.0 ** -20          # metres: the grid of the accumulated displacements
 MODEL_DT = 0.0625             # 2^-4 s
@@ -34,8 +36,7 @@ CLASSES = (0, 60, 130, 220)   # cells[my, mx] = CLASSES[(mx & 1) + 2 (my & 1)]
 # a near-goal tick drops ObstaclesCritic's repulsive term, which is all that tells 60 from 0:
 # its scenes use four classes that the critical term separates
 CLASSES_NEAR_GOAL = (0, 130, 175, 220)
-ALL_CRITICS = ("obstacles", "path_align", "path_follow", "goal_angle", "prefer_forward", "cost", "goal",
-               "constraint", "twirling", "path_angle", "velocity_deadband", "path_align_legacy")
+ALL_CRITICS = H.ALL_CRITICS
 
 
 @dataclass
@@ -76,12 +77,9 @@ class EdgeScene:
         obj.set_noise(*self.noise)
 
 
-def critics_of(names):
-    """Default parameters, only the named critics enabled."""
-    cr = default_critics()
-    for n in ALL_CRITICS:
-        getattr(cr, n).enabled = 1 if n in names else 0
-    return cr
+def critics_of(names, **over):
+    """Default parameters (every cost_power too), only the named critics enabled."""
+    return H.critics_of(names, power=None, **over)
 
 
 def checkerboard(W, H, classes=CLASSES):
@@ -402,15 +400,7 @@ def subset_scenes(B, T):
 
 WAVE, LANE = A.SMPC_FLAG_WAVE_PER_ROLLOUT, A.SMPC_FLAG_LANE_PER_ROLLOUT
 STORE = A.SMPC_FLAG_STORE_TRAJECTORIES
-FIVE = ("obstacles", "path_align", "path_follow", "goal_angle", "prefer_forward")
-
-
-def _lane(*a):
-    return "smpc_pass_lane<" + ", ".join(str(v).lower() if isinstance(v, bool) else str(v) for v in a) + ">"
-
-
-def _wave(r, mode, full):
-    return f"smpc_pass<{r}, {mode}, {'true' if full else 'false'}>"
+FIVE = H.FIVE
 
 
 @dataclass
@@ -432,26 +422,26 @@ class Form:
 _T, _F = True, False
 FORMS = {
     # wave per rollout
-    "wave-64": Form(4096, 64, WAVE, {}, ("obstacles",), 0, _wave(1, 0, _T), primary_scenes(4096, 64)),
-    "wave-30": Form(4096, 30, WAVE, {}, ("obstacles",), 0, _wave(1, 0, _F), subset_scenes(4096, 30)),
-    "wave-100": Form(4096, 100, WAVE, {}, ("obstacles",), 0, _wave(2, 0, _F), subset_scenes(4096, 100)),
-    "wave-64-cost": Form(4096, 64, WAVE, {}, ("cost",), 0, _wave(1, 3, _T), subset_scenes(4096, 64), "cost"),
+    "wave-64": Form(4096, 64, WAVE, {}, ("obstacles",), 0, wave(1, 0, _T), primary_scenes(4096, 64)),
+    "wave-30": Form(4096, 30, WAVE, {}, ("obstacles",), 0, wave(1, 0, _F), subset_scenes(4096, 30)),
+    "wave-100": Form(4096, 100, WAVE, {}, ("obstacles",), 0, wave(2, 0, _F), subset_scenes(4096, 100)),
+    "wave-64-cost": Form(4096, 64, WAVE, {}, ("cost",), 0, wave(1, 3, _T), subset_scenes(4096, 64), "cost"),
     # (trajectory write-out: the general pass; its trajectories are compared bit for bit)
-    "wave-64-store": Form(4096, 64, WAVE | STORE, {}, ("obstacles",), 0, _wave(1, 2, _T), subset_scenes(4096, 64)),
+    "wave-64-store": Form(4096, 64, WAVE | STORE, {}, ("obstacles",), 0, wave(1, 2, _T), subset_scenes(4096, 64)),
     # lane per rollout: parking form, whole and ragged horizon; re-read form; a partial last wave
-    "lane-64": Form(4096, 64, LANE, {}, ("obstacles",), 1, _lane(_T, _T, _F, 1, _F, _F, _T, 0, _F),
+    "lane-64": Form(4096, 64, LANE, {}, ("obstacles",), 1, lane(),
                     primary_scenes(4096, 64)),
-    "lane-56": Form(4096, 56, LANE, {}, ("obstacles",), 1, _lane(_F, _T, _F, 1, _F, _F, _T, 56, _F),
+    "lane-56": Form(4096, 56, LANE, {}, ("obstacles",), 1, lane(56),
                     subset_scenes(4096, 56)),
-    "lane-rr-128": Form(4096, 128, LANE, {}, ("obstacles",), 1, _lane(_T, _T, _F, 2, _T, _F, _T, 0, _F),
+    "lane-rr-128": Form(4096, 128, LANE, {}, ("obstacles",), 1, lane(128),
                         subset_scenes(4096, 128)),
     "lane-rr-64": Form(4096, 64, LANE, {"SMPC_LANE_REREAD": "1"}, ("obstacles",), 1,
-                       _lane(_T, _T, _F, 1, _T, _F, _T, 0, _F), subset_scenes(4096, 64)),
-    "lane-64-70001": Form(70001, 64, LANE, {}, ("obstacles",), 1, _lane(_T, _T, _F, 1, _F, _F, _T, 0, _F),
+                       lane(rr=True), subset_scenes(4096, 64)),
+    "lane-64-70001": Form(70001, 64, LANE, {}, ("obstacles",), 1, lane(),
                           [scene_key("o2", 0, "border", True, B=70001)]),
     # a near-goal tick: the GoalAngle instance, ObstaclesCritic's repulsive term off.  The default
     # five critics (GoalAngle must be on; the other three are gated off by the distance to the goal)
-    "lane-64-near-goal": Form(4096, 64, LANE, {}, FIVE, 1, _lane(_T, _T, _F, 1, _F, _T, _T, 0, _F),
+    "lane-64-near-goal": Form(4096, 64, LANE, {}, FIVE, 1, lane(ga=True),
                               [scene_key("o2", 0, near_goal=True), scene_key("o0", 1, "far", near_goal=True),
                                scene_key("o1", 0, "border", True, near_goal=True)]),
     # split horizon
@@ -464,11 +454,11 @@ FORMS = {
     "split-4-48": Form(16384, 48, 0, {"SMPC_PASS": "split"}, ("obstacles",), 2, "smpc_pass_split<4, false>",
                        subset_scenes(16384, 48)),
     # a non-holonomic model: vy held at 0, x edges only
-    "lane-64-diff": Form(4096, 64, LANE, {}, ("obstacles",), 1, _lane(_T, _T, _F, 1, _F, _F, _T, 0, _F),
+    "lane-64-diff": Form(4096, 64, LANE, {}, ("obstacles",), 1, lane(),
                          [scene_key("o2", 0, holonomic=False), scene_key("o1", 1, holonomic=False)]),
 }
 # the grouped launch's instance (smpc_group_optimize), two members on different origins
-GROUP_KERNEL = _lane(_T, _T, _T, 1, _F, _F, _T, 0, _F)
+GROUP_KERNEL = lane(many=True)
 GROUP_SCENES = [scene_key("o2", 0), scene_key("o3", 1, "border", True)]
 # the standard parity bar (tests/helpers.assert_parity) with a zero flip budget: the default five
 PARITY_SCENES = [scene_key("o2", 0), scene_key("o4", 1, "far")]

@@ -35,6 +35,7 @@ import numpy as np
 from mpcholonavigation_amd import _abi as A
 from mpcholonavigation_amd.tick import Tick, default_config
 from tests import edge_scenes as E
+from tests.kernel_names import lane, lane_nh, lane_pow, wave
 
 U = 1 << 20                   # integer units per metre: every coordinate below is an int of 2^-20 m
 MODEL_DT = E.MODEL_DT
@@ -104,10 +105,8 @@ ONLY = ("path_align",)
 
 
 def critics_of(names, step=4, pa_power=1):
-    cr = E.critics_of(names)
-    cr.path_align.trajectory_point_step = step
-    cr.path_align.cost_power = pa_power
-    return cr
+    """E.critics_of with PathAlign's trajectory_point_step and cost_power of the scene."""
+    return E.critics_of(names, path_align__trajectory_point_step=step, path_align__cost_power=pa_power)
 
 
 FAMILIES = ("filler", "full_stall", "runs", "ties", "equalities", "quirk", "overrun", "back_forth", "scout")
@@ -770,11 +769,6 @@ def subset(B, T, **kw):
 
 WAVE, LANE = E.WAVE, E.LANE
 _T, _F = True, False
-_lane, _wave = E._lane, E._wave
-
-
-def _spell(name, args):
-    return name + "<" + ", ".join(str(v).lower() if isinstance(v, bool) else str(v) for v in args) + ">"
 
 
 @dataclass
@@ -798,32 +792,32 @@ class Form:
 _SPLIT = {"SMPC_PASS": "split"}
 FORMS = {
     # wave per rollout, PathAlign alone
-    "wave-64": Form(4096, 64, WAVE, {}, ONLY, 0, _wave(1, 0, _T), primary(4096, 64)),
-    "wave-30": Form(4096, 30, WAVE, {}, ONLY, 0, _wave(1, 0, _F), subset(4096, 30)),
-    "wave-100": Form(2048, 100, WAVE, {}, ONLY, 0, _wave(2, 0, _F), subset(2048, 100)),
-    "wave-128": Form(2048, 128, WAVE, {}, ONLY, 0, _wave(2, 0, _T), subset(2048, 128)),
-    "wave-200": Form(512, 200, WAVE, {}, ONLY, 0, _wave(4, 0, _F), subset(512, 200)),
+    "wave-64": Form(4096, 64, WAVE, {}, ONLY, 0, wave(1, 0, _T), primary(4096, 64)),
+    "wave-30": Form(4096, 30, WAVE, {}, ONLY, 0, wave(1, 0, _F), subset(4096, 30)),
+    "wave-100": Form(2048, 100, WAVE, {}, ONLY, 0, wave(2, 0, _F), subset(2048, 100)),
+    "wave-128": Form(2048, 128, WAVE, {}, ONLY, 0, wave(2, 0, _T), subset(2048, 128)),
+    "wave-200": Form(512, 200, WAVE, {}, ONLY, 0, wave(4, 0, _F), subset(512, 200)),
     # the general pass: sqrtf
-    "wave-64-pow2": Form(4096, 64, WAVE, {}, ONLY, 0, _wave(1, 2, _T), squared(4096, 64), pa_power=2),
+    "wave-64-pow2": Form(4096, 64, WAVE, {}, ONLY, 0, wave(1, 2, _T), squared(4096, 64), pa_power=2),
     # trajectory_point_step 1: 63 samples, one segment per wave, the << 32 step of the chain
-    "wave-64-step1": Form(1024, 64, WAVE, {}, ONLY, 0, _wave(1, 0, _T), subset(1024, 64, step=1), step=1),
-    "wave-64-step2": Form(2048, 64, WAVE, {}, ONLY, 0, _wave(1, 0, _T), subset(2048, 64, step=2), step=2),
-    "wave-64-step7": Form(4096, 64, WAVE, {}, ONLY, 0, _wave(1, 0, _T), subset(4096, 64, step=7), step=7),
-    "wave-30-step29": Form(4096, 30, WAVE, {}, ONLY, 0, _wave(1, 0, _F), subset(4096, 30, step=29), step=29),
+    "wave-64-step1": Form(1024, 64, WAVE, {}, ONLY, 0, wave(1, 0, _T), subset(1024, 64, step=1), step=1),
+    "wave-64-step2": Form(2048, 64, WAVE, {}, ONLY, 0, wave(1, 0, _T), subset(2048, 64, step=2), step=2),
+    "wave-64-step7": Form(4096, 64, WAVE, {}, ONLY, 0, wave(1, 0, _T), subset(4096, 64, step=7), step=7),
+    "wave-30-step29": Form(4096, 30, WAVE, {}, ONLY, 0, wave(1, 0, _F), subset(4096, 30, step=29), step=29),
     # lane per rollout: the five critics, and the list without ObstaclesCritic
-    "lane-64": Form(4096, 64, LANE, {}, FIVE, 1, _lane(_T, _T, _F, 1, _F, _F, _T, 0, _F), primary(4096, 64)),
-    "lane-56": Form(4096, 56, LANE, {}, FIVE, 1, _lane(_F, _T, _F, 1, _F, _F, _T, 56, _F), subset(4096, 56)),
-    "lane-40": Form(4096, 40, LANE, {}, FIVE, 1, _lane(_F, _T, _F, 1, _F, _F, _T, 0, _F), subset(4096, 40)),
-    "lane-rr-128": Form(4096, 128, LANE, {}, FIVE, 1, _lane(_T, _T, _F, 2, _T, _F, _T, 0, _F), subset(4096, 128)),
-    "lane-rr-64": Form(4096, 64, LANE, {"SMPC_LANE_REREAD": "1"}, FIVE, 1, _lane(_T, _T, _F, 1, _T, _F, _T, 0, _F),
+    "lane-64": Form(4096, 64, LANE, {}, FIVE, 1, lane(), primary(4096, 64)),
+    "lane-56": Form(4096, 56, LANE, {}, FIVE, 1, lane(56), subset(4096, 56)),
+    "lane-40": Form(4096, 40, LANE, {}, FIVE, 1, lane(full=False), subset(4096, 40)),
+    "lane-rr-128": Form(4096, 128, LANE, {}, FIVE, 1, lane(128), subset(4096, 128)),
+    "lane-rr-64": Form(4096, 64, LANE, {"SMPC_LANE_REREAD": "1"}, FIVE, 1, lane(rr=True),
                        subset(4096, 64)),
-    "lane-64-no-obst": Form(4096, 64, LANE, {}, NO_OBST, 1, _lane(_T, _F, _F, 1, _F, _F, _T, 0, _F), primary(4096, 64)),
-    "lane-56-no-obst": Form(4096, 56, LANE, {}, NO_OBST, 1, _lane(_F, _F, _F, 1, _F, _F, _F, 0, _F), subset(4096, 56)),
-    "lane-40-no-obst": Form(4096, 40, LANE, {}, NO_OBST, 1, _lane(_F, _F, _F, 1, _F, _F, _F, 0, _F), subset(4096, 40)),
+    "lane-64-no-obst": Form(4096, 64, LANE, {}, NO_OBST, 1, lane(obst=False), primary(4096, 64)),
+    "lane-56-no-obst": Form(4096, 56, LANE, {}, NO_OBST, 1, lane(full=False, obst=False, quads=False), subset(4096, 56)),
+    "lane-40-no-obst": Form(4096, 40, LANE, {}, NO_OBST, 1, lane(full=False, obst=False, quads=False), subset(4096, 40)),
     # the power rows and the rows without a vy stream: from 61 440 rollouts up (the table tiled)
-    "lane-pow-64": Form(61440, 64, 0, {}, FIVE, 1, _spell("smpc_pass_lane_pow", (_T, _T, _F, 1, _F, _F, _T, 0, _F)),
+    "lane-pow-64": Form(61440, 64, 0, {}, FIVE, 1, lane_pow(),
                         squared(61440, 64), pa_power=2),
-    "lane-nh-64": Form(61440, 64, 0, {}, FIVE, 1, _spell("smpc_pass_lane_nh", (_T, _T, _F, 1, _F, _F, _T, 0, _F)),
+    "lane-nh-64": Form(61440, 64, 0, {}, FIVE, 1, lane_nh(),
                        subset(61440, 64, holonomic=False)),
     # split horizon
     "split-4-64": Form(16384, 64, 0, _SPLIT, FIVE, 2, "smpc_pass_split<4, true>", subset(16384, 64)),
@@ -836,8 +830,8 @@ FORMS = {
 }
 # grouped launches: three members on different plans
 GROUP_SCENES = [scene_key("alt"), scene_key("cluster", "o2", invalid=True), scene_key("repeat")]
-GROUP_LANE_KERNEL = _lane(_T, _T, _T, 1, _F, _F, _T, 0, _F)
-GROUP_WAVE_KERNEL = "smpc_pass_many<1, 0, true>"
+GROUP_LANE_KERNEL = lane(many=True)
+GROUP_WAVE_KERNEL = wave(1, 0, True, many=True)
 
 
 def all_scene_keys():

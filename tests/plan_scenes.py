@@ -15,16 +15,16 @@ Every scene is the synthetic costmap of make_scenario (200 x 200 cells at 0.05 m
           so that no near-goal gate closes.
   lethal  the short plan with lethal cells under the points P - 11, P - 7 and P - 3.
   near    make_scenario(near_goal=True)'s own plan and goal, the plan resampled to P points."""
-import ctypes as C
 import functools
 from types import SimpleNamespace
 
 import numpy as np
 
 from mpcholonavigation_amd import _abi as A
-from mpcholonavigation_amd.optimizer import LIB_PATH
 from mpcholonavigation_amd.synthetic import make_noise, make_scenario
-from mpcholonavigation_amd.tick import Tick, default_config, default_critics
+from mpcholonavigation_amd.tick import Tick, default_config
+from tests import harness as H
+from tests.harness import DEPLOYED, FIVE, LANE, NO_OBST  # noqa: F401
 from tests.helpers import configure
 
 KIND_WAVE, KIND_LANE, KIND_SPLIT = 0, 1, 2
@@ -35,27 +35,13 @@ WIN_WIDE = 144 * 144     # ... at T > 64 (plan_launch: the reach of the horizon,
 _WORDS = ("off_lut", "off_px", "off_py", "off_pyaw", "off_D", "off_valid", "off_scr", "off_pts4", "off_prune",
           "scr_stride", "scr_pts", "scr_ring", "scr_c", "seg_shift", "group", "total")
 
-FIVE = ("obstacles", "path_align", "path_follow", "goal_angle", "prefer_forward")
-NO_OBST = FIVE[1:]
-DEPLOYED = ("constraint", "cost", "goal", "goal_angle", "path_align", "path_follow", "path_angle",
-            "prefer_forward", "twirling")
-LANE = A.SMPC_FLAG_LANE_PER_ROLLOUT
 ARC_RADIUS = 6.0
 LAND_BEFORE_END = 9      # the short plan: indices between the furthest reached point and the plan's end
 
 
-@functools.lru_cache(maxsize=None)
-def _lib():
-    lb = C.CDLL(LIB_PATH)
-    lb.smpc_debug_lds_layout.restype = C.c_int
-    lb.smpc_debug_lds_layout.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-    return lb
-
-
 def lds_layout(kind, window_bytes, P, T, arg):
     """SmpcLds of a launch as a dict (arg: PathAlign samples / re-read form / segments)."""
-    out = np.zeros(16, np.uint32)
-    assert _lib().smpc_debug_lds_layout(kind, window_bytes, P, T, arg, out.ctypes.data) == 0
+    out = H.debug_lds_layout(kind, window_bytes, P, T, arg)
     return {w: int(out[k]) for k, w in enumerate(_WORDS)}
 
 
@@ -74,19 +60,6 @@ def lane_limit(T, obstacles=True, rr=False, window=None):
 def split_limit(T, nseg):
     """The split pass takes a tick only where the lane pass would (plan_launch: split_now needs lane_now)."""
     return min(lane_limit(T), plan_limit(KIND_SPLIT, WIN, T, nseg))
-
-
-def critics_of(names, powers=None, footprint=()):
-    cr = default_critics()
-    for n in ("obstacles", "path_align", "path_follow", "goal_angle", "prefer_forward", "cost", "goal",
-              "constraint", "twirling", "path_angle", "velocity_deadband", "path_align_legacy"):
-        sub = getattr(cr, n)
-        sub.enabled = 1 if n in names else 0
-        sub.cost_power = (powers or {}).get(n, 1)
-    cr.constraint.vx_max, cr.constraint.vy_max, cr.constraint.vx_min = 0.35, 0.2, -0.1
-    for n in footprint:
-        getattr(cr, n).consider_footprint = 1
-    return cr
 
 
 # ---- plans ------------------------------------------------------------------------------------------
@@ -147,7 +120,7 @@ def _config(sc, flags=0):
 
 
 def _critics(sc):
-    cr = critics_of(sc.names, dict(sc.powers), sc.footprint)
+    cr = H.critics_of(sc.names, dict(sc.powers), sc.footprint, constraint_band=True)
     cr.path_align.trajectory_point_step = sc.step
     if sc.P < 40:
         cr.path_align.offset_from_furthest = 1       # (as test_path_length_edges: PathAlign live on a short plan)
@@ -241,11 +214,7 @@ def oracle_tick(sc, fast=False):
 
 def gpu_context(Smpc, monkeypatch, sc):
     """A context of the library configured for the scene (the knobs are read when it is created)."""
-    for k, v in sc.env:
-        monkeypatch.setenv(k, v)
-    g = Smpc(_config(sc, sc.flags))
-    for k, _ in sc.env:
-        monkeypatch.delenv(k)
+    g = H.create_with_env(Smpc, monkeypatch, _config(sc, sc.flags), sc.env)
     scn, tick = inputs(sc)
     configure(g, scn, critics=_critics(sc), noise=_noise(sc.B, sc.T, sc.noise_seed))
     if sc.footprint:

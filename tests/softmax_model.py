@@ -67,14 +67,14 @@ import numpy as np
 
 from mpcholonavigation_amd import _abi as A
 from mpcholonavigation_amd.synthetic import make_noise, make_scenario
-from mpcholonavigation_amd.tick import default_config, default_critics
+from mpcholonavigation_amd.tick import default_config
+from tests import harness as H
+from tests.kernel_names import lane, lane_pow, wave
 
 EPS = 2.0 ** -24
 CHUNK = 8192
 OMNI, DIFF, ACKER = A.SMPC_MODEL_OMNI, A.SMPC_MODEL_DIFF_DRIVE, A.SMPC_MODEL_ACKERMANN
-FIVE = ("obstacles", "path_align", "path_follow", "goal_angle", "prefer_forward")
-ALL_CRITICS = FIVE + ("cost", "goal", "constraint", "twirling", "path_angle", "velocity_deadband",
-                      "path_align_legacy")
+FIVE, ALL_CRITICS = H.FIVE, H.ALL_CRITICS
 
 
 # ---- the judge -------------------------------------------------------------------------------
@@ -274,24 +274,12 @@ BINDING = (0.305, -0.35, 0.002, 0.004)       # just above the warm start (0.3, 0
 RADIUS = 20.0                                # an Ackermann radius that the update's wz crosses: 0.3 / 20 rad/s
 
 
-def _spell(name, args):
-    return name + "<" + ", ".join(str(v).lower() if isinstance(v, bool) else str(v) for v in args) + ">"
-
-
-def _wave(r, mode, full):
-    return _spell("smpc_pass", (r, mode, full))
-
-
-def _lane(*a):
-    return _spell("smpc_pass_lane", a)
-
-
 _T, _F = True, False
-LANE_64 = _lane(_T, _T, _F, 1, _F, _F, _T, 0, _F)
-LANE_56 = _lane(_F, _T, _F, 1, _F, _F, _T, 56, _F)
-LANE_RR_128 = _lane(_T, _T, _F, 2, _T, _F, _T, 0, _F)
-LANE_POW_64 = _spell("smpc_pass_lane_pow", (_T, _T, _F, 1, _F, _F, _T, 0, _F))
-GROUP_64 = _lane(_T, _T, _T, 1, _F, _F, _T, 0, _F)
+LANE_64 = lane()
+LANE_56 = lane(56)
+LANE_RR_128 = lane(128)
+LANE_POW_64 = lane_pow()
+GROUP_64 = lane(many=True)
 SPLIT = {"SMPC_PASS": "split"}
 FUSED = {"SMPC_FUSED_REDUCE": "1"}
 
@@ -336,25 +324,25 @@ def _c(name, path, B, T, kind, kernel, **kw):
 # would weigh nothing.  tests/test_softmax_update_cpu.py asserts that every defect is seen.)
 CASES = [
     # wave per rollout, R = 1: ragged horizon, ragged last block, fewer rollouts than a block
-    _c("wave-1000x30", "wave", 1000, 30, 0, _wave(1, 0, _F)),
-    _c("wave-2000x56", "wave", 2000, 56, 0, _wave(1, 0, _F)),
-    _c("wave-1x64", "wave", 1, 64, 0, _wave(1, 0, _T), tie=False),
-    _c("wave-17x64", "wave", 17, 64, 0, _wave(1, 0, _T)),
-    _c("wave-65x2", "wave", 65, 2, 0, _wave(1, 0, _F), tie=False),   # (a tie at 63 would hide a per-64 minimum)
+    _c("wave-1000x30", "wave", 1000, 30, 0, wave(1, 0, _F)),
+    _c("wave-2000x56", "wave", 2000, 56, 0, wave(1, 0, _F)),
+    _c("wave-1x64", "wave", 1, 64, 0, wave(1, 0, _T), tie=False),
+    _c("wave-17x64", "wave", 17, 64, 0, wave(1, 0, _T)),
+    _c("wave-65x2", "wave", 65, 2, 0, wave(1, 0, _F), tie=False),   # (a tie at 63 would hide a per-64 minimum)
     # the regimes on the wave pass
-    _c("wave-1000x30-w30", "wave", 1000, 30, 0, _wave(1, 0, _F), wscale=30.0),
-    _c("wave-1000x30-t0.05", "wave", 1000, 30, 0, _wave(1, 0, _F), temperature=0.05),
-    _c("wave-1000x30-t0.01-g0", "wave", 1000, 30, 0, _wave(1, 0, _F), temperature=0.01, gamma=0.0),
-    _c("wave-1000x30-t0.01-single", "wave", 1000, 30, 0, _wave(1, 0, _F), temperature=0.01, gamma=0.1, tie=False,
+    _c("wave-1000x30-w30", "wave", 1000, 30, 0, wave(1, 0, _F), wscale=30.0),
+    _c("wave-1000x30-t0.05", "wave", 1000, 30, 0, wave(1, 0, _F), temperature=0.05),
+    _c("wave-1000x30-t0.01-g0", "wave", 1000, 30, 0, wave(1, 0, _F), temperature=0.01, gamma=0.0),
+    _c("wave-1000x30-t0.01-single", "wave", 1000, 30, 0, wave(1, 0, _F), temperature=0.01, gamma=0.1, tie=False,
        noise_seed=4),
-    _c("wave-2000x56-binding", "wave", 2000, 56, 0, _wave(1, 0, _F), constraints=BINDING),
-    _c("wave-1000x30-all-collide", "wave", 1000, 30, 0, _wave(1, 0, _F), all_lethal=True),
-    _c("wave-1000x30-two-iterations", "wave", 1000, 30, 0, _wave(1, 0, _F), iterations=2, temperature=0.05),
+    _c("wave-2000x56-binding", "wave", 2000, 56, 0, wave(1, 0, _F), constraints=BINDING),
+    _c("wave-1000x30-all-collide", "wave", 1000, 30, 0, wave(1, 0, _F), all_lethal=True),
+    _c("wave-1000x30-two-iterations", "wave", 1000, 30, 0, wave(1, 0, _F), iterations=2, temperature=0.05),
     # R = 2 and R = 4
-    _c("wave-513x100", "wave", 513, 100, 0, _wave(2, 0, _F)),
-    _c("wave-6000x200", "wave", 6000, 200, 0, _wave(4, 0, _F), temperature=0.05),
+    _c("wave-513x100", "wave", 513, 100, 0, wave(2, 0, _F)),
+    _c("wave-6000x200", "wave", 6000, 200, 0, wave(4, 0, _F), temperature=0.05),
     # the general pass (MODE 2)
-    _c("general-2000x56", "general", 2000, 56, 0, _wave(1, 2, _F), flags=STORE, gamma=0.1),
+    _c("general-2000x56", "general", 2000, 56, 0, wave(1, 2, _F), flags=STORE, gamma=0.1),
     # lane per rollout, parking form
     _c("lane-4096x64", "lane", 4096, 64, 1, LANE_64, flags=LANE),
     _c("lane-4100x56", "lane", 4100, 56, 1, LANE_56, flags=LANE, temperature=0.05),
@@ -378,14 +366,14 @@ CASES = [
     _c("split-2-16384x64", "split", 16384, 64, 2, "smpc_pass_split<2, true>",
        env={"SMPC_PASS": "split", "SMPC_SPLIT_NSEG": "2"}, temperature=0.05),
     # the reduction inside the scoring launch
-    _c("fused-2000x56", "fused", 2000, 56, 0, _wave(1, 0, _F), env=FUSED, temperature=0.05),
+    _c("fused-2000x56", "fused", 2000, 56, 0, wave(1, 0, _F), env=FUSED, temperature=0.05),
     _c("fused-lane-4096x64", "fused", 4096, 64, 1, LANE_64, flags=LANE, env=FUSED, temperature=0.05),
     # the other motion models
-    _c("ackermann-2000x56", "ackermann", 2000, 56, 0, _wave(1, 0, _F), model=ACKER),
-    _c("diff-drive-2000x56", "diff-drive", 2000, 56, 0, _wave(1, 0, _F), model=DIFF, temperature=0.05),
+    _c("ackermann-2000x56", "ackermann", 2000, 56, 0, wave(1, 0, _F), model=ACKER),
+    _c("diff-drive-2000x56", "diff-drive", 2000, 56, 0, wave(1, 0, _F), model=DIFF, temperature=0.05),
     # shards: G = 3 on 3001 rollouts cut unevenly, the best rollout in the last shard; one whole shard off the map
-    _c("shards-3001x56", "shards", 3001, 56, 0, _wave(1, 0, _F), cuts=(0, 1000, 1937, 3001), temperature=0.05),
-    _c("shards-3001x56-one-collides", "shards", 3001, 56, 0, _wave(1, 0, _F), cuts=(0, 1000, 1937, 3001),
+    _c("shards-3001x56", "shards", 3001, 56, 0, wave(1, 0, _F), cuts=(0, 1000, 1937, 3001), temperature=0.05),
+    _c("shards-3001x56-one-collides", "shards", 3001, 56, 0, wave(1, 0, _F), cuts=(0, 1000, 1937, 3001),
        collide_rows=(1000, 1937)),
     # a group of three members, one neg_inv_temp each
     _c("group-t0.3", "group", 2048, 64, 1, GROUP_64, flags=LANE, noise_seed=950),
@@ -432,9 +420,7 @@ class Built:
 
 
 def critics_of(case):
-    cr = default_critics()
-    for n in ALL_CRITICS:
-        getattr(cr, n).enabled = 1 if n in FIVE else 0
+    cr = H.critics_of(FIVE, power=None)
     for n in ("path_align", "path_follow", "prefer_forward", "goal_angle"):
         sub = getattr(cr, n)
         sub.cost_weight = float(np.float32(sub.cost_weight * case.wscale))

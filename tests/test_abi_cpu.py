@@ -9,16 +9,9 @@ import pytest
 
 from mpcholonavigation_amd import _abi as A
 from mpcholonavigation_amd.tick import default_config, default_critics
+from tests.harness import lib  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    ge.build()
-    from mpcholonavigation_amd.optimizer import load_library
-    return load_library()
 
 
 def _declared_functions():
@@ -34,6 +27,36 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
         assert hasattr(lib, name), f"{name} declared in smpc.h but not exported"
         assert name in A.PROTOTYPES, f"{name} has no ctypes prototype"
     assert sorted(A.PROTOTYPES) == declared
+
+
+def test_every_developer_entry_point_is_declared_exported_and_bound(lib):
+    """include/smpc_debug.h (developer aids, no part of the ABI): libsmpc.so exports every function
+    it declares, _abi.DEBUG_PROTOTYPES mirrors exactly those, and no smpc_debug_* / smpc_selftest_*
+    function is defined in the library's sources without a declaration in one of the two headers."""
+    src = open(os.path.join(ROOT, "include", "smpc_debug.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    declared = sorted(set(re.findall(r"\b(smpc_[a-z_0-9]+)\s*\(", src)))
+    assert len(declared) >= 11 and "smpc_debug_last_pass_kernel" in declared
+    for name in declared:
+        assert hasattr(lib, name), f"{name} declared in smpc_debug.h but not exported"
+        assert name in A.DEBUG_PROTOTYPES, f"{name} has no ctypes prototype"
+        assert name not in A.PROTOTYPES, f"{name} is bound twice"
+        assert getattr(lib, name).argtypes == A.DEBUG_PROTOTYPES[name][1], f"{name} not bound by load_library"
+    assert sorted(A.DEBUG_PROTOTYPES) == declared
+    known = set(declared) | set(_declared_functions())
+    csrc = os.path.join(ROOT, "mpcholonavigation_amd", "csrc")
+    defined = set()
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith(".cpp"):
+            txt = open(os.path.join(csrc, f)).read()
+            txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+            txt = re.sub(r"//[^\n]*", "", txt)
+            # a definition: the name at the start of a declarator, its parameter list, then the body
+            defined |= set(re.findall(r"^[A-Za-z_][\w \*]*?\b(smpc_(?:debug|selftest)_[a-z_0-9]+)\s*\([^;{}]*\)\s*\{",
+                                      txt, flags=re.M))
+    assert len(defined) >= 11 and "smpc_debug_stats_ms" in defined
+    for name in sorted(defined):
+        assert name in known, f"{name} is defined under csrc/ but declared in neither smpc.h nor smpc_debug.h"
 
 
 def test_every_symbol_of_the_host_header_is_exported(lib):

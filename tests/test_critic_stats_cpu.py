@@ -6,20 +6,12 @@ import re
 import subprocess
 import tempfile
 
-import pytest
 
 from mpcholonavigation_amd import _abi as A
+from tests.harness import lib  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROWS = ("sum", "min", "max", "weighted", "at_best")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    ge.build()
-    from mpcholonavigation_amd.optimizer import load_library
-    return load_library()
 
 
 def header(name="smpc.h"):

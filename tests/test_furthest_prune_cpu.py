@@ -7,12 +7,10 @@ For every plan, every table entry K and a grid of fractions phi, theta = float32
 for a furthest point some rollout has already attained.  No endpoint may be called prunable while
 its F exceeds theta: zero violations.  So that never pruning does not pass, on the straight plan
 at least 99 % of the endpoints with F <= theta - 0.01 must be called prunable."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
-from mpcholonavigation_amd.optimizer import LIB_PATH
+from tests.harness import debug_prune_table, lib  # noqa: F401
 
 f32 = np.float32
 ENTRIES = 16
@@ -20,19 +18,8 @@ FLOATS = 4 + 8 * ENTRIES
 RES = 0.05
 
 
-@pytest.fixture(scope="module")
-def lib():
-    lb = C.CDLL(LIB_PATH)
-    lb.smpc_debug_prune_table.restype = C.c_int
-    lb.smpc_debug_prune_table.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
-    return lb
-
-
 def table(lib, px, py, k0, on=1):
-    px = np.ascontiguousarray(px, f32)
-    py = np.ascontiguousarray(py, f32)
-    out = np.zeros(FLOATS, f32)
-    assert lib.smpc_debug_prune_table(px.ctypes.data, py.ctypes.data, len(px), k0, on, out.ctypes.data) == 0
+    out = debug_prune_table(px, py, k0, on, FLOATS)
     head = out[:4].view(np.uint32)
     return int(head[0]), int(head[1]), out[4:].reshape(ENTRIES, 8)
 

@@ -10,8 +10,6 @@ Scenes: make_case's scene (and the wall scene for the collision critics), the sp
 control sequence non-zero on every control; limits 3 / -3 / 3 / 3.5 at model_dt 0.05 with the
 default standard deviations, on which tests/test_accel_limits_cpu.py counts more than 10 % of the
 elements limited."""
-import ctypes
-
 import numpy as np
 import pytest
 
@@ -19,32 +17,14 @@ from mpcholonavigation_amd import _abi as A
 from mpcholonavigation_amd.synthetic import make_noise, wall_beside_path
 from mpcholonavigation_amd.tick import Tick, default_config
 from tests import accel_model as am
-from tests.footprint_scenes import FIVE, critics_of, list_critics, setup
+from tests.footprint_scenes import classes, critics_of, list_critics, setup
+from tests.harness import FIVE, LANE, OUT_FIELDS, bits, close, last_kernel, mod  # noqa: F401
 from tests.helpers import make_case, rel_err
 
 pytestmark = pytest.mark.gpu
 
 LIM = (3.0, -3.0, 3.0, 3.5)
-LANE = A.SMPC_FLAG_LANE_PER_ROLLOUT
 SPEED = (0.25, 0.05, -0.1)
-OUT_FIELDS = ("fail_flag", "furthest_valid", "furthest_reached_path_point", "non_colliding", "min_cost", "sum_w",
-              "passes", "pass_kind")
-
-
-@pytest.fixture(scope="module")
-def mod():
-    from mpcholonavigation_amd import optimizer
-    return optimizer
-
-
-def last_kernel(g):
-    f = g.lib.smpc_debug_last_pass_kernel
-    f.restype, f.argtypes = ctypes.c_char_p, []
-    return f().decode()
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def same_noise(got, want, label):
@@ -102,11 +82,6 @@ def same_tick(ga, gb, ra, rb, label, skip=()):
             continue
         assert getattr(oa, f) == getattr(ob, f), (label, f, getattr(oa, f), getattr(ob, f))
     assert np.array_equal(bits(ga.get_costs()), bits(gb.get_costs())), label
-
-
-def close(*objs):
-    for o in objs:
-        o.close()
 
 
 # ---- 1. the kernel against the model -----------------------------------------------------------
@@ -342,10 +317,6 @@ def test_the_limiter_follows_the_noise_the_tick_scores_with(mod, B, T, flags):
 
 
 # ---- 9. host ----------------------------------------------------------------------------------------
-
-def classes(names):
-    return ["".join(w.capitalize() for w in n.split("_")) + "Critic" for n in names]
-
 
 def host(cfg, scn, noise, limits=None):
     from mpcholonavigation_amd.host_optimizer import Optimizer

@@ -18,30 +18,17 @@ that premise, and that the scenes are adversarial, on the oracle alone), so here
 With the guard bands forced to zero (cell_eps = cell_eps_w = 0 in smpc_prepare.cpp; every index
 stays bounds-checked) this file fails in every family: DESIGN.md section 7 has the counts.
 """
-import ctypes
-
 import numpy as np
 import pytest
 
 from tests import edge_scenes as E
+from tests.harness import Smpc, create_with_env, last_kernel  # noqa: F401
 from tests.helpers import assert_parity
 
 pytestmark = pytest.mark.gpu
 
 CASES = sorted(((name, key) for name, f in E.FORMS.items() for key in f.scenes),
                key=lambda c: (E.scene_name(c[1]), c[0]))       # (forms that share a scene: side by side)
-
-
-@pytest.fixture(scope="module")
-def Smpc():
-    from mpcholonavigation_amd.optimizer import Smpc as S
-    return S
-
-
-def last_kernel(g):
-    f = g.lib.smpc_debug_last_pass_kernel
-    f.restype, f.argtypes = ctypes.c_char_p, []
-    return f().decode()
 
 
 _oracle_cache = {}
@@ -64,11 +51,7 @@ def oracle_run(oracle_lib, key, names):
 
 
 def make_ctx(Smpc, monkeypatch, scn, flags, env, names):
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)          # (the knobs are read when the context is created)
-    g = Smpc(scn.config(flags=flags))
-    for k in env:
-        monkeypatch.delenv(k)
+    g = create_with_env(Smpc, monkeypatch, scn.config(flags=flags), env)
     scn.configure(g, E.critics_of(names))
     return g
 

@@ -23,8 +23,6 @@ D. SMPC_FLAG_LANE_PER_ROLLOUT contexts drawing with the device RNG: the breakdow
    call with a list that has no path critic.
 
 The float32 CPU oracle is used in B, C and D only, at B <= 256 rollouts (C: 400)."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -33,33 +31,17 @@ from mpcholonavigation_amd.synthetic import make_noise
 from mpcholonavigation_amd.tick import Tick
 from tests import softmax_model as sm
 from tests.footprint_scenes import CIRCUMSCRIBED, FOOTPRINT, LAYER_SCALING, LISTS, critics_of, setup, wall_case
+from tests.harness import FIVE, OUT_FIELDS, Oracle, Smpc, copy_of, last_kernel, shifted  # noqa: F401
 from tests.helpers import configure, cost_flips
-from tests.test_gpu_critic_stats import (CONTROL, EPS, FIVE, ORDER, OUT_FIELDS, Oracle, Smpc, check_statistics,  # noqa: F401
-                                         critics, last_kernel, mask_of, row_parity, scene, slices_of,
-                                         sliced_float32_statistics, statistics_ratios)
+from tests.kernel_names import wave_at
+from tests.stats_scenes import (CONTROL, EPS, NO_FURTHEST, ORDER, check_statistics, critics, mask_of, row_parity, scene,
+                                slices_of, sliced_float32_statistics, statistics_ratios)
 
 pytestmark = pytest.mark.gpu
 
 DIFF, ACKER, OMNI = A.SMPC_MODEL_DIFF_DRIVE, A.SMPC_MODEL_ACKERMANN, A.SMPC_MODEL_OMNI
 MODEL_NAME = {DIFF: "DiffDrive", ACKER: "Ackermann", OMNI: "Omni"}
 SLICE = 16384
-
-
-def copy_of(cfg, **kw):
-    c2 = type(cfg)()
-    C.memmove(C.byref(c2), C.byref(cfg), C.sizeof(cfg))
-    for k, v in kw.items():
-        setattr(c2, k, v)
-    return c2
-
-
-def kernel(g):
-    return last_kernel(g).decode()
-
-
-def wave_name(T, mode):
-    r = 1 if T <= 64 else 2 if T <= 128 else 4
-    return f"smpc_pass<{r}, {mode}, {'true' if T == 64 * r else 'false'}>"
 
 
 def rounding_bound(st):
@@ -104,7 +86,7 @@ def judged(g, cfg, scn, label, S):
     rw, re = statistics_ratios(st, costs, cfg)
     print(f"[critic stats reach] {label}: {S} slices, weighted {rw:.3f} effective_samples {re:.3f} of the bar; "
           f"effective samples {st.effective_samples:.2f}, best {st.best_rollout} in slice {st.best_rollout // SLICE}; "
-          f"tick ran {kernel(g)}")
+          f"tick ran {last_kernel(g)}")
     if max(rw, re) > 1.0:
         fw, fe = statistics_ratios(st, costs, cfg, sliced_float32_statistics(st.per_rollout, costs, cfg))
         print(f"[critic stats reach] {label}: the float32 restatement: weighted {fw:.3f} effective_samples {fe:.3f} of the bar")
@@ -132,8 +114,8 @@ def test_rows_add_up_to_the_ticks_costs_across_slices(Smpc, B, T):
     cfg, scn, g = wall_ctx(Smpc, B, T, power=2, flags=A.SMPC_FLAG_WAVE_PER_ROLLOUT if B > 61440 else 0)
     st = g.critic_stats(scn.tick, scn.u0, per_rollout=True)
     _, out = g.optimize(scn.tick, scn.u0)
-    print(f"[critic stats reach] rows add up {B}x{T}: tick ran {kernel(g)}")
-    assert last_kernel(g).startswith(b"smpc_pass<") and out.pass_kind == 0
+    print(f"[critic stats reach] rows add up {B}x{T}: tick ran {last_kernel(g)}")
+    assert last_kernel(g).startswith("smpc_pass<") and out.pass_kind == 0
     costs = g.get_costs().astype(np.float64)
     err = np.abs(st.per_rollout.astype(np.float64).sum(axis=0) - costs)
     bound = rounding_bound(st)
@@ -257,7 +239,7 @@ FP_SHAPES = [(256, 56), (128, 100), (64, 200)]       # R = 1, 2 and 4, each ragg
 def footprint_ctx(Smpc, which, B, T, power, closed_in=False, footprint=True):
     names, coll = LISTS[which]
     cfg, scn, noise = wall_case(B, T, closed_in=closed_in)
-    cr = critics_of(names, (coll,) if footprint else (), power)
+    cr = critics_of(names, power, (coll,) if footprint else ())
     return cfg, scn, noise, cr, setup(Smpc(cfg), scn, cr, noise)
 
 
@@ -276,7 +258,7 @@ def test_footprint_rows_match_the_oracle_critic_by_critic(Smpc, Oracle, B, T, wh
     assert og.fail_flag == oo.fail_flag == 0
     flips = cost_flips(g.get_costs(), o.get_costs())
     print(f"[critic stats reach] footprint {which} {B}x{T} power {power}: {flips} flips of the totals, "
-          f"{oo.non_colliding} of {B} clear, tick ran {kernel(g)}")
+          f"{oo.non_colliding} of {B} clear, tick ran {last_kernel(g)}")
     assert flips == 0, "pick another seed: the totals already flip"
     assert 0 < oo.non_colliding < B and og.non_colliding == oo.non_colliding
     st = g.critic_stats(scn.tick, scn.u0, per_rollout=True)
@@ -286,7 +268,7 @@ def test_footprint_rows_match_the_oracle_critic_by_critic(Smpc, Oracle, B, T, wh
         if n not in names:
             assert not st.scored_mask >> k & 1 and not st.per_rollout[k].any(), n
             continue
-        o1 = setup(Oracle(cfg0), scn, critics_of((n,), (n,) if n == coll else (), power), noise)
+        o1 = setup(Oracle(cfg0), scn, critics_of((n,), power, (n,) if n == coll else ()), noise)
         o1.optimize(scn.tick, scn.u0)
         ref = o1.get_costs()
         row_parity(st.per_rollout[k], ref, T, f"footprint {which} {B}x{T} power {power} {n}")
@@ -313,8 +295,8 @@ def test_footprint_rows_add_up_to_the_ticks_costs(Smpc, B, T, which, power):
     _, out = g.optimize(scn.tick, scn.u0)
     costs = g.get_costs()
     total = st.per_rollout.astype(np.float64).sum(axis=0)
-    print(f"[critic stats reach] footprint {which} {B}x{T} power {power}: tick ran {kernel(g)}")
-    assert out.pass_kind == 0 and out.fail_flag == 0 and kernel(g) == wave_name(T, 4 if power == 1 else 2)
+    print(f"[critic stats reach] footprint {which} {B}x{T} power {power}: tick ran {last_kernel(g)}")
+    assert out.pass_kind == 0 and out.fail_flag == 0 and last_kernel(g) == wave_at(T, 4 if power == 1 else 2)
     if power == 2:
         err, bound = np.abs(total - costs), rounding_bound(st)
         print(f"[critic stats reach] footprint rows add up: max err / bound {float((err / np.maximum(bound, 1e-300)).max()):.3f}")
@@ -336,15 +318,15 @@ def test_every_footprint_collides(Smpc, which, kept, power):
     st = g.critic_stats(scn.tick, scn.u0, per_rollout=True)
     assert st.fail_flag and st.scored_mask == mask_of(kept), bin(st.scored_mask)
     _, out = g.optimize(scn.tick, scn.u0)
-    print(f"[critic stats reach] closed in {which} power {power}: tick ran {kernel(g)}, {out.passes} passes")
+    print(f"[critic stats reach] closed in {which} power {power}: tick ran {last_kernel(g)}, {out.passes} passes")
     assert out.fail_flag == 1 and out.non_colliding == 0
     costs = g.get_costs()
     total = st.per_rollout.astype(np.float64).sum(axis=0)
     if power == 2:
-        assert kernel(g) == wave_name(T, 2)
+        assert last_kernel(g) == wave_at(T, 2)
         assert np.all(np.abs(total - costs) <= rounding_bound(st))
     else:
-        assert kernel(g) == wave_name(T, 4)
+        assert last_kernel(g) == wave_at(T, 4)
         row_parity(costs, total, T, f"closed in {which}: lean tick against the rows")
     for k, n in enumerate(ORDER):
         assert n in kept or not st.per_rollout[k].any(), n
@@ -363,8 +345,8 @@ def moving_ticks(g, scn, before=None, ticks=10):
         if before:
             before(tk, u)
         u, out = g.optimize(tk, u)
-        log.append((u.copy(), tuple(getattr(out, n) for n in OUT_FIELDS), g.get_costs(), kernel(g)))
-        u = np.concatenate([u[:, 1:], u[:, -1:]], axis=1)
+        log.append((u.copy(), tuple(getattr(out, n) for n in OUT_FIELDS), g.get_costs(), last_kernel(g)))
+        u = shifted(u)
     return log
 
 
@@ -384,7 +366,7 @@ def test_both_collision_critics_with_a_footprint_are_refused_and_nothing_moves(S
     B, T = 256, 56
     names = LISTS["deployed"][0] + ("obstacles",)
     cfg, scn, noise = wall_case(B, T)
-    cr = critics_of(names, ("cost", "obstacles"))
+    cr = critics_of(names, footprint=("cost", "obstacles"))
     g, twin = (setup(Smpc(cfg), scn, cr, noise) for _ in range(2))
     refused = []
 
@@ -402,10 +384,10 @@ def test_both_collision_critics_with_a_footprint_are_refused_and_nothing_moves(S
     assert len(refused) == 10 and plain[0][1][OUT_FIELDS.index("fail_flag")] == 0
     same_ticks(plain, probed)
     # (either switch refuses while both critics are in the list); without ObstaclesCritic the same context answers
-    g.set_critics(critics_of(names, ("cost",)))
+    g.set_critics(critics_of(names, footprint=("cost",)))
     with pytest.raises(SmpcError):
         g.critic_stats(scn.tick, scn.u0)
-    g.set_critics(critics_of(LISTS["deployed"][0], ("cost",)))
+    g.set_critics(critics_of(LISTS["deployed"][0], footprint=("cost",)))
     st = g.critic_stats(scn.tick, scn.u0)
     assert st.scored("CostCritic") and not st.scored("ObstaclesCritic") and not st.fail_flag
 
@@ -420,7 +402,7 @@ def test_host_face_with_a_footprint_leaves_eval_control_alone():
     from mpcholonavigation_amd.host_optimizer import Optimizer
     B, T = 2000, 56
     cfg, scn, noise = wall_case(B, T)
-    cr = critics_of(LISTS["deployed"][0], ("cost",))
+    cr = critics_of(LISTS["deployed"][0], footprint=("cost",))
     hosts = []
     for _ in range(2):
         h = Optimizer(cfg, cr, 20.0, critics=DEPLOYED_CLASSES)
@@ -482,7 +464,7 @@ def test_nonholonomic_rows_match_the_oracle(Smpc, Oracle, B, T, model, power, ki
     assert og.fail_flag == oo.fail_flag == 0
     label = f"{MODEL_NAME[model]} {B}x{T} {kind} power {power}"
     flips = cost_flips(g.get_costs(), o.get_costs())
-    print(f"[critic stats reach] {label}: {flips} flips of the totals, tick ran {kernel(g)}")
+    print(f"[critic stats reach] {label}: {flips} flips of the totals, tick ran {last_kernel(g)}")
     assert flips == 0, "pick another seed: the totals already flip"
     st = g.critic_stats(scn.tick, u0, per_rollout=True)
     assert st.batch == B and not st.fail_flag
@@ -517,7 +499,6 @@ def test_nonholonomic_rows_match_the_oracle(Smpc, Oracle, B, T, model, power, ki
 LANE_SHAPES = [(192, 64), (130, 56), (257, 60)]     # whole groups; ragged horizon, partial group; the noise tests' shape
 # a list without a path critic: no furthest-point pre-pass runs in front of the stats pass, and that
 # pre-pass relayouts the noise itself (launch_furthest) — here only score_rows' own call does
-NO_FURTHEST = ("obstacles", "goal_angle", "prefer_forward")
 LANE_LISTS = {"five": FIVE, "no-path-critic": NO_FURTHEST}
 
 
@@ -570,8 +551,8 @@ def test_lane_context_rows_on_device_noise(Smpc, Oracle, B, T, model, which):
     label = f"lane context {MODEL_NAME[model]} {B}x{T} {which}"
     rows_against_the_oracle(Oracle, st, cfg, scn, noise, label, names=names)
     _, out = g.optimize(scn.tick, scn.u0)
-    print(f"[critic stats reach] {label}: tick ran {kernel(g)}")
-    assert out.pass_kind == 1 and kernel(g).startswith("smpc_pass_lane") and out.fail_flag == 0
+    print(f"[critic stats reach] {label}: tick ran {last_kernel(g)}")
+    assert out.pass_kind == 1 and last_kernel(g).startswith("smpc_pass_lane") and out.fail_flag == 0
     costs = g.get_costs()
     row_parity(costs, st.per_rollout.astype(np.float64).sum(axis=0), T, f"{label}: lane tick against the rows")
     assert np.array_equal(st.at_best, st.per_rollout[:, st.best_rollout])
@@ -593,7 +574,7 @@ def test_lane_context_rows_with_a_background_draw_pending(Smpc, Oracle, B, T, mo
         g.redraw_noise_async()
         st = g.critic_stats(scn.tick, u, per_rollout=True) if ask else None
         u2, out = g.optimize(scn.tick, u)
-        runs.append((u2, tuple(getattr(out, n) for n in OUT_FIELDS), g.get_costs(), kernel(g)))
+        runs.append((u2, tuple(getattr(out, n) for n in OUT_FIELDS), g.get_costs(), last_kernel(g)))
     same_ticks(runs[:1], runs[1:])
     label = f"pending draw {MODEL_NAME[model]} {B}x{T} {which}"
     print(f"[critic stats reach] {label}: second tick ran {runs[1][3]}")

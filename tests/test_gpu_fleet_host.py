@@ -24,85 +24,13 @@ import pytest
 from mpcholonavigation_amd import _abi as A
 from mpcholonavigation_amd.synthetic import make_noise, make_scenario
 from mpcholonavigation_amd.tick import Tick, default_config, default_critics
-from tests.footprint_scenes import CIRCUMSCRIBED, DEPLOYED, FIVE, FOOTPRINT, LAYER_SCALING, list_critics, setup, wall_case
+from tests.footprint_scenes import (CIRCUMSCRIBED, FOOTPRINT, FREQ, INTS, LAYER_SCALING, NOT_TAKEN, THROWN, classes, dress,
+                                    fleet_of, host, list_critics, moved_along, round_with_twins, same, setup, wall_case,
+                                    wall_pair)
+from tests.harness import DEPLOYED, FIVE, close, shifted
 from tests.helpers import rel_err
 
 pytestmark = pytest.mark.gpu
-
-FREQ = 20.0
-THROWN, NOT_TAKEN = -10, 1
-INTS = ("furthest_valid", "furthest_reached_path_point", "non_colliding", "fail_flag")
-
-
-def classes(names):
-    return ["".join(w.capitalize() for w in n.split("_")) + "Critic" for n in names]
-
-
-def host(cfg, scn, cr, names, noise=None, footprint=True, **kw):
-    """A sortham::Optimizer on a scene: costmap, footprint, supplied noise."""
-    from mpcholonavigation_amd.host_optimizer import Optimizer
-    h = Optimizer(cfg, cr, FREQ, critics=classes(names), cost_scaling_factor=scn.cost_scaling_factor,
-                  inflation_radius=scn.inflation_radius, **kw)
-    dress(h, scn, noise, footprint)
-    return h
-
-
-def dress(h, scn, noise, footprint=True):
-    h.set_costmap(scn.cells, scn.origin_x, scn.origin_y, scn.resolution, inscribed_radius=scn.inscribed_radius)
-    if footprint:
-        h.set_footprint(FOOTPRINT, CIRCUMSCRIBED, LAYER_SCALING)
-    if noise is not None:
-        h.set_noise(*noise)
-
-
-def wall_pair(B=256, T=56, seed=1234, cfg_kw=None, supply_noise=True, **kw):
-    """(member, twin, scn, cfg): two deployed-list optimizers on the wall scene with the same everything."""
-    cfg, scn, _ = wall_case(B, T)
-    for k, v in (cfg_kw or {}).items():
-        setattr(cfg, k, v)
-    noise = make_noise(B, T, std=(cfg.vx_std, cfg.vy_std, cfg.wz_std), seed=seed) if supply_noise else None
-    cr = list_critics("deployed")
-    return tuple(host(cfg, scn, cr, DEPLOYED, noise, **kw) for _ in range(2)) + (scn, cfg)
-
-
-def moved(t, k):
-    """The scene's tick with the pose k control periods further along the path, at cruise speed."""
-    return Tick(t.pose_x + 0.015 * k, t.pose_y, t.pose_yaw, (0.3, 0.0, 0.0), t.path_x, t.path_y, t.path_yaw,
-                t.goal_x, t.goal_y)
-
-
-def same(member, twin, r, tw_t, out_t, label):
-    assert r.status == 0, (label, r.status, r.error)
-    assert np.array_equal(r.twist, tw_t), (label, r.twist, tw_t)
-    assert np.array_equal(member.get_control_sequence(), twin.get_control_sequence()), label
-    assert np.array_equal(member.get_optimized_trajectory(), twin.get_optimized_trajectory()), label
-    for f in INTS + ("min_cost", "sum_w"):
-        assert getattr(r.out, f) == getattr(out_t, f), (label, f, getattr(r.out, f), getattr(out_t, f))
-
-
-def round_with_twins(fleet, members, twins, ticks, label, take=None):
-    """One fleet round, the twins' own eval_control on the same inputs, every taken member compared.
-    -> (results, single ticks added, batched launches added)."""
-    before = fleet.stats()
-    res = fleet.eval_control(ticks, take=take)
-    after = fleet.stats()
-    for i, (m, t) in enumerate(zip(members, twins)):
-        if take is not None and not take[i]:
-            assert res[i].status == NOT_TAKEN
-            continue
-        tw_t, out_t = t.eval_control(ticks[i])
-        same(m, t, res[i], tw_t, out_t, f"{label} member {i}")
-    return res, after.single_ticks - before.single_ticks, after.batched_launches - before.batched_launches
-
-
-def close(*objs):
-    for o in objs:
-        o.close()
-
-
-def fleet_of(members):
-    from mpcholonavigation_amd.host_optimizer import FleetOptimizer
-    return FleetOptimizer(members)
 
 
 # ---- 1. closed loop, equal bits ------------------------------------------------------------------
@@ -115,7 +43,7 @@ def test_closed_loop_every_member_equals_its_twin(B, T):
     assert all(m.get_constraints()[1] for m in members)          # shifting on
     log = []
     for k in range(8):
-        res, d_single, d_batched = round_with_twins(fleet, members, twins, [moved(scn.tick, k)] * 3, f"{B}x{T} round {k}")
+        res, d_single, d_batched = round_with_twins(fleet, members, twins, [moved_along(scn.tick, k)] * 3, f"{B}x{T} round {k}")
         passes = [r.out.passes for r in res]
         log.append((passes, d_single, d_batched))
         assert all(r.out.pass_kind == 0 for r in res), k
@@ -155,7 +83,7 @@ def test_closed_loop_against_the_reference_host_logic_on_the_oracle():
         oracles.append(o)
     fleet = fleet_of(members)
     for k in range(8):
-        tick = moved(scn.tick, k)
+        tick = moved_along(scn.tick, k)
         res = fleet.eval_control([tick] * 3)
         for i, (m, o) in enumerate(zip(members, oracles)):
             tw_o, out_o = o.eval_control(tick)
@@ -182,7 +110,7 @@ def test_a_member_left_out_is_untouched_and_goes_on_as_its_twin():
     for k in range(8):
         take = [1, 0, 1] if k in (2, 3) else [1, 1, 1]           # rounds 3 and 4 without member 1
         u, c = members[1].get_control_sequence(), members[1].get_constraints()[0]
-        ticks = [moved(scn.tick, k)] * 3
+        ticks = [moved_along(scn.tick, k)] * 3
         if not take[1]:
             ticks[1] = None                                       # not looked at
         res, _, _ = round_with_twins(fleet, members, twins, ticks, f"take round {k}", take=take)
@@ -198,7 +126,7 @@ def test_a_member_left_out_is_untouched_and_goes_on_as_its_twin():
     after = fleet.stats()
     assert (after.batched_launches, after.single_ticks, after.retries) == (before.batched_launches, before.single_ticks, before.retries)
     assert all(np.array_equal(m.get_control_sequence(), s) for m, s in zip(members, state))
-    round_with_twins(fleet, members, twins, [moved(scn.tick, 8)] * 3, "after the empty round")
+    round_with_twins(fleet, members, twins, [moved_along(scn.tick, 8)] * 3, "after the empty round")
     fleet.close()
     close(*members, *twins)
 
@@ -220,7 +148,7 @@ def test_a_member_that_cannot_plan_throws_alone(retry):
     members, twins, scn = [p[0] for p in pairs], [p[1] for p in pairs], pairs[0][2]
     fleet = fleet_of(members)
     for k in range(2):
-        ticks = [moved(scn.tick, k), bad_scn.tick, moved(scn.tick, k)]
+        ticks = [moved_along(scn.tick, k), bad_scn.tick, moved_along(scn.tick, k)]
         res = fleet.eval_control(ticks)
         assert res[1].status == THROWN and "Optimizer fail to compute path" in res[1].error, (res[1].status, res[1].error)
         with pytest.raises(RuntimeError, match="Optimizer fail to compute path"):
@@ -309,7 +237,7 @@ def test_members_are_used_through_their_own_handles_between_rounds():
     def rounds(n, label):
         nonlocal k
         for _ in range(n):
-            out = round_with_twins(fleet, members, twins, [moved(scn.tick, k)] * 3, f"{label} round {k}")
+            out = round_with_twins(fleet, members, twins, [moved_along(scn.tick, k)] * 3, f"{label} round {k}")
             k += 1
         return out
 
@@ -405,7 +333,7 @@ def test_regenerate_noises_members_draw_their_twins_epochs():
     fleet = fleet_of(members)
     costs = []
     for k in range(6):
-        res, _, _ = round_with_twins(fleet, members, twins, [moved(scn.tick, k)] * 3, f"regenerate round {k}")
+        res, _, _ = round_with_twins(fleet, members, twins, [moved_along(scn.tick, k)] * 3, f"regenerate round {k}")
         costs.append(res[0].out.min_cost)
     assert len(set(costs)) == len(costs)                         # a new epoch every round
     fleet.close()
@@ -413,10 +341,6 @@ def test_regenerate_noises_members_draw_their_twins_epochs():
 
 
 # ---- 8. smpc_group_optimize_some directly ---------------------------------------------------------------
-
-def shifted(u):
-    return np.concatenate([u[:, 1:], u[:, -1:]], axis=1)
-
 
 def test_the_subset_call_on_a_group():
     """take=None (smpc_group_optimize, now a call of the subset entry) against a full take on a second
@@ -433,7 +357,7 @@ def test_the_subset_call_on_a_group():
     ga, gb = mod.SmpcGroup(sets[0]), mod.SmpcGroup(sets[1])
     us = [scn.u0] * 3
     for k in range(6):
-        ticks = [moved(scn.tick, k)] * 3
+        ticks = [moved_along(scn.tick, k)] * 3
         skip = k == 3
         take = [1, 0, 1] if skip else [1, 1, 1]
         costs = sets[1][1].get_costs()
@@ -479,8 +403,8 @@ def test_a_round_that_fails_as_a_whole_moves_nobody_and_the_next_one_is_the_twin
     members, twins, scn = [p[0] for p in trio], [p[1] for p in trio], trio[0][2]
     fleet = fleet_of(members)
     for k in range(3):
-        round_with_twins(fleet, members, twins, [moved(scn.tick, k)] * 3, f"before round {k}")
-    t = moved(scn.tick, 3)
+        round_with_twins(fleet, members, twins, [moved_along(scn.tick, k)] * 3, f"before round {k}")
+    t = moved_along(scn.tick, 3)
     n = 1025
     px = (t.pose_x + 0.002 * np.arange(n)).astype(np.float32)
     long = Tick(t.pose_x, t.pose_y, t.pose_yaw, t.speed, px, np.full(n, t.path_y[0], np.float32), np.zeros(n, np.float32),
@@ -495,7 +419,7 @@ def test_a_round_that_fails_as_a_whole_moves_nobody_and_the_next_one_is_the_twin
         assert np.array_equal(m.get_control_sequence(), u) and np.array_equal(m.get_constraints()[0], c)
     assert fleet.stats().retries == stats.retries
     for k in range(3, 6):
-        res, d_single, d_batched = round_with_twins(fleet, members, twins, [moved(scn.tick, k)] * 3, f"after round {k}")
+        res, d_single, d_batched = round_with_twins(fleet, members, twins, [moved_along(scn.tick, k)] * 3, f"after round {k}")
     assert d_batched == 1
     fleet.close()
     close(*members, *twins)

@@ -8,8 +8,6 @@ shards and the host optimizer's C face.
 Scene, footprint, lists and shapes: tests/footprint_scenes.py.  The bar is the one of
 test_gpu_parity.py::test_consider_footprint_parity on the same scene: assert_parity with
 max_flips=3, fail_flag and non_colliding exact."""
-import ctypes
-
 import numpy as np
 import pytest
 
@@ -17,41 +15,16 @@ from mpcholonavigation_amd import _abi as A
 from mpcholonavigation_amd.tick import Tick
 from tests.footprint_scenes import (CIRCUMSCRIBED, FOOTPRINT, LAYER_SCALING, SHAPES, critics_of, keep,
                                     list_critics, oracle_tick, setup, wall_case)
+from tests.harness import Oracle, Smpc, create_with_env, last_kernel  # noqa: F401
 from tests.helpers import assert_parity, rel_err
+from tests.kernel_names import wave_at
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def Smpc():
-    from mpcholonavigation_amd.optimizer import Smpc as S
-    return S
-
-
-@pytest.fixture(scope="module")
-def Oracle():
-    from oracle.loader import Oracle as O, build
-    build()
-    return O
-
-
-def last_kernel(g):
-    f = g.lib.smpc_debug_last_pass_kernel
-    f.restype, f.argtypes = ctypes.c_char_p, []
-    return f().decode()
-
-
-def wave(T, mode):
-    r = 1 if T <= 64 else 2 if T <= 128 else 4
-    return f"smpc_pass<{r}, {mode}, {'true' if T == 64 * r else 'false'}>"
-
-
 def general_route(Smpc, monkeypatch, cfg):
     """A context whose footprint ticks keep the general pass (the knob is read at smpc_create)."""
-    monkeypatch.setenv("SMPC_FOOTPRINT_PASS", "general")
-    g = Smpc(cfg)
-    monkeypatch.delenv("SMPC_FOOTPRINT_PASS")
-    return g
+    return create_with_env(Smpc, monkeypatch, cfg, {"SMPC_FOOTPRINT_PASS": "general"})
 
 
 def check(g, ug, og, ref, label):
@@ -69,7 +42,7 @@ def test_deployed_list_with_costs_footprint_runs_mode_4(Smpc, B, T):
     for k in range(2):       # the first tick without a furthest-point prediction, the second speculated
         u, out = g.optimize(scn.tick, u)
         print(f"[footprint] deployed {B}x{T} tick {k}: pass_kind {out.pass_kind} kernel {last_kernel(g)}")
-        assert (out.pass_kind, last_kernel(g)) == (0, wave(T, 4)), k
+        assert (out.pass_kind, last_kernel(g)) == (0, wave_at(T, 4)), k
     g.close()
 
 
@@ -90,9 +63,9 @@ def test_the_knob_keeps_the_general_pass(Smpc, monkeypatch):
 
 
 @pytest.mark.parametrize("why,critics", [
-    ("both collision critics with a footprint", lambda: critics_of(("cost", "obstacles", "path_follow"), ("cost",))),
-    ("a cost_power of 2", lambda: critics_of(("cost", "path_follow", "prefer_forward"), ("cost",), power=2)),
-    ("VelocityDeadband in the list", lambda: critics_of(("cost", "path_follow", "velocity_deadband"), ("cost",)))])
+    ("both collision critics with a footprint", lambda: critics_of(("cost", "obstacles", "path_follow"), footprint=("cost",))),
+    ("a cost_power of 2", lambda: critics_of(("cost", "path_follow", "prefer_forward"), 2, ("cost",))),
+    ("VelocityDeadband in the list", lambda: critics_of(("cost", "path_follow", "velocity_deadband"), footprint=("cost",)))])
 def test_what_stays_on_the_general_pass(Smpc, why, critics):
     cfg, scn, noise = wall_case(256, 56)
     g = setup(Smpc(cfg), scn, critics(), noise)
@@ -121,7 +94,7 @@ def test_parity_with_the_oracle(Smpc, which, B, T):
     cfg, scn, noise = wall_case(B, T)
     g = setup(Smpc(cfg), scn, list_critics(which), noise)
     ug, og = g.optimize(scn.tick, scn.u0)
-    assert last_kernel(g) == wave(T, 4)
+    assert last_kernel(g) == wave_at(T, 4)
     check(g, ug, og, on, f"footprint lean {which} {B}x{T}")
     g.close()
 
@@ -150,7 +123,7 @@ def test_lean_and_general_route_agree(Smpc, monkeypatch, B, T):
         g = general_route(Smpc, monkeypatch, cfg) if route == "general" else Smpc(cfg)
         setup(g, scn, list_critics("deployed"), noise)
         u, out = g.optimize(scn.tick, scn.u0)
-        assert last_kernel(g) == wave(T, 4 if route == "lean" else 2)
+        assert last_kernel(g) == wave_at(T, 4 if route == "lean" else 2)
         check(g, u, out, ref, f"{route} route {B}x{T}")
         res[route] = keep(u, out, g.get_costs())
         g.close()

@@ -8,67 +8,17 @@ the full grid, and every wave takes groups gw, gw + 2048, ...: every wave runs t
 3 x 2048 x 64 = 393 216 rollouts.  A wave's first group has no bound of its own yet: wave 0 of a
 block scans it, the other seven leave its endpoints in LDS and judge them behind their second
 group against wave 0's maximum; second and third groups have the wave's own bound."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
-from mpcholonavigation_amd import _abi as A
 from mpcholonavigation_amd.synthetic import make_noise, make_scenario
-from mpcholonavigation_amd.tick import Tick, default_config, default_critics
+from mpcholonavigation_amd.tick import Tick, default_config
+from tests.harness import DEPLOYED, LANE, Oracle, Smpc, critics_of, furthest_f, scan_count, shifted  # noqa: F401
 from tests.helpers import assert_parity, configure, make_case
 
 pytestmark = pytest.mark.gpu
 
-LANE = A.SMPC_FLAG_LANE_PER_ROLLOUT
 B3 = 393216
-DEPLOYED = ("constraint", "cost", "goal", "goal_angle", "path_align", "path_follow", "path_angle",
-            "prefer_forward", "twirling")
-
-
-@pytest.fixture(scope="module")
-def Smpc():
-    from mpcholonavigation_amd.optimizer import Smpc as S
-    return S
-
-
-@pytest.fixture(scope="module")
-def Oracle():
-    from oracle.loader import Oracle as O, build
-    build()
-    return O
-
-
-def critic_set(names):
-    cr = default_critics()
-    for n in ("obstacles", "path_align", "path_follow", "goal_angle", "prefer_forward", "cost", "goal",
-              "constraint", "twirling", "path_angle", "velocity_deadband"):
-        getattr(cr, n).enabled = 1 if n in names else 0
-    return cr
-
-
-def shift(u):
-    return np.concatenate([u[:, 1:], u[:, -1:]], axis=1)
-
-
-def furthest_f(g):
-    """The float F = index + fraction the last tick's pass reported (tuple slot 2)."""
-    fn = g.lib.smpc_debug_furthest_f
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
-    f = C.c_float(0)
-    if fn(g.h, C.byref(f)) != 0:      # no critic of the tick consumed the furthest point
-        return float("nan")
-    return f.value
-
-
-def scan_count(g):
-    fn = g.lib.smpc_debug_lane_scan_count
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint32)]
-    n, groups = C.c_ulonglong(0), C.c_uint32(0)
-    assert fn(g.h, C.byref(n), C.byref(groups)) == 0
-    return n.value, groups.value
 
 
 def pair(Smpc, monkeypatch, B, T, scn, critics=None, flags=LANE, seed=77, timeline=False):
@@ -105,7 +55,7 @@ def same_ticks(on, off, ticks, u0, label, kind=1):
         assert oa.passes == ob.passes, (label, k, oa.passes, ob.passes)
         assert oa.fail_flag == ob.fail_flag
         seen.append((int(oa.furthest_reached_path_point), round(fa, 3), int(oa.passes)))
-        u = shift(ua)
+        u = shifted(ua)
     print(f"[furthest prune] {label}: (furthest point, F, passes) per tick: {seen}")
     return seen
 
@@ -179,7 +129,7 @@ def test_parity_with_the_oracle(Smpc, Oracle):
         assert og.pass_kind == 1
         assert og.furthest_reached_path_point == oo.furthest_reached_path_point, label
         assert_parity(ug, og, uo, oo, g.get_costs(), o.get_costs(), max_flips=1, label=f"prune {label}", report=False)
-        u = shift(uo)
+        u = shifted(uo)
     g.close()
 
 
@@ -195,12 +145,12 @@ def test_share_of_groups_that_scan(Smpc, monkeypatch):
         u = scn.u0
         for _ in range(3):                  # the first tick has no prediction: it does not speculate
             un, out = g.optimize(scn.tick, u)
-            u = shift(un)
+            u = shifted(un)
         scan_count(g)                       # (clears)
         passes = 0
         for _ in range(n):
             un, out = g.optimize(scn.tick, u)
-            u = shift(un)
+            u = shifted(un)
             passes += out.passes
         got, groups = scan_count(g)
         assert groups == B3 // 64 and passes == n
@@ -222,7 +172,7 @@ def test_goal_angle_instance_is_untouched(Smpc, monkeypatch):
 def test_deployed_list_instance_is_untouched(Smpc, monkeypatch):
     T = 56
     scn = make_scenario(T)
-    on, off = pair(Smpc, monkeypatch, 70000, T, scn, critics=critic_set(DEPLOYED))
+    on, off = pair(Smpc, monkeypatch, 70000, T, scn, critics=critics_of(DEPLOYED, power=None))
     same_ticks(on, off, [scn.tick] * 4, scn.u0, "deployed-list instance")
 
 
@@ -251,7 +201,7 @@ def test_grouped_instances_are_untouched(Smpc, monkeypatch):
         seen = []
         for _ in range(4):
             res = grp.optimize([s.tick for s in scns], us)
-            us = [shift(u) for u, _ in res]
+            us = [shifted(u) for u, _ in res]
             seen.append([(u.copy(), int(o.furthest_reached_path_point), int(o.non_colliding), int(o.passes)) for u, o in res] +
                         [m.get_costs() for m in members])
         results.append(seen)

@@ -19,11 +19,11 @@ import pytest
 from mpcholonavigation_amd import _abi as A
 from mpcholonavigation_amd.synthetic import make_noise, make_scenario, wall_beside_path
 from mpcholonavigation_amd.tick import Tick, default_config
-from tests.footprint_scenes import critics_of, list_critics, setup, wall_case
+from tests.footprint_scenes import (critics_of, fleet_of, list_critics, moved_along, round_with_twins, setup, wall_member,
+                                    wall_pair)
+from tests.harness import FIVE, OUT_FIELDS, close, copy_of, mod, moved, shifted  # noqa: F401
 from tests.helpers import configure
-from tests.test_gpu_critic_stats import CONTROL, FIVE, ORDER, OUT_FIELDS, critics, mask_of, scene
-from tests.test_gpu_critic_stats_reach import NO_FURTHEST, copy_of
-from tests.test_gpu_group_wave import close, mod, moved, shifted, wall_member  # noqa: F401
+from tests.stats_scenes import CONTROL, NO_FURTHEST, ORDER, critics, mask_of, scene
 
 pytestmark = pytest.mark.gpu
 
@@ -381,12 +381,11 @@ def test_fleet_host_statistics_equal_the_twins_and_leave_the_loop_alone():
     of every round of a ten-tick closed loop: the statistics are the twins' bit for bit, and the Twists
     of the fleet's rounds are those of a second set of twins that were never asked — the breakdowns
     moved nothing.  One member is left out of the statistics on odd ticks."""
-    from tests import test_gpu_fleet_host as fh
-    trio = [fh.wall_pair(256 if i else 72, 56, seed=500 + i) for i in range(3)]
+    trio = [wall_pair(256 if i else 72, 56, seed=500 + i) for i in range(3)]
     members, twins, scn = [p[0] for p in trio], [p[1] for p in trio], trio[0][2]
-    fleet = fh.fleet_of(members)
+    fleet = fleet_of(members)
     for k in range(10):
-        ticks = [fh.moved(scn.tick, k)] * 3
+        ticks = [moved_along(scn.tick, k)] * 3
         take = None if k % 2 == 0 else (True, False, True)
         res = fleet.critic_stats(ticks, take=take, per_rollout=(k < 2))
         for i in range(3):
@@ -396,23 +395,23 @@ def test_fleet_host_statistics_equal_the_twins_and_leave_the_loop_alone():
             # (the twin's own breakdown leaves its loop alone: test_gpu_critic_stats.py holds that)
             same_stats(res[i], twins[i].critic_stats(ticks[i], per_rollout=(k < 2)), f"host tick {k} member {i}")
             assert res[i].scored("CostCritic") and res[i].scored("ControlCost") and res[i].batch == (256 if i else 72)
-        fh.round_with_twins(fleet, members, twins, ticks, f"host round {k}")
+        round_with_twins(fleet, members, twins, ticks, f"host round {k}")
     # ungrouped in between (a round of the members' own eval_control leaves the fleet so): the call regroups
-    fleet.run_rounds([fh.moved(scn.tick, 10)] * 3, 1, alone=True)
+    fleet.run_rounds([moved_along(scn.tick, 10)] * 3, 1, alone=True)
     for t in twins:
-        t.eval_control(fh.moved(scn.tick, 10))
-    res = fleet.critic_stats([fh.moved(scn.tick, 11)] * 3)
+        t.eval_control(moved_along(scn.tick, 10))
+    res = fleet.critic_stats([moved_along(scn.tick, 11)] * 3)
     for i in range(3):
-        same_stats(res[i], twins[i].critic_stats(fh.moved(scn.tick, 11)), f"host after ungroup member {i}")
-    fh.round_with_twins(fleet, members, twins, [fh.moved(scn.tick, 11)] * 3, "host round after ungroup")
+        same_stats(res[i], twins[i].critic_stats(moved_along(scn.tick, 11)), f"host after ungroup member {i}")
+    round_with_twins(fleet, members, twins, [moved_along(scn.tick, 11)] * 3, "host round after ungroup")
     # a member that was shut down: SMPC_ERR_STATE in its entry, the others have theirs
     members[1].close()
-    res = fleet.critic_stats([fh.moved(scn.tick, 12)] * 3)
+    res = fleet.critic_stats([moved_along(scn.tick, 12)] * 3)
     assert isinstance(res[1], Exception) and res[1].code == A.SMPC_ERR_STATE
     for i in (0, 2):
-        same_stats(res[i], twins[i].critic_stats(fh.moved(scn.tick, 12)), f"host with a member gone, member {i}")
+        same_stats(res[i], twins[i].critic_stats(moved_along(scn.tick, 12)), f"host with a member gone, member {i}")
     fleet.close()
-    fh.close(members[0], members[2], *twins)
+    close(members[0], members[2], *twins)
 
 
 def test_a_member_on_several_trips_of_a_grid_smaller_than_the_launch(mod, monkeypatch):

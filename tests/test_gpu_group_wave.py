@@ -22,7 +22,6 @@ context makes by itself in prepare_tick; a grouped tick's blocks are handed over
 pass over all riding members, which does not consult it.  The guard itself is the same code on both
 routes: block 0 of a member's share of smpc_pass_many echoes the number it read, the reduction hands
 it on, fetch_out compares."""
-import ctypes
 import os
 
 import numpy as np
@@ -31,59 +30,17 @@ import pytest
 from mpcholonavigation_amd import _abi as A
 from mpcholonavigation_amd.synthetic import make_noise, make_scenario, wall_beside_path
 from mpcholonavigation_amd.tick import Tick, default_config, default_critics
-from tests.footprint_scenes import list_critics, oracle_tick, setup, wall_case
+from tests.footprint_scenes import list_critics, oracle_tick, same_bits, setup, wall_case, wall_member
+from tests.harness import close, last_kernel, mod, moved, shifted  # noqa: F401
 from tests.helpers import assert_parity, configure
+from tests.kernel_names import wave
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def mod():
-    from mpcholonavigation_amd import optimizer
-    return optimizer
-
-
-def last_kernel(g):
-    f = g.lib.smpc_debug_last_pass_kernel
-    f.restype, f.argtypes = ctypes.c_char_p, []
-    return f().decode()
-
-
 def row(T, mode, many=True):
-    return f"smpc_pass{'_many' if many else ''}<1, {mode}, {'true' if T == 64 else 'false'}>"
-
-
-def moved(t, dx):
-    return Tick(t.pose_x + dx, t.pose_y, t.pose_yaw, t.speed, t.path_x, t.path_y, t.path_yaw, t.goal_x, t.goal_y)
-
-
-def shifted(u):
-    return np.concatenate([u[:, 1:], u[:, -1:]], axis=1)
-
-
-def same_bits(member, twin, res_g, res_t, label):
-    """Everything a tick reports, grouped against alone: equal, not close."""
-    (ug, og), (ut, ot) = res_g, res_t
-    assert np.array_equal(ug, ut), label
-    for f in ("min_cost", "sum_w", "furthest_valid", "furthest_reached_path_point", "non_colliding", "fail_flag"):
-        assert getattr(og, f) == getattr(ot, f), (label, f, getattr(og, f), getattr(ot, f))
-    assert np.array_equal(member.get_costs(), twin.get_costs()), label
-
-
-def wall_member(mod, B, T, which="deployed", footprint=True, noise_seed=1234, cfg_kw=None, critics=None, **case_kw):
-    """(member, twin, scn): two contexts on the wall scene with the same everything."""
-    cfg, scn, _ = wall_case(B, T, **case_kw)
-    for k, v in (cfg_kw or {}).items():
-        setattr(cfg, k, v)
-    noise = make_noise(B, T, std=(cfg.vx_std, cfg.vy_std, cfg.wz_std), seed=noise_seed)
-    cr = critics if critics is not None else list_critics(which, footprint)
-    fp = bool(cr.cost.consider_footprint or cr.obstacles.consider_footprint)
-    return tuple(setup(mod.Smpc(cfg), scn, cr, noise, fp) for _ in range(2)) + (scn,)
-
-
-def close(*objs):
-    for o in objs:
-        o.close()
+    """The grouped row of a horizon of at most 64 steps (many=False: a member ticked alone)."""
+    return wave(1, mode, T == 64, many)
 
 
 # ---- 1. the instance, by name ----------------------------------------------------------------

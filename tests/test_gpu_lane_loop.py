@@ -10,57 +10,29 @@ sequence, tick output and per-rollout costs with the CPU oracle at assert_parity
 (no flip allowance: the default synthetic scene needs none at these sizes); where cheap, also with a
 wave-per-rollout context on the same inputs.
 """
-import ctypes
-
 import numpy as np
 import pytest
 
 from mpcholonavigation_amd import _abi as A
-from mpcholonavigation_amd.tick import Tick, default_critics
+from mpcholonavigation_amd.tick import Tick
+from tests.harness import FIVE, Oracle, Smpc, copy_of, critics_of, last_kernel, oracle_tick  # noqa: F401
 from tests.helpers import assert_parity, configure, make_case
+from tests.kernel_names import lane
 
 pytestmark = pytest.mark.gpu
 
-F, Tr = False, True
-
-
-def lane(*args):
-    return "smpc_pass_lane<" + ", ".join(str(a).lower() if isinstance(a, bool) else str(a) for a in args) + ">"
-
-
-FULL64 = lane(Tr, Tr, F, 1, F, F, Tr, 0, F)
-QUADS = lane(F, Tr, F, 1, F, F, Tr, 0, F)
-TC56 = lane(F, Tr, F, 1, F, F, Tr, 56, F)
-RAGGED = lane(F, Tr, F, 1, F, F, F, 0, F)
-
-
-def last_kernel(g):
-    f = g.lib.smpc_debug_last_pass_kernel
-    f.restype, f.argtypes = ctypes.c_char_p, []
-    return f().decode()
-
-
-@pytest.fixture(scope="module")
-def Smpc():
-    from mpcholonavigation_amd.optimizer import Smpc as S
-    return S
-
-
-@pytest.fixture(scope="module")
-def Oracle():
-    from oracle.loader import Oracle as O, build
-    build()
-    return O
+FULL64 = lane()
+QUADS = lane(full=False)
+TC56 = lane(56)
+RAGGED = lane(full=False, quads=False)
+NO_PATH_ALIGN = tuple(n for n in FIVE if n != "path_align")
 
 
 def five(path_align=True, pa_offset=None):
     """The five critics of the lane pass at their defaults; PathAlign off or with another
     offset_from_furthest on request."""
-    cr = default_critics()
-    cr.path_align.enabled = 1 if path_align else 0
-    if pa_offset is not None:
-        cr.path_align.offset_from_furthest = pa_offset
-    return cr
+    over = {} if pa_offset is None else {"path_align__offset_from_furthest": pa_offset}
+    return critics_of(FIVE if path_align else NO_PATH_ALIGN, power=None, **over)
 
 
 def with_plan(tick, path_x):
@@ -73,8 +45,7 @@ def with_plan(tick, path_x):
 
 def lane_tick(Smpc, cfg, scn, noise, critics=None, tick=None, wave=False):
     """One tick on a context of its own: the forced lane pass, or the wave-per-rollout pass."""
-    c2 = type(cfg)()
-    ctypes.memmove(ctypes.byref(c2), ctypes.byref(cfg), ctypes.sizeof(cfg))
+    c2 = copy_of(cfg)
     c2.flags |= A.SMPC_FLAG_WAVE_PER_ROLLOUT if wave else A.SMPC_FLAG_LANE_PER_ROLLOUT
     g = Smpc(c2)
     configure(g, scn, critics=critics, noise=noise)
@@ -88,11 +59,7 @@ def check(Smpc, Oracle, cfg, scn, noise, kernel, label, critics=None, tick=None,
     """Lane pass against the oracle (and the wave pass) on the same inputs; returns the lane pass's
     and the oracle's per-rollout costs."""
     ug, og, cg, ran = lane_tick(Smpc, cfg, scn, noise, critics, tick)
-    o = Oracle(cfg)
-    configure(o, scn, critics=critics, noise=noise)
-    uo, oo = o.optimize(tick or scn.tick, scn.u0)
-    co = o.get_costs().copy()
-    o.close()
+    uo, oo, co = oracle_tick(Oracle, cfg, scn, noise, critics, tick)
     print(f"[lane loop] {label}: kernel {ran}, pass_kind {og.pass_kind}, non_colliding {og.non_colliding} "
           f"(oracle {oo.non_colliding}), furthest {og.furthest_reached_path_point}")
     assert og.pass_kind == 1 and ran == kernel, (label, ran)

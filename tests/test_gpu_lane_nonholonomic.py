@@ -14,65 +14,27 @@ those for the plain ticks too.  Three things are checked at the smallest batch t
 Every non-holonomic case has a sideways measured speed (0.3 m/s) and a stale caller vy row (0.123):
 an instance that still looked at vy would show.
 """
-import ctypes
-
 import numpy as np
 import pytest
 
 from mpcholonavigation_amd import _abi as A
-from mpcholonavigation_amd.tick import Tick, default_critics
+from mpcholonavigation_amd.tick import Tick
+from tests.harness import (DEPLOYED, FIVE, NO_OBST, Oracle, Smpc,  # noqa: F401
+                           copy_of, create_with_env, critics_of, last_kernel)
 from tests.helpers import assert_parity, configure, make_case
+from tests.kernel_names import LANE_NH_ROW, LANE_ROW, lane, lane_pow
 
 pytestmark = pytest.mark.gpu
 
 B = 61440
-FIVE = ("obstacles", "path_align", "path_follow", "goal_angle", "prefer_forward")
-NO_OBST = FIVE[1:]
-DEPLOYED = ("constraint", "cost", "goal", "goal_angle", "path_align", "path_follow", "path_angle",
-            "prefer_forward", "twirling")
 DIFF, ACKER, OMNI = A.SMPC_MODEL_DIFF_DRIVE, A.SMPC_MODEL_ACKERMANN, A.SMPC_MODEL_OMNI
 MODEL_NAME = {DIFF: "DiffDrive", ACKER: "Ackermann", OMNI: "Omni"}
 KNOB = {"SMPC_NONHOLO_PASS": "omni"}
 F, Tr = False, True
 
 
-def critics_of(names=FIVE, power=1):
-    cr = default_critics()
-    for n in ("obstacles", "path_align", "path_follow", "goal_angle", "prefer_forward", "cost", "goal",
-              "constraint", "twirling", "path_angle", "velocity_deadband", "path_align_legacy"):
-        sub = getattr(cr, n)
-        sub.enabled = 1 if n in names else 0
-        sub.cost_power = power
-    return cr
-
-
-def last_kernel(g):
-    f = g.lib.smpc_debug_last_pass_kernel
-    f.restype, f.argtypes = ctypes.c_char_p, []
-    return f().decode()
-
-
-def spell(name, args):
-    return name + "<" + ", ".join(str(a).lower() if isinstance(a, bool) else str(a) for a in args) + ">"
-
-
-def lane(*args):
-    return spell("smpc_pass_lane", args)
-
-
-def lane_nh(*args):
-    return spell("smpc_pass_lane_nh", args)
-
-
-def lane_pow(*args):
-    return spell("smpc_pass_lane_pow", args)
-
-
 # the instance without a vy stream, and the Omni-form instance of the same tick, by horizon
-NH_KERNEL = {64: lane_nh(Tr, Tr, F, 1, F, F, Tr, 0, F), 56: lane_nh(F, Tr, F, 1, F, F, Tr, 56, F),
-             40: lane_nh(F, Tr, F, 1, F, F, Tr, 0, F)}
-OMNI_KERNEL = {64: lane(Tr, Tr, F, 1, F, F, Tr, 0, F), 56: lane(F, Tr, F, 1, F, F, Tr, 56, F),
-               40: lane(F, Tr, F, 1, F, F, Tr, 0, F)}
+NH_KERNEL, OMNI_KERNEL = LANE_NH_ROW, LANE_ROW
 
 _CASES = {}
 
@@ -84,11 +46,7 @@ def case(batch, T, model=DIFF, **kw):
     if key not in _CASES:
         _CASES[key] = make_case(batch, T, **kw)
     cfg, scn, noise = _CASES[key]
-    c2 = type(cfg)()
-    ctypes.memmove(ctypes.byref(c2), ctypes.byref(cfg), ctypes.sizeof(cfg))
-    c2.motion_model = model
-    c2.ackermann_min_turning_r = 0.5
-    return c2, scn, noise
+    return copy_of(cfg, motion_model=model, ackermann_min_turning_r=0.5), scn, noise
 
 
 def sideways(t, dx=0.0, dy=0.0, yaw=None, **kw):
@@ -98,7 +56,7 @@ def sideways(t, dx=0.0, dy=0.0, yaw=None, **kw):
 
 
 def colliding(scn):
-    """test_gpu_lane_powers.colliding_tick: the robot 0.45 m beside the plan, heading into the obstacles."""
+    """test_gpu_lane_powers.py's colliding tick: the robot 0.45 m beside the plan, heading into the obstacles."""
     return sideways(scn.tick, dy=-0.45, yaw=-0.3)
 
 
@@ -114,29 +72,11 @@ def stale_u0(scn, model, T):
 
 
 def make_ctx(Smpc, monkeypatch, cfg, scn, noise, critics=None, env=None, seed=None):
-    env = env or {}
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)          # (the knobs are read when the context is created)
-    g = Smpc(cfg)
-    for k in env:
-        monkeypatch.delenv(k)
-    configure(g, scn, critics=critics if critics is not None else critics_of(), noise=noise)
+    g = create_with_env(Smpc, monkeypatch, cfg, env)
+    configure(g, scn, critics=critics if critics is not None else critics_of(FIVE), noise=noise)
     if seed is not None:
         g.seed(seed)
     return g
-
-
-@pytest.fixture(scope="module")
-def Smpc():
-    from mpcholonavigation_amd.optimizer import Smpc as S
-    return S
-
-
-@pytest.fixture(scope="module")
-def Oracle():
-    from oracle.loader import Oracle as O, build
-    build()
-    return O
 
 
 # ---- a. routing, pinned by name ----------------------------------------------------------------------
@@ -158,14 +98,14 @@ def test_plain_cruise_tick_runs_the_instance_without_vy(Smpc, monkeypatch, model
 
 # (id, model, batch, horizon, config flags, critic names, cost_power, near the goal, environment) -> kernel
 UNCHANGED = [
-    ("omni-64", OMNI, B, 64, 0, FIVE, 1, F, {}, lane(Tr, Tr, F, 1, F, F, Tr, 0, F)),
-    ("diff-30-ragged", DIFF, B, 30, 0, FIVE, 1, F, {}, lane(F, Tr, F, 1, F, F, F, 0, F)),
-    ("diff-64-near-goal", DIFF, B, 64, 0, FIVE, 1, Tr, {}, lane(Tr, Tr, F, 1, F, Tr, Tr, 0, F)),
-    ("diff-64-no-obstacles-critic", DIFF, B, 64, 0, NO_OBST, 1, F, {}, lane(Tr, F, F, 1, F, F, Tr, 0, F)),
-    ("diff-64-cost-power-2", DIFF, B, 64, 0, FIVE, 2, F, {}, lane_pow(Tr, Tr, F, 1, F, F, Tr, 0, F)),
-    ("diff-64-deployed-nine", DIFF, B, 64, 0, DEPLOYED, 1, F, {}, lane(Tr, Tr, F, 1, F, F, Tr, 0, Tr)),
-    ("diff-4096-lane-flag", DIFF, 4096, 64, A.SMPC_FLAG_LANE_PER_ROLLOUT, FIVE, 1, F, {}, lane(Tr, Tr, F, 1, F, F, Tr, 0, F)),
-    ("diff-64-knob-omni", DIFF, B, 64, 0, FIVE, 1, F, KNOB, lane(Tr, Tr, F, 1, F, F, Tr, 0, F)),
+    ("omni-64", OMNI, B, 64, 0, FIVE, 1, F, {}, lane()),
+    ("diff-30-ragged", DIFF, B, 30, 0, FIVE, 1, F, {}, lane(full=False, quads=False)),
+    ("diff-64-near-goal", DIFF, B, 64, 0, FIVE, 1, Tr, {}, lane(ga=True)),
+    ("diff-64-no-obstacles-critic", DIFF, B, 64, 0, NO_OBST, 1, F, {}, lane(obst=False)),
+    ("diff-64-cost-power-2", DIFF, B, 64, 0, FIVE, 2, F, {}, lane_pow()),
+    ("diff-64-deployed-nine", DIFF, B, 64, 0, DEPLOYED, 1, F, {}, lane(dep=True)),
+    ("diff-4096-lane-flag", DIFF, 4096, 64, A.SMPC_FLAG_LANE_PER_ROLLOUT, FIVE, 1, F, {}, lane()),
+    ("diff-64-knob-omni", DIFF, B, 64, 0, FIVE, 1, F, KNOB, lane()),
 ]
 
 
@@ -193,7 +133,7 @@ def test_tick_stripped_after_a_tick_without_vy_runs_the_plain_row(Smpc, monkeypa
     u, out = g.optimize(sideways(scn.tick, fail_flag_in=True), np.zeros_like(scn.u0))
     print(f"[nonholo] stripped: pass_kind {out.pass_kind} kernel {last_kernel(g)}")
     assert out.fail_flag == 1
-    assert (out.pass_kind, last_kernel(g)) == (1, lane(Tr, F, F, 1, F, F, Tr, 0, F))
+    assert (out.pass_kind, last_kernel(g)) == (1, lane(obst=False))
     g.close()
 
 
@@ -312,7 +252,7 @@ def test_tick_without_vy_matches_the_oracle(Smpc, Oracle, monkeypatch, c):
     name, model, T, coll = c
     cfg, scn, noise = case(B, T, model, **({"seed": 44} if coll else {}))
     g, o = make_ctx(Smpc, monkeypatch, cfg, scn, noise), Oracle(cfg)
-    configure(o, scn, critics=critics_of(), noise=noise)
+    configure(o, scn, critics=critics_of(FIVE), noise=noise)
     tick = colliding(scn) if coll else sideways(scn.tick)
     tick.goal_checker_xy_tolerance = 0.25
     u0 = stale_u0(scn, model, T)
@@ -330,7 +270,7 @@ def test_tick_without_vy_matches_the_oracle(Smpc, Oracle, monkeypatch, c):
         assert np.all(ratio >= 0.5 * (1 - 1e-6))
         cfg2, _, _ = case(B, T, DIFF)
         o2 = Oracle(cfg2)
-        configure(o2, scn, critics=critics_of(), noise=noise)
+        configure(o2, scn, critics=critics_of(FIVE), noise=noise)
         ud, _ = o2.optimize(tick, u0)
         assert not np.array_equal(ud[2], uo[2])
         o2.close()

@@ -7,66 +7,29 @@ wave pass; below that, and for everything else the general pass scores (path ori
 trajectory_point_step, T > 64), the route is unchanged.  Every case here runs the smallest batch the
 rule reaches, 61 440 rollouts (960 groups), against the CPU oracle on the same stored noise.
 """
-import ctypes
-
 import numpy as np
 import pytest
 
 from mpcholonavigation_amd import _abi as A
-from mpcholonavigation_amd.tick import Tick, default_critics
+from mpcholonavigation_amd.tick import Tick
+from tests.harness import FIVE, Oracle, Smpc, copy_of, critics_of, last_kernel  # noqa: F401
 from tests.helpers import assert_parity, configure, make_case, twist_component_errors
+from tests.kernel_names import LANE_POW_ROW, lane, lane_pow, wave
 
 pytestmark = pytest.mark.gpu
 
 B = 61440
-FIVE = ("obstacles", "path_align", "path_follow", "goal_angle", "prefer_forward")
 ALL2 = {n: 2 for n in FIVE}
 MIXED = {"obstacles": 2, "path_align": 1, "path_follow": 2, "goal_angle": 3, "prefer_forward": 3}
 POWERS = {"all2": ALL2, "mixed": MIXED, "obst2": {"obstacles": 2}, "obst2-pfw3": {"obstacles": 2, "prefer_forward": 3}}
 F, Tr = False, True
 
 
-def critics_of(powers, names=FIVE):
-    """The five critics on, everything else off; cost_power 1 except where `powers` says otherwise."""
-    cr = default_critics()
-    for n in ("obstacles", "path_align", "path_follow", "goal_angle", "prefer_forward", "cost", "goal",
-              "constraint", "twirling", "path_angle", "velocity_deadband", "path_align_legacy"):
-        sub = getattr(cr, n)
-        sub.enabled = 1 if n in names else 0
-        sub.cost_power = powers.get(n, 1)
-    return cr
-
-
-def last_kernel(g):
-    f = g.lib.smpc_debug_last_pass_kernel
-    f.restype, f.argtypes = ctypes.c_char_p, []
-    return f().decode()
-
-
-def spell(name, args):
-    return name + "<" + ", ".join(str(a).lower() if isinstance(a, bool) else str(a) for a in args) + ">"
-
-
-def lane_pow(*args):
-    return spell("smpc_pass_lane_pow", args)
-
-
-def lane(*args):
-    return spell("smpc_pass_lane", args)
-
-
-def wave(r, mode, full):
-    return f"smpc_pass<{r}, {mode}, {'true' if full else 'false'}>"
-
-
 # the power instance of each tick shape: (T, near the goal) -> kernel
 POW_KERNEL = {
-    (64, F): lane_pow(Tr, Tr, F, 1, F, F, Tr, 0, F),
-    (56, F): lane_pow(F, Tr, F, 1, F, F, Tr, 56, F),
-    (40, F): lane_pow(F, Tr, F, 1, F, F, Tr, 0, F),
-    (30, F): lane_pow(F, Tr, F, 1, F, F, F, 0, F),
-    (64, Tr): lane_pow(Tr, Tr, F, 1, F, Tr, Tr, 0, F),
-    (40, Tr): lane_pow(F, Tr, F, 1, F, Tr, F, 0, F),
+    **{(T, F): row for T, row in LANE_POW_ROW.items()},
+    (64, Tr): lane_pow(ga=True),
+    (40, Tr): lane_pow(full=False, ga=True, quads=False),
 }
 
 _CASES = {}
@@ -79,28 +42,13 @@ def case(batch, T, **kw):
     if key not in _CASES:
         _CASES[key] = make_case(batch, T, **kw)
     cfg, scn, noise = _CASES[key]
-    c2 = type(cfg)()
-    ctypes.memmove(ctypes.byref(c2), ctypes.byref(cfg), ctypes.sizeof(cfg))
-    return c2, scn, noise
+    return copy_of(cfg), scn, noise
 
 
 def colliding_tick(scn):
     """The robot 0.45 m beside the plan, heading into the obstacles: a few hundred rollouts collide."""
     t = scn.tick
     return Tick(t.pose_x, t.pose_y - 0.45, -0.3, t.speed, t.path_x, t.path_y, t.path_yaw, t.goal_x, t.goal_y)
-
-
-@pytest.fixture(scope="module")
-def Smpc():
-    from mpcholonavigation_amd.optimizer import Smpc as S
-    return S
-
-
-@pytest.fixture(scope="module")
-def Oracle():
-    from oracle.loader import Oracle as O, build
-    build()
-    return O
 
 
 def effective_samples(costs, temperature):
@@ -160,7 +108,7 @@ def check_against_oracle(Smpc, Oracle, cfg, scn, noise, critics, tick, label, ke
 def test_power_tick_runs_the_power_instance(Smpc, T, near):
     cfg, scn, noise = case(B, T, near_goal=near)
     g = Smpc(cfg)
-    configure(g, scn, critics=critics_of(ALL2), noise=noise)
+    configure(g, scn, critics=critics_of(FIVE, ALL2), noise=noise)
     u = scn.u0
     for k in range(2):       # the first tick without a furthest-point prediction, the second speculated
         u, out = g.optimize(scn.tick, u)
@@ -172,9 +120,9 @@ def test_power_tick_runs_the_power_instance(Smpc, T, near):
 def test_power_1_tick_keeps_its_instance(Smpc):
     cfg, scn, noise = case(B, 64, near_goal=False)
     g = Smpc(cfg)
-    configure(g, scn, critics=critics_of({}), noise=noise)
+    configure(g, scn, critics=critics_of(FIVE, {}), noise=noise)
     _, out = g.optimize(scn.tick, scn.u0)
-    assert (out.pass_kind, last_kernel(g)) == (1, lane(Tr, Tr, F, 1, F, F, Tr, 0, F))
+    assert (out.pass_kind, last_kernel(g)) == (1, lane())
     g.close()
 
 
@@ -200,7 +148,7 @@ def test_power_tick_outside_the_rule_stays_on_the_wave_pass(Smpc, c):
     name, batch, T, flags, change, kernel = c
     cfg, scn, noise = case(batch, T, near_goal=False)
     cfg.flags |= flags
-    cr = critics_of(ALL2)
+    cr = critics_of(FIVE, ALL2)
     if change:
         change(cr)
     g = Smpc(cfg)
@@ -224,7 +172,7 @@ def test_power_tick_matches_the_oracle(Smpc, Oracle, T, near, pw):
     and from each other by 1e-4..1e-2 (where small, the per-rollout costs carry the check), with 15-100
     effective samples: a power on the wrong critic, on the sum or not at all cannot pass."""
     cfg, scn, noise = case(B, T, near_goal=near)
-    check_against_oracle(Smpc, Oracle, cfg, scn, noise, critics_of(POWERS[pw]), scn.tick,
+    check_against_oracle(Smpc, Oracle, cfg, scn, noise, critics_of(FIVE, POWERS[pw]), scn.tick,
                          f"{B}x{T} {'near goal ' if near else ''}{pw}", kernel=POW_KERNEL[(T, near)])
 
 
@@ -235,7 +183,7 @@ def test_power_tick_matches_the_oracle(Smpc, Oracle, T, near, pw):
 def test_power_tick_with_colliding_rollouts_matches_the_oracle(Smpc, Oracle, T, pw):
     """collision_cost through the power (1e5 squared) next to ordinary costs."""
     cfg, scn, noise = case(B, T, seed=44)
-    og, oo = check_against_oracle(Smpc, Oracle, cfg, scn, noise, critics_of(POWERS[pw]), colliding_tick(scn),
+    og, oo = check_against_oracle(Smpc, Oracle, cfg, scn, noise, critics_of(FIVE, POWERS[pw]), colliding_tick(scn),
                                   f"colliding {B}x{T} {pw}", kernel=POW_KERNEL[(T, F)])
     assert 0 < oo.non_colliding < B
     assert og.non_colliding == oo.non_colliding
@@ -246,7 +194,7 @@ def test_power_tick_with_colliding_rollouts_matches_the_oracle(Smpc, Oracle, T, 
 def test_power_tick_two_iterations_matches_the_oracle(Smpc, Oracle):
     cfg, scn, noise = case(B, 64, near_goal=False)
     cfg.iteration_count = 2
-    check_against_oracle(Smpc, Oracle, cfg, scn, noise, critics_of(ALL2), scn.tick, f"{B}x64 all2 two iterations",
+    check_against_oracle(Smpc, Oracle, cfg, scn, noise, critics_of(FIVE, ALL2), scn.tick, f"{B}x64 all2 two iterations",
                          kernel=POW_KERNEL[(64, F)], min_ess=0.0)
 
 
@@ -258,7 +206,7 @@ def test_stripped_power_tick_runs_and_matches_the_oracle(Smpc, Oracle):
     cfg, scn, noise = case(B, 64, near_goal=False)
     g, o = Smpc(cfg), Oracle(cfg)
     for obj in (g, o):
-        configure(obj, scn, critics=critics_of(ALL2), noise=noise)
+        configure(obj, scn, critics=critics_of(FIVE, ALL2), noise=noise)
     _, out = g.optimize(scn.tick, scn.u0)
     o.optimize(scn.tick, scn.u0)
     assert (out.pass_kind, last_kernel(g)) == (1, POW_KERNEL[(64, F)])
@@ -281,7 +229,7 @@ def test_all_collide_power_tick_matches_the_oracle(Smpc, Oracle):
     cfg, scn, noise = case(B, 64, all_lethal=True)
     g, o = Smpc(cfg), Oracle(cfg)
     for obj in (g, o):
-        configure(obj, scn, critics=critics_of(ALL2), noise=noise)
+        configure(obj, scn, critics=critics_of(FIVE, ALL2), noise=noise)
     ug, og = g.optimize(scn.tick, scn.u0)
     uo, oo = o.optimize(scn.tick, scn.u0)
     print(f"[lane powers] all collide: pass_kind {og.pass_kind} kernel {last_kernel(g)} passes {og.passes}")

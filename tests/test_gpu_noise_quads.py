@@ -15,88 +15,35 @@ The rows of smpc_pass_lane_pow and smpc_pass_lane_nh are reached from 61 440 rol
 (smpc_prepare.cpp plan_launch): at 197 rollouts a cost_power = 2 tick and a DiffDrive tick take the
 route the host gives them there, and the two rows proper are run once each at 61 440 x 40.
 """
-import ctypes
-
 import numpy as np
 import pytest
 
 from mpcholonavigation_amd import _abi as A
 from mpcholonavigation_amd.synthetic import make_noise, make_scenario
-from mpcholonavigation_amd.tick import default_config, default_critics
+from mpcholonavigation_amd.tick import default_config
+from tests import harness as H
 from tests import noise_model as nm
+from tests.harness import DEPLOYED, FIVE, LANE, Oracle, Smpc, last_kernel, oracle_tick  # noqa: F401
 from tests.helpers import assert_parity, configure, make_case
+from tests.kernel_names import LANE_ROW, lane, lane_nh, lane_pow
 
 pytestmark = pytest.mark.gpu
 
-LANE = A.SMPC_FLAG_LANE_PER_ROLLOUT
-F, Tr = False, True
 B_PARITY = 197
 ROUND_TRIP = [(130, 64), (130, 56), (130, 40), (130, 30), (130, 128), (64, 4)]
-ALL_CRITICS = ("obstacles", "path_align", "path_follow", "goal_angle", "prefer_forward", "cost", "goal",
-               "constraint", "twirling", "path_angle", "velocity_deadband", "path_align_legacy")
-FIVE = ALL_CRITICS[:5]
-DEPLOYED = ("constraint", "cost", "goal", "goal_angle", "path_align", "path_follow", "path_angle",
-            "prefer_forward", "twirling")      # robot_bringup/config/nav2_params.yaml:222
 
 
-def spell(name, args):
-    return name + "<" + ", ".join(str(a).lower() if isinstance(a, bool) else str(a) for a in args) + ">"
-
-
-def lane(*args):
-    return spell("smpc_pass_lane", args)
-
-
-KERNEL = {64: lane(Tr, Tr, F, 1, F, F, Tr, 0, F), 56: lane(F, Tr, F, 1, F, F, Tr, 56, F),
-          40: lane(F, Tr, F, 1, F, F, Tr, 0, F), 30: lane(F, Tr, F, 1, F, F, F, 0, F),
-          128: lane(Tr, Tr, F, 2, Tr, F, Tr, 0, F)}
-
-
-def last_kernel(g):
-    f = g.lib.smpc_debug_last_pass_kernel
-    f.restype, f.argtypes = ctypes.c_char_p, []
-    return f().decode()
+KERNEL = LANE_ROW
 
 
 def critics_of(names=FIVE, power=1):
-    cr = default_critics()
-    for n in ALL_CRITICS:
-        sub = getattr(cr, n)
-        sub.enabled = 1 if n in names else 0
-        sub.cost_power = power
-    cr.constraint.vx_max, cr.constraint.vy_max, cr.constraint.vx_min = 0.35, 0.2, -0.1
-    return cr
+    return H.critics_of(names, power, constraint_band=True)
 
 
 def copy_cfg(cfg, flags=0, **fields):
-    c2 = type(cfg)()
-    ctypes.memmove(ctypes.byref(c2), ctypes.byref(cfg), ctypes.sizeof(cfg))
+    c2 = H.copy_of(cfg, **fields)
     c2.flags |= flags
-    for k, v in fields.items():
-        setattr(c2, k, v)
     return c2
-
-
-@pytest.fixture(scope="module")
-def Smpc():
-    from mpcholonavigation_amd.optimizer import Smpc as S
-    return S
-
-
-@pytest.fixture(scope="module")
-def Oracle():
-    from oracle.loader import Oracle as O, build
-    build()
-    return O
-
-
-def oracle_tick(Oracle, cfg, scn, noise, critics=None, tick=None, u0=None):
-    o = Oracle(cfg)
-    configure(o, scn, critics=critics, noise=noise)
-    uo, oo = o.optimize(tick or scn.tick, scn.u0 if u0 is None else u0)
-    co = o.get_costs().copy()
-    o.close()
-    return uo, oo, co
 
 
 def gpu_tick(Smpc, cfg, scn, noise, critics=None):
@@ -186,12 +133,12 @@ def test_reread_form_against_oracle(Smpc, Oracle):
 def test_near_goal_tick_against_oracle(Smpc, Oracle):
     """GoalAngle live: the T = 64 row that issues the next quad's loads in front of the quad's last step."""
     cfg, scn, noise = make_case(B_PARITY, 64, near_goal=True)
-    check(Smpc, Oracle, cfg, scn, noise, "near goal", kernel=lane(Tr, Tr, F, 1, F, Tr, Tr, 0, F))
+    check(Smpc, Oracle, cfg, scn, noise, "near goal", kernel=lane(ga=True))
 
 
 def test_deployed_list_against_oracle(Smpc, Oracle):
     cfg, scn, noise = make_case(B_PARITY, 56)
-    check(Smpc, Oracle, cfg, scn, noise, "deployed list, T = 56", kernel=lane(F, Tr, F, 1, F, F, Tr, 56, Tr),
+    check(Smpc, Oracle, cfg, scn, noise, "deployed list, T = 56", kernel=lane(56, dep=True),
           critics=critics_of(DEPLOYED))
 
 
@@ -214,10 +161,10 @@ def test_power_and_no_vy_rows_at_their_smallest_batch(Smpc, Oracle, what):
     cfg, scn, noise = make_case(61440, 40)
     if what == "cost-power-2":
         check(Smpc, Oracle, cfg, scn, noise, what, critics=critics_of(FIVE, power=2),
-              kernel=spell("smpc_pass_lane_pow", (F, Tr, F, 1, F, F, Tr, 0, F)))
+              kernel=lane_pow(full=False))
     else:
         check(Smpc, Oracle, copy_cfg(cfg, motion_model=A.SMPC_MODEL_DIFF_DRIVE), scn, noise, what,
-              kernel=spell("smpc_pass_lane_nh", (F, Tr, F, 1, F, F, Tr, 0, F)))
+              kernel=lane_nh(full=False))
 
 
 def test_group_of_two_against_oracle(Smpc, Oracle):

@@ -17,17 +17,10 @@ from mpcholonavigation_amd import _abi as A
 from mpcholonavigation_amd.synthetic import make_scenario
 from mpcholonavigation_amd.tick import default_config
 from tests import noise_model as nm
+from tests.harness import LANE, Smpc  # noqa: F401
 from tests.helpers import configure
 
 pytestmark = pytest.mark.gpu
-
-LANE = A.SMPC_FLAG_LANE_PER_ROLLOUT
-
-
-@pytest.fixture(scope="module")
-def Smpc():
-    from mpcholonavigation_amd.optimizer import Smpc as S
-    return S
 
 
 @pytest.fixture(scope="module")

@@ -11,22 +11,10 @@ import pytest
 from mpcholonavigation_amd import _abi as A
 from mpcholonavigation_amd.synthetic import make_noise, make_scenario
 from mpcholonavigation_amd.tick import Tick, default_config, default_critics
+from tests.harness import DEPLOYED, FIVE, Oracle, Smpc, bar_tick, dressed_critics  # noqa: F401
 from tests.helpers import assert_parity, configure, cost_flips, make_case, rel_err, twist
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def Smpc():
-    from mpcholonavigation_amd.optimizer import Smpc as S
-    return S
-
-
-@pytest.fixture(scope="module")
-def Oracle():
-    from oracle.loader import Oracle as O, build
-    build()
-    return O
 
 
 def run_pair(Smpc, Oracle, cfg, scn, noise, critics=None, tick=None, u0=None, store=False,
@@ -481,14 +469,9 @@ def test_a_stale_tick_block_fails_the_tick_and_the_context_recovers(Smpc, monkey
     another tick's block fails loudly.  SMPC_DEBUG_STALE_TICK=3 withholds the third tick's block: that
     tick must fail (not return the second tick's answer), the context falls back to the stream copy,
     and the next tick is what a context that never saw the fault computes."""
-    import ctypes
     cfg, scn, noise = make_case(4096, 64)
     cfg.flags |= A.SMPC_FLAG_LANE_PER_ROLLOUT
-
-    def bar(g):
-        f = g.lib.smpc_debug_bar_tick
-        f.restype, f.argtypes = ctypes.c_int, [ctypes.c_void_p]
-        return f(g.h)
+    bar = bar_tick
 
     good = Smpc(cfg)
     if not bar(good):
@@ -600,25 +583,6 @@ def test_lane_per_rollout_pass_parity(Smpc, Oracle, B, T, M):
                       label=f"lane pass {B}x{T} near={near}")
 
 
-def _extra_critics(names, power=1, **over):
-    cr = default_critics()
-    for n in ("obstacles", "path_align", "path_follow", "goal_angle", "prefer_forward", "cost", "goal",
-              "constraint", "twirling", "path_angle", "velocity_deadband", "path_align_legacy"):
-        sub = getattr(cr, n)
-        sub.enabled = 1 if n in names else 0
-        sub.cost_power = power
-    for k in range(3):
-        cr.velocity_deadband.deadband_velocities[k] = 0.08
-    cr.constraint.vx_max, cr.constraint.vy_max, cr.constraint.vx_min = 0.35, 0.2, -0.1
-    for path, v in over.items():
-        sub, field = path.split("__")
-        setattr(getattr(cr, sub), field, v)
-    return cr
-
-
-FIVE_NAMES = ("obstacles", "path_align", "path_follow", "goal_angle", "prefer_forward")
-DEPLOYED = ("constraint", "cost", "goal", "goal_angle", "path_align", "path_follow", "path_angle",
-            "prefer_forward", "twirling")      # robot_bringup/config/nav2_params.yaml:222
 ALL11 = DEPLOYED + ("obstacles", "velocity_deadband")
 
 
@@ -633,7 +597,7 @@ def test_other_registered_critics_parity(Smpc, Oracle, names, power, near, B, T)
     is pinned by the reference's critics_tests.cpp KATs in test_oracle_reference_kats.py)."""
     cfg, scn, noise = make_case(B, T, near_goal=near)
     # a robot heading away from the path so that PathAngle's gate opens, reversing allowed
-    cr = _extra_critics(names, power, path_angle__max_angle_to_furthest=0.05,
+    cr = dressed_critics(names, power, path_angle__max_angle_to_furthest=0.05,
                         path_angle__forward_preference=0 if power == 2 else 1)
     tick = scn.tick
     tick.goal_checker_xy_tolerance = 0.25
@@ -663,7 +627,7 @@ def test_path_align_legacy_critic_parity(Smpc, Oracle, names, power, yaw, B, T, 
     (some nearest points invalid, then the occupancy gate closed), at a lane-pass batch (which
     falls to the wave pass: the critic lives in the general mode only)."""
     cfg, scn, noise = make_case(B, T)
-    cr = _extra_critics(names, power, path_align_legacy__use_path_orientations=yaw)
+    cr = dressed_critics(names, power, path_align_legacy__use_path_orientations=yaw)
     t = scn.tick
     P = len(t.path_x)
     pyaw = (0.3 * np.sin(0.2 * np.arange(P))).astype(np.float32) if yaw else t.path_yaw
@@ -689,7 +653,7 @@ def test_path_align_legacy_critic_parity(Smpc, Oracle, names, power, yaw, B, T, 
                       label=f"legacy {names} power {power} yaw {yaw} blocked {blocked} tick {k}", report=(k == 0))
         u = np.concatenate([uo[:, 1:], uo[:, -1:]], axis=1)
     # two different sampling steps in one list are refused, not guessed
-    cr2 = _extra_critics(("path_align", "path_align_legacy"), 1, path_align_legacy__trajectory_point_step=3)
+    cr2 = dressed_critics(("path_align", "path_align_legacy"), 1, path_align_legacy__trajectory_point_step=3)
     g.set_critics(cr2)
     from mpcholonavigation_amd.optimizer import SmpcError
     with pytest.raises(SmpcError) as e:
@@ -711,7 +675,7 @@ def test_deployed_list_cruise_tick_on_the_lane_pass(Smpc, Oracle, B, T, names):
     gives the same tick within float reassociation."""
     cfg, scn, noise = make_case(B, T)
     cfg.flags |= A.SMPC_FLAG_LANE_PER_ROLLOUT
-    cr = _extra_critics(names)
+    cr = dressed_critics(names)
     g, o = Smpc(cfg), Oracle(cfg)
     for obj in (g, o):
         configure(obj, scn, critics=cr, noise=noise)
@@ -784,7 +748,7 @@ def test_consider_footprint_parity(Smpc, Oracle, names, fp_obs, fp_cost, B, T):
     infl[d > 0.55] = 0
     cells = np.where(cells == 254, 254, infl).astype(np.uint8)
     scn.cells = cells
-    cr = _extra_critics(names)
+    cr = dressed_critics(names)
     cr.obstacles.consider_footprint = int(fp_obs)
     cr.cost.consider_footprint = int(fp_cost)
     g, o = Smpc(cfg), Oracle(cfg)
@@ -803,7 +767,7 @@ def test_consider_footprint_parity(Smpc, Oracle, names, fp_obs, fp_cost, B, T):
 
 def test_consider_footprint_needs_a_footprint(Smpc):
     cfg, scn, noise = make_case(256, 30)
-    cr = _extra_critics(("cost",))
+    cr = dressed_critics(("cost",))
     cr.cost.consider_footprint = 1
     g = Smpc(cfg)
     configure(g, scn, critics=cr, noise=noise)
@@ -849,7 +813,7 @@ def test_both_collision_critics_with_a_footprint(Smpc, Oracle, fp_obs, fp_cost, 
         u0 = np.zeros_like(scn.u0)
         u0[0] = -0.2
     scn.cells = cells
-    cr = _extra_critics(("constraint", "cost", "obstacles", "path_follow", "prefer_forward", "goal"))
+    cr = dressed_critics(("constraint", "cost", "obstacles", "path_follow", "prefer_forward", "goal"))
     cr.obstacles.consider_footprint, cr.cost.consider_footprint = fp_obs, fp_cost
     g, o = Smpc(cfg), Oracle(cfg)
     for obj in (g, o):
@@ -870,7 +834,7 @@ def test_both_collision_critics_with_a_footprint(Smpc, Oracle, fp_obs, fp_cost, 
 
 def test_sharded_tick_refuses_both_collision_critics_with_a_footprint(Smpc):
     cfg, scn, noise = make_case(256, 30)
-    cr = _extra_critics(("cost", "obstacles"))
+    cr = dressed_critics(("cost", "obstacles"))
     cr.cost.consider_footprint = 1
     g = Smpc(cfg)
     configure(g, scn, critics=cr, noise=noise)
@@ -889,7 +853,7 @@ def test_sharded_tick_refuses_both_collision_critics_with_a_footprint(Smpc):
         g2.shard_tick(scn2.tick, scn2.u0)
 
 
-@pytest.mark.parametrize("B,T,names", [(2000, 56, FIVE_NAMES), (3000, 40, None)])
+@pytest.mark.parametrize("B,T,names", [(2000, 56, FIVE), (3000, 40, None)])
 def test_a_second_pass_of_an_iteration_reads_what_the_first_read(Smpc, B, T, names, monkeypatch):
     """iteration_count > 1: iteration k starts from the control sequence iteration k - 1 left on the
     device, and a re-score inside iteration k (all rollouts colliding, the counting pass above) must
@@ -897,7 +861,7 @@ def test_a_second_pass_of_an_iteration_reads_what_the_first_read(Smpc, B, T, nam
     SMPC_DEBUG_REPEAT_PASS launches every iteration's pass twice: same bits as once."""
     cfg, scn, noise = make_case(B, T)
     cfg.iteration_count = 3
-    cr = _extra_critics(names) if names else None
+    cr = dressed_critics(names) if names else None
     outs = []
     for repeat in (False, True):
         if repeat:
@@ -932,7 +896,7 @@ def test_all_collide_with_a_footprint_is_rescored_with_the_footprint(Smpc, Oracl
     scn.tick = Tick(t.pose_x, t.pose_y, 0.0, (0.0, 0.0, 0.0), t.path_x, t.path_y, t.path_yaw, t.goal_x, t.goal_y)
     u0 = np.zeros_like(scn.u0)
     u0[0] = -0.2                                          # backing off: most centres never reach the wall
-    cr = _extra_critics(names)
+    cr = dressed_critics(names)
     getattr(cr, fp_critic).consider_footprint = 1
     g, o = Smpc(cfg), Oracle(cfg)
     for obj in (g, o):
@@ -957,7 +921,7 @@ def test_cost_and_obstacles_critics_together(Smpc, Oracle, B, T):
     ObstaclesCritic's terms are ADDED to CostCritic's — they once replaced them (found by
     tools/fuzz_parity.py: 263 of 400 costs off by up to 4 %)."""
     cfg, scn, noise = make_case(B, T)
-    cr = _extra_critics(("obstacles", "cost", "path_follow", "prefer_forward", "constraint"))
+    cr = dressed_critics(("obstacles", "cost", "path_follow", "prefer_forward", "constraint"))
     g, o = Smpc(cfg), Oracle(cfg)
     for obj in (g, o):
         configure(obj, scn, critics=cr, noise=noise)
@@ -965,9 +929,6 @@ def test_cost_and_obstacles_critics_together(Smpc, Oracle, B, T):
     uo, oo = o.optimize(scn.tick, scn.u0)
     assert og.non_colliding == oo.non_colliding
     assert_parity(ug, og, uo, oo, g.get_costs(), o.get_costs(), max_flips=2, label=f"cost + obstacles {B}x{T}")
-
-
-FIVE = ("obstacles", "path_align", "path_follow", "goal_angle", "prefer_forward")
 
 
 @pytest.mark.parametrize("model,names,B,T,iters", [
@@ -990,7 +951,7 @@ def test_non_holonomic_motion_models_parity(Smpc, Oracle, model, names, B, T, it
     cfg.motion_model = model
     cfg.iteration_count = iters
     cfg.ackermann_min_turning_r = 0.5
-    cr = _extra_critics(names, 1)
+    cr = dressed_critics(names, 1)
     tick = scn.tick
     tick.speed = (tick.speed[0], 0.3, tick.speed[2])   # sideways speed: ignored by these models
     tick.goal_checker_xy_tolerance = 0.25

@@ -12,71 +12,41 @@ The list reaches every row of the three instance tables that a tick can reach:
   smpc_pass_split   3 rows, all reached
   smpc_pass        24 rows, all reached (MODE 1, furthest only, through smpc_shard_furthest)
 """
-import ctypes
-
 import numpy as np
 import pytest
 
-from mpcholonavigation_amd import _abi as A
 from mpcholonavigation_amd.synthetic import make_noise, make_scenario
-from mpcholonavigation_amd.tick import Tick, default_config, default_critics
+from mpcholonavigation_amd.tick import Tick, default_config
+from tests.harness import (DEPLOYED, FIVE, LANE, NO_OBST, Smpc,  # noqa: F401
+                           create_with_env, critics_of, last_kernel, shifted)
 from tests.helpers import configure, make_case
+from tests.kernel_names import lane, wave
 
 pytestmark = pytest.mark.gpu
-
-FIVE = ("obstacles", "path_align", "path_follow", "goal_angle", "prefer_forward")
-NO_OBST = FIVE[1:]
-DEPLOYED = ("constraint", "cost", "goal", "goal_angle", "path_align", "path_follow", "path_angle",
-            "prefer_forward", "twirling")
-LANE = A.SMPC_FLAG_LANE_PER_ROLLOUT
-
-
-def critics_of(names, power=1):
-    cr = default_critics()
-    for n in ("obstacles", "path_align", "path_follow", "goal_angle", "prefer_forward", "cost", "goal",
-              "constraint", "twirling", "path_angle", "velocity_deadband", "path_align_legacy"):
-        sub = getattr(cr, n)
-        sub.enabled = 1 if n in names else 0
-        sub.cost_power = power
-    return cr
-
-
-def last_kernel(g):
-    f = g.lib.smpc_debug_last_pass_kernel
-    f.restype, f.argtypes = ctypes.c_char_p, []
-    return f().decode()
-
-
-def lane(*args):
-    return "smpc_pass_lane<" + ", ".join(str(a).lower() if isinstance(a, bool) else str(a) for a in args) + ">"
-
-
-def wave(r, mode, full):
-    return f"smpc_pass<{r}, {mode}, {'true' if full else 'false'}>"
 
 
 # (id, batch, horizon, config flags, critic names, cost_power, near the goal, environment) -> (pass_kind, kernel)
 F, Tr = False, True
 TICKS = [
     # lane, plain: the five critics, with and without ObstaclesCritic
-    ("lane-64", 2048, 64, LANE, FIVE, 1, F, {}, 1, lane(Tr, Tr, F, 1, F, F, Tr, 0, F)),
-    ("lane-56", 2048, 56, LANE, FIVE, 1, F, {}, 1, lane(F, Tr, F, 1, F, F, Tr, 56, F)),
-    ("lane-40", 2048, 40, LANE, FIVE, 1, F, {}, 1, lane(F, Tr, F, 1, F, F, Tr, 0, F)),
-    ("lane-30", 2048, 30, LANE, FIVE, 1, F, {}, 1, lane(F, Tr, F, 1, F, F, F, 0, F)),
-    ("lane-64-no-obst", 2048, 64, LANE, NO_OBST, 1, F, {}, 1, lane(Tr, F, F, 1, F, F, Tr, 0, F)),
-    ("lane-56-no-obst", 2048, 56, LANE, NO_OBST, 1, F, {}, 1, lane(F, F, F, 1, F, F, F, 0, F)),
-    ("lane-40-no-obst", 2048, 40, LANE, NO_OBST, 1, F, {}, 1, lane(F, F, F, 1, F, F, F, 0, F)),
-    ("lane-30-no-obst", 2048, 30, LANE, NO_OBST, 1, F, {}, 1, lane(F, F, F, 1, F, F, F, 0, F)),
-    ("lane-64-by-size", 61440, 64, 0, FIVE, 1, F, {}, 1, lane(Tr, Tr, F, 1, F, F, Tr, 0, F)),
+    ("lane-64", 2048, 64, LANE, FIVE, 1, F, {}, 1, lane()),
+    ("lane-56", 2048, 56, LANE, FIVE, 1, F, {}, 1, lane(56)),
+    ("lane-40", 2048, 40, LANE, FIVE, 1, F, {}, 1, lane(full=False)),
+    ("lane-30", 2048, 30, LANE, FIVE, 1, F, {}, 1, lane(full=False, quads=False)),
+    ("lane-64-no-obst", 2048, 64, LANE, NO_OBST, 1, F, {}, 1, lane(obst=False)),
+    ("lane-56-no-obst", 2048, 56, LANE, NO_OBST, 1, F, {}, 1, lane(full=False, obst=False, quads=False)),
+    ("lane-40-no-obst", 2048, 40, LANE, NO_OBST, 1, F, {}, 1, lane(full=False, obst=False, quads=False)),
+    ("lane-30-no-obst", 2048, 30, LANE, NO_OBST, 1, F, {}, 1, lane(full=False, obst=False, quads=False)),
+    ("lane-64-by-size", 61440, 64, 0, FIVE, 1, F, {}, 1, lane()),
     # lane, GoalAngle: a near-goal tick
-    ("lane-ga-64", 2048, 64, LANE, FIVE, 1, Tr, {}, 1, lane(Tr, Tr, F, 1, F, Tr, Tr, 0, F)),
-    ("lane-ga-40", 2048, 40, LANE, FIVE, 1, Tr, {}, 1, lane(F, Tr, F, 1, F, Tr, F, 0, F)),
+    ("lane-ga-64", 2048, 64, LANE, FIVE, 1, Tr, {}, 1, lane(ga=True)),
+    ("lane-ga-40", 2048, 40, LANE, FIVE, 1, Tr, {}, 1, lane(full=False, ga=True, quads=False)),
     # lane, deployed list: a cruise tick
-    ("lane-dep-64", 2048, 64, LANE, DEPLOYED, 1, F, {}, 1, lane(Tr, Tr, F, 1, F, F, Tr, 0, Tr)),
-    ("lane-dep-56", 2048, 56, LANE, DEPLOYED, 1, F, {}, 1, lane(F, Tr, F, 1, F, F, Tr, 56, Tr)),
+    ("lane-dep-64", 2048, 64, LANE, DEPLOYED, 1, F, {}, 1, lane(dep=True)),
+    ("lane-dep-56", 2048, 56, LANE, DEPLOYED, 1, F, {}, 1, lane(56, dep=True)),
     # lane, re-read
-    ("lane-rr-128", 2048, 128, LANE, FIVE, 1, F, {}, 1, lane(Tr, Tr, F, 2, Tr, F, Tr, 0, F)),
-    ("lane-rr-64", 2048, 64, LANE, FIVE, 1, F, {"SMPC_LANE_REREAD": "1"}, 1, lane(Tr, Tr, F, 1, Tr, F, Tr, 0, F)),
+    ("lane-rr-128", 2048, 128, LANE, FIVE, 1, F, {}, 1, lane(128)),
+    ("lane-rr-64", 2048, 64, LANE, FIVE, 1, F, {"SMPC_LANE_REREAD": "1"}, 1, lane(rr=True)),
     # split
     ("split-4-full", 16384, 64, 0, FIVE, 1, F, {}, 2, "smpc_pass_split<4, true>"),
     ("split-4-masked", 20000, 60, 0, FIVE, 1, F, {}, 2, "smpc_pass_split<4, false>"),
@@ -107,21 +77,11 @@ TICKS = [
 
 
 def make_ctx(Smpc, monkeypatch, B, T, flags, names, power, near, env):
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)          # (the knobs are read when the context is created)
     cfg, scn, noise = make_case(B, T, near_goal=near)
     cfg.flags |= flags
-    g = Smpc(cfg)
-    for k in env:
-        monkeypatch.delenv(k)
+    g = create_with_env(Smpc, monkeypatch, cfg, env)
     configure(g, scn, critics=critics_of(names, power), noise=noise)
     return g, scn
-
-
-@pytest.fixture(scope="module")
-def Smpc():
-    from mpcholonavigation_amd.optimizer import Smpc as S
-    return S
 
 
 @pytest.mark.parametrize("case", TICKS, ids=[c[0] for c in TICKS])
@@ -155,12 +115,12 @@ def test_furthest_only_pass_runs_the_pinned_instance(Smpc, monkeypatch, T, r, fu
 
 # (id, batch, horizon, critic names) -> kernel of a member scored alone, kernel of the batched launch
 GROUPS = [
-    ("group-64", 2048, 64, FIVE, lane(Tr, Tr, F, 1, F, F, Tr, 0, F), lane(Tr, Tr, Tr, 1, F, F, Tr, 0, F)),
-    ("group-56", 2048, 56, FIVE, lane(F, Tr, F, 1, F, F, Tr, 56, F), lane(F, Tr, Tr, 1, F, F, F, 0, F)),
-    ("group-64-no-obst", 2048, 64, NO_OBST, lane(Tr, F, F, 1, F, F, Tr, 0, F), lane(Tr, F, Tr, 1, F, F, Tr, 0, F)),
-    ("group-40-no-obst", 2048, 40, NO_OBST, lane(F, F, F, 1, F, F, F, 0, F), lane(F, F, Tr, 1, F, F, F, 0, F)),
-    ("group-dep-64", 4096, 64, DEPLOYED, lane(Tr, Tr, F, 1, F, F, Tr, 0, Tr), lane(Tr, Tr, Tr, 1, F, F, Tr, 0, Tr)),
-    ("group-dep-56", 4096, 56, DEPLOYED, lane(F, Tr, F, 1, F, F, Tr, 56, Tr), lane(F, Tr, Tr, 1, F, F, Tr, 56, Tr)),
+    ("group-64", 2048, 64, FIVE, lane(), lane(many=True)),
+    ("group-56", 2048, 56, FIVE, lane(56), lane(full=False, many=True, quads=False)),
+    ("group-64-no-obst", 2048, 64, NO_OBST, lane(obst=False), lane(obst=False, many=True)),
+    ("group-40-no-obst", 2048, 40, NO_OBST, lane(full=False, obst=False, quads=False), lane(full=False, obst=False, many=True, quads=False)),
+    ("group-dep-64", 4096, 64, DEPLOYED, lane(dep=True), lane(many=True, dep=True)),
+    ("group-dep-56", 4096, 56, DEPLOYED, lane(56, dep=True), lane(full=False, many=True, tc=56, dep=True)),
 ]
 
 
@@ -185,7 +145,7 @@ def test_group_runs_the_pinned_instance(Smpc, case):
     seen = []
     for k in range(5):
         res = grp.optimize([scn.tick for scn in scns], us)
-        us = [np.concatenate([u[:, 1:], u[:, -1:]], axis=1) for u, _ in res]
+        us = [shifted(u) for u, _ in res]
         assert all(o.pass_kind == 1 for _, o in res)
         seen.append(last_kernel(members[0]))
     print(f"[selection] {name}: kernel launched last, per tick: {seen}")
@@ -199,11 +159,11 @@ def test_group_runs_the_pinned_instance(Smpc, case):
 # a tick whose flags are stripped after the launch was planned (fail_flag_in: the retry after
 # fallback() scores nothing, critic_manager.cpp:70-73) runs what the stripped flags have an instance for
 DOWNGRADES = [
-    ("reread-128-to-wave", 2048, 128, LANE, {}, 1, lane(Tr, Tr, F, 2, Tr, F, Tr, 0, F), 0, wave(2, 0, Tr)),
-    ("reread-64-to-wave", 2048, 64, LANE, {"SMPC_LANE_REREAD": "1"}, 1, lane(Tr, Tr, F, 1, Tr, F, Tr, 0, F), 0, wave(1, 0, Tr)),
-    ("split-to-lane", 16384, 64, 0, {}, 2, "smpc_pass_split<4, true>", 1, lane(Tr, F, F, 1, F, F, Tr, 0, F)),
-    ("split-masked-to-lane", 20000, 60, 0, {}, 2, "smpc_pass_split<4, false>", 1, lane(F, F, F, 1, F, F, F, 0, F)),
-    ("lane-56-stays-lane", 2048, 56, LANE, {}, 1, lane(F, Tr, F, 1, F, F, Tr, 56, F), 1, lane(F, F, F, 1, F, F, F, 0, F)),
+    ("reread-128-to-wave", 2048, 128, LANE, {}, 1, lane(128), 0, wave(2, 0, Tr)),
+    ("reread-64-to-wave", 2048, 64, LANE, {"SMPC_LANE_REREAD": "1"}, 1, lane(rr=True), 0, wave(1, 0, Tr)),
+    ("split-to-lane", 16384, 64, 0, {}, 2, "smpc_pass_split<4, true>", 1, lane(obst=False)),
+    ("split-masked-to-lane", 20000, 60, 0, {}, 2, "smpc_pass_split<4, false>", 1, lane(full=False, obst=False, quads=False)),
+    ("lane-56-stays-lane", 2048, 56, LANE, {}, 1, lane(56), 1, lane(full=False, obst=False, quads=False)),
 ]
 
 

@@ -21,29 +21,16 @@ are adversarial, on the oracle alone), so here, for both ticks of every (form, s
 With findClosestPathPt broken three ways in one kernel family at a time this file fails in that
 family: DESIGN.md section 7 has the counts.
 """
-import ctypes
-
 import numpy as np
 import pytest
 
 from tests import path_point_scenes as S
+from tests.harness import Smpc, create_with_env, last_kernel  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 CASES = sorted(((name, key) for name, f in S.FORMS.items() for key in f.scenes),
                key=lambda c: (S.scene_name(c[1]), c[0]))
-
-
-@pytest.fixture(scope="module")
-def Smpc():
-    from mpcholonavigation_amd.optimizer import Smpc as Cls
-    return Cls
-
-
-def last_kernel(g):
-    f = g.lib.smpc_debug_last_pass_kernel
-    f.restype, f.argtypes = ctypes.c_char_p, []
-    return f().decode()
 
 
 _oracle_cache = {}
@@ -90,11 +77,7 @@ def check(label, out, costs, j, out_ref, c_ref, tol, obstacles, B):
 
 
 def make_ctx(Smpc, monkeypatch, scn, flags, env, critics):
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)          # (the knobs are read when the context is created)
-    g = Smpc(scn.config(flags=flags))
-    for k in env:
-        monkeypatch.delenv(k)
+    g = create_with_env(Smpc, monkeypatch, scn.config(flags=flags), env)
     scn.configure(g, critics)
     return g
 

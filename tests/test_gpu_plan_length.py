@@ -27,39 +27,18 @@ flags, and the two builds may not differ in a cell lookup that assert_parity can
 weighs on the Twist (plan_scenes.hidden_flip_influence).  A scene on which the two reference builds
 disagree is a knife edge and proves nothing; such a scene got another noise seed
 (plan_scenes.RESEEDED), nothing else."""
-import ctypes
-
 import numpy as np
 import pytest
 
 from mpcholonavigation_amd import _abi as A
 from tests import plan_scenes as S
+from tests.harness import Smpc, last_kernel, scan_count  # noqa: F401
 from tests.helpers import assert_parity
+from tests.kernel_names import LANE_ROW, LANE_ROW_NO_OBST, lane, lane_nh, lane_pow, wave_at
 from tests.plan_scenes import DEPLOYED, FIVE, NO_OBST, scene
 
 gpu = pytest.mark.gpu
-F, Tr = False, True
 DIFF = A.SMPC_MODEL_DIFF_DRIVE
-
-
-def spell(kernel, args):
-    return kernel + "<" + ", ".join(str(a).lower() if isinstance(a, bool) else str(a) for a in args) + ">"
-
-
-def lane(*args):
-    """smpc_pass_lane<FULL, OBST, MANY, NCH, RR, GA, QUADS, TC, DEP>"""
-    return spell("smpc_pass_lane", args)
-
-
-def wave(T, mode, many=False):
-    r = 1 if T <= 64 else (2 if T <= 128 else 4)
-    return f"smpc_pass{'_many' if many else ''}<{r}, {mode}, {'true' if T in (64, 128, 256) else 'false'}>"
-
-
-LANE_ROW = {64: lane(Tr, Tr, F, 1, F, F, Tr, 0, F), 56: lane(F, Tr, F, 1, F, F, Tr, 56, F),
-            40: lane(F, Tr, F, 1, F, F, Tr, 0, F), 30: lane(F, Tr, F, 1, F, F, F, 0, F)}
-LANE_ROW_NO_OBST = {64: lane(Tr, F, F, 1, F, F, Tr, 0, F), 56: lane(F, F, F, 1, F, F, F, 0, F),
-                    40: lane(F, F, F, 1, F, F, F, 0, F), 30: lane(F, F, F, 1, F, F, F, 0, F)}
 
 
 def lane_cases():
@@ -71,15 +50,15 @@ def lane_cases():
         for plan in ("long", "short"):
             out.append(scene(f"lane-{tag}-64-P*-1-{plan}", 2048, 64, p - 1, plan, names, kernel=rows[64]))
             out.append(scene(f"lane-{tag}-64-P*-{plan}", 2048, 64, p, plan, names, kernel=rows[64]))
-            out.append(scene(f"lane-{tag}-64-P*+1-{plan}", 2048, 64, p + 1, plan, names, kind=0, kernel=wave(64, 0)))
+            out.append(scene(f"lane-{tag}-64-P*+1-{plan}", 2048, 64, p + 1, plan, names, kind=0, kernel=wave_at(64, 0)))
         out.append(scene(f"lane-{tag}-64-P*-lethal", 2048, 64, p, "lethal", names, kernel=rows[64]))
         for plan in ("long", "short"):
             out.append(scene(f"lane-{tag}-64-P*-{plan}-70000", 70000, 64, p, plan, names, kernel=rows[64]))
-        out.append(scene(f"lane-{tag}-64-P*+1-short-70000", 70000, 64, p + 1, "short", names, kind=0, kernel=wave(64, 0)))
+        out.append(scene(f"lane-{tag}-64-P*+1-short-70000", 70000, 64, p + 1, "short", names, kind=0, kernel=wave_at(64, 0)))
         for T in (56, 40, 30):
             pt = S.lane_limit(T, obst)
             out.append(scene(f"lane-{tag}-{T}-P*-short", 2048, T, pt, "short", names, kernel=rows[T]))
-            out.append(scene(f"lane-{tag}-{T}-P*+1-short", 2048, T, pt + 1, "short", names, kind=0, kernel=wave(T, 0)))
+            out.append(scene(f"lane-{tag}-{T}-P*+1-short", 2048, T, pt + 1, "short", names, kind=0, kernel=wave_at(T, 0)))
     return out
 
 
@@ -87,21 +66,21 @@ def row_cases():
     """The other rows of the lane tables at P*: GoalAngle, the deployed list, cost powers, no vy
     stream, the re-read form."""
     p = S.lane_limit(64)
-    pow_row = spell("smpc_pass_lane_pow", (Tr, Tr, F, 1, F, F, Tr, 0, F))
-    nh_row = spell("smpc_pass_lane_nh", (Tr, Tr, F, 1, F, F, Tr, 0, F))
+    pow_row = lane_pow()
+    nh_row = lane_nh()
     return [
-        scene("lane-ga-64-P*", 2048, 64, p, "near", kernel=lane(Tr, Tr, F, 1, F, Tr, Tr, 0, F)),
-        scene("lane-ga-40-P*", 2048, 40, S.lane_limit(40), "near", kernel=lane(F, Tr, F, 1, F, Tr, F, 0, F)),
-        scene("lane-dep-64-P*", 2048, 64, p, "short", DEPLOYED, kernel=lane(Tr, Tr, F, 1, F, F, Tr, 0, Tr)),
-        scene("lane-dep-64-P*-lethal", 2048, 64, p, "lethal", DEPLOYED, kernel=lane(Tr, Tr, F, 1, F, F, Tr, 0, Tr)),
-        scene("lane-dep-56-P*", 2048, 56, S.lane_limit(56), "short", DEPLOYED, kernel=lane(F, Tr, F, 1, F, F, Tr, 56, Tr)),
-        scene("lane-dep-64-P*+1", 2048, 64, p + 1, "short", DEPLOYED, kind=0, kernel=wave(64, 3)),
+        scene("lane-ga-64-P*", 2048, 64, p, "near", kernel=lane(ga=True)),
+        scene("lane-ga-40-P*", 2048, 40, S.lane_limit(40), "near", kernel=lane(full=False, ga=True, quads=False)),
+        scene("lane-dep-64-P*", 2048, 64, p, "short", DEPLOYED, kernel=lane(dep=True)),
+        scene("lane-dep-64-P*-lethal", 2048, 64, p, "lethal", DEPLOYED, kernel=lane(dep=True)),
+        scene("lane-dep-56-P*", 2048, 56, S.lane_limit(56), "short", DEPLOYED, kernel=lane(56, dep=True)),
+        scene("lane-dep-64-P*+1", 2048, 64, p + 1, "short", DEPLOYED, kind=0, kernel=wave_at(64, 3)),
         scene("lane-pow-64-P*", 61440, 64, p, "short", powers={"path_align": 2}, kernel=pow_row),
         scene("lane-nh-64-P*", 61440, 64, p, "short", model=DIFF, kernel=nh_row),
         scene("lane-rr-128-P*", 2048, 128, S.lane_limit(128, rr=True, window=S.WIN_WIDE), "long",
-              kernel=lane(Tr, Tr, F, 2, Tr, F, Tr, 0, F)),
+              kernel=lane(128)),
         scene("lane-rr-64-P*", 2048, 64, S.lane_limit(64, rr=True), "short", env=(("SMPC_LANE_REREAD", "1"),),
-              kernel=lane(Tr, Tr, F, 1, Tr, F, Tr, 0, F)),
+              kernel=lane(rr=True)),
     ]
 
 
@@ -114,7 +93,7 @@ def split_cases():
         p = S.split_limit(T, nseg)
         out.append(scene(f"split-{tag}-P*-short", B, T, p, "short", flags=0, env=env, kind=2, kernel=kernel))
         out.append(scene(f"split-{tag}-P*-lethal", B, T, p, "lethal", flags=0, env=env, kind=2, kernel=kernel))
-        out.append(scene(f"split-{tag}-P*+1-short", B, T, p + 1, "short", flags=0, env=env, kind=0, kernel=wave(T, 0)))
+        out.append(scene(f"split-{tag}-P*+1-short", B, T, p + 1, "short", flags=0, env=env, kind=0, kernel=wave_at(T, 0)))
     return out
 
 
@@ -132,7 +111,7 @@ def wave_cases():
             for mode in WAVE_MODES:
                 P = S.plan_limit(S.KIND_WAVE, S.WIN_WIDE, T, (T - 1) // step)
                 out.append(scene(f"wave-{T}-mode-{mode}-nsamp-{(T - 1) // step}", 500, T, P, "long", flags=0, step=step,
-                                 kind=0, kernel=wave(T, mode), **WAVE_MODES[mode]))
+                                 kind=0, kernel=wave_at(T, mode), **WAVE_MODES[mode]))
     return out
 
 
@@ -157,18 +136,6 @@ def find(builder, name):
     scenes = builder()
     assert [s.name for s in scenes] == IDS[builder], "the written-out ids and the scenes differ"
     return next(s for s in scenes if s.name == name)
-
-
-@pytest.fixture(scope="module")
-def Smpc():
-    from mpcholonavigation_amd.optimizer import Smpc as S_
-    return S_
-
-
-def last_kernel(g):
-    f = g.lib.smpc_debug_last_pass_kernel
-    f.restype, f.argtypes = ctypes.c_char_p, []
-    return f().decode()
 
 
 def judge(g, sc, u, out, label=None, kernel=None):
@@ -273,23 +240,14 @@ def group_round(Smpc, monkeypatch, scenes, kind, kernel):
 def test_lane_group_of_unequal_plans(Smpc, monkeypatch):
     """smpc_group_optimize sizes ONE lane layout from the longest member's plan; the members' own P differ."""
     scenes = lane_group_scenes()
-    group_round(Smpc, monkeypatch, scenes, 1, lane(Tr, Tr, Tr, 1, F, F, Tr, 0, F))
+    group_round(Smpc, monkeypatch, scenes, 1, lane(many=True))
 
 
 @gpu
 def test_wave_group_of_unequal_plans(Smpc, monkeypatch):
     """smpc_pass_many carries one layout per member."""
     scenes = wave_group_scenes()
-    group_round(Smpc, monkeypatch, scenes, 0, wave(64, 0, many=True))
-
-
-def scan_count(g):
-    fn = g.lib.smpc_debug_lane_scan_count
-    fn.restype = ctypes.c_int
-    fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_uint32)]
-    n, groups = ctypes.c_ulonglong(0), ctypes.c_uint32(0)
-    assert fn(g.h, ctypes.byref(n), ctypes.byref(groups)) == 0
-    return n.value, groups.value
+    group_round(Smpc, monkeypatch, scenes, 0, wave_at(64, 0, many=True))
 
 
 @gpu

@@ -455,13 +455,9 @@ def test_grouped_contexts_with_the_deployed_critic_list():
     pass's deployed-list instances too, and the group gives exactly what each member gives alone
     — bit for bit, over a closed loop — in one launch from the second tick on."""
     from mpcholonavigation_amd.optimizer import Smpc, SmpcGroup
+    from tests.harness import DEPLOYED, critics_of
     from tests.helpers import configure
-    names = ("constraint", "cost", "goal", "goal_angle", "path_align", "path_follow", "path_angle",
-             "prefer_forward", "twirling")
-    cr = default_critics()
-    for n in ("obstacles", "path_align", "path_follow", "goal_angle", "prefer_forward", "cost", "goal",
-              "constraint", "twirling", "path_angle", "velocity_deadband"):
-        getattr(cr, n).enabled = 1 if n in names else 0
+    cr = critics_of(DEPLOYED, power=None)
     n, B, T = 3, 4096, 64
     cases = []
     for i in range(n):

@@ -38,14 +38,13 @@ no furthest-point prediction and re-scores every member alone).
 
 Every test prints its largest error in units, per row.
 """
-import ctypes
-
 import numpy as np
 import pytest
 
 from mpcholonavigation_amd.synthetic import make_scenario
 from mpcholonavigation_amd.tick import default_config
 from tests import softmax_model as sm
+from tests.harness import Oracle, Smpc, create_with_env, last_kernel  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -55,27 +54,13 @@ GROUP = [c for c in sm.CASES if c.path == "group"]
 FLOOR_MAX_B = 70001
 
 
-@pytest.fixture(scope="module")
-def Smpc():
-    from oracle import loader
-    from mpcholonavigation_amd.optimizer import Smpc as S
-    loader.build()
-    return S
-
-
-def last_kernel(g):
-    f = g.lib.smpc_debug_last_pass_kernel
-    f.restype, f.argtypes = ctypes.c_char_p, []
-    return f().decode()
+@pytest.fixture(scope="module", autouse=True)
+def _oracle_built(Oracle):
+    """The float64 model's reference runs call the oracle's library: built before the first test."""
 
 
 def create(Smpc, monkeypatch, case, cfg):
-    for k, v in case.env:
-        monkeypatch.setenv(k, v)          # (the knobs are read when the context is created)
-    g = Smpc(cfg)
-    for k, _ in case.env:
-        monkeypatch.delenv(k)
-    return g
+    return create_with_env(Smpc, monkeypatch, cfg, case.env)
 
 
 def tick(Smpc, monkeypatch, bt, u_in=None, **cfg_kw):

@@ -5,18 +5,14 @@ self-consistency properties there).  The CPU oracle needs ~2 s per 262 144-rollo
 Noise: the bench's own — the device RNG's stored tensors (smpc_seed), read back and handed to
 the oracle — so the kernel under test runs on exactly the tensors it is timed on.
 """
-import numpy as np
 import pytest
 
 from mpcholonavigation_amd.synthetic import make_scenario
 from mpcholonavigation_amd.tick import default_config
+from tests.harness import shifted
 from tests.helpers import assert_parity, configure
 
 pytestmark = pytest.mark.gpu
-
-
-def _shift(u):
-    return np.concatenate([u[:, 1:], u[:, -1:]], axis=1)
 
 
 def _run(B, T, map_size, expect_lane, max_hard, label, double_sums=False):
@@ -55,7 +51,7 @@ def _run(B, T, map_size, expect_lane, max_hard, label, double_sums=False):
         assert_parity(ug, og, uo, oo, g.get_costs(), o.get_costs(), max_flips=max_hard,
                       label=f"{label} tick {k}")
         # both continue from the ORACLE's sequence, so a tolerated difference does not compound
-        u_g = u_o = _shift(uo)
+        u_g = u_o = shifted(uo)
     g.close()
 
 

@@ -5,20 +5,12 @@ import ctypes as C
 import os
 import re
 
-import pytest
 
 from mpcholonavigation_amd import _abi as A
+from tests.harness import lib  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("smpc_group_critic_breakdown", "smpc_group_breakdown_counts")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    ge.build()
-    from mpcholonavigation_amd.optimizer import load_library
-    return load_library()
 
 
 def header(name):

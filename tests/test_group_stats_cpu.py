@@ -2,17 +2,9 @@
 NULL group is refused — nothing here creates a context."""
 import ctypes as C
 
-import pytest
 
 from mpcholonavigation_amd import _abi as A
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as ge
-    ge.build()
-    from mpcholonavigation_amd.optimizer import load_library
-    return load_library()
+from tests.harness import lib  # noqa: F401
 
 
 def test_the_symbol_is_exported_and_bound(lib):

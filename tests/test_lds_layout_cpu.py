@@ -9,12 +9,10 @@ GPU (an LDS write out of range is dropped, a read returns 0), so this is where i
 The admission limits (largest P with total <= 160 KB) are pinned as literals.  plan_launch drops a
 tick from the lane pass to the wave pass where the lane layout no longer fits: a layout change that
 shrinks what rides the lane pass is a diff here, not only a slower tick."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
-from mpcholonavigation_amd.optimizer import LIB_PATH
+from tests.harness import lib  # noqa: F401
 from tests.plan_scenes import KIND_LANE, KIND_SPLIT, KIND_WAVE, LDS_PER_CU, lds_layout, plan_limit
 
 WORDS = ("off_lut", "off_px", "off_py", "off_pyaw", "off_D", "off_valid", "off_scr", "off_pts4", "off_prune",
@@ -28,14 +26,6 @@ LUT_ENTRY = 8                                  # SmpcLut {crit, rep}: two floats
 LANE_BLOCK = 512                               # smpc_lane.hip:48, :54 (both forms)
 SPLIT_BLOCK = 512                              # smpc_split.hip:46
 PARK_STRIDE = 68                               # LANE_PARK_STRIDE, smpc_lane_common.h:23
-
-
-@pytest.fixture(scope="module")
-def lib():
-    lb = C.CDLL(LIB_PATH)
-    lb.smpc_debug_lds_layout.restype = C.c_int
-    lb.smpc_debug_lds_layout.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-    return lb
 
 
 def sweep(lib, kind, window, T, arg):

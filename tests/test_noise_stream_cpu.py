@@ -10,13 +10,7 @@ import pytest
 
 from mpcholonavigation_amd.tick import default_config
 from tests import noise_model as nm
-
-
-@pytest.fixture(scope="module")
-def Oracle():
-    from oracle.loader import Oracle as O, build
-    build()
-    return O
+from tests.harness import Oracle  # noqa: F401
 
 
 @pytest.mark.parametrize("ctr,key,expect", nm.KNOWN_ANSWERS)
