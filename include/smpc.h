@@ -382,6 +382,39 @@ int smpc_get_acceleration_limits(const smpc_ctx* ctx, float out[4]);
  * non-holonomic model: zeros).  SMPC_ERR_STATE when the limits are off or no tick has run. */
 int smpc_get_limited_noise(smpc_ctx* ctx, float* noise_vx, float* noise_vy, float* noise_wz);
 
+/* Moving obstacles: discs whose centres are indexed by the trajectory point, scored against every
+ * rollout in front of the critics of every iteration.  n discs, 0 <= n <= SMPC_MAX_MOVING_OBSTACLES;
+ * disc k has its centre at xy[(k*T + t)*2 + {0,1}] (costmap world frame, T = time_steps) when the
+ * robot is at trajectory point t — the indexing of smpc_get_trajectories — and radius[k] > 0 is the
+ * centre-to-centre distance below which the robot collides with it (the caller adds the two radii).
+ * For rollout b with the trajectory points (x[b][t], y[b][t]) the scoring passes form, in float,
+ *   d = sqrtf(dx*dx + dy*dy);   q = clamp((radius[k] + margin - d) / margin, 0, 1)
+ *   m(b) = repulsion_weight * (sum over t,k of q) / T + (any d < radius[k] ? collision_cost : 0)
+ * and m(b) is what the rollout's cost starts from: iteration 0 scores every critic of the tick on
+ * top of m(b), iteration k > 0 on top of (float)((double)cost_prev + m_k(b)) with m_k from that
+ * iteration's own control sequence.  Every pass of an iteration starts from the same value.  The
+ * term has no cost_power, never sets fail_flag and does not enter non_colliding; a tick with
+ * fail_flag_in scores nothing, this term included.
+ * smpc_set_moving_obstacles copies before it returns; the table holds from the next tick until it
+ * is replaced and survives smpc_reset.  n == 0 (xy, radius and p may be NULL): off — the default;
+ * nothing is allocated, uploaded or launched.  collision_cost >= 0, repulsion_weight >= 0,
+ * margin > 0, radius > 0, everything finite: anything else is SMPC_ERR_INVALID; n above the maximum
+ * is SMPC_ERR_UNSUPPORTED.  (Additions under ABI 3.) */
+#define SMPC_MAX_MOVING_OBSTACLES 64
+typedef struct smpc_moving_obstacles_params {
+  float collision_cost;     /* added once to a rollout that comes closer than radius[k] to a disc */
+  float repulsion_weight;
+  float margin;             /* metres beyond radius[k] over which q falls from 1 to 0 */
+  uint32_t reserved;
+} smpc_moving_obstacles_params;
+void smpc_moving_obstacles_params_default(smpc_moving_obstacles_params* p);
+int smpc_set_moving_obstacles(smpc_ctx* ctx, const smpc_moving_obstacles_params* p, const float* xy,
+                              const float* radius, uint32_t n);
+/* m [B] and hit [B] (0 / 1; may be NULL) of the last tick's last iteration.  SMPC_ERR_STATE when
+ * the term is off, no tick has scored this table yet, or the last tick had fail_flag_in (it scored
+ * nothing: an earlier tick's values are not handed out as its own). */
+int smpc_get_moving_obstacle_costs(smpc_ctx* ctx, float* m, uint8_t* hit);
+
 int smpc_set_critics(smpc_ctx* ctx, const smpc_critic_params* p);
 
 /* Replaces the Costmap2D* the critics hold

@@ -29,6 +29,9 @@ int smpc_debug_bar_tick(const smpc_ctx* ctx);
 /* SMPC_FLAG_PROFILE: GPU time of the last acceleration-limit launch */
 int smpc_debug_limit_ms(smpc_ctx* ctx, float* ms);
 
+/* SMPC_FLAG_PROFILE: GPU time of the last moving-obstacle launch */
+int smpc_debug_moving_ms(smpc_ctx* ctx, float* ms);
+
 /* SMPC_FLAG_PROFILE: GPU time of the last breakdown's scoring pass and of
  * its reduction */
 int smpc_debug_stats_ms(const smpc_ctx* ctx, float* pass_ms, float* reduce_ms);

@@ -80,6 +80,14 @@ int sortham_optimizer_set_speed_limit(sortham_optimizer* o, double speed_limit, 
  * Before or after initialize; kept across reset and across a re-initialize. */
 int sortham_optimizer_set_acceleration_limits(sortham_optimizer* o, float ax_max, float ax_min,
                                               float ay_max, float az_max);
+/* Optimizer::setMovingObstacles / clearMovingObstacles (n == 0): the table of
+ * smpc_set_moving_obstacles, xy [n][time_steps][2], radius [n].  Before or after initialize; kept
+ * across reset and across a re-initialize. */
+int sortham_optimizer_set_moving_obstacles(sortham_optimizer* o, const smpc_moving_obstacles_params* params,
+                                           const float* xy, const float* radius, uint32_t n,
+                                           uint32_t time_steps);
+/* smpc_get_moving_obstacle_costs of the object's context: m [batch_size], hit [batch_size] or NULL */
+int sortham_optimizer_moving_obstacle_costs(sortham_optimizer* o, float* m, uint8_t* hit, uint32_t batch_size);
 int sortham_optimizer_reset(sortham_optimizer* o);
 /* control_sequence_ as {vx[T], vy[T], wz[T]} */
 int sortham_optimizer_get_control_sequence(sortham_optimizer* o, float* u);
@@ -137,6 +145,20 @@ int sortham_fleet_eval_control(sortham_fleet* fleet, const smpc_tick_in* ins, co
  * context), and the retries the fleet ran alone.  Any pointer may be NULL. */
 int sortham_fleet_stats(const sortham_fleet* fleet, uint64_t* batched_launches, uint64_t* single_ticks,
                         uint64_t* retries);
+/* FleetOptimizer::setMutualAvoidance: before a round's ticks every member taken gets one moving
+ * obstacle per other member — a member taken this round as the trajectory of its control sequence
+ * from this round's pose, one not taken as a disc standing at its last pose, one never taken left
+ * out — with radius robot_radius[i] + robot_radius[j].  robot_radius[n], n the fleet's size;
+ * n == 0: off (the default), every member's table cleared. */
+int sortham_fleet_set_mutual_avoidance(sortham_fleet* fleet, const smpc_moving_obstacles_params* params,
+                                       const float* robot_radius, uint32_t n);
+/* The table that rule gives member i of n (pure host code, no fleet needed): state[n] 0 never seen,
+ * 1 standing, 2 moving; pose[n][3] x, y, yaw; u[n][3][time_steps]; model_dt[n]; holonomic[n];
+ * robot_radius[n].  Out: xy [discs][time_steps][2] and radius [discs] (room for n - 1 discs), *discs. */
+int sortham_fleet_avoidance_table(uint32_t i, uint32_t n, uint32_t time_steps, const uint8_t* state,
+                                  const double* pose, const float* u, const float* model_dt,
+                                  const uint8_t* holonomic, const float* robot_radius, float* xy,
+                                  float* radius, uint32_t* discs);
 /* FleetOptimizer::getCriticStats: sortham_optimizer_critic_stats for the members taken, the fleet
  * staying grouped (smpc.h: smpc_group_critic_breakdown).  ins[n], take[n] as for
  * sortham_fleet_eval_control; stats[n]; per_rollout: NULL, or n pointers of which any may be NULL,

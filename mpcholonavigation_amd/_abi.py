@@ -258,6 +258,19 @@ class SmpcCriticStats(C.Structure):
     ]
 
 
+SMPC_MAX_MOVING_OBSTACLES = 64
+
+
+class SmpcMovingObstaclesParams(C.Structure):
+    """smpc_moving_obstacles_params — the moving-obstacle term (smpc_set_moving_obstacles)."""
+    _fields_ = [
+        ("collision_cost", C.c_float),
+        ("repulsion_weight", C.c_float),
+        ("margin", C.c_float),
+        ("reserved", C.c_uint32),
+    ]
+
+
 # name -> (restype, argtypes) for every symbol include/smpc.h declares.
 _ctx = C.c_void_p
 PROTOTYPES = {
@@ -273,6 +286,10 @@ PROTOTYPES = {
     "smpc_set_acceleration_limits": (C.c_int, [_ctx, C.c_float, C.c_float, C.c_float, C.c_float]),
     "smpc_get_acceleration_limits": (C.c_int, [_ctx, C.POINTER(C.c_float)]),
     "smpc_get_limited_noise": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "smpc_moving_obstacles_params_default": (None, [C.POINTER(SmpcMovingObstaclesParams)]),
+    "smpc_set_moving_obstacles": (C.c_int, [_ctx, C.POINTER(SmpcMovingObstaclesParams), C.c_void_p, C.c_void_p,
+                                            C.c_uint32]),
+    "smpc_get_moving_obstacle_costs": (C.c_int, [_ctx, C.c_void_p, C.c_void_p]),
     "smpc_set_critics": (C.c_int, [_ctx, C.POINTER(SmpcCriticParams)]),
     "smpc_set_costmap": (C.c_int, [_ctx, C.c_void_p, C.c_uint32, C.c_uint32, C.c_double,
                                    C.c_double, C.c_double, C.c_int, C.c_float, C.c_float,
@@ -335,6 +352,7 @@ DEBUG_PROTOTYPES = {
     "smpc_debug_last_pass_kernel": (C.c_char_p, []),
     "smpc_debug_bar_tick": (C.c_int, [_ctx]),
     "smpc_debug_limit_ms": (C.c_int, [_ctx, C.POINTER(C.c_float)]),
+    "smpc_debug_moving_ms": (C.c_int, [_ctx, C.POINTER(C.c_float)]),
     "smpc_debug_stats_ms": (C.c_int, [_ctx, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "smpc_debug_furthest_f": (C.c_int, [_ctx, C.POINTER(C.c_float)]),
     "smpc_debug_tail_timeline": (C.c_int, [_ctx, C.POINTER(C.c_ulonglong)]),

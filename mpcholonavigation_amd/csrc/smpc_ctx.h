@@ -29,6 +29,7 @@
 #include "smpc_dev.h"
 #include "smpc_inst.h"   // the scoring-pass instances: tables, selectors, launch
 #include "smpc_limit.h"  // smpc_limit_noise: its arguments
+#include "smpc_moving.h" // smpc_moving_cost: its arguments
 
 // nothing below is part of the C-ABI: keep it out of the dynamic symbol table
 #pragma GCC visibility push(hidden)
@@ -69,6 +70,8 @@ hipError_t smpc_launch_box_muller(const uint32_t* r0, const uint32_t* r1, uint32
 
 // smpc_limit.hip: the stored noise of an iteration into its limited noise, in either layout
 hipError_t smpc_launch_limit_noise(const SmpcLimitArgs& a, bool group_major, hipStream_t st);
+// smpc_moving.hip: the moving-obstacle term of an iteration into the passes' starting costs, from either layout
+hipError_t smpc_launch_moving_cost(const SmpcMovingArgs& a, bool group_major, hipStream_t st);
 
 namespace smpc_impl {
 
@@ -398,6 +401,26 @@ struct smpc_ctx {
   uint32_t lim_iter = 0;                 // counts iterations (begin_limit_iteration); never 0 once a tick ran
   uint32_t lim_rm_iter = 0, lim_gm_iter = 0;   // the iteration each layout's buffer holds (0: none)
   hipEvent_t ev_lim[2] = {};             // SMPC_FLAG_PROFILE: around the last limiter launch
+  // Moving obstacles (smpc_set_moving_obstacles).  While mov_K > 0, every iteration's
+  // passes start their costs from the moving-obstacle term: use_moving_seed (smpc_api.cpp) launches
+  // smpc_moving_cost once per iteration, in front of the first pass, into the buffer the passes read
+  // as costs_prev.  Buffers: allocated by the first smpc_set_moving_obstacles with n > 0, each on its own.
+  uint32_t mov_K = 0;                    // discs in the table; 0: off
+  smpc_moving_obstacles_params mov_par{};
+  float* mov_tab_tk = nullptr;           // [T][K]{x, y, guarded squared reach, radius}: the group-major launch's table;
+                                         // the ONE device allocation the next two point into
+  float* mov_tab_kt = nullptr;           // [K][T]{x, y}: the row-major launch's
+  float* mov_disc = nullptr;             // [K]{radius, radius + margin, guarded squared reach, 0}
+  float* mov_stage = nullptr;            // pinned: the same three regions, what the uploads read
+  hipEvent_t ev_mov_up = nullptr;        // behind the last upload
+  bool mov_up_recorded = false;
+  hipStream_t mov_up_stream = nullptr;   // the stream it went out on (a kernel on another stream waits for the event)
+  float* mov_m = nullptr;                // [B] m of the last scored iteration
+  uint8_t* mov_hit = nullptr;            // [B] its hits
+  float* mov_stats_seed = nullptr;       // [B] the seed of smpc_critic_breakdown's own cost buffer (first use)
+  uint32_t mov_iter = 0;                 // the iteration (lim_iter) whose seed is in place (0: none)
+  bool mov_scored = false;               // mov_m and mov_hit hold a tick's values
+  hipEvent_t ev_mov[2] = {};             // SMPC_FLAG_PROFILE: around the last smpc_moving_cost launch
   hipEvent_t ev_stats[4] = {};   // SMPC_FLAG_PROFILE: around the scoring pass and around the reduction
   float stats_pass_ms = 0.f, stats_reduce_ms = 0.f;
   std::string err;
@@ -495,6 +518,16 @@ void begin_limit_iteration(smpc_ctx* c, const float* u_dev);
 // be launched with d reads; made first (one launch on c->stream) if no pass of the iteration read
 // that layout yet.  Limits off: nothing.
 int use_limited_noise(smpc_ctx* c, SmpcDev& d, bool group_major);
+// ---- moving obstacles ----
+// d (behind use_limited_noise: its noise pointers are the iteration's) starts its costs from the
+// moving-obstacle term: SD_COST_SEED in d.flags — set here, behind the choice of the instance, which
+// never sees the bit — and, if no pass of the iteration was seeded yet, one smpc_moving_cost launch on
+// c->stream into d.costs_prev, reading the layout the pass reads.  Off, or fail_flag_in: nothing.
+int use_moving_seed(smpc_ctx* c, SmpcDev& d, bool group_major);
+// the same for a first-iteration pass on the [B,T] noise that keeps costs of its own (the critic
+// breakdown): m into a buffer of the ctx's (allocated at the first call), which becomes
+// d.costs_prev; the tick's own m and hits (smpc_get_moving_obstacle_costs) are left alone
+int seed_own_costs(smpc_ctx* c, SmpcDev& d);
 int update_time_major(smpc_ctx* c);
 int ensure_row_major(smpc_ctx* c);
 int draw_noise(smpc_ctx* c);

@@ -27,6 +27,8 @@
 #define SD_FP_COST 0x40000u        // CostCritic consider_footprint
 #define SD_PATH_ALIGN_LEGACY 0x80000u   // PathAlignLegacyCritic past its host-side gates (still gated per S)
 #define SD_PAL_USE_PATH_YAW 0x100000u  // ... with use_path_orientations
+#define SD_COST_SEED 0x200000u         // costs start from costs_prev on iteration 0 too: the moving-obstacle term (smpc_moving.hip)
+#define SD_COST_SEED_TO_ACCUMULATE 15u   // SD_COST_SEED >> 15 == SD_ACCUMULATE: one test of both with small constants only
 #define SD_EXTRA_CRITICS (SD_CONSTRAINT | SD_COST | SD_GOAL | SD_TWIRLING | SD_PATH_ANGLE | SD_DEADBAND | \
                           SD_FP_OBSTACLES | SD_FP_COST | SD_PATH_ALIGN_LEGACY)
 

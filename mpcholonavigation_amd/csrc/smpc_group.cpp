@@ -248,7 +248,11 @@ int smpc_group_optimize_some(smpc_group* g, const smpc_tick_in* ins, float* cons
       {
         // a member with acceleration limits: its limiter goes out here, on the group's stream (c->stream
         // while grouped) ahead of the grouped pass, and its parameter block points at the limited noise
-        const int rc = use_limited_noise(c, hd[j], !l.wave);
+        int rc = use_limited_noise(c, hd[j], !l.wave);
+        if (rc != SMPC_OK) return rc;
+        // a member with moving obstacles: its seed kernel goes out the same way, and the member keeps
+        // riding the batched launch (SD_COST_SEED is set behind the choice of the instance)
+        rc = use_moving_seed(c, hd[j], !l.wave);
         if (rc != SMPC_OK) return rc;
       }
       hr[j].partials = c->d_partials;

@@ -716,7 +716,7 @@ LANE_PASS_KERNEL(const SmpcDev p0, const SmpcLds L, const SmpcDev* __restrict__ 
 #include "smpc_lane_furthest.inc"
 #undef LANE_FURTHEST_PRUNE
     }
-    float cost = (p.flags & SD_ACCUMULATE) ? p.costs_prev[bl] : 0.f;
+    float cost = (p.flags & (SD_ACCUMULATE | SD_COST_SEED)) ? p.costs_prev[bl] : 0.f;
     if constexpr (POW) {
       // costs with general cost powers: every critic's per-rollout total goes through
       // data.costs += pow(total * weight, power) on its own, with the arithmetic of smpc_pass

@@ -639,7 +639,7 @@ __global__ void __launch_bounds__(SPLIT_BLOCK, 2) smpc_pass_split(const SmpcDev 
       F_local = fmaxf(F_local, m);
     }
     // costs (every cost_power == 1): the association of smpc_pass_lane
-    float cost = (p.flags & SD_ACCUMULATE) ? p.costs_prev[bl] : 0.f;
+    float cost = (p.flags & (SD_ACCUMULATE | SD_COST_SEED)) ? p.costs_prev[bl] : 0.f;
     const bool collided = alive == 0.f;
     float lin = (collided ? 0.f : p.obs_critical_w * crit) + p.obs_rep_over_T * rep;
     float uni = collided ? p.obs_critical_w * p.obs_collision_cost : 0.f;

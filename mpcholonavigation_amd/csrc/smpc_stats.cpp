@@ -152,6 +152,10 @@ static int score_rows(smpc_ctx* c, const StatsBufs& sb, uint32_t flags, const fl
     // acceleration limits: the [B,T] limited noise (a lane context has it only because of this call)
     rc = use_limited_noise(c, d, false);
     if (rc != SMPC_OK) return rc;
+    // moving obstacles: the costs start from m, as the tick's do — no row carries the term, so the
+    // rows add up to the cost minus m
+    rc = seed_own_costs(c, d);
+    if (rc != SMPC_OK) return rc;
   }
   c->launched = true;
   if (prof) HIPCK(c, hipEventRecord(c->ev_stats[0], c->stream));
@@ -483,7 +487,9 @@ int smpc_group_critic_breakdown(smpc_group* g, const smpc_tick_in* ins, const fl
     d.partials = sb.partials;
     d.tail = 0;
     {
-      const int rc = use_limited_noise(c, d, false);
+      int rc = use_limited_noise(c, d, false);
+      if (rc != SMPC_OK) return give_up(rc);
+      rc = seed_own_costs(c, d);   // (a member with moving obstacles: its seed kernel on the group's stream, as in a round)
       if (rc != SMPC_OK) return give_up(rc);
     }
     hg[j].lds = pg.lds;

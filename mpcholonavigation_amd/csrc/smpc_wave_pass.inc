@@ -543,7 +543,7 @@ __global__ void __launch_bounds__((R == 4 ? 512 : 1024), (R == 4 ? 2 : 4)) WAVE_
     }
     if (FURTHEST_ONLY) continue;
 
-    float cost = (p.flags & SD_ACCUMULATE) ? p.costs_prev[b] : 0.f;
+    float cost = ((p.flags | (p.flags >> SD_COST_SEED_TO_ACCUMULATE)) & SD_ACCUMULATE) ? p.costs_prev[b] : 0.f;
     float lin = 0.f;    // MODE 0: per-lane sum of every additive per-step term
     float uni = 0.f;    // MODE 0: wave-uniform terms
     double lin_d = 0.0; // MODE 3: per-lane sum of the terms the reference forms in double

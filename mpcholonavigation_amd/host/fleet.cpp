@@ -2,11 +2,103 @@
 #include "fleet.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <exception>
 
 namespace SORTHAM_HOST_NS
 {
+
+// where member j is at each trajectory point, [T][2]: its control sequence integrated from its pose
+// (moving), or the pose itself (standing)
+static void peerTrack(
+  uint32_t j, uint32_t T, const uint8_t * state, const double * pose, const float * u, const float * model_dt,
+  const uint8_t * holonomic, float * out)
+{
+  const Pose2D at{pose[3 * j], pose[3 * j + 1], pose[3 * j + 2]};
+  if (state[j] == FLEET_PEER_MOVING) {
+    models::ControlSequence seq;
+    const float * uj = u + static_cast<size_t>(j) * 3 * T;
+    seq.vx.assign(uj, uj + T);
+    seq.vy.assign(uj + T, uj + 2 * T);
+    seq.wz.assign(uj + 2 * T, uj + 3 * T);
+    const auto traj = integrateControlSequence(seq, T, model_dt[j], at, holonomic[j] != 0);
+    for (uint32_t t = 0; t < T; ++t) {
+      out[2 * t] = traj[t][0];
+      out[2 * t + 1] = traj[t][1];
+    }
+  } else {
+    for (uint32_t t = 0; t < T; ++t) {
+      out[2 * t] = static_cast<float>(at.x);
+      out[2 * t + 1] = static_cast<float>(at.y);
+    }
+  }
+}
+
+// member i's table from every seen member's track [n][T][2]: the others', in the order of j
+static void assembleAvoidanceTable(
+  uint32_t i, uint32_t n, uint32_t T, const uint8_t * state, const float * tracks, const float * robot_radius,
+  std::vector<float> & xy, std::vector<float> & radius)
+{
+  xy.clear();
+  radius.clear();
+  for (uint32_t j = 0; j < n; ++j) {
+    if (j == i || state[j] == FLEET_PEER_UNSEEN) {
+      continue;
+    }
+    radius.push_back(robot_radius[i] + robot_radius[j]);
+    const float * tr = tracks + static_cast<size_t>(j) * T * 2;
+    xy.insert(xy.end(), tr, tr + static_cast<size_t>(T) * 2);
+  }
+}
+
+void buildMutualAvoidanceTable(
+  uint32_t i, uint32_t n, uint32_t T, const uint8_t * state, const double * pose, const float * u,
+  const float * model_dt, const uint8_t * holonomic, const float * robot_radius, std::vector<float> & xy,
+  std::vector<float> & radius)
+{
+  std::vector<float> tracks(static_cast<size_t>(n) * T * 2, 0.0f);
+  for (uint32_t j = 0; j < n; ++j) {
+    if (j != i && state[j] != FLEET_PEER_UNSEEN) {
+      peerTrack(j, T, state, pose, u, model_dt, holonomic, &tracks[static_cast<size_t>(j) * T * 2]);
+    }
+  }
+  assembleAvoidanceTable(i, n, T, state, tracks.data(), robot_radius, xy, radius);
+}
+
+void FleetOptimizer::setMutualAvoidance(
+  const smpc_moving_obstacles_params & params, const std::vector<float> & robot_radius)
+{
+  if (robot_radius.empty()) {
+    const bool was_on = !avoid_radius_.empty();
+    avoid_radius_.clear();
+    for (Optimizer * m : members_) {
+      if (was_on && m) {
+        m->clearMovingObstacles();
+      }
+    }
+    return;
+  }
+  if (robot_radius.size() != members_.size()) {
+    throw FleetError(SMPC_ERR_INVALID, "setMutualAvoidance: one radius per member");
+  }
+  if (members_.size() - 1 > SMPC_MAX_MOVING_OBSTACLES) {
+    throw FleetError(SMPC_ERR_UNSUPPORTED, "setMutualAvoidance: more than SMPC_MAX_MOVING_OBSTACLES other members");
+  }
+  bool ok = std::isfinite(params.collision_cost) && std::isfinite(params.repulsion_weight) &&
+    std::isfinite(params.margin) && params.collision_cost >= 0.0f && params.repulsion_weight >= 0.0f &&
+    params.margin > 0.0f;
+  for (float r : robot_radius) {
+    ok = ok && std::isfinite(r) && r > 0.0f;
+  }
+  if (!ok) {
+    throw FleetError(
+            SMPC_ERR_INVALID,
+            "setMutualAvoidance: collision_cost >= 0, repulsion_weight >= 0, margin > 0, every radius > 0, all finite");
+  }
+  avoid_params_ = params;
+  avoid_radius_ = robot_radius;
+}
 
 FleetOptimizer::FleetOptimizer(const std::vector<Optimizer *> & members)
 {
@@ -196,6 +288,63 @@ int FleetOptimizer::evalControl(
       return fail(SMPC_ERR_STATE, "member " + std::to_string(i) + ": " + e.what());
     }
     take_[s] = 1;
+  }
+  // ---- mutual avoidance: every member taken gets the others as moving obstacles ----------------
+  seen_.resize(n, 0);
+  last_pose_.resize(3 * n, 0.0);
+  for (size_t i = 0; i < n; ++i) {
+    if (taken(i)) {
+      seen_[i] = 1;
+      last_pose_[3 * i] = poses[i].x;
+      last_pose_[3 * i + 1] = poses[i].y;
+      last_pose_[3 * i + 2] = poses[i].yaw;
+    }
+  }
+  if (!avoid_radius_.empty()) {
+    const uint32_t T = members_[owner_[0]]->settings_.time_steps;   // (one for the whole group)
+    std::vector<uint8_t> state(n, FLEET_PEER_UNSEEN), holo(n, 0);
+    std::vector<float> u(n * 3 * static_cast<size_t>(T), 0.0f), dt(n, 0.0f);
+    for (size_t j = 0; j < n; ++j) {
+      const Optimizer * m = members_[j];
+      if (!seen_[j] || !m) {
+        continue;
+      }
+      state[j] = taken(j) ? FLEET_PEER_MOVING : FLEET_PEER_STANDING;
+      holo[j] = m->isHolonomic() ? 1 : 0;
+      dt[j] = m->settings_.model_dt;
+      if (taken(j)) {
+        std::memcpy(&u[j * 3 * T], m->control_sequence_.vx.data(), T * sizeof(float));
+        std::memcpy(&u[j * 3 * T + T], m->control_sequence_.vy.data(), T * sizeof(float));
+        std::memcpy(&u[j * 3 * T + 2 * T], m->control_sequence_.wz.data(), T * sizeof(float));
+      }
+    }
+    // every seen member's track once per round; a member's table is the others' tracks put together
+    std::vector<float> tracks(n * static_cast<size_t>(T) * 2, 0.0f);
+    for (size_t j = 0; j < n; ++j) {
+      if (state[j] != FLEET_PEER_UNSEEN) {
+        peerTrack(
+          static_cast<uint32_t>(j), T, state.data(), last_pose_.data(), u.data(), dt.data(), holo.data(),
+          &tracks[j * static_cast<size_t>(T) * 2]);
+      }
+    }
+    std::vector<float> xy, radius;
+    for (size_t i = 0; i < n; ++i) {
+      if (!taken(i)) {
+        continue;
+      }
+      assembleAvoidanceTable(
+        static_cast<uint32_t>(i), static_cast<uint32_t>(n), T, state.data(), tracks.data(), avoid_radius_.data(), xy,
+        radius);
+      try {
+        if (radius.empty()) {
+          members_[i]->clearMovingObstacles();
+        } else {
+          members_[i]->setMovingObstacles(avoid_params_, xy, radius);
+        }
+      } catch (const std::exception & e) {
+        return fail(SMPC_ERR_STATE, "member " + std::to_string(i) + ": " + e.what());
+      }
+    }
   }
   // ---- ONE grouped tick for all of them ------------------------------------------------------
   // (a context keeps the text of its last error: remembered, to tell which member met this one)

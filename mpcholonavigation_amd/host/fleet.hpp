@@ -63,6 +63,21 @@ struct FleetStats
   uint64_t retries{0};            // optimize() calls of the fallback loop
 };
 
+// What a fleet knows of member j when it builds the others' obstacle tables.
+constexpr uint8_t FLEET_PEER_UNSEEN = 0;     // never taken: left out
+constexpr uint8_t FLEET_PEER_STANDING = 1;   // not taken this round: a disc standing at its last pose
+constexpr uint8_t FLEET_PEER_MOVING = 2;     // taken this round: its control sequence integrated from this round's pose
+
+// The moving-obstacle table of member i (smpc_set_moving_obstacles) from what the fleet knows of the
+// n members: one disc per other member j that has been seen, in the order of j, radius
+// robot_radius[i] + robot_radius[j]; a moving j by integrateControlSequence on u[j] = [3][T] (vx, vy,
+// wz) from pose[j] = {x, y, yaw}, a standing j at pose[j] for every t.  xy: [discs][T][2], radius:
+// [discs].  Pure host code: no context, no device.
+void buildMutualAvoidanceTable(
+  uint32_t i, uint32_t n, uint32_t time_steps, const uint8_t * state, const double * pose, const float * u,
+  const float * model_dt, const uint8_t * holonomic, const float * robot_radius, std::vector<float> & xy,
+  std::vector<float> & radius);
+
 class FleetOptimizer : public FleetLink
 {
 public:
@@ -104,6 +119,14 @@ public:
     const std::vector<float> & goal_checker_xy_tolerances, const std::vector<uint8_t> & take,
     std::vector<MemberCriticStats> & out, const std::vector<float *> & per_rollout = {});
 
+  // Mutual avoidance: before a round's ticks every member taken gets the others as moving obstacles
+  // (buildMutualAvoidanceTable; Optimizer::setMovingObstacles, so the table replaces whatever the
+  // member had).  robot_radius: one per member, > 0; empty: off — the default — and every member's
+  // table is cleared.  Throws FleetError(SMPC_ERR_INVALID) for a wrong count or values the library
+  // would refuse.  Members share time_steps (smpc_group_create) and are expected to share model_dt:
+  // trajectory point t of one member is then the time of point t of another.
+  void setMutualAvoidance(const smpc_moving_obstacles_params & params, const std::vector<float> & robot_radius);
+
   FleetStats stats() const;
   const std::string & lastError() const {return err_;}
 
@@ -132,6 +155,11 @@ private:
   std::vector<float *> u_ptr_;
   std::vector<uint8_t> take_;
   std::vector<std::string> errs_before_;
+  // mutual avoidance: the parameters, one radius per member (empty: off), and where each member was seen last
+  smpc_moving_obstacles_params avoid_params_{};
+  std::vector<float> avoid_radius_;
+  std::vector<uint8_t> seen_;
+  std::vector<double> last_pose_;     // [members][3]
   FleetStats stats_{};                // of the groups already dropped, and the retries
   std::string err_;
 };

@@ -1,4 +1,5 @@
 // fleet_c.cpp — extern "C" face of sortham_ns::FleetOptimizer (include/smpc_host.h).
+#include <algorithm>
 #include <exception>
 #include <new>
 
@@ -165,6 +166,46 @@ int sortham_fleet_critic_stats(
       f->handles[i]->err = res[i].error;
     }
   }
+  return SMPC_OK;
+}
+
+int sortham_fleet_set_mutual_avoidance(
+  sortham_fleet * f, const smpc_moving_obstacles_params * params, const float * robot_radius, uint32_t n)
+{
+  if (!f || (n && (!params || !robot_radius))) {
+    return SMPC_ERR_INVALID;
+  }
+  try {
+    smpc_moving_obstacles_params p{};
+    if (params) {
+      p = *params;
+    }
+    f->fleet->setMutualAvoidance(p, n ? std::vector<float>(robot_radius, robot_radius + n) : std::vector<float>());
+    return SMPC_OK;
+  } catch (const sortham_ns::FleetError & e) {
+    f->err = e.what();
+    return e.code;
+  } catch (const std::exception & e) {
+    f->err = e.what();
+    return SORTHAM_ERR_THROWN;
+  }
+}
+
+int sortham_fleet_avoidance_table(
+  uint32_t i, uint32_t n, uint32_t time_steps, const uint8_t * state, const double * pose, const float * u,
+  const float * model_dt, const uint8_t * holonomic, const float * robot_radius, float * xy, float * radius,
+  uint32_t * discs)
+{
+  if (!state || !pose || !u || !model_dt || !holonomic || !robot_radius || !xy || !radius || !discs || i >= n ||
+    time_steps == 0)
+  {
+    return SMPC_ERR_INVALID;
+  }
+  std::vector<float> t_xy, t_r;
+  sortham_ns::buildMutualAvoidanceTable(i, n, time_steps, state, pose, u, model_dt, holonomic, robot_radius, t_xy, t_r);
+  std::copy(t_xy.begin(), t_xy.end(), xy);
+  std::copy(t_r.begin(), t_r.end(), radius);
+  *discs = static_cast<uint32_t>(t_r.size());
   return SMPC_OK;
 }
 

@@ -172,6 +172,7 @@ void Optimizer::initialize(
     keep = nullptr;
     ck(ctx_, smpc_set_critics(ctx_, &critics_.params), "smpc_set_critics");
     pushAccelerationLimits();
+    pushMovingObstacles();
     // as a fresh context: noise supplied through setNoise() does not survive initialize(), and the
     // draw starts from the seed's first epoch again (same seed, same noise as a new object)
     supplied_noise_ = false;
@@ -194,6 +195,7 @@ void Optimizer::initialize(
   have_built_ = true;
   ck(ctx_, smpc_set_critics(ctx_, &critics_.params), "smpc_set_critics");
   pushAccelerationLimits();
+  pushMovingObstacles();
   // NoiseGenerator::initialize draws once (noise_generator.cpp:26-42) ...
   ck(ctx_, smpc_seed(ctx_, noise_seed_), "smpc_seed");
   // ... and Optimizer::initialize ends in reset(), which draws again (H7)
@@ -234,6 +236,68 @@ void Optimizer::setAccelerationLimits(float ax_max, float ax_min, float ay_max, 
     accel_limits_ = before;   // refused: the context keeps what it had
     throw;
   }
+}
+
+void Optimizer::pushMovingObstacles()
+{
+  const uint32_t n = static_cast<uint32_t>(moving_radius_.size());
+  if (moving_xy_.size() != static_cast<size_t>(n) * settings_.time_steps * 2) {
+    throw std::runtime_error("moving obstacles: xy must hold [n][time_steps][2] floats");
+  }
+  ck(
+    ctx_, smpc_set_moving_obstacles(ctx_, &moving_params_, n ? moving_xy_.data() : nullptr,
+    n ? moving_radius_.data() : nullptr, n), "smpc_set_moving_obstacles");
+}
+
+void Optimizer::setMovingObstacles(
+  const smpc_moving_obstacles_params & params, const std::vector<float> & xy,
+  const std::vector<float> & radius)
+{
+  // the library's rules, so that a table set before initialize() is one the context will take
+  const size_t n = radius.size();
+  if (n > SMPC_MAX_MOVING_OBSTACLES) {
+    throw std::runtime_error("setMovingObstacles: more than SMPC_MAX_MOVING_OBSTACLES obstacles");
+  }
+  if (n == 0 ? !xy.empty() : xy.size() % (2 * n) != 0 || (ctx_ && xy.size() != n * settings_.time_steps * 2)) {
+    throw std::runtime_error("setMovingObstacles: xy must hold [n][time_steps][2] floats");
+  }
+  bool ok = std::isfinite(params.collision_cost) && std::isfinite(params.repulsion_weight) &&
+    std::isfinite(params.margin) && params.collision_cost >= 0.0f && params.repulsion_weight >= 0.0f &&
+    params.margin > 0.0f;
+  for (float r : radius) {ok = ok && std::isfinite(r) && r > 0.0f;}
+  for (float v : xy) {ok = ok && std::isfinite(v);}
+  if (n && !ok) {
+    throw std::runtime_error(
+            "setMovingObstacles: collision_cost >= 0, repulsion_weight >= 0, margin > 0, radius > 0, all finite");
+  }
+  const smpc_moving_obstacles_params p_before = moving_params_;
+  std::vector<float> xy_before = std::move(moving_xy_), r_before = std::move(moving_radius_);
+  moving_params_ = params;
+  moving_xy_ = xy;
+  moving_radius_ = radius;
+  if (!ctx_) {return;}   // initialize() hands them to the context it creates
+  try {
+    pushMovingObstacles();
+  } catch (...) {
+    moving_params_ = p_before;   // refused: the context keeps what it had
+    moving_xy_ = std::move(xy_before);
+    moving_radius_ = std::move(r_before);
+    throw;
+  }
+}
+
+void Optimizer::clearMovingObstacles()
+{
+  moving_xy_.clear();
+  moving_radius_.clear();
+  if (ctx_) {pushMovingObstacles();}
+}
+
+void Optimizer::getMovingObstacleCosts(std::vector<float> & m, std::vector<uint8_t> & hit)
+{
+  m.resize(settings_.batch_size);
+  hit.resize(settings_.batch_size);
+  ck(ctx_, smpc_get_moving_obstacle_costs(ctx_, m.data(), hit.data()), "smpc_get_moving_obstacle_costs");
 }
 
 void Optimizer::reset()
@@ -449,18 +513,17 @@ void Optimizer::setSpeedLimit(double speed_limit, bool percentage)
   }
 }
 
-std::vector<std::array<float, 3>> Optimizer::getOptimizedTrajectory()
+std::vector<std::array<float, 3>> integrateControlSequence(
+  const models::ControlSequence & sequence, unsigned int T, float dt, const Pose2D & pose, bool holonomic)
 {
   // integrateStateVelocities(trajectory, sequence) — optimizer.cpp:275-311: the control
   // sequence itself is integrated (no measured-speed first column here)
-  const unsigned int T = settings_.time_steps;
-  const float dt = settings_.model_dt;
-  const float initial_yaw = static_cast<float>(pose_.yaw);
+  const float initial_yaw = static_cast<float>(pose.yaw);
   std::vector<std::array<float, 3>> traj(T);
   std::vector<float> yaws(T);
   float acc = 0.0f;
   for (unsigned int t = 0; t < T; ++t) {
-    const float inc = control_sequence_.wz[t] * dt;
+    const float inc = sequence.wz[t] * dt;
     acc = t == 0 ? inc : acc + inc;
     yaws[t] = acc + initial_yaw;
   }
@@ -468,18 +531,23 @@ std::vector<std::array<float, 3>> Optimizer::getOptimizedTrajectory()
   for (unsigned int t = 0; t < T; ++t) {
     const float c = t == 0 ? cosf(initial_yaw) : cosf(yaws[t - 1]);
     const float s = t == 0 ? sinf(initial_yaw) : sinf(yaws[t - 1]);
-    float dx = control_sequence_.vx[t] * c;
-    float dy = control_sequence_.vx[t] * s;
-    if (isHolonomic()) {
-      dx = dx - control_sequence_.vy[t] * s;
-      dy = dy + control_sequence_.vy[t] * c;
+    float dx = sequence.vx[t] * c;
+    float dy = sequence.vx[t] * s;
+    if (holonomic) {
+      dx = dx - sequence.vy[t] * s;
+      dy = dy + sequence.vy[t] * c;
     }
     ax = t == 0 ? dx * dt : ax + dx * dt;
     ay = t == 0 ? dy * dt : ay + dy * dt;
-    traj[t] = {static_cast<float>(pose_.x + static_cast<double>(ax)),
-      static_cast<float>(pose_.y + static_cast<double>(ay)), yaws[t]};
+    traj[t] = {static_cast<float>(pose.x + static_cast<double>(ax)),
+      static_cast<float>(pose.y + static_cast<double>(ay)), yaws[t]};
   }
   return traj;
+}
+
+std::vector<std::array<float, 3>> Optimizer::getOptimizedTrajectory()
+{
+  return integrateControlSequence(control_sequence_, settings_.time_steps, settings_.model_dt, pose_, isHolonomic());
 }
 
 void Optimizer::getGeneratedTrajectories(

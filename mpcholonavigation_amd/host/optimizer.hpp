@@ -124,6 +124,13 @@ void savitskyGolayFilter(
 
 class Optimizer;
 
+// integrateStateVelocities(trajectory, sequence) (ref optimizer.cpp:275-311) as a free function: the
+// [T][3] x, y, yaw of a control sequence integrated from a pose, no measured-speed first column.  What
+// Optimizer::getOptimizedTrajectory returns, and what a fleet predicts a member's motion with.
+std::vector<std::array<float, 3>> integrateControlSequence(
+  const models::ControlSequence & sequence, unsigned int time_steps, float model_dt,
+  const Pose2D & pose, bool holonomic);
+
 // the arguments of Optimizer::evalControl as one value (getCriticStats)
 struct TickInput
 {
@@ -190,6 +197,16 @@ public:
   // ay_max > 0, az_max > 0; all zero: off, the default).  Before or after initialize(); kept across
   // reset() and across whatever recreates the context.  Throws where the library refuses the values.
   void setAccelerationLimits(float ax_max, float ax_min, float ay_max, float az_max);
+  // Moving obstacles (smpc_set_moving_obstacles): xy [n][T][2] disc centres per trajectory point in the
+  // costmap's world frame, radius [n] centre-to-centre collision distances.  Before or after
+  // initialize(); kept across reset() and across whatever recreates the context, as the limits are.
+  // Throws where the library refuses the values (the table then stays what it was).
+  void setMovingObstacles(
+    const smpc_moving_obstacles_params & params, const std::vector<float> & xy,
+    const std::vector<float> & radius);
+  void clearMovingObstacles();
+  // m [B] and hit [B] of the last tick's last iteration (smpc_get_moving_obstacle_costs)
+  void getMovingObstacleCosts(std::vector<float> & m, std::vector<uint8_t> & hit);
   void reset();                                             // ref :116-132
 
   // ref :345-360: [T][3] x, y, yaw of the optimal sequence
@@ -228,6 +245,7 @@ protected:
   void setMotionModel(const std::string & model);  // ref :412-426
   void pushConstraints();
   void pushAccelerationLimits();
+  void pushMovingObstacles();
 
   models::OptimizerSettings settings_{};
   models::ControlSequence control_sequence_{};
@@ -239,6 +257,8 @@ protected:
   bool visualize_{false};
   bool lane_per_rollout_{false};
   std::array<float, 4> accel_limits_{{0.0f, 0.0f, 0.0f, 0.0f}};   // ax_max, ax_min, ay_max, az_max; all zero: off
+  smpc_moving_obstacles_params moving_params_{};
+  std::vector<float> moving_xy_, moving_radius_;   // empty: off
   uint64_t noise_seed_{0};
   bool supplied_noise_{false};
   int device_{-1};

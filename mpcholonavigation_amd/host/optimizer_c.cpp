@@ -202,6 +202,38 @@ int sortham_optimizer_set_acceleration_limits(
   return guarded(o, [&]() {o->opt.setAccelerationLimits(ax_max, ax_min, ay_max, az_max);});
 }
 
+int sortham_optimizer_set_moving_obstacles(
+  sortham_optimizer * o, const smpc_moving_obstacles_params * params, const float * xy, const float * radius,
+  uint32_t n, uint32_t time_steps)
+{
+  if (!o || (n && (!params || !xy || !radius || time_steps == 0))) {return SMPC_ERR_INVALID;}
+  if (n > SMPC_MAX_MOVING_OBSTACLES) {return SMPC_ERR_UNSUPPORTED;}
+  return guarded(
+    o, [&]() {
+      if (n == 0) {
+        o->opt.clearMovingObstacles();
+        return;
+      }
+      o->opt.setMovingObstacles(
+        *params, std::vector<float>(xy, xy + static_cast<size_t>(n) * time_steps * 2),
+        std::vector<float>(radius, radius + n));
+    });
+}
+
+int sortham_optimizer_moving_obstacle_costs(sortham_optimizer * o, float * m, uint8_t * hit, uint32_t batch_size)
+{
+  if (!o || !m) {return SMPC_ERR_INVALID;}
+  return guarded(
+    o, [&]() {
+      std::vector<float> vm;
+      std::vector<uint8_t> vh;
+      o->opt.getMovingObstacleCosts(vm, vh);
+      if (vm.size() != batch_size) {throw std::runtime_error("moving_obstacle_costs: batch_size is not the optimizer's");}
+      std::memcpy(m, vm.data(), vm.size() * sizeof(float));
+      if (hit) {std::memcpy(hit, vh.data(), vh.size());}
+    });
+}
+
 int sortham_optimizer_set_speed_limit(sortham_optimizer * o, double speed_limit, int percentage)
 {
   if (!o) {return SMPC_ERR_INVALID;}

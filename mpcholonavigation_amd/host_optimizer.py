@@ -56,6 +56,9 @@ PROTOTYPES = {
     "sortham_optimizer_last_tick": (C.c_int, [_ctx, C.POINTER(A.SmpcTickOut)]),
     "sortham_optimizer_set_speed_limit": (C.c_int, [_ctx, C.c_double, C.c_int]),
     "sortham_optimizer_set_acceleration_limits": (C.c_int, [_ctx, C.c_float, C.c_float, C.c_float, C.c_float]),
+    "sortham_optimizer_set_moving_obstacles": (C.c_int, [_ctx, C.POINTER(A.SmpcMovingObstaclesParams), C.c_void_p,
+                                                         C.c_void_p, C.c_uint32, C.c_uint32]),
+    "sortham_optimizer_moving_obstacle_costs": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_uint32]),
     "sortham_optimizer_reset": (C.c_int, [_ctx]),
     "sortham_optimizer_get_control_sequence": (C.c_int, [_ctx, C.c_void_p]),
     "sortham_optimizer_set_control_sequence": (C.c_int, [_ctx, C.c_void_p]),
@@ -86,6 +89,16 @@ FLEET_STATS_PROTOTYPES = {
                                              C.POINTER(A.SmpcCriticStats), C.POINTER(C.c_void_p), C.c_void_p]),
 }
 
+# mutual avoidance (FleetOptimizer::setMutualAvoidance) and its table function: bound with them
+FLEET_AVOIDANCE_PROTOTYPES = {
+    "sortham_fleet_set_mutual_avoidance": (C.c_int, [_ctx, C.POINTER(A.SmpcMovingObstaclesParams), C.c_void_p,
+                                                     C.c_uint32]),
+    "sortham_fleet_avoidance_table": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.POINTER(C.c_uint32)]),
+}
+FLEET_PEER_UNSEEN, FLEET_PEER_STANDING, FLEET_PEER_MOVING = 0, 1, 2
+
 TICKS_SHIFT, TICKS_REDRAW_ASYNC, TICKS_SHARD, TICKS_SHARD_SPECULATE = 1, 2, 4, 8
 
 DEFAULT_CRITICS = ["ObstaclesCritic", "PathAlignCritic", "PathFollowCritic", "GoalAngleCritic",
@@ -107,8 +120,42 @@ def load_fleet_library():
     if not _fleet_bound:
         A.bind(lib, FLEET_PROTOTYPES)
         A.bind(lib, FLEET_STATS_PROTOTYPES)
+        A.bind(lib, FLEET_AVOIDANCE_PROTOTYPES)
         _fleet_bound = True
     return lib
+
+
+def moving_params(collision_cost=None, repulsion_weight=None, margin=None):
+    """smpc_moving_obstacles_params: the library's defaults with the given fields replaced."""
+    from .optimizer import load_library as load_smpc
+    p = A.SmpcMovingObstaclesParams()
+    load_smpc().smpc_moving_obstacles_params_default(C.byref(p))
+    for name, v in (("collision_cost", collision_cost), ("repulsion_weight", repulsion_weight), ("margin", margin)):
+        if v is not None:
+            setattr(p, name, v)
+    return p
+
+
+def mutual_avoidance_table(i, state, pose, u, model_dt, holonomic, robot_radius):
+    """sortham_fleet_avoidance_table: the moving-obstacle table FleetOptimizer gives member i.
+    state [n] (FLEET_PEER_*), pose [n, 3], u [n, 3, T], model_dt [n], holonomic [n], robot_radius [n]
+    -> (xy [discs, T, 2], radius [discs])."""
+    lib = load_fleet_library()
+    u = np.ascontiguousarray(u, np.float32)
+    n, _, T = u.shape
+    state = np.ascontiguousarray(state, np.uint8)
+    pose = np.ascontiguousarray(pose, np.float64)
+    model_dt = np.ascontiguousarray(model_dt, np.float32)
+    holonomic = np.ascontiguousarray(holonomic, np.uint8)
+    robot_radius = np.ascontiguousarray(robot_radius, np.float32)
+    xy = np.zeros((max(n - 1, 1), T, 2), np.float32)
+    radius = np.zeros(max(n - 1, 1), np.float32)
+    discs = C.c_uint32(0)
+    rc = lib.sortham_fleet_avoidance_table(i, n, T, _ptr(state), _ptr(pose), _ptr(u), _ptr(model_dt), _ptr(holonomic),
+                                           _ptr(robot_radius), _ptr(xy), _ptr(radius), C.byref(discs))
+    if rc != 0:
+        raise ValueError(f"sortham_fleet_avoidance_table: error {rc}")
+    return xy[:discs.value], radius[:discs.value]
 
 
 def _ptr(a):
@@ -243,6 +290,27 @@ class Optimizer:
         """Bounds on how fast a sampled control may change (all zero: off); kept across reset()."""
         self._ck(self.lib.sortham_optimizer_set_acceleration_limits(self.h, ax_max, ax_min, ay_max, az_max))
 
+    def set_moving_obstacles(self, xy=None, radius=None, collision_cost=None, repulsion_weight=None, margin=None):
+        """Optimizer::setMovingObstacles: xy [n, T, 2], radius [n] (optimizer.Smpc.set_moving_obstacles);
+        xy None or empty: clearMovingObstacles.  Kept across reset() and a re-initialize."""
+        p = moving_params(collision_cost, repulsion_weight, margin)
+        if xy is None or len(xy) == 0:
+            self._ck(self.lib.sortham_optimizer_set_moving_obstacles(self.h, C.byref(p), None, None, 0, self.T))
+            return
+        xy = np.ascontiguousarray(xy, dtype=np.float32)
+        radius = np.ascontiguousarray(radius, dtype=np.float32).reshape(-1)
+        if xy.ndim != 3 or xy.shape[1:] != (self.T, 2) or radius.shape[0] != xy.shape[0]:
+            raise ValueError("xy must be [n, time_steps, 2] and radius [n]")
+        self._ck(self.lib.sortham_optimizer_set_moving_obstacles(self.h, C.byref(p), _ptr(xy), _ptr(radius),
+                                                                 xy.shape[0], self.T))
+
+    def moving_obstacle_costs(self):
+        """(m [B] float32, hit [B] bool) of the last tick's last iteration."""
+        m = np.empty(self.B, np.float32)
+        hit = np.empty(self.B, np.uint8)
+        self._ck(self.lib.sortham_optimizer_moving_obstacle_costs(self.h, _ptr(m), _ptr(hit), self.B))
+        return m, hit.astype(bool)
+
     def set_speed_limit(self, speed_limit, percentage):
         self._ck(self.lib.sortham_optimizer_set_speed_limit(self.h, speed_limit, int(percentage)))
 
@@ -375,6 +443,15 @@ class FleetOptimizer:
             else:
                 res.append(critic_stats_from_c(A.SmpcCriticStats.from_buffer_copy(st[i]), names, rows[i]))
         return res
+
+    def set_mutual_avoidance(self, robot_radius=None, collision_cost=None, repulsion_weight=None, margin=None):
+        """FleetOptimizer::setMutualAvoidance: from the next round on every member taken scores the other
+        members as moving obstacles.  robot_radius: one per member; None or empty: off."""
+        p = moving_params(collision_cost, repulsion_weight, margin)
+        r = np.zeros(0, np.float32) if robot_radius is None else np.ascontiguousarray(robot_radius, np.float32).reshape(-1)
+        rc = self.lib.sortham_fleet_set_mutual_avoidance(self.h, C.byref(p), _ptr(r) if len(r) else None, len(r))
+        if rc != 0:
+            raise FleetError(rc, self.lib.sortham_fleet_last_error(self.h).decode())
 
     def run_rounds(self, ticks, n_rounds, take=None, alone=False):
         """sortham_fleet_run_rounds: n_rounds rounds on the same inputs from the compiled loop of

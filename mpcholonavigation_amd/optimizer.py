@@ -153,6 +153,31 @@ class Smpc:
         self._ck(self.lib.smpc_get_limited_noise(self.h, _ptr(out[0]), _ptr(out[1]), _ptr(out[2])))
         return out
 
+    def set_moving_obstacles(self, xy=None, radius=None, collision_cost=None, repulsion_weight=None, margin=None):
+        """Discs that move with the trajectory index: xy [n, T, 2] (costmap world frame: where disc k
+        is when the robot is at trajectory point t), radius [n] (centre-to-centre collision distance).
+        Parameters left None keep the library's defaults.  xy None or empty: off."""
+        p = A.SmpcMovingObstaclesParams()
+        self.lib.smpc_moving_obstacles_params_default(C.byref(p))
+        for name, v in (("collision_cost", collision_cost), ("repulsion_weight", repulsion_weight), ("margin", margin)):
+            if v is not None:
+                setattr(p, name, v)
+        if xy is None or len(xy) == 0:
+            self._ck(self.lib.smpc_set_moving_obstacles(self.h, C.byref(p), None, None, 0))
+            return
+        xy = np.ascontiguousarray(xy, dtype=np.float32)
+        radius = np.ascontiguousarray(radius, dtype=np.float32).reshape(-1)
+        if xy.ndim != 3 or xy.shape[1:] != (self.T, 2) or radius.shape[0] != xy.shape[0]:
+            raise ValueError("xy must be [n, time_steps, 2] and radius [n]")
+        self._ck(self.lib.smpc_set_moving_obstacles(self.h, C.byref(p), _ptr(xy), _ptr(radius), xy.shape[0]))
+
+    def moving_obstacle_costs(self):
+        """(m [B] float32, hit [B] bool) of the last tick's last iteration."""
+        m = np.empty(self.B, np.float32)
+        hit = np.empty(self.B, np.uint8)
+        self._ck(self.lib.smpc_get_moving_obstacle_costs(self.h, _ptr(m), _ptr(hit)))
+        return m, hit.astype(bool)
+
     def set_critics(self, p: A.SmpcCriticParams):
         self._ck(self.lib.smpc_set_critics(self.h, C.byref(p)))
 
