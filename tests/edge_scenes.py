@@ -205,12 +205,14 @@ def build_scene(origin=(0.0, 0.0), resolution=0.05, size=(200, 200), B=4096, T=6
 
 # ---- the judge: float64 / NumPy ----------------------------------------------------------------
 
-def _class_terms(scn, critics, critic):
+def _class_terms(scn, critics, critic, consider_footprint=False, using_footprint=False):
     """Per cost value 0..255: (collides, what a lookup adds to the critical sum, to the repulsive
     sum), in float64 from the float32 parameters.  ObstaclesCritic: obstacles_critic.cpp:99-171;
-    CostCritic: cost_critic.cpp:108-155; consider_footprint off."""
+    CostCritic: cost_critic.cpp:108-155.  consider_footprint: the critic's switch, under which 253
+    is no collision (inCollision); using_footprint: the cost is a walked footprint cost, whose
+    distance takes no inscribed-radius offset (obstacles_critic.cpp:106-108)."""
     c = np.arange(256, dtype=np.float64)
-    collide = (c == 254) | (c == 253) | ((c == 255) & (not scn.track_unknown))
+    collide = (c == 254) | ((c == 253) & (not consider_footprint)) | ((c == 255) & (not scn.track_unknown))
     crit = np.zeros(256)
     rep = np.zeros(256)
     if critic == "obstacles":
@@ -218,7 +220,7 @@ def _class_terms(scn, critics, critic):
         k, r_in, R = (float(np.float32(v)) for v in (scn.cost_scaling_factor, scn.inscribed_radius, scn.inflation_radius))
         margin = float(np.float32(p.collision_margin_distance))
         with np.errstate(divide="ignore"):
-            d = (k * r_in - np.log(c) + np.log(253.0)) / k - r_in
+            d = (k * r_in - np.log(c) + np.log(253.0)) / k - (0.0 if using_footprint else r_in)
         live = c >= 1
         crit[live & (d < margin)] = (margin - d)[live & (d < margin)]
         if not scn.near_goal:
@@ -240,6 +242,23 @@ def _weights(critics, critic, T):
     p = critics.cost
     w = float(np.float32(p.cost_weight) / np.float32(254.0)) / T
     return 0.0, w, w * float(np.float32(p.collision_cost))
+
+
+def _rollout_costs(hit, crit_t, rep_t, critics, critic, T):
+    """A critic's loop over one rollout's poses, for all rollouts: hit / crit_t / rep_t [B, T] are
+    each pose's collision and its two terms; the loop breaks at the first collision.
+    Returns (costs [B] float64, collided [B], first colliding step [B], T where none)."""
+    collided = hit.any(axis=1)
+    first = np.where(collided, hit.argmax(axis=1), T)
+    before = np.arange(T)[None, :] < first[:, None]           # lookups scored before the break
+    crit = np.where(before, crit_t, 0.0).sum(axis=1)
+    rep = np.where(before, rep_t, 0.0).sum(axis=1)
+    cw, rw, collision = _weights(critics, critic, T)
+    if critic == "obstacles":
+        costs = np.where(collided, collision, cw * crit) + rw * rep
+    else:
+        costs = np.where(collided, collision, rw * rep)
+    return costs, collided, first
 
 
 def trajectories(scn):
@@ -276,17 +295,7 @@ def model(scn, critics, critic="obstacles"):
     x, y = trajectories(scn)
     cost, _, _, _ = lookups(scn, x, y)
     collide_c, crit_c, rep_c = _class_terms(scn, critics, critic)
-    hit = collide_c[cost]
-    collided = hit.any(axis=1)
-    first = np.where(collided, hit.argmax(axis=1), scn.T)
-    before = np.arange(scn.T)[None, :] < first[:, None]       # lookups scored before the break
-    crit = np.where(before, crit_c[cost], 0.0).sum(axis=1)
-    rep = np.where(before, rep_c[cost], 0.0).sum(axis=1)
-    cw, rw, collision = _weights(critics, critic, scn.T)
-    if critic == "obstacles":
-        costs = np.where(collided, collision, cw * crit) + rw * rep
-    else:
-        costs = np.where(collided, collision, rw * rep)
+    costs, collided, first = _rollout_costs(collide_c[cost], crit_c[cost], rep_c[cost], critics, critic, scn.T)
     reached = np.arange(scn.T)[None, :] <= first[:, None]
     return dict(x=x, y=y, costs=costs, collided=collided, reached=reached,
                 non_colliding=int((~collided).sum()), fail_flag=int(collided.all()))
