@@ -1,14 +1,10 @@
-// smpc_api.cpp — host side of the C-ABI declared in include/smpc.h.
-//
-// Owns device memory, the per-tick upload block and the launch sequence; does
-// the O(P) host work the reference's critics do once per tick (goal-distance
-// gates, path validity, cumulative path lengths, the per-candidate PathAlign /
-// PathFollow tables) and the 256-entry Obstacles lookup table.  All [B,T] work
-// is in smpc_kernels.hip.  There is no CPU fallback: without a HIP device
-// smpc_create() fails.
+// smpc_api.cpp — host side of the C-ABI declared in include/smpc.h: the context's lifecycle
+// (smpc_create, free_ctx), the setters, the costmap, the launch helpers the tick drivers share,
+// fetch_out and the single-GPU tick (smpc_optimize).  The rest of the host side by topic: smpc_ctx.h
+// lists the files.  All [B,T] work is in the .hip files.  There is no CPU fallback: without a HIP
+// device smpc_create() fails.
 
 #include "smpc_ctx.h"
-#include "../../include/smpc_debug.h"   // the developer entry points defined below
 
 #include <emmintrin.h>
 
@@ -29,7 +25,7 @@ int fail(smpc_ctx* c, int code, const std::string& msg)
 int wait_map_upload(smpc_ctx* c)
 {
   if (!c->map_pending) return SMPC_OK;
-  HIPCK(c, hipEventSynchronize(c->ev_map));
+  HIPCK(c, hipEventSynchronize(c->ev_map.get()));
   c->map_pending = false;
   return SMPC_OK;
 }
@@ -49,7 +45,7 @@ void bar_copy(void* dev_dst, const void* host_src, size_t n)
 void bar_flush(const smpc_ctx* c)
 {
   // one posted MMIO write, ordered behind the drained stores and in front of the doorbell
-  if (c->hdp_flush) *c->hdp_flush = 1u;
+  if (c->tick.hdp_flush) *c->tick.hdp_flush = 1u;
 }
 
 // HDP_MEM_FLUSH_CNTL of HIP device `dev` (matched by PCI location), through the HSA runtime the
@@ -94,206 +90,16 @@ void free_ctx(smpc_ctx* c)
 {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  for (float* p : {c->d_tvx, c->d_nvx, c->d_nvy, c->d_nwz, c->d_costs[0], c->d_costs[1], c->d_traj[0],
-         c->d_traj[1], c->d_traj[2], c->d_partials, c->d_tuple, c->d_out, c->d_u_iter, c->d_furthest})
-    if (p) (void)hipFree(p);
-  if (c->d_stats || c->d_stats_part) {
-    (void)hipStreamSynchronize(c->stream);   // (a breakdown abandoned on an error may still be writing them)
-    if (c->d_stats) (void)hipFree(c->d_stats);
-    if (c->d_stats_part) (void)hipFree(c->d_stats_part);
-  }
-  for (hipEvent_t e : c->ev_stats) if (e) (void)hipEventDestroy(e);
-  if (c->l_gm || c->l_rm[0] || c->l_rm[1] || c->l_rm[2]) {
-    (void)hipStreamSynchronize(c->stream);
-    for (float* p : {c->l_gm, c->l_rm[0], c->l_rm[1], c->l_rm[2]})
-      if (p) (void)hipFree(p);
-  }
-  for (hipEvent_t e : c->ev_lim) if (e) (void)hipEventDestroy(e);
-  if (c->mov_tab_tk || c->mov_stage || c->mov_m || c->mov_hit || c->mov_stats_seed) {
-    (void)hipStreamSynchronize(c->stream);
-    if (c->mov_up_recorded) (void)hipEventSynchronize(c->ev_mov_up);
-    for (void* p : {static_cast<void*>(c->mov_tab_tk), static_cast<void*>(c->mov_m), static_cast<void*>(c->mov_hit),
-                    static_cast<void*>(c->mov_stats_seed)})
-      if (p) (void)hipFree(p);
-    if (c->mov_stage) (void)hipHostFree(c->mov_stage);
-  }
-  if (c->ev_mov_up) (void)hipEventDestroy(c->ev_mov_up);
-  for (hipEvent_t e : c->ev_mov) if (e) (void)hipEventDestroy(e);
-  if (c->fill_stream) {
-    (void)hipStreamSynchronize(c->fill_stream);
-    (void)hipStreamDestroy(c->fill_stream);
-  }
-  if (c->ev_fill) (void)hipEventDestroy(c->ev_fill);
-  for (float* p : {c->b_tvx, c->b_nvx, c->b_nvy, c->b_nwz})
-    if (p) (void)hipFree(p);
-  if (c->d_map) (void)hipFree(c->d_map);
-  if (c->d_timeline) (void)hipFree(c->d_timeline);
-  if (c->map.cells) (void)hipHostFree(c->map.cells);
-  if (c->ev_map) (void)hipEventDestroy(c->ev_map);
-  if (c->d_tick && !c->defer_upload) (void)hipFree(c->d_tick);
-  if (c->d_lut) (void)hipFree(c->d_lut);
-  if (c->d_lut_fp) (void)hipFree(c->d_lut_fp);
-  if (c->h_lut_fp) (void)hipHostFree(c->h_lut_fp);
-  if (c->h_lut) (void)hipHostFree(c->h_lut);
-  if (c->h_tick && !c->defer_upload) (void)hipHostFree(c->h_tick);   // (a group's slot is not ours)
-  if (c->h_out) (void)hipHostFree(c->h_out);
-  if (c->comm && rccl()) (void)rccl()->CommDestroy(c->comm);
-  if (c->d_all) (void)hipFree(c->d_all);
-  for (uint32_t r = 0; r < c->p2p.world; ++r)
-    if (r != c->p2p.rank && c->p2p.peer[r]) (void)hipIpcCloseMemHandle(c->p2p.peer[r]);
-  if (c->p2p_mailbox) (void)hipFree(c->p2p_mailbox);
-  if (c->ev0) (void)hipEventDestroy(c->ev0);
-  if (c->ev1) (void)hipEventDestroy(c->ev1);
-  for (hipEvent_t e : c->evp) if (e) (void)hipEventDestroy(e);
-  if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-  delete c;
-}
-
-void begin_limit_iteration(smpc_ctx* c, const float* u_dev)
-{
-  c->lim_u_dev = u_dev;
-  if (++c->lim_iter == 0) ++c->lim_iter;
-}
-
-// The limiter's launch for one layout.  The buffers of that layout are allocated here, at the
-// first tick that reads it.
-static int limit_noise(smpc_ctx* c, bool group_major)
-{
-  const uint32_t B = c->cfg.batch_size, T = c->cfg.time_steps;
-  SmpcLimitArgs a{};
-  if (group_major) {
-    const size_t ngm = SMPC_GM_ELEMS(B, T);
-    if (!c->l_gm) {
-      HIPCK(c, hipMalloc(&c->l_gm, 3 * ngm * sizeof(float)));
-      HIPCK(c, hipMemsetAsync(c->l_gm, 0, 3 * ngm * sizeof(float), c->stream));   // (vy of a non-holonomic model stays zero)
-    }
-    a.src[0] = c->d_tvx; a.src[1] = c->holonomic ? c->d_tvy : nullptr; a.src[2] = c->d_twz;
-    a.dst[0] = c->l_gm; a.dst[1] = c->holonomic ? c->l_gm + ngm : nullptr; a.dst[2] = c->l_gm + 2 * ngm;
-  } else {
-    const int rc = ensure_row_major(c);
-    if (rc != SMPC_OK) return rc;
-    for (int k = 0; k < 3; ++k)
-      if (!c->l_rm[k] && (k != 1 || c->holonomic)) HIPCK(c, hipMalloc(&c->l_rm[k], static_cast<size_t>(B) * T * sizeof(float)));
-    a.src[0] = c->d_nvx; a.src[1] = c->holonomic ? c->d_nvy : nullptr; a.src[2] = c->d_nwz;
-    for (int k = 0; k < 3; ++k) a.dst[k] = c->l_rm[k];
-  }
-  a.B = B; a.T = T;
-  a.u_dev = c->lim_u_dev;
-  if (!a.u_dev) {
-    // iteration 0: the control sequence as prepare_tick put it into the tick block's host copy
-    // (vy row zeroed for a non-holonomic model), whichever way the block itself travels
-    const TickLayout tl = tick_layout(T, std::max(c->P, 1u));
-    memcpy(a.u_arg, c->h_tick + tl.u, 3 * T * sizeof(float));
-  }
-  a.v0[0] = c->dev.svx; a.v0[1] = c->dev.svy; a.v0[2] = c->dev.swz;
-  const float dt = c->cfg.model_dt;
-  a.dhi[0] = dt * c->lim[0]; a.dhi[1] = dt * c->lim[2]; a.dhi[2] = dt * c->lim[3];
-  a.dlo[0] = dt * c->lim[1]; a.dlo[1] = -a.dhi[1]; a.dlo[2] = -a.dhi[2];
-  const bool prof = (c->cfg.flags & SMPC_FLAG_PROFILE) != 0;
-  if (prof) {
-    for (hipEvent_t& e : c->ev_lim)
-      if (!e) HIPCK(c, hipEventCreate(&e));
-    HIPCK(c, hipEventRecord(c->ev_lim[0], c->stream));
-  }
-  c->launched = true;
-  HIPCK(c, smpc_launch_limit_noise(a, group_major, c->stream));
-  if (prof) HIPCK(c, hipEventRecord(c->ev_lim[1], c->stream));
-  return SMPC_OK;
-}
-
-int use_limited_noise(smpc_ctx* c, SmpcDev& d, bool group_major)
-{
-  if (!c->lim_on) return SMPC_OK;
-  uint32_t& have = group_major ? c->lim_gm_iter : c->lim_rm_iter;
-  if (have != c->lim_iter || c->lim_iter == 0) {
-    if (c->lim_iter == 0) begin_limit_iteration(c, nullptr);
-    const int rc = limit_noise(c, group_major);
-    if (rc != SMPC_OK) return rc;
-    have = c->lim_iter;
-  }
-  if (group_major) {
-    const size_t ngm = SMPC_GM_ELEMS(c->cfg.batch_size, c->cfg.time_steps);
-    d.tvx = c->l_gm; d.tvy = c->l_gm + ngm; d.twz = c->l_gm + 2 * ngm;
-  } else {
-    d.nvx = c->l_rm[0]; d.nwz = c->l_rm[2];
-    if (c->holonomic) d.nvy = c->l_rm[1];   // (else: the stored zeros, untouched)
-  }
-  return SMPC_OK;
-}
-
-// The moving-obstacle kernel's launch for the pass about to go out with d: the noise d points at, in
-// the layout that pass reads; m into `seed` (added to its content when d accumulates).
-static int moving_cost(smpc_ctx* c, const SmpcDev& d, bool group_major, float* seed, float* m_out, uint8_t* hit_out)
-{
-  const uint32_t T = c->cfg.time_steps;
-  SmpcMovingArgs a{};
-  if (group_major) {
-    a.n[0] = d.tvx; a.n[1] = c->holonomic ? d.tvy : nullptr; a.n[2] = d.twz;
-    a.tab = c->mov_tab_tk;
-  } else {
-    const int rc = ensure_row_major(c);
-    if (rc != SMPC_OK) return rc;
-    a.n[0] = d.nvx; a.n[1] = c->holonomic ? d.nvy : nullptr; a.n[2] = d.nwz;
-    a.tab = c->mov_tab_kt;
-  }
-  if (c->mov_up_recorded && c->mov_up_stream != c->stream) {
-    // the table went up on the stream the ctx had then: this one waits for it (once)
-    HIPCK(c, hipStreamWaitEvent(c->stream, c->ev_mov_up, 0));
-    c->mov_up_stream = c->stream;
-  }
-  a.disc = c->mov_disc;
-  a.seed = seed; a.m_out = m_out; a.hit_out = hit_out;
-  a.B = c->cfg.batch_size; a.T = T; a.K = c->mov_K;
-  a.add = (d.flags & SD_ACCUMULATE) ? 1u : 0u;
-  a.u_dev = c->lim_u_dev;   // the iteration's u: as the limiter takes it
-  if (!a.u_dev) {
-    const TickLayout tl = tick_layout(T, std::max(c->P, 1u));
-    memcpy(a.u_arg, c->h_tick + tl.u, 3 * T * sizeof(float));
-  }
-  a.x0 = d.x0; a.y0 = d.y0; a.yaw0 = d.yaw0; a.cos0 = d.cos0; a.sin0 = d.sin0; a.dt = d.dt;
-  a.v0[0] = d.svx; a.v0[1] = d.svy; a.v0[2] = d.swz;
-  a.collision_cost = c->mov_par.collision_cost;
-  a.repulsion_weight = c->mov_par.repulsion_weight;
-  a.margin = c->mov_par.margin;
-  const bool prof = (c->cfg.flags & SMPC_FLAG_PROFILE) != 0;
-  if (prof) {
-    for (hipEvent_t& e : c->ev_mov)
-      if (!e) HIPCK(c, hipEventCreate(&e));
-    HIPCK(c, hipEventRecord(c->ev_mov[0], c->stream));
-  }
-  c->launched = true;
-  HIPCK(c, smpc_launch_moving_cost(a, group_major, c->stream));
-  if (prof) HIPCK(c, hipEventRecord(c->ev_mov[1], c->stream));
-  return SMPC_OK;
-}
-
-int use_moving_seed(smpc_ctx* c, SmpcDev& d, bool group_major)
-{
-  if (c->mov_K == 0) return SMPC_OK;
-  if (c->fail_in) {
-    c->mov_scored = false;   // this tick scores nothing: there is no "last tick's m" behind it
-    return SMPC_OK;
-  }
-  if (c->lim_iter == 0) begin_limit_iteration(c, nullptr);
-  if (c->mov_iter != c->lim_iter) {
-    const int rc = moving_cost(c, d, group_major, const_cast<float*>(d.costs_prev), c->mov_m, c->mov_hit);
-    if (rc != SMPC_OK) return rc;
-    c->mov_iter = c->lim_iter;
-    c->mov_scored = true;
-  }
-  d.flags |= SD_COST_SEED;
-  return SMPC_OK;
-}
-
-int seed_own_costs(smpc_ctx* c, SmpcDev& d)
-{
-  if (c->mov_K == 0 || c->fail_in) return SMPC_OK;
-  if (!c->mov_stats_seed) HIPCK(c, hipMalloc(&c->mov_stats_seed, c->cfg.batch_size * sizeof(float)));
-  const int rc = moving_cost(c, d, false, c->mov_stats_seed, nullptr, nullptr);
-  if (rc != SMPC_OK) return rc;
-  d.costs_prev = c->mov_stats_seed;
-  d.flags |= SD_COST_SEED;
-  return SMPC_OK;
+  // what may still be reading or writing the buffers: the ticks' stream (a breakdown or a tick
+  // abandoned on an error), the background draw, and the last moving-obstacle upload
+  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  if (c->noise.fill_stream) (void)hipStreamSynchronize(c->noise.fill_stream.get());
+  if (c->mov.up_recorded) (void)hipEventSynchronize(c->mov.ev_up.get());
+  // the two links to other processes, which are not plain frees
+  for (uint32_t r = 0; r < c->shard.p2p.world; ++r)
+    if (r != c->shard.p2p.rank && c->shard.p2p.peer[r]) (void)hipIpcCloseMemHandle(c->shard.p2p.peer[r]);
+  if (c->shard.comm && rccl()) (void)rccl()->CommDestroy(c->shard.comm);
+  delete c;   // every buffer, event and stream: its holder's destructor (smpc_own.h)
 }
 
 int launch_furthest(smpc_ctx* c, float* d_furthest)
@@ -359,12 +165,12 @@ void fill_score_args(smpc_ctx* c, uint32_t flags, const float* u_dev, const floa
   }
   d.d_furthest = d_furthest;
   d.furthest_hint = furthest_hint;
-  d.costs = c->d_costs[c->costs_cur];
-  d.costs_prev = c->d_costs[c->costs_cur ^ 1];
+  d.costs = c->d_costs[c->costs_cur].get();
+  d.costs_prev = c->d_costs[c->costs_cur ^ 1].get();
   fin = SmpcFinal{};
   fin.enabled = finish ? 1 : 0;
   fin.vx_max = c->c_vx_max; fin.vx_min = c->c_vx_min; fin.vy_max = c->c_vy; fin.wz_max = c->c_wz;
-  fin.u_dev = c->d_out; fin.u_host = c->h_out_dev; fin.furthest_used = finish_furthest;
+  fin.u_dev = c->d_out.get(); fin.u_host = c->h_out_dev; fin.furthest_used = finish_furthest;
   if (finish && c->knobs.poll) {
     fin.done_counter = scratch_word(c, SMPC_SCRATCH_REDUCE_COUNTER);
     fin.seq = next_seq(c);
@@ -424,7 +230,7 @@ int launch_score(smpc_ctx* c, uint32_t flags, const float* u_dev, const float* d
     if (rc != SMPC_OK) return rc;
   }
   const bool prof = (c->cfg.flags & SMPC_FLAG_PROFILE) && c->evp_used + 2 <= 8;
-  if (prof) HIPCK(c, hipEventRecord(c->evp[c->evp_used], c->stream));
+  if (prof) HIPCK(c, hipEventRecord(c->evp[c->evp_used].get(), c->stream));
   const uint32_t nblk = pass.geom->grid;
   // The block that finishes last reduces the partials inside the scoring launch (smpc_tail.h);
   // larger grids, and launches whose LDS was not sized for it, take the separate reduction.
@@ -439,7 +245,7 @@ int launch_score(smpc_ctx* c, uint32_t flags, const float* u_dev, const float* d
     // the tail's "gave up waiting" mark of an earlier tick must not fail this one (no launch of
     // this ctx is in flight here: every tick ends with fetch_out); the mailbox exchange's mark
     // in the same word is sticky by design and stays
-    float& mark = c->h_out[SMPC_RESULT_AT(d.T) + SMPC_R_MARK];
+    float& mark = c->h_out.get()[SMPC_RESULT_AT(d.T) + SMPC_R_MARK];
     if (mark == SMPC_MARK_TAIL_LATE) mark = SMPC_MARK_NONE;
     d.tail = 1;
     d.tail_counter = scratch_word(c, SMPC_SCRATCH_TAIL_COUNTER);
@@ -458,12 +264,12 @@ int launch_score(smpc_ctx* c, uint32_t flags, const float* u_dev, const float* d
     HIPCK(c, wave_launch(static_cast<const WaveInst*>(pass.inst), d, pass.geom->lds, nblk, pass.geom->block, c->stream));
   }
   if (prof) {
-    HIPCK(c, hipEventRecord(c->evp[c->evp_used + 1], c->stream));
+    HIPCK(c, hipEventRecord(c->evp[c->evp_used + 1].get(), c->stream));
     c->evp_used += 2;
   }
-  if (!tail) HIPCK(c, smpc_launch_reduce(c->d_partials, nblk, d.T, d.neg_inv_temp, d_tuple, fin, c->stream));
+  if (!tail) HIPCK(c, smpc_launch_reduce(c->d_partials.get(), nblk, d.T, d.neg_inv_temp, d_tuple, fin, c->stream));
   if (finish && c->acker_r >= 0.f)
-    HIPCK(c, smpc_launch_ackermann(c->d_out, c->h_out_dev, d.T, c->acker_r, c->acker_seq, c->stream));
+    HIPCK(c, smpc_launch_ackermann(c->d_out.get(), c->h_out_dev, d.T, c->acker_r, c->acker_seq, c->stream));
   c->passes++;
   return SMPC_OK;
 }
@@ -478,9 +284,9 @@ int launch_combine(smpc_ctx* c, const float* d_tuples, uint32_t n, const float* 
   }
   const bool acker = c->acker_r >= 0.f;
   HIPCK(c, smpc_launch_combine(d_tuples, n, T, c->dev.neg_inv_temp, c->c_vx_max, c->c_vx_min,
-                               c->c_vy, c->c_wz, c->d_out, c->d_out + SMPC_RESULT_AT(T), d_furthest_used,
+                               c->c_vy, c->c_wz, c->d_out.get(), c->d_out.get() + SMPC_RESULT_AT(T), d_furthest_used,
                                c->h_out_dev, acker ? 0u : seq, c->stream));
-  if (acker) HIPCK(c, smpc_launch_ackermann(c->d_out, c->h_out_dev, T, c->acker_r, seq, c->stream));
+  if (acker) HIPCK(c, smpc_launch_ackermann(c->d_out.get(), c->h_out_dev, T, c->acker_r, seq, c->stream));
   return SMPC_OK;
 }
 
@@ -490,11 +296,11 @@ void store_control_sequence(const smpc_ctx* c, float* u_inout)
 {
   const uint32_t T = c->cfg.time_steps;
   if (c->holonomic) {
-    memcpy(u_inout, c->h_out, 3 * T * sizeof(float));
+    memcpy(u_inout, c->h_out.get(), 3 * T * sizeof(float));
     return;
   }
-  memcpy(u_inout, c->h_out, T * sizeof(float));
-  memcpy(u_inout + 2 * T, c->h_out + 2 * T, T * sizeof(float));
+  memcpy(u_inout, c->h_out.get(), T * sizeof(float));
+  memcpy(u_inout + 2 * T, c->h_out.get() + 2 * T, T * sizeof(float));
 }
 
 // the pass's echo of the tick block's number (SmpcDev::canary): anything but this tick's number
@@ -502,14 +308,14 @@ void store_control_sequence(const smpc_ctx* c, float* u_inout)
 static int check_canary(smpc_ctx* c)
 {
   c->launched = false;
-  if (!c->canary_expect) return SMPC_OK;
-  const uint32_t got = reinterpret_cast<const volatile uint32_t*>(c->h_out)[SMPC_RESULT_AT(c->cfg.time_steps) + SMPC_R_CANARY];
-  if (got == c->canary_expect) return SMPC_OK;
+  if (!c->tick.canary_expect) return SMPC_OK;
+  const uint32_t got = reinterpret_cast<const volatile uint32_t*>(c->h_out.get())[SMPC_RESULT_AT(c->cfg.time_steps) + SMPC_R_CANARY];
+  if (got == c->tick.canary_expect) return SMPC_OK;
   char msg[200];
   snprintf(msg, sizeof(msg), "the scoring pass read tick block %u, not %u: the per-tick upload did not reach the "
-           "device in time (CPU stores through the BAR: %s); SMPC_NO_BAR_TICK=1 selects the copy", got, c->canary_expect,
-           c->bar_tick ? "on" : "off");
-  c->bar_tick = false;   // later ticks of this ctx take the copy
+           "device in time (CPU stores through the BAR: %s); SMPC_NO_BAR_TICK=1 selects the copy", got, c->tick.canary_expect,
+           c->tick.bar_tick ? "on" : "off");
+  c->tick.bar_tick = false;   // later ticks of this ctx take the copy
   return fail(c, SMPC_ERR_DEVICE, msg);
 }
 
@@ -520,7 +326,7 @@ int fetch_out(smpc_ctx* c)
   // runtime's stream wait), and fall back to the stream wait, which also surfaces errors.
   if (c->poll_seq) {
     const volatile uint32_t* flag =
-      reinterpret_cast<const volatile uint32_t*>(c->h_out + SMPC_RESULT_AT(c->cfg.time_steps) + SMPC_R_DONE);
+      reinterpret_cast<const volatile uint32_t*>(c->h_out.get() + SMPC_RESULT_AT(c->cfg.time_steps) + SMPC_R_DONE);
     const uint32_t want = c->poll_seq;
     c->poll_seq = 0;
     const uint32_t nwords = c->poll_words;   // > 0: one word per reducing block, from flag[1] on (SMPC_R_BLOCK_DONE)
@@ -553,7 +359,7 @@ float profile_pass_ms(smpc_ctx* c)
   uint32_t n = 0;
   for (uint32_t i = 0; i + 1 < c->evp_used; i += 2) {
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, c->evp[i], c->evp[i + 1]) == hipSuccess) {
+    if (hipEventElapsedTime(&ms, c->evp[i].get(), c->evp[i + 1].get()) == hipSuccess) {
       sum += ms;
       n++;
     }
@@ -576,9 +382,9 @@ int fill_tick_out(smpc_ctx* c, smpc_tick_out* out, bool fail_flag, bool furthest
   out->passes = c->passes;
   if (device_ms && (c->cfg.flags & SMPC_FLAG_PROFILE)) {
     // the polled flag can beat the event's completion signal by a few microseconds
-    HIPCK(c, hipEventSynchronize(c->ev1));
+    HIPCK(c, hipEventSynchronize(c->ev1.get()));
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) out->device_ms = ms;
+    if (hipEventElapsedTime(&ms, c->ev0.get(), c->ev1.get()) == hipSuccess) out->device_ms = ms;
   }
   out->score_pass_ms = profile_pass_ms(c);
   out->pass_kind = c->last_pass_kind;
@@ -600,141 +406,6 @@ uint32_t scoring_flags(const smpc_ctx* c, bool fail_sticky)
   // CriticManager::evalTrajectoriesScores breaks on fail_flag (critic_manager.cpp:70-73)
   const uint32_t keep = SD_STORE_TRAJ | SD_TRACK_UNKNOWN;
   return fail_sticky ? (c->gate_flags & keep) : c->gate_flags;
-}
-
-// keep the group-major copies (smpc_dev.h: SMPC_GM_INDEX) in step with the [B,T] tensors
-int update_time_major(smpc_ctx* c)
-{
-  if (!c->use_tpr) return SMPC_OK;
-  const uint32_t B = c->cfg.batch_size, T = c->cfg.time_steps;
-  HIPCK(c, smpc_launch_relayout(c->d_nvx, c->d_tvx, B, T, true, c->stream));
-  HIPCK(c, smpc_launch_relayout(c->d_nvy, c->d_tvy, B, T, true, c->stream));
-  HIPCK(c, smpc_launch_relayout(c->d_nwz, c->d_twz, B, T, true, c->stream));
-  return SMPC_OK;
-}
-
-// the [B,T] tensors (wave-per-rollout pass, smpc_get_noise) from the group-major copy, when a
-// device-RNG draw filled only that one
-int ensure_row_major(smpc_ctx* c)
-{
-  if (c->rm_valid) return SMPC_OK;
-  const uint32_t B = c->cfg.batch_size, T = c->cfg.time_steps;
-  HIPCK(c, smpc_launch_relayout(c->d_tvx, c->d_nvx, B, T, false, c->stream));
-  if (c->holonomic) HIPCK(c, smpc_launch_relayout(c->d_tvy, c->d_nvy, B, T, false, c->stream));
-  HIPCK(c, smpc_launch_relayout(c->d_twz, c->d_nwz, B, T, false, c->stream));
-  c->rm_valid = true;
-  return SMPC_OK;
-}
-
-// One epoch of the device RNG into the given set of tensors, on stream st (no wait).
-// rm_valid_out: whether the [B,T] tensors of the set hold the draw (else only the group-major ones)
-static int launch_draw(smpc_ctx* c, float* nvx, float* nvy, float* nwz, float* tvx, float* tvy, float* twz,
-                       hipStream_t st, bool* rm_valid_out)
-{
-  const uint64_t n = static_cast<uint64_t>(c->cfg.batch_size) * c->cfg.time_steps;
-  const uint64_t base = c->cfg.shard_offset * c->cfg.time_steps;
-  const uint32_t B = c->cfg.batch_size, T = c->cfg.time_steps;
-  if (c->use_tpr && (T & 3u) == 0 && !getenv("SMPC_NO_FUSED_FILL")) {
-    // lane-per-rollout contexts: draw straight into the group-major layout that pass reads —
-    // one write of the noise instead of a write, a read and a second write (fill + transpose);
-    // the [B,T] copy is made only if something asks for it (ensure_row_major)
-    HIPCK(c, smpc_launch_fill_noise_tm(tvx, B, T, base, c->seed, 0, c->epoch, c->cfg.vx_std, st));
-    HIPCK(c, smpc_launch_fill_noise_tm(twz, B, T, base, c->seed, 1, c->epoch, c->cfg.wz_std, st));
-    if (c->holonomic)
-      HIPCK(c, smpc_launch_fill_noise_tm(tvy, B, T, base, c->seed, 2, c->epoch, c->cfg.vy_std, st));
-    else
-      HIPCK(c, hipMemsetAsync(tvy, 0, SMPC_GM_ELEMS(B, T) * sizeof(float), st));
-    *rm_valid_out = false;
-    return SMPC_OK;
-  }
-  // draw order vx, wz, vy (noise_generator.cpp:107-122)
-  HIPCK(c, smpc_launch_fill_noise(nvx, n, base, c->seed, 0, c->epoch, c->cfg.vx_std, st));
-  HIPCK(c, smpc_launch_fill_noise(nwz, n, base, c->seed, 1, c->epoch, c->cfg.wz_std, st));
-  // noises_vy_ keeps its zeros for a non-holonomic model (noise_generator.cpp:117-121)
-  if (c->holonomic) HIPCK(c, smpc_launch_fill_noise(nvy, n, base, c->seed, 2, c->epoch, c->cfg.vy_std, st));
-  if (c->use_tpr) {
-    HIPCK(c, smpc_launch_relayout(nvx, tvx, B, T, true, st));
-    HIPCK(c, smpc_launch_relayout(nvy, tvy, B, T, true, st));
-    HIPCK(c, smpc_launch_relayout(nwz, twz, B, T, true, st));
-  }
-  *rm_valid_out = true;
-  return SMPC_OK;
-}
-
-// a draw requested with smpc_redraw_noise_async that no tick has taken yet is dropped (whoever
-// calls this is about to overwrite the noise anyway)
-int cancel_redraw(smpc_ctx* c)
-{
-  if (!c->redraw_pending) return SMPC_OK;
-  HIPCK(c, hipEventSynchronize(c->ev_fill));
-  c->redraw_pending = false;
-  return SMPC_OK;
-}
-
-// The tick about to be prepared takes the noise drawn in the background, if there is any: its
-// stream waits for the draw ON THE DEVICE and the two sets of tensors change places.
-int absorb_redraw(smpc_ctx* c)
-{
-  if (!c->redraw_pending) return SMPC_OK;
-  HIPCK(c, hipStreamWaitEvent(c->stream, c->ev_fill, 0));
-  std::swap(c->d_nvx, c->b_nvx);
-  std::swap(c->d_nvy, c->b_nvy);
-  std::swap(c->d_nwz, c->b_nwz);
-  std::swap(c->d_tvx, c->b_tvx);
-  std::swap(c->d_tvy, c->b_tvy);
-  std::swap(c->d_twz, c->b_twz);
-  c->rm_valid = c->redraw_rm_valid;
-  c->redraw_pending = false;
-  c->noise_gen++;
-  return SMPC_OK;
-}
-
-int draw_noise(smpc_ctx* c)
-{
-  int rc = cancel_redraw(c);
-  if (rc != SMPC_OK) return rc;
-  bool rm = true;
-  rc = launch_draw(c, c->d_nvx, c->d_nvy, c->d_nwz, c->d_tvx, c->d_tvy, c->d_twz, c->stream, &rm);
-  if (rc != SMPC_OK) return rc;
-  HIPCK(c, hipStreamSynchronize(c->stream));
-  c->have_noise = true;
-  c->rm_valid = rm;
-  c->noise_gen++;
-  return SMPC_OK;
-}
-
-// NoiseGenerator::generateNextNoises as the reference runs it (noise_generator.cpp:54-63,97-105:
-// a thread draws the next tensors while the optimizer goes on): the next epoch goes into the
-// OTHER set of tensors on a stream of its own, and the call returns at once.
-int redraw_async(smpc_ctx* c)
-{
-  if (c->redraw_pending) return SMPC_OK;   // (the reference's signal is not counted either)
-  const size_t n = static_cast<size_t>(c->cfg.batch_size) * c->cfg.time_steps * sizeof(float);
-  if (!c->fill_stream) {
-    HIPCK(c, hipStreamCreateWithFlags(&c->fill_stream, hipStreamNonBlocking));
-    HIPCK(c, hipEventCreateWithFlags(&c->ev_fill, hipEventDisableTiming));
-  }
-  if (c->use_tpr && !c->b_tvx) {
-    const size_t ngm = SMPC_GM_ELEMS(c->cfg.batch_size, c->cfg.time_steps) * sizeof(float);
-    HIPCK(c, hipMalloc(&c->b_tvx, 3 * ngm));
-    HIPCK(c, hipMemset(c->b_tvx, 0, 3 * ngm));   // (the padding steps of a ragged horizon: zeros)
-    c->b_tvy = c->b_tvx + ngm / sizeof(float);
-    c->b_twz = c->b_tvy + ngm / sizeof(float);
-  }
-  if (!c->b_nvx) {
-    HIPCK(c, hipMalloc(&c->b_nvx, n));
-    HIPCK(c, hipMalloc(&c->b_nvy, n));
-    HIPCK(c, hipMalloc(&c->b_nwz, n));
-    if (!c->holonomic) HIPCK(c, hipMemset(c->b_nvy, 0, n));
-  }
-  c->epoch++;
-  bool rm = true;
-  const int rc = launch_draw(c, c->b_nvx, c->b_nvy, c->b_nwz, c->b_tvx, c->b_tvy, c->b_twz, c->fill_stream, &rm);
-  if (rc != SMPC_OK) return rc;
-  HIPCK(c, hipEventRecord(c->ev_fill, c->fill_stream));
-  c->redraw_rm_valid = rm;
-  c->redraw_pending = true;
-  return SMPC_OK;
 }
 
 // the developer knobs (smpc_ctx.h: Knobs), read once per context
@@ -895,33 +566,33 @@ int smpc_create(const smpc_config* cfg, smpc_ctx** out)
   {
     int large_bar = 0;
     if (hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, dev) != hipSuccess) large_bar = 0;
-    c->bar_tick = large_bar != 0 && c->knobs.bar_tick;
-    if (c->bar_tick && c->knobs.hdp_flush) {
-      c->hdp_flush = find_hdp_flush(dev);
+    c->tick.bar_tick = large_bar != 0 && c->knobs.bar_tick;
+    if (c->tick.bar_tick && c->knobs.hdp_flush) {
+      c->tick.hdp_flush = find_hdp_flush(dev);
       // without the device's HDP flush register the stores may sit in the host data path's
       // cache when the pass starts: such a device takes the stream copy (SMPC_NO_HDP_FLUSH=1, an
       // experiment, keeps the stores without the flush; the canary then guards every tick)
-      if (!c->hdp_flush) c->bar_tick = false;
+      if (!c->tick.hdp_flush) c->tick.bar_tick = false;
     }
   }
-  CK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
-  c->stream = c->own_stream;
+  CK(c->own_stream.ensure(hipStreamNonBlocking));
+  c->stream = c->own_stream.get();
   if (getenv("SMPC_LANE_TIMELINE")) {
     static_assert(SMPC_TAIL_STAMPS_AT == 8192 + kMaxGrid * 8, "the tail's stamps sit behind the lane pass's");
-    CK(hipMalloc(&c->d_timeline, (SMPC_SCAN_COUNT_AT + kMaxGrid * 8) * sizeof(unsigned long long)));
-    CK(hipMemset(c->d_timeline, 0, (SMPC_SCAN_COUNT_AT + kMaxGrid * 8) * sizeof(unsigned long long)));
+    CK(c->d_timeline.ensure(SMPC_SCAN_COUNT_AT + kMaxGrid * 8));
+    CK(hipMemset(c->d_timeline.get(), 0, (SMPC_SCAN_COUNT_AT + kMaxGrid * 8) * sizeof(unsigned long long)));
   }
-  CK(hipEventCreate(&c->ev0));
-  CK(hipEventCreateWithFlags(&c->ev_map, hipEventDisableTiming));
-  CK(hipEventCreate(&c->ev1));
-  for (auto& e : c->evp) CK(hipEventCreate(&e));
+  CK(c->ev0.ensure());
+  CK(c->ev_map.ensure(hipEventDisableTiming));
+  CK(c->ev1.ensure());
+  for (Event& e : c->evp) CK(e.ensure());
   const uint32_t T = cfg->time_steps;
   c->R = T <= 64 ? 1 : (T <= 128 ? 2 : 4);
-  const size_t n = static_cast<size_t>(cfg->batch_size) * T * sizeof(float);
-  CK(hipMalloc(&c->d_nvx, n));
-  CK(hipMalloc(&c->d_nvy, n));
-  if (!c->holonomic) CK(hipMemset(c->d_nvy, 0, n));   // noises_vy_ (noise_generator.cpp:76-91)
-  CK(hipMalloc(&c->d_nwz, n));
+  const size_t BT = static_cast<size_t>(cfg->batch_size) * T, n = BT * sizeof(float);
+  CK(c->noise.cur.nvx.ensure(BT));
+  CK(c->noise.cur.nvy.ensure(BT));
+  if (!c->holonomic) CK(hipMemset(c->noise.cur.nvy.get(), 0, n));   // noises_vy_ (noise_generator.cpp:76-91)
+  CK(c->noise.cur.nwz.ensure(BT));
   {
     // which streaming pass: a wave per rollout (latency, small batches) or a lane per
     // rollout (throughput, large batches); SMPC_PASS=wave|lane overrides for experiments
@@ -945,48 +616,49 @@ int smpc_create(const smpc_config* cfg, smpc_ctx** out)
     // the group-major copies (smpc_dev.h: SMPC_GM_INDEX): the batch padded to whole groups of 64
     const size_t ngm = SMPC_GM_ELEMS(cfg->batch_size, T) * sizeof(float);
     if (3ull * ngm >= (1ull << 32)) tpr = false;   // its buffer descriptor spans the three noise tensors
-    c->use_tpr = tpr;
+    c->noise.use_tpr = tpr;
     if (tpr) {
       // back to back: the lane pass addresses the three through one buffer descriptor
-      CK(hipMalloc(&c->d_tvx, 3 * ngm));
-      c->d_tvy = c->d_tvx + ngm / sizeof(float);
-      c->d_twz = c->d_tvy + ngm / sizeof(float);
-      CK(hipMemset(c->d_tvx, 0, 3 * ngm));   // the padding steps of a ragged horizon, and vy of a non-holonomic model
+      CK(c->noise.cur.tvx.ensure(3 * ngm / sizeof(float)));
+      c->noise.cur.tvy = c->noise.cur.tvx.get() + ngm / sizeof(float);
+      c->noise.cur.twz = c->noise.cur.tvy + ngm / sizeof(float);
+      CK(hipMemset(c->noise.cur.tvx.get(), 0, 3 * ngm));   // the padding steps of a ragged horizon, and vy of a non-holonomic model
       CK(lane_set_lds_limit(static_cast<int>(kLdsPerCu)));
       CK(split_set_lds_limit(static_cast<int>(kLdsPerCu)));
     }
   }
-  CK(hipMalloc(&c->d_costs[0], cfg->batch_size * sizeof(float)));
-  CK(hipMalloc(&c->d_costs[1], cfg->batch_size * sizeof(float)));
-  CK(hipMemset(c->d_costs[0], 0, cfg->batch_size * sizeof(float)));
-  CK(hipMemset(c->d_costs[1], 0, cfg->batch_size * sizeof(float)));
+  CK(c->d_costs[0].ensure(cfg->batch_size));
+  CK(c->d_costs[1].ensure(cfg->batch_size));
+  CK(hipMemset(c->d_costs[0].get(), 0, cfg->batch_size * sizeof(float)));
+  CK(hipMemset(c->d_costs[1].get(), 0, cfg->batch_size * sizeof(float)));
   if (cfg->flags & SMPC_FLAG_STORE_TRAJECTORIES) {
     for (int i = 0; i < 3; ++i) {
-      CK(hipMalloc(&c->d_traj[i], n));
-      CK(hipMemset(c->d_traj[i], 0, n));
+      CK(c->d_traj[i].ensure(BT));
+      CK(hipMemset(c->d_traj[i].get(), 0, n));
     }
   }
-  c->tick_cap = tick_layout(T, SMPC_MAX_PATH).total;
-  CK(hipMalloc(&c->d_tick, c->tick_cap));
-  CK(hipHostMalloc(&c->h_tick, c->tick_cap, hipHostMallocDefault));
-  CK(hipMalloc(&c->d_lut, 256 * sizeof(SmpcLut)));
-  CK(hipMemset(c->d_lut, 0, 256 * sizeof(SmpcLut)));
-  CK(hipMalloc(&c->d_lut_fp, 512 * sizeof(SmpcLut)));
-  CK(hipMemset(c->d_lut_fp, 0, 512 * sizeof(SmpcLut)));
-  CK(hipHostMalloc(&c->h_lut_fp, 512 * sizeof(SmpcLut), hipHostMallocDefault));
-  CK(hipHostMalloc(&c->h_lut, 256 * sizeof(SmpcLut), hipHostMallocDefault));
+  c->tick.cap = tick_layout(T, SMPC_MAX_PATH).total;
+  CK(c->tick.own_d.ensure(c->tick.cap));
+  CK(c->tick.own_h.ensure(c->tick.cap));
+  c->tick.view_own();
+  CK(c->d_lut.ensure(256));
+  CK(hipMemset(c->d_lut.get(), 0, 256 * sizeof(SmpcLut)));
+  CK(c->d_lut_fp.ensure(512));
+  CK(hipMemset(c->d_lut_fp.get(), 0, 512 * sizeof(SmpcLut)));
+  CK(c->h_lut_fp.ensure(512));
+  CK(c->h_lut.ensure(256));
   const size_t TL = SMPC_TUPLE_HEADER + 3 * static_cast<size_t>(T);
-  CK(hipMalloc(&c->d_partials, (kMaxGrid * TL + 16) * sizeof(float)));   // + the canary's slot (SMPC_CANARY_SLOT)
-  CK(hipMemset(c->d_partials, 0, (kMaxGrid * TL + 16) * sizeof(float)));
-  CK(hipMalloc(&c->d_tuple, TL * sizeof(float)));
-  CK(hipMalloc(&c->d_out, SMPC_RESULT_FLOATS(T) * sizeof(float)));
-  CK(hipMalloc(&c->d_u_iter, 3 * T * sizeof(float)));
+  CK(c->d_partials.ensure(kMaxGrid * TL + 16));   // + the canary's slot (SMPC_CANARY_SLOT)
+  CK(hipMemset(c->d_partials.get(), 0, (kMaxGrid * TL + 16) * sizeof(float)));
+  CK(c->d_tuple.ensure(TL));
+  CK(c->d_out.ensure(SMPC_RESULT_FLOATS(T)));
+  CK(c->d_u_iter.ensure(3 * T));
   // (the mirror ends in kPollWords completion words, one per publishing block: smpc_reduce_blocks(T), at most 25 at T = 256)
-  CK(hipHostMalloc(&c->h_out, SMPC_RESULT_HOST_FLOATS(T) * sizeof(float), hipHostMallocMapped));
-  memset(c->h_out, 0, SMPC_RESULT_HOST_FLOATS(T) * sizeof(float));
-  CK(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->h_out_dev), c->h_out, 0));
-  CK(hipMalloc(&c->d_furthest, SMPC_SCRATCH_WORDS * sizeof(uint32_t)));
-  CK(hipMemset(c->d_furthest, 0, SMPC_SCRATCH_WORDS * sizeof(uint32_t)));
+  CK(c->h_out.ensure(SMPC_RESULT_HOST_FLOATS(T), hipHostMallocMapped));
+  memset(c->h_out.get(), 0, SMPC_RESULT_HOST_FLOATS(T) * sizeof(float));
+  CK(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->h_out_dev), c->h_out.get(), 0));
+  CK(c->d_furthest.ensure(SMPC_SCRATCH_WORDS));
+  CK(hipMemset(c->d_furthest.get(), 0, SMPC_SCRATCH_WORDS * sizeof(uint32_t)));
   CK(wave_set_lds_limit(static_cast<int>(kLdsPerCu)));
   // the memsets above went to the default stream; the ctx works on its own non-blocking one
   CK(hipDeviceSynchronize());
@@ -1005,12 +677,12 @@ int smpc_reset(smpc_ctx* c)
   // NoiseGenerator::reset re-draws (noise_generator.cpp:76-95)
   c->c_vx_max = c->cfg.vx_max; c->c_vx_min = c->cfg.vx_min;
   c->c_vy = c->cfg.vy_max; c->c_wz = c->cfg.wz_max;
-  HIPCK(c, hipMemsetAsync(c->d_costs[0], 0, c->cfg.batch_size * sizeof(float), c->stream));
-  HIPCK(c, hipMemsetAsync(c->d_costs[1], 0, c->cfg.batch_size * sizeof(float), c->stream));
+  HIPCK(c, hipMemsetAsync(c->d_costs[0].get(), 0, c->cfg.batch_size * sizeof(float), c->stream));
+  HIPCK(c, hipMemsetAsync(c->d_costs[1].get(), 0, c->cfg.batch_size * sizeof(float), c->stream));
   c->tick_ready = false;
   c->pred.forget();
-  if (c->rng_mode) {
-    c->epoch++;
+  if (c->noise.rng_mode) {
+    c->noise.epoch++;
     return draw_noise(c);
   }
   HIPCK(c, hipStreamSynchronize(c->stream));
@@ -1021,173 +693,6 @@ int smpc_set_constraints(smpc_ctx* c, float vx_max, float vx_min, float vy_max, 
 {
   if (!c) return SMPC_ERR_INVALID;
   c->c_vx_max = vx_max; c->c_vx_min = vx_min; c->c_vy = vy_max; c->c_wz = wz_max;
-  return SMPC_OK;
-}
-
-int smpc_set_acceleration_limits(smpc_ctx* c, float ax_max, float ax_min, float ay_max, float az_max)
-{
-  if (!c) return SMPC_ERR_INVALID;
-  const bool off = ax_max == 0.f && ax_min == 0.f && ay_max == 0.f && az_max == 0.f;
-  if (!off) {
-    if (!std::isfinite(ax_max) || !std::isfinite(ax_min) || !std::isfinite(ay_max) || !std::isfinite(az_max))
-      return fail(c, SMPC_ERR_INVALID, "acceleration limits must be finite");
-    if (!(ax_max > 0.f) || !(ax_min < 0.f) || !(ay_max > 0.f) || !(az_max > 0.f))
-      return fail(c, SMPC_ERR_INVALID, "acceleration limits: ax_max > 0, ax_min < 0, ay_max > 0, az_max > 0 (all four 0: off)");
-  }
-  c->lim_on = !off;
-  c->lim[0] = ax_max; c->lim[1] = ax_min; c->lim[2] = ay_max; c->lim[3] = az_max;
-  // what the buffers hold was made with the limits as they were: nothing to hand out until a tick ran
-  c->lim_rm_iter = c->lim_gm_iter = 0;
-  return SMPC_OK;
-}
-
-int smpc_get_acceleration_limits(const smpc_ctx* c, float out[4])
-{
-  if (!c || !out) return SMPC_ERR_INVALID;
-  memcpy(out, c->lim, sizeof(c->lim));
-  return SMPC_OK;
-}
-
-int smpc_get_limited_noise(smpc_ctx* c, float* nvx, float* nvy, float* nwz)
-{
-  if (!c) return SMPC_ERR_INVALID;
-  if (!c->lim_on) return fail(c, SMPC_ERR_STATE, "no limited noise: the acceleration limits are off");
-  const bool rm = c->lim_iter != 0 && c->lim_rm_iter == c->lim_iter;
-  const bool gm = c->lim_iter != 0 && c->lim_gm_iter == c->lim_iter;
-  if (!rm && !gm) return fail(c, SMPC_ERR_STATE, "no limited noise: no tick has run with these acceleration limits");
-  HIPCK(c, hipSetDevice(c->device));
-  const uint32_t B = c->cfg.batch_size, T = c->cfg.time_steps;
-  const size_t n = static_cast<size_t>(B) * T * sizeof(float);
-  if (!rm) {
-    // the last iteration's passes read the group-major layout only: the [B,T] form is made from it
-    const size_t ngm = SMPC_GM_ELEMS(B, T);
-    for (int k = 0; k < 3; ++k) {
-      if (k == 1 && !c->holonomic) continue;
-      if (!c->l_rm[k]) HIPCK(c, hipMalloc(&c->l_rm[k], n));
-      HIPCK(c, smpc_launch_relayout(c->l_gm + k * ngm, c->l_rm[k], B, T, false, c->stream));
-    }
-    c->lim_rm_iter = c->lim_iter;
-  }
-  HIPCK(c, hipStreamSynchronize(c->stream));
-  if (nvx) HIPCK(c, hipMemcpy(nvx, c->l_rm[0], n, hipMemcpyDeviceToHost));
-  if (nvy) {
-    if (c->holonomic) HIPCK(c, hipMemcpy(nvy, c->l_rm[1], n, hipMemcpyDeviceToHost));
-    else memset(nvy, 0, n);
-  }
-  if (nwz) HIPCK(c, hipMemcpy(nwz, c->l_rm[2], n, hipMemcpyDeviceToHost));
-  return SMPC_OK;
-}
-
-// developer aid (SMPC_FLAG_PROFILE): GPU time of the last smpc_limit_noise launch, by HIP events
-int smpc_debug_limit_ms(smpc_ctx* c, float* ms)
-{
-  if (!c || !ms || !c->ev_lim[0] || !c->ev_lim[1]) return SMPC_ERR_INVALID;
-  HIPCK(c, hipSetDevice(c->device));
-  HIPCK(c, hipEventSynchronize(c->ev_lim[1]));
-  HIPCK(c, hipEventElapsedTime(ms, c->ev_lim[0], c->ev_lim[1]));
-  return SMPC_OK;
-}
-
-void smpc_moving_obstacles_params_default(smpc_moving_obstacles_params* p)
-{
-  if (!p) return;
-  p->collision_cost = 10000.0f;
-  p->repulsion_weight = 5.0f;
-  p->margin = 0.5f;
-  p->reserved = 0;
-}
-
-int smpc_set_moving_obstacles(smpc_ctx* c, const smpc_moving_obstacles_params* p, const float* xy, const float* radius, uint32_t n)
-{
-  if (!c) return SMPC_ERR_INVALID;
-  if (n == 0) {
-    // off: the buffers stay (a controller that clears and sets the table every few ticks), nothing reads them
-    c->mov_K = 0;
-    c->mov_iter = 0;
-    c->mov_scored = false;
-    return SMPC_OK;
-  }
-  if (n > SMPC_MAX_MOVING_OBSTACLES) return fail(c, SMPC_ERR_UNSUPPORTED, "more than SMPC_MAX_MOVING_OBSTACLES moving obstacles");
-  if (!p || !xy || !radius) return fail(c, SMPC_ERR_INVALID, "null argument");
-  if (!std::isfinite(p->collision_cost) || !std::isfinite(p->repulsion_weight) || !std::isfinite(p->margin) ||
-      !(p->collision_cost >= 0.f) || !(p->repulsion_weight >= 0.f) || !(p->margin > 0.f))
-    return fail(c, SMPC_ERR_INVALID, "moving obstacles: collision_cost >= 0, repulsion_weight >= 0, margin > 0, all finite");
-  const uint32_t B = c->cfg.batch_size, T = c->cfg.time_steps;
-  if (T > SMPC_MOVING_MAX_T) return fail(c, SMPC_ERR_UNSUPPORTED, "moving obstacles: more than 256 time steps");
-  for (uint32_t k = 0; k < n; ++k)
-    if (!std::isfinite(radius[k]) || !(radius[k] > 0.f)) return fail(c, SMPC_ERR_INVALID, "moving obstacles: every radius must be finite and > 0");
-  for (size_t i = 0; i < static_cast<size_t>(n) * T * 2; ++i)
-    if (!std::isfinite(xy[i])) return fail(c, SMPC_ERR_INVALID, "moving obstacles: every centre must be finite");
-  // Buffers, each checked on its own (a call that failed half way picks up where it stopped): the
-  // table's three regions — [T][K] quads | [K][T] pairs | [K] disc constants — in ONE device
-  // allocation sized for the most discs a table can hold, a pinned staging copy of the same size, and
-  // the event behind the last upload.
-  HIPCK(c, hipSetDevice(c->device));
-  const size_t cap = static_cast<size_t>(SMPC_MAX_MOVING_OBSTACLES) * T;
-  const size_t tab_floats = cap * 6 + SMPC_MAX_MOVING_OBSTACLES * 4;
-  if (!c->mov_tab_tk) HIPCK(c, hipMalloc(&c->mov_tab_tk, tab_floats * sizeof(float)));
-  if (!c->mov_stage) HIPCK(c, hipHostMalloc(reinterpret_cast<void**>(&c->mov_stage), tab_floats * sizeof(float), hipHostMallocDefault));
-  if (!c->ev_mov_up) HIPCK(c, hipEventCreateWithFlags(&c->ev_mov_up, hipEventDisableTiming));
-  if (!c->mov_hit) HIPCK(c, hipMalloc(&c->mov_hit, B));
-  if (!c->mov_m) HIPCK(c, hipMalloc(&c->mov_m, B * sizeof(float)));
-  // the upload before this one may still be reading the staging copy
-  if (c->mov_up_recorded) HIPCK(c, hipEventSynchronize(c->ev_mov_up));
-  // the table in the two forms the launches read (smpc_moving.h), then the disc constants: written
-  // straight into the staging copy — this is the copy the call makes before it returns
-  // (packed for THIS table, each region 16-byte aligned: the upload is one run)
-  const size_t n_tk = static_cast<size_t>(T) * n * 4, n_kt = (static_cast<size_t>(n) * T * 2 + 3) & ~static_cast<size_t>(3);
-  const size_t used = n_tk + n_kt + 4 * static_cast<size_t>(n);
-  float* tk = c->mov_stage;
-  float* kt = tk + n_tk;
-  float* disc = kt + n_kt;
-  for (uint32_t k = 0; k < n; ++k) {
-    const float reach = radius[k] + p->margin;
-    const float reach2 = reach * reach * SMPC_MOVING_REACH_GUARD;
-    disc[4 * k + 0] = radius[k]; disc[4 * k + 1] = reach; disc[4 * k + 2] = reach2; disc[4 * k + 3] = 0.f;
-    for (uint32_t t = 0; t < T; ++t) {
-      const float x = xy[(static_cast<size_t>(k) * T + t) * 2], y = xy[(static_cast<size_t>(k) * T + t) * 2 + 1];
-      float* e = tk + (static_cast<size_t>(t) * n + k) * 4;
-      e[0] = x; e[1] = y; e[2] = reach2; e[3] = radius[k];
-      kt[(static_cast<size_t>(k) * T + t) * 2] = x;
-      kt[(static_cast<size_t>(k) * T + t) * 2 + 1] = y;
-    }
-  }
-  // ONE upload on the ctx's stream, behind whatever of the last tick still reads the table, nothing
-  // waited for (a fleet's 15 neighbours at T = 56: 20 KB).  The next tick's kernel follows on the same
-  // stream, or waits for the event where the ctx has changed streams since (a group formed or
-  // dropped): moving_cost.
-  HIPCK(c, hipMemcpyAsync(c->mov_tab_tk, tk, used * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  c->mov_tab_kt = c->mov_tab_tk + n_tk;
-  c->mov_disc = c->mov_tab_kt + n_kt;
-  HIPCK(c, hipEventRecord(c->ev_mov_up, c->stream));
-  c->mov_up_recorded = true;
-  c->mov_up_stream = c->stream;
-  c->mov_par = *p;
-  c->mov_K = n;
-  c->mov_iter = 0;
-  c->mov_scored = false;
-  return SMPC_OK;
-}
-
-int smpc_get_moving_obstacle_costs(smpc_ctx* c, float* m, uint8_t* hit)
-{
-  if (!c || !m) return fail(c, SMPC_ERR_INVALID, "null argument");
-  if (c->mov_K == 0) return fail(c, SMPC_ERR_STATE, "no moving-obstacle costs: the term is off");
-  if (!c->mov_scored) return fail(c, SMPC_ERR_STATE, "no moving-obstacle costs: no tick has scored this table");
-  HIPCK(c, hipSetDevice(c->device));
-  HIPCK(c, hipStreamSynchronize(c->stream));
-  HIPCK(c, hipMemcpy(m, c->mov_m, c->cfg.batch_size * sizeof(float), hipMemcpyDeviceToHost));
-  if (hit) HIPCK(c, hipMemcpy(hit, c->mov_hit, c->cfg.batch_size, hipMemcpyDeviceToHost));
-  return SMPC_OK;
-}
-
-// developer aid (SMPC_FLAG_PROFILE): GPU time of the last smpc_moving_cost launch, by HIP events
-int smpc_debug_moving_ms(smpc_ctx* c, float* ms)
-{
-  if (!c || !ms || !c->ev_mov[0] || !c->ev_mov[1]) return SMPC_ERR_INVALID;
-  HIPCK(c, hipSetDevice(c->device));
-  HIPCK(c, hipEventSynchronize(c->ev_mov[1]));
-  HIPCK(c, hipEventElapsedTime(ms, c->ev_mov[0], c->ev_mov[1]));
   return SMPC_OK;
 }
 
@@ -1229,22 +734,14 @@ int smpc_set_costmap(smpc_ctx* c, const uint8_t* cells, uint32_t width, uint32_t
   HostCostmap& m = c->map;
   const size_t bytes = static_cast<size_t>(width) * height;
   bool same_size = m.set && m.W == width && m.H == height;
-  if (bytes > c->d_map_bytes) {
+  if (bytes > c->d_map.capacity()) {
     // the stream may still read the old device copy (an un-waited tick): drain it first
     HIPCK(c, hipStreamSynchronize(c->stream));
-    if (c->d_map) HIPCK(c, hipFree(c->d_map));
-    c->d_map = nullptr;
-    c->d_map_bytes = 0;
-    HIPCK(c, hipMalloc(&c->d_map, (bytes + 255) / 256 * 256));
-    c->d_map_bytes = bytes;
+    HIPCK(c, c->d_map.ensure((bytes + 255) / 256 * 256));
     same_size = false;
   }
-  if (bytes > m.cap) {
-    if (m.cells) HIPCK(c, hipHostFree(m.cells));
-    m.cells = nullptr;
-    m.cap = 0;
-    HIPCK(c, hipHostMalloc(reinterpret_cast<void**>(&m.cells), (bytes + 4095) / 4096 * 4096, hipHostMallocDefault));
-    m.cap = bytes;
+  if (bytes > m.cells.capacity()) {
+    HIPCK(c, m.cells.ensure((bytes + 4095) / 4096 * 4096));
     same_size = false;
   }
   // The controller hands over the whole costmap every tick (controller.cpp:99-103) while the
@@ -1254,14 +751,14 @@ int smpc_set_costmap(smpc_ctx* c, const uint8_t* cells, uint32_t width, uint32_t
   if (same_size) {
     for (uint32_t y = 0; y < height; ++y) {
       const size_t o = static_cast<size_t>(y) * width;
-      if (memcmp(m.cells + o, cells + o, width) != 0) {
-        memcpy(m.cells + o, cells + o, width);
+      if (memcmp(m.cells.get() + o, cells + o, width) != 0) {
+        memcpy(m.cells.get() + o, cells + o, width);
         if (y < y0) y0 = y;
         y1 = y;
       }
     }
   } else {
-    memcpy(m.cells, cells, bytes);
+    memcpy(m.cells.get(), cells, bytes);
     y0 = 0;
     y1 = height - 1;
   }
@@ -1279,8 +776,8 @@ int smpc_set_costmap(smpc_ctx* c, const uint8_t* cells, uint32_t width, uint32_t
   c->map_bytes_last = 0;
   if (y0 <= y1) {
     const size_t o = static_cast<size_t>(y0) * width, n = static_cast<size_t>(y1 - y0 + 1) * width;
-    HIPCK(c, hipMemcpyAsync(c->d_map + o, m.cells + o, n, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipEventRecord(c->ev_map, c->stream));
+    HIPCK(c, hipMemcpyAsync(c->d_map.get() + o, m.cells.get() + o, n, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipEventRecord(c->ev_map.get(), c->stream));
     c->map_pending = true;
     c->map_bytes_last = n;
     c->map_bytes_total += n;
@@ -1301,11 +798,11 @@ int smpc_update_costmap_region(smpc_ctx* c, const uint8_t* cells, uint32_t row_s
   int rc = wait_map_upload(c);
   if (rc != SMPC_OK) return rc;
   for (uint32_t y = 0; y < height; ++y)
-    memcpy(m.cells + static_cast<size_t>(y0 + y) * m.W + x0, cells + static_cast<size_t>(y) * row_stride, width);
+    memcpy(m.cells.get() + static_cast<size_t>(y0 + y) * m.W + x0, cells + static_cast<size_t>(y) * row_stride, width);
   const size_t o = static_cast<size_t>(y0) * m.W + x0;
-  HIPCK(c, hipMemcpy2DAsync(c->d_map + o, m.W, m.cells + o, m.W, width, height, hipMemcpyHostToDevice,
+  HIPCK(c, hipMemcpy2DAsync(c->d_map.get() + o, m.W, m.cells.get() + o, m.W, width, height, hipMemcpyHostToDevice,
                             c->stream));
-  HIPCK(c, hipEventRecord(c->ev_map, c->stream));
+  HIPCK(c, hipEventRecord(c->ev_map.get(), c->stream));
   c->map_pending = true;
   c->map_bytes_last = static_cast<uint64_t>(width) * height;
   c->map_bytes_total += c->map_bytes_last;
@@ -1317,74 +814,6 @@ int smpc_costmap_upload_bytes(const smpc_ctx* c, uint64_t* last_call, uint64_t* 
   if (!c) return SMPC_ERR_INVALID;
   if (last_call) *last_call = c->map_bytes_last;
   if (total) *total = c->map_bytes_total;
-  return SMPC_OK;
-}
-
-int smpc_set_noise(smpc_ctx* c, const float* nvx, const float* nvy, const float* nwz)
-{
-  if (!c || !nvx || !nvy || !nwz) return SMPC_ERR_INVALID;
-  HIPCK(c, hipSetDevice(c->device));
-  const size_t n = static_cast<size_t>(c->cfg.batch_size) * c->cfg.time_steps * sizeof(float);
-  {
-    const int rc = cancel_redraw(c);
-    if (rc != SMPC_OK) return rc;
-  }
-  HIPCK(c, hipMemcpyAsync(c->d_nvx, nvx, n, hipMemcpyHostToDevice, c->stream));
-  if (c->holonomic) HIPCK(c, hipMemcpyAsync(c->d_nvy, nvy, n, hipMemcpyHostToDevice, c->stream));
-  HIPCK(c, hipMemcpyAsync(c->d_nwz, nwz, n, hipMemcpyHostToDevice, c->stream));
-  {
-    int rc = update_time_major(c);
-    if (rc != SMPC_OK) return rc;
-  }
-  HIPCK(c, hipStreamSynchronize(c->stream));
-  c->have_noise = true;
-  c->rm_valid = true;
-  c->rng_mode = false;
-  c->noise_gen++;
-  return SMPC_OK;
-}
-
-int smpc_seed(smpc_ctx* c, uint64_t seed)
-{
-  if (!c) return SMPC_ERR_INVALID;
-  HIPCK(c, hipSetDevice(c->device));
-  c->seed = seed;
-  c->epoch = 0;
-  c->rng_mode = true;
-  return draw_noise(c);
-}
-
-int smpc_redraw_noise(smpc_ctx* c)
-{
-  if (!c) return SMPC_ERR_INVALID;
-  if (!c->rng_mode) return fail(c, SMPC_ERR_STATE, "smpc_redraw_noise needs device-RNG mode (smpc_seed)");
-  HIPCK(c, hipSetDevice(c->device));
-  c->epoch++;
-  return draw_noise(c);
-}
-
-int smpc_redraw_noise_async(smpc_ctx* c)
-{
-  if (!c) return SMPC_ERR_INVALID;
-  if (!c->rng_mode) return fail(c, SMPC_ERR_STATE, "smpc_redraw_noise_async needs device-RNG mode (smpc_seed)");
-  HIPCK(c, hipSetDevice(c->device));
-  return redraw_async(c);
-}
-
-int smpc_get_noise(smpc_ctx* c, float* nvx, float* nvy, float* nwz)
-{
-  if (!c) return SMPC_ERR_INVALID;
-  if (!c->have_noise) return fail(c, SMPC_ERR_STATE, "no noise yet");
-  HIPCK(c, hipSetDevice(c->device));
-  const size_t n = static_cast<size_t>(c->cfg.batch_size) * c->cfg.time_steps * sizeof(float);
-  {
-    const int rc = ensure_row_major(c);
-    if (rc != SMPC_OK) return rc;
-  }
-  HIPCK(c, hipStreamSynchronize(c->stream));
-  if (nvx) HIPCK(c, hipMemcpy(nvx, c->d_nvx, n, hipMemcpyDeviceToHost));
-  if (nvy) HIPCK(c, hipMemcpy(nvy, c->d_nvy, n, hipMemcpyDeviceToHost));
-  if (nwz) HIPCK(c, hipMemcpy(nwz, c->d_nwz, n, hipMemcpyDeviceToHost));
   return SMPC_OK;
 }
 
@@ -1407,9 +836,9 @@ int smpc_optimize(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_tick
   // time when profiling (`timed`), and the host round trip for the result (`fetch`).  dF: the
   // furthest point on the device, for the critics and reported as the one they used.
   auto score = [&](uint32_t flags, const float* u_dev, const float* dF, uint32_t hintS, bool timed, bool fetch) -> int {
-    int e = launch_score(c, flags, u_dev, dF, hintS, c->d_tuple, true, dF);
+    int e = launch_score(c, flags, u_dev, dF, hintS, c->d_tuple.get(), true, dF);
     if (e != SMPC_OK) return e;
-    if (timed && (c->cfg.flags & SMPC_FLAG_PROFILE)) HIPCK(c, hipEventRecord(c->ev1, c->stream));
+    if (timed && (c->cfg.flags & SMPC_FLAG_PROFILE)) HIPCK(c, hipEventRecord(c->ev1.get(), c->stream));
     const bool first = c->passes == 1;
     if (timing && first) t_launch = clk::now();
     if (fetch) e = fetch_out(c);
@@ -1436,8 +865,8 @@ int smpc_optimize(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_tick
     // the same control sequence as the first
     const float* u_dev = nullptr;
     if (it > 0) {
-      HIPCK(c, hipMemcpyAsync(c->d_u_iter, c->d_out, 3 * T * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-      u_dev = c->d_u_iter;
+      HIPCK(c, hipMemcpyAsync(c->d_u_iter.get(), c->d_out.get(), 3 * T * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+      u_dev = c->d_u_iter.get();
       begin_limit_iteration(c, u_dev);   // this iteration limits the stored noise afresh, against its own u
     }
     c->costs_cur = it & 1;
@@ -1448,7 +877,7 @@ int smpc_optimize(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_tick
       if (S_known) {
         hintS = S_host;
       } else if (S_on_device) {
-        dF = c->d_furthest;
+        dF = c->d_furthest.get();
       } else if (speculate && c->pred.hint_valid) {
         // score with the previous tick's furthest point; the pass reports the true
         // one and a miss is re-scored below, so the result is exact either way
@@ -1456,10 +885,10 @@ int smpc_optimize(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_tick
         hintS = c->pred.hint;
         flags |= SD_LOCAL_FURTHEST;
       } else {
-        rc = launch_furthest(c, c->d_furthest);
+        rc = launch_furthest(c, c->d_furthest.get());
         if (rc != SMPC_OK) return rc;
         S_on_device = true;
-        dF = c->d_furthest;
+        dF = c->d_furthest.get();
       }
     }
     // ---- the iteration's first pass.  One host round trip where something hangs on it: fail_flag
@@ -1542,9 +971,9 @@ int smpc_get_trajectories(smpc_ctx* c, float* x, float* y, float* yaws)
   HIPCK(c, hipSetDevice(c->device));
   HIPCK(c, hipStreamSynchronize(c->stream));
   const size_t n = static_cast<size_t>(c->cfg.batch_size) * c->cfg.time_steps * sizeof(float);
-  if (x) HIPCK(c, hipMemcpy(x, c->d_traj[0], n, hipMemcpyDeviceToHost));
-  if (y) HIPCK(c, hipMemcpy(y, c->d_traj[1], n, hipMemcpyDeviceToHost));
-  if (yaws) HIPCK(c, hipMemcpy(yaws, c->d_traj[2], n, hipMemcpyDeviceToHost));
+  if (x) HIPCK(c, hipMemcpy(x, c->d_traj[0].get(), n, hipMemcpyDeviceToHost));
+  if (y) HIPCK(c, hipMemcpy(y, c->d_traj[1].get(), n, hipMemcpyDeviceToHost));
+  if (yaws) HIPCK(c, hipMemcpy(yaws, c->d_traj[2].get(), n, hipMemcpyDeviceToHost));
   return SMPC_OK;
 }
 
@@ -1553,93 +982,8 @@ int smpc_get_costs(smpc_ctx* c, float* costs)
   if (!c || !costs) return SMPC_ERR_INVALID;
   HIPCK(c, hipSetDevice(c->device));
   HIPCK(c, hipStreamSynchronize(c->stream));
-  HIPCK(c, hipMemcpy(costs, c->d_costs[c->costs_cur], c->cfg.batch_size * sizeof(float),
+  HIPCK(c, hipMemcpy(costs, c->d_costs[c->costs_cur].get(), c->cfg.batch_size * sizeof(float),
                      hipMemcpyDeviceToHost));
-  return SMPC_OK;
-}
-
-int smpc_selftest_sincos(smpc_ctx* c, const float* x, uint32_t n, float* sin_out, float* cos_out)
-{
-  if (!c || !x || !sin_out || !cos_out || n == 0) return fail(c, SMPC_ERR_INVALID, "null argument");
-  HIPCK(c, hipSetDevice(c->device));
-  float *dx = nullptr, *ds = nullptr, *dc = nullptr;
-  HIPCK(c, hipMalloc(&dx, n * sizeof(float)));
-  HIPCK(c, hipMalloc(&ds, n * sizeof(float)));
-  HIPCK(c, hipMalloc(&dc, n * sizeof(float)));
-  HIPCK(c, hipMemcpyAsync(dx, x, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  HIPCK(c, smpc_launch_sincos(dx, n, ds, dc, c->stream));
-  HIPCK(c, hipMemcpyAsync(sin_out, ds, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  HIPCK(c, hipMemcpyAsync(cos_out, dc, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  HIPCK(c, hipStreamSynchronize(c->stream));
-  (void)hipFree(dx); (void)hipFree(ds); (void)hipFree(dc);
-  return SMPC_OK;
-}
-
-int smpc_selftest_philox(smpc_ctx* c, const uint32_t* ctr, const uint32_t* key, uint32_t n, uint32_t* out)
-{
-  if (!c || !ctr || !key || !out || n == 0 || n > (1u << 26)) return fail(c, SMPC_ERR_INVALID, "bad argument");
-  HIPCK(c, hipSetDevice(c->device));
-  const size_t bytes = static_cast<size_t>(n) * 4 * sizeof(uint32_t);
-  uint32_t *dc = nullptr, *dout = nullptr;
-  HIPCK(c, hipMalloc(&dc, bytes));
-  HIPCK(c, hipMalloc(&dout, bytes));
-  HIPCK(c, hipMemcpyAsync(dc, ctr, bytes, hipMemcpyHostToDevice, c->stream));
-  HIPCK(c, smpc_launch_philox(dc, key[0], key[1], n, dout, c->stream));
-  HIPCK(c, hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIPCK(c, hipStreamSynchronize(c->stream));
-  (void)hipFree(dc); (void)hipFree(dout);
-  return SMPC_OK;
-}
-
-int smpc_selftest_box_muller(smpc_ctx* c, const uint32_t* r0, const uint32_t* r1, uint32_t n, float* z0, float* z1)
-{
-  if (!c || !r0 || !r1 || !z0 || !z1 || n == 0 || n > (1u << 26)) return fail(c, SMPC_ERR_INVALID, "bad argument");
-  HIPCK(c, hipSetDevice(c->device));
-  const size_t bytes = static_cast<size_t>(n) * sizeof(uint32_t);
-  uint32_t *d0 = nullptr, *d1 = nullptr;
-  float *dz0 = nullptr, *dz1 = nullptr;
-  HIPCK(c, hipMalloc(&d0, bytes));
-  HIPCK(c, hipMalloc(&d1, bytes));
-  HIPCK(c, hipMalloc(&dz0, bytes));
-  HIPCK(c, hipMalloc(&dz1, bytes));
-  HIPCK(c, hipMemcpyAsync(d0, r0, bytes, hipMemcpyHostToDevice, c->stream));
-  HIPCK(c, hipMemcpyAsync(d1, r1, bytes, hipMemcpyHostToDevice, c->stream));
-  HIPCK(c, smpc_launch_box_muller(d0, d1, n, dz0, dz1, c->stream));
-  HIPCK(c, hipMemcpyAsync(z0, dz0, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIPCK(c, hipMemcpyAsync(z1, dz1, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIPCK(c, hipStreamSynchronize(c->stream));
-  (void)hipFree(d0); (void)hipFree(d1); (void)hipFree(dz0); (void)hipFree(dz1);
-  return SMPC_OK;
-}
-
-int smpc_selftest_lane_reduce(smpc_ctx* c, const float* v, const float* w, float* out)
-{
-  if (!c || !v || !w || !out) return fail(c, SMPC_ERR_INVALID, "null argument");
-  HIPCK(c, hipSetDevice(c->device));
-  float *dv = nullptr, *dw = nullptr, *dout = nullptr;
-  HIPCK(c, hipMalloc(&dv, 64 * 64 * sizeof(float)));
-  HIPCK(c, hipMalloc(&dw, 64 * sizeof(float)));
-  HIPCK(c, hipMalloc(&dout, 64 * sizeof(float)));
-  HIPCK(c, hipMemcpyAsync(dv, v, 64 * 64 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  HIPCK(c, hipMemcpyAsync(dw, w, 64 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  HIPCK(c, smpc_launch_lane_reduce(dv, dw, dout, c->stream));
-  HIPCK(c, hipMemcpyAsync(out, dout, 64 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  HIPCK(c, hipStreamSynchronize(c->stream));
-  (void)hipFree(dv); (void)hipFree(dw); (void)hipFree(dout);
-  return SMPC_OK;
-}
-int smpc_selftest_row_reduce(smpc_ctx* c, const float* v, uint32_t n, float* out)
-{
-  if (!c || !v || !out || (n != 16 && n != 32)) return fail(c, SMPC_ERR_INVALID, "bad argument");
-  HIPCK(c, hipSetDevice(c->device));
-  float *dv = nullptr, *dout = nullptr;
-  HIPCK(c, hipMalloc(&dv, 64 * n * sizeof(float)));
-  HIPCK(c, hipMalloc(&dout, 64 * sizeof(float)));
-  HIPCK(c, hipMemcpyAsync(dv, v, 64 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  HIPCK(c, smpc_launch_row_reduce(dv, dout, n, c->stream));
-  HIPCK(c, hipMemcpyAsync(out, dout, 64 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  HIPCK(c, hipStreamSynchronize(c->stream));
-  (void)hipFree(dv); (void)hipFree(dout);
   return SMPC_OK;
 }
 
@@ -1648,124 +992,9 @@ int smpc_set_stream(smpc_ctx* c, void* hip_stream)
   if (!c) return SMPC_ERR_INVALID;
   const int rc = wait_map_upload(c);   // it went out on the stream being left
   if (rc != SMPC_OK) return rc;
-  c->stream = hip_stream == SMPC_STREAM_OWN ? c->own_stream : static_cast<hipStream_t>(hip_stream);
+  c->stream = hip_stream == SMPC_STREAM_OWN ? c->own_stream.get() : static_cast<hipStream_t>(hip_stream);
   return SMPC_OK;
 }
-
-// developer aid: smpc_grid_tail's stamps of the last launch, [8 reducers][16] in s_memrealtime ticks (10 ns)
-int smpc_debug_tail_timeline(smpc_ctx* c, unsigned long long* out)
-{
-  if (!c || !out || !c->d_timeline) return SMPC_ERR_INVALID;
-  HIPCK(c, hipSetDevice(c->device));
-  HIPCK(c, hipStreamSynchronize(c->stream));
-  HIPCK(c, hipMemcpy(out, c->d_timeline + SMPC_TAIL_STAMPS_AT, 8 * 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  return SMPC_OK;
-}
-
-// developer aid: stage durations of the last lane-pass launch, from the stamps of wave 0 of
-// every block (shader clocks; stages: entry -> LDS staged -> constants -> group 1 -> group 2
-// -> all waves at the final barrier -> partial written); out[7][3] = min, median, max
-int smpc_debug_lane_timeline(smpc_ctx* c, double* out, uint32_t* n_blocks)
-{
-  if (!c || !out || !c->d_timeline) return SMPC_ERR_INVALID;
-  HIPCK(c, hipSetDevice(c->device));
-  HIPCK(c, hipStreamSynchronize(c->stream));
-  const uint32_t nb = c->plan.lane.grid;
-  std::vector<unsigned long long> h(static_cast<size_t>(nb) * 8);
-  HIPCK(c, hipMemcpy(h.data(), c->d_timeline, h.size() * sizeof(h[0]), hipMemcpyDeviceToHost));
-  unsigned long long t0 = ~0ull;
-  for (uint32_t b = 0; b < nb; ++b) t0 = std::min(t0, h[b * 8]);
-  for (int k = 0; k < 7; ++k) {
-    std::vector<double> v;
-    for (uint32_t b = 0; b < nb; ++b)
-      if (h[b * 8 + k]) v.push_back(static_cast<double>(h[b * 8 + k] - (k ? h[b * 8 + k - 1] : t0)));
-    std::sort(v.begin(), v.end());
-    out[3 * k] = v.empty() ? 0 : v.front();
-    out[3 * k + 1] = v.empty() ? 0 : v[v.size() / 2];
-    out[3 * k + 2] = v.empty() ? 0 : v.back();
-  }
-  // out[21..28]: per wave of the block, median of (end of its groups - stamp 2 of wave 0)
-  std::vector<unsigned long long> hw(static_cast<size_t>(nb) * 8);
-  HIPCK(c, hipMemcpy(hw.data(), c->d_timeline + 8192, hw.size() * sizeof(hw[0]), hipMemcpyDeviceToHost));
-  for (int w = 0; w < 8; ++w) {
-    std::vector<double> v;
-    for (uint32_t b = 0; b < nb; ++b)
-      if (hw[b * 8 + w] && h[b * 8 + 2]) v.push_back(static_cast<double>(hw[b * 8 + w] - h[b * 8 + 2]));
-    std::sort(v.begin(), v.end());
-    out[21 + w] = v.empty() ? 0 : v[v.size() / 2];
-  }
-  if (n_blocks) *n_blocks = nb;
-  return SMPC_OK;
-}
-
-// developer aid (SMPC_LANE_TIMELINE=1): how many groups of the lane pass took the furthest-point scan
-// since the last call (the instances with the prune test count; smpc_lane_furthest.inc), and how
-// many groups a launch of the current plan has; the counts are cleared
-int smpc_debug_lane_scan_count(smpc_ctx* c, unsigned long long* scanned, uint32_t* groups_per_launch)
-{
-  if (!c || !scanned || !c->d_timeline) return SMPC_ERR_INVALID;
-  HIPCK(c, hipSetDevice(c->device));
-  HIPCK(c, hipStreamSynchronize(c->stream));
-  std::vector<unsigned long long> h(static_cast<size_t>(kMaxGrid) * 8);
-  HIPCK(c, hipMemcpy(h.data(), c->d_timeline + SMPC_SCAN_COUNT_AT, h.size() * sizeof(h[0]), hipMemcpyDeviceToHost));
-  HIPCK(c, hipMemset(c->d_timeline + SMPC_SCAN_COUNT_AT, 0, h.size() * sizeof(h[0])));
-  unsigned long long sum = 0;
-  for (unsigned long long v : h) sum += v;
-  *scanned = sum;
-  if (groups_per_launch) *groups_per_launch = (c->cfg.batch_size + 63u) / 64u;
-  return SMPC_OK;
-}
-
-// developer aid (tests): the float F = index + fraction the last tick's scoring pass reported (the
-// tuple's slot 2, smpc_dev.h), as remember_furthest kept it for the next prediction — the value
-// itself while the stored noise stays the same from tick to tick
-int smpc_debug_furthest_f(const smpc_ctx* c, float* F)
-{
-  if (!c || !F || !c->pred.hint_valid) return SMPC_ERR_INVALID;
-  *F = c->pred.hint_F;
-  return SMPC_OK;
-}
-
-// developer aid, host only (tests/test_furthest_prune_cpu.py): the prune table prepare_tick would
-// write for this plan and first index; out: SMPC_PRUNE_FLOATS floats
-int smpc_debug_prune_table(const float* px, const float* py, uint32_t P, uint32_t k0, int on, float* out)
-{
-  if (!px || !py || !out) return SMPC_ERR_INVALID;
-  build_prune_table(px, py, P, k0, on != 0, out);
-  return SMPC_OK;
-}
-
-// developer aid, host only (tests/test_lds_layout_cpu.py): the LDS carve-up a scoring pass is
-// launched with — kind 0: the wave pass (make_lds; arg = PathAlign samples per rollout), 1: the lane
-// pass (lane_lds; arg != 0: the re-read form), 2: the split pass (split_lds; arg = segments, 2 or
-// 4) — for a costmap window of window_bytes cells (0: no costmap lookup), P path points and T
-// steps, with the block sizes plan_launch uses.  out: the 16 words of SmpcLds in declaration order.
-int smpc_debug_lds_layout(int kind, uint32_t window_bytes, uint32_t P, uint32_t T, uint32_t arg, uint32_t* out)
-{
-  if (!out || T == 0) return SMPC_ERR_INVALID;
-  SmpcLds L{};
-  if (kind == 0) {
-    const int R = T <= 64 ? 1 : (T <= 128 ? 2 : 4);   // (smpc_create)
-    L = make_lds(window_bytes, P, T, pass_block(R) / 64, window_bytes != 0, arg);
-  } else if (kind == 1) {
-    L = lane_lds(window_bytes, P, T, arg != 0);
-  } else if (kind == 2 && (arg == 2 || arg == 4)) {
-    L = split_lds(window_bytes, P, T, arg);
-  } else {
-    return SMPC_ERR_INVALID;
-  }
-  static_assert(sizeof(SmpcLds) == 16 * sizeof(uint32_t), "SmpcLds: 16 words");
-  memcpy(out, &L, sizeof(L));
-  return SMPC_OK;
-}
-
-// developer aid (bench.py labels its roofline with it): the scoring-pass instance the calling
-// thread launched last, spelled as rocprofv3's kernel trace spells it
-const char* smpc_debug_last_pass_kernel(void) {return smpc_last_pass_kernel;}
-
-// developer aid: how this ctx hands its per-tick inputs to the device — 1: CPU stores through the
-// PCIe BAR, 0: a copy on the stream (or, for wave-pass contexts, inside the kernel arguments)
-int smpc_debug_bar_tick(const smpc_ctx* c) {return c && c->bar_tick ? 1 : 0;}
 
 int smpc_set_profile(smpc_ctx* c, int enable)
 {

@@ -1,12 +1,17 @@
 // smpc_ctx.h — what the translation units behind include/smpc.h share: the context object,
 // the launchers of the .hip files, and the host-side helpers (smpc_impl).  Internal: not part of
 // the C-ABI.
-//   smpc_api.cpp      lifecycle, setters, the single-GPU tick (smpc_optimize), launch helpers
-//   smpc_prepare.cpp  per-tick host work: gates, path tables, lookup tables, LDS carve-up
-//   smpc_shard.cpp    batch-sharded tick, RCCL resolved at run time
-//   smpc_group.cpp    several planning instances per launch (the group object: smpc_group.h)
-//   smpc_stats.cpp    per-critic breakdown of a tick (smpc_critic_breakdown) and of a group's
-//                     members (smpc_group_critic_breakdown)
+//   smpc_api.cpp          lifecycle, setters, the costmap, the single-GPU tick (smpc_optimize), launch helpers
+//   smpc_noise.cpp        the stored noise: smpc_set_noise, the device RNG's draws, the background redraw
+//   smpc_limit_host.cpp   acceleration limits: the setters and the limiter's launch (use_limited_noise)
+//   smpc_moving_host.cpp  moving obstacles: the table's upload and the seed kernel's launch (use_moving_seed)
+//   smpc_debug.cpp        the smpc_selftest_* and smpc_debug_* entries (include/smpc_debug.h)
+//   smpc_prepare.cpp      per-tick host work: gates, path tables, lookup tables, LDS carve-up
+//   smpc_shard.cpp        batch-sharded tick, RCCL resolved at run time
+//   smpc_group.cpp        several planning instances per launch (the group object: smpc_group.h)
+//   smpc_stats.cpp        per-critic breakdown of a tick (smpc_critic_breakdown) and of a group's
+//                         members (smpc_group_critic_breakdown)
+// What they allocate is held by the holders of smpc_own.h, as members of the context's parts below.
 #ifndef SMPC_CTX_H_
 #define SMPC_CTX_H_
 
@@ -30,6 +35,7 @@
 #include "smpc_inst.h"   // the scoring-pass instances: tables, selectors, launch
 #include "smpc_limit.h"  // smpc_limit_noise: its arguments
 #include "smpc_moving.h" // smpc_moving_cost: its arguments
+#include "smpc_own.h"    // DevBuf, PinnedBuf, Event, Stream
 
 // nothing below is part of the C-ABI: keep it out of the dynamic symbol table
 #pragma GCC visibility push(hidden)
@@ -112,8 +118,8 @@ constexpr uint32_t kLdsPerCu = 160 * 1024;
 inline uint32_t align_up(uint32_t v, uint32_t a) {return (v + a - 1) / a * a;}
 
 struct HostCostmap {
-  uint8_t* cells = nullptr;   // pinned mirror of the device copy: the host-side lookups read it
-  size_t cap = 0;             // (path validity, first rollout point) and uploads DMA out of it
+  PinnedBuf<uint8_t> cells;   // pinned mirror of the device copy: the host-side lookups read it
+                              // (path validity, first rollout point) and uploads DMA out of it
   uint32_t W = 0, H = 0;
   double ox = 0, oy = 0, res = 1;
   bool track_unknown = false;
@@ -229,7 +235,7 @@ struct FurthestPredictor {
   double anchor_ex = 0, anchor_ey = 0, cur_ex = 0, cur_ey = 0;
   bool anchor_e_valid = false, cur_e_valid = false;
   std::vector<float> anchor_px, anchor_py;
-  uint32_t noise_gen_remembered = 0;   // smpc_ctx::noise_gen as of the last remember_furthest
+  uint32_t noise_gen_remembered = 0;   // NoiseStore::noise_gen as of the last remember_furthest
   // smpc_reset: no prediction and no drift; the anchor stays (unread while hint_valid is false, and
   // the next remember_furthest overwrites it)
   void forget()
@@ -245,40 +251,156 @@ struct FurthestPredictor {
 
 }  // namespace smpc_impl
 
+// ---- the context's parts.  Each owns what it allocates (smpc_own.h): a buffer is one declaration,
+// and free_ctx names none of them.  In every part the events and streams stand in front of the
+// buffers, so that the buffers go first when the part is destroyed. ----
+namespace smpc_impl {
+
+// One set of noise tensors: the three [B,T] tensors, and the group-major copies (smpc_dev.h:
+// SMPC_GM_INDEX) for the lane-per-rollout and split passes in ONE allocation, tvx, that vy and wz
+// follow (tvy and twz: views into it).
+struct NoiseSet {
+  DevBuf<float> nvx, nvy, nwz;
+  DevBuf<float> tvx;
+  float* tvy = nullptr;
+  float* twz = nullptr;
+};
+
+// The stored noise.  Written by smpc_noise.cpp: smpc_set_noise, the device RNG's draws (smpc_seed,
+// smpc_redraw_noise[_async], draw_noise) and absorb_redraw at the head of a tick.  Two writers in
+// smpc_api.cpp: smpc_create allocates `cur` and decides use_tpr, and smpc_reset advances `epoch`
+// itself before it calls draw_noise.
+struct NoiseStore {
+  // smpc_redraw_noise_async (regenerate_noises = true): the next epoch is drawn into `next` on
+  // fill_stream while the host and the device go on; the next tick's stream waits for ev_fill and
+  // the sets change places (absorb_redraw).
+  Stream fill_stream;
+  Event ev_fill;
+  NoiseSet cur;              // what the ticks score with
+  NoiseSet next;             // the background draw (allocated by the first one)
+  bool redraw_pending = false, redraw_rm_valid = true;
+  uint32_t noise_gen = 0;    // counts changes of the noise the ticks score with (pred.noise_gen_remembered:
+                             // as of the last remember_furthest)
+  bool use_tpr = false;      // group-major noise kept: the lane-per-rollout pass may run
+  bool rm_valid = true;      // the [B,T] tensors hold the current noise (a device-RNG draw fills the
+                             // group-major copy only; ensure_row_major() makes the other on demand)
+  bool have_noise = false, rng_mode = false;
+  uint64_t seed = 0;
+  uint32_t epoch = 0;
+};
+
+// Acceleration limits (smpc_set_acceleration_limits).  While `on`, every pass reads
+// the LIMITED noise of its iteration in place of the stored noise: use_limited_noise makes it, once
+// per iteration and layout, in front of the first pass that reads that layout.  Buffers: allocated at
+// the first tick that reads their layout.  Written by the functions of smpc_limit_host.cpp only;
+// begin_limit_iteration is called by prepare_tick (every tick) and by smpc_optimize (iterations > 0).
+// smpc_critic_breakdown runs prepare_tick and use_limited_noise like a tick and does NOT put the
+// counters back: it advances `iter`, leaves `rm_iter` at it, and smpc_get_limited_noise after a
+// breakdown hands out the breakdown's limited noise.
+struct Limiter {
+  Event ev[2];                      // SMPC_FLAG_PROFILE: around the last limiter launch
+  bool on = false;
+  float lim[4] = {0.f, 0.f, 0.f, 0.f};   // ax_max, ax_min, ay_max, az_max
+  DevBuf<float> l_rm[3];            // [B,T] each (vy: holonomic models only)
+  DevBuf<float> l_gm;               // group-major, vx | vy | wz back to back like NoiseSet::tvx (vy of a non-holonomic model: zeros)
+  const float* u_dev = nullptr;     // the iteration's u on the device; null: the tick block's host copy (iteration 0)
+  uint32_t iter = 0;                // counts iterations (begin_limit_iteration); never 0 once a tick ran
+  uint32_t rm_iter = 0, gm_iter = 0;   // the iteration each layout's buffer holds (0: none)
+};
+
+// Moving obstacles (smpc_set_moving_obstacles).  While K > 0, every iteration's
+// passes start their costs from the moving-obstacle term: use_moving_seed launches smpc_moving_cost
+// once per iteration, in front of the first pass, into the buffer the passes read as costs_prev.
+// Buffers: allocated by the first smpc_set_moving_obstacles with n > 0, each on its own.  Written by
+// the functions of smpc_moving_host.cpp only.  smpc_critic_breakdown seeds through seed_own_costs,
+// which writes stats_seed and leaves iter, scored, m and hit alone: they stay the last tick's.
+struct MovingObstacles {
+  Event ev_up;                      // behind the last upload
+  Event ev[2];                      // SMPC_FLAG_PROFILE: around the last smpc_moving_cost launch
+  uint32_t K = 0;                   // discs in the table; 0: off
+  smpc_moving_obstacles_params par{};
+  DevBuf<float> tab_tk;             // [T][K]{x, y, guarded squared reach, radius}: the group-major launch's table;
+                                    // the ONE device allocation the next two point into
+  float* tab_kt = nullptr;          // [K][T]{x, y}: the row-major launch's
+  float* disc = nullptr;            // [K]{radius, radius + margin, guarded squared reach, 0}
+  PinnedBuf<float> stage;           // the same three regions, what the uploads read
+  bool up_recorded = false;
+  hipStream_t up_stream = nullptr;  // the stream it went out on (a kernel on another stream waits for the event)
+  DevBuf<float> m;                  // [B] m of the last scored iteration
+  DevBuf<uint8_t> hit;              // [B] its hits
+  DevBuf<float> stats_seed;         // [B] the seed of smpc_critic_breakdown's own cost buffer (first use)
+  uint32_t iter = 0;                // the iteration (Limiter::iter) whose seed is in place (0: none)
+  bool scored = false;              // m and hit hold a tick's values
+};
+
+// The batch-sharded tick's links to the other shards.  Written by smpc_shard.cpp only.
+struct ShardLink {
+  // native RCCL exchange (smpc_shard_tick)
+  ncclComm_t comm = nullptr;
+  int comm_rank = 0, comm_world = 0;
+  DevBuf<float> d_all;         // [world][SMPC_TUPLE_HEADER + 3T] gathered shard tuples
+  // collective-free exchange (smpc_shard_p2p_*): the own mailbox (fine-grained device memory,
+  // exported over IPC) and the peers' mailboxes as mapped into this process (free_ctx unmaps them)
+  DevBuf<float> p2p_mailbox;
+  SmpcP2P p2p{};               // world == 0: not set up
+  uint32_t p2p_xseq = 0;
+  uint32_t p2p_timeout_ms = 10000;   // bound of the in-kernel wait for the peers (smpc_shard_p2p_set_timeout)
+  bool p2p_failed = false;           // an exchange timed out: no further mailbox tick until re-init
+  smpc_tick_in step_in{};       // step-wise sharded API: this tick's inputs (smpc_shard_begin .. smpc_shard_combine),
+  std::vector<float> step_px, step_py;   // with the path it points at copied here
+  bool step_remembered = false;
+};
+
+// smpc_critic_breakdown's buffers of its own, allocated at the first call: the 13 rows and the
+// totals [14][ld], the pass's partials, a furthest-point word, the result (one float allocation),
+// and the reduction's double partials.  Written by smpc_stats.cpp only.
+struct BreakdownBufs {
+  Event ev[4];                 // SMPC_FLAG_PROFILE: around the scoring pass and around the reduction
+  DevBuf<float> d_stats;
+  DevBuf<double> d_part;
+  uint32_t ld = 0;
+  float pass_ms = 0.f, reduce_ms = 0.f;
+};
+
+// The per-tick block.  `own_d` / `own_h` are the context's own block, allocated by smpc_create and
+// the context's for life.  `d_tick` / `h_tick` are the VIEWS everything else reads and writes
+// (prepare_tick, the kernels' parameter blocks, the limiter's u): the own block, or — while the
+// context is a group's member — its slot of the group's arena.  smpc_group_create repoints the
+// views, smpc_group_destroy points them back at the owner; nobody frees through a view.
+struct TickBlock {
+  DevBuf<uint8_t> own_d;
+  PinnedBuf<uint8_t> own_h;
+  uint8_t* d_tick = nullptr;
+  uint8_t* h_tick = nullptr;
+  void view_own() {d_tick = own_d.get(); h_tick = own_h.get();}
+  size_t cap = 0;
+  // The per-tick upload as CPU stores straight into device memory (large-BAR systems: every
+  // MI355X host maps the whole HBM) instead of a copy on the stream: no blit kernel (3.4 us) and
+  // no dependent-dispatch gap (4 us) in front of the scoring pass.  SMPC_NO_BAR_TICK=1: the copy.
+  // (Tick state, not a knob: a device capability, cleared at run time when a hand-over fails.)
+  bool bar_tick = false;
+  volatile uint32_t* hdp_flush = nullptr;   // HDP_MEM_FLUSH_CNTL of this device, or null
+  size_t used = 0;              // bytes of the tick block this tick fills (a multiple of 16)
+  uint32_t no = 0;              // number of the tick block last handed over (its canary word)
+  uint32_t canary_expect = 0;   // != 0: fetch_out checks the pass's echo against it
+};
+
+}  // namespace smpc_impl
+
 struct smpc_ctx {
   smpc_config cfg{};
   smpc_critic_params critics{};
   float c_vx_max = 0, c_vx_min = 0, c_vy = 0, c_wz = 0;
   int device = 0;
   int num_cu = 256;
-  hipStream_t own_stream = nullptr, stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  hipEvent_t evp[8] = {};   // SMPC_FLAG_PROFILE: pairs around up to 4 scoring passes
+  // streams and events first: the buffers below go before them
+  smpc_impl::Stream own_stream;
+  hipStream_t stream = nullptr;   // the one the ticks run on: own_stream, a caller's (smpc_set_stream) or a group's
+  smpc_impl::Event ev0, ev1;
+  smpc_impl::Event evp[8];   // SMPC_FLAG_PROFILE: pairs around up to 4 scoring passes
   uint32_t evp_used = 0;
-  // tensors
-  float* d_nvx = nullptr;
-  float* d_nvy = nullptr;
-  float* d_nwz = nullptr;
-  float* d_tvx = nullptr;       // group-major copies (smpc_dev.h: SMPC_GM_INDEX) for the lane-per-rollout and split passes:
-  float* d_tvy = nullptr;       // one allocation, vy and wz follow vx
-  float* d_twz = nullptr;
-  // A second set of noise tensors for smpc_redraw_noise_async (regenerate_noises = true): the
-  // next epoch is drawn into it on fill_stream while the host and the device go on; the next
-  // tick's stream waits for ev_fill and the sets change places (absorb_redraw).
-  float* b_nvx = nullptr;
-  float* b_nvy = nullptr;
-  float* b_nwz = nullptr;
-  float* b_tvx = nullptr;       // (one allocation, vy and wz follow vx)
-  float* b_tvy = nullptr;
-  float* b_twz = nullptr;
-  hipStream_t fill_stream = nullptr;
-  hipEvent_t ev_fill = nullptr;
-  bool redraw_pending = false, redraw_rm_valid = true;
-  uint32_t noise_gen = 0;              // counts changes of the noise the ticks score with (pred.noise_gen_remembered:
-                                       // as of the last remember_furthest)
-  bool use_tpr = false;      // group-major noise kept: the lane-per-rollout pass may run
-  bool rm_valid = true;      // the [B,T] tensors hold the current noise (a device-RNG draw fills the
-                             // group-major copy only; ensure_row_major() makes the other on demand)
+  smpc_impl::Event ev_map;           // behind the last costmap upload
+  smpc_impl::NoiseStore noise;
   smpc_impl::Knobs knobs;
   smpc_impl::PassPlan plan;              // this tick's scoring pass (plan_launch)
   smpc_impl::OccCache occ_wave, occ_lane, occ_split;
@@ -291,19 +413,9 @@ struct smpc_ctx {
   // consider_footprint: robot footprint (smpc_set_footprint) and the LUT pair built for it
   std::vector<double> fp_x, fp_y;
   double fp_circumscribed_radius = 0.0, fp_layer_scale = -1.0;
-  SmpcLut* d_lut_fp = nullptr;   // [2][256]
-  SmpcLut* h_lut_fp = nullptr;   // pinned
-  // native RCCL exchange of the batch-sharded tick (smpc_shard_tick)
-  ncclComm_t comm = nullptr;
-  int comm_rank = 0, comm_world = 0;
-  float* d_all = nullptr;     // [world][SMPC_TUPLE_HEADER + 3T] gathered shard tuples
-  // collective-free exchange (smpc_shard_p2p_*): the own mailbox (fine-grained device memory,
-  // exported over IPC) and the peers' mailboxes as mapped into this process
-  float* p2p_mailbox = nullptr;
-  SmpcP2P p2p{};               // world == 0: not set up
-  uint32_t p2p_xseq = 0;
-  uint32_t p2p_timeout_ms = 10000;   // bound of the in-kernel wait for the peers (smpc_shard_p2p_set_timeout)
-  bool p2p_failed = false;           // an exchange timed out: no further mailbox tick until re-init
+  smpc_impl::DevBuf<SmpcLut> d_lut_fp;      // [2][256]
+  smpc_impl::PinnedBuf<SmpcLut> h_lut_fp;
+  smpc_impl::ShardLink shard;
   bool pang_any = false;        // this tick: PathAngleCritic is live for some candidate furthest point (prepare_tick, from
                                 // path_angle_gates; plan_launch reads it)
   // the lane pass's prune table as last built, and what it was built for (prepare_tick)
@@ -311,47 +423,31 @@ struct smpc_ctx {
   std::vector<float> prune_px, prune_py;
   uint32_t prune_k0 = 0;
   bool in_group = false;        // member of an smpc_group: full-size blocks always (the group fills the CUs by itself)
-  float* d_costs[2] = {nullptr, nullptr};
-  float* d_traj[3] = {nullptr, nullptr, nullptr};
+  smpc_impl::DevBuf<float> d_costs[2];
+  smpc_impl::DevBuf<float> d_traj[3];
   int costs_cur = 0;
-  bool have_noise = false, rng_mode = false;
-  uint64_t seed = 0;
-  uint32_t epoch = 0;
   // costmap
   smpc_impl::HostCostmap map;
-  uint8_t* d_map = nullptr;
-  size_t d_map_bytes = 0;
-  hipEvent_t ev_map = nullptr;       // behind the last costmap upload
-  bool map_pending = false;          // that upload may still be reading the pinned mirror
+  smpc_impl::DevBuf<uint8_t> d_map;
+  bool map_pending = false;          // the last upload may still be reading the pinned mirror
   uint64_t map_bytes_last = 0, map_bytes_total = 0;   // uploaded by the last call / so far
-  unsigned long long* d_timeline = nullptr;   // SMPC_LANE_TIMELINE=1 (developer aid)
+  smpc_impl::DevBuf<unsigned long long> d_timeline;   // SMPC_LANE_TIMELINE=1 (developer aid)
   // per-tick block
-  SmpcLut* d_lut = nullptr;
-  SmpcLut* h_lut = nullptr;     // pinned
+  smpc_impl::DevBuf<SmpcLut> d_lut;
+  smpc_impl::PinnedBuf<SmpcLut> h_lut;
   uint64_t lut_key = 0, map_version = 1, critics_version = 1;
   bool lut_valid = false;
-  uint8_t* d_tick = nullptr;
-  uint8_t* h_tick = nullptr;  // pinned
-  size_t tick_cap = 0;
-  // The per-tick upload as CPU stores straight into device memory (large-BAR systems: every
-  // MI355X host maps the whole HBM) instead of a copy on the stream: no blit kernel (3.4 us) and
-  // no dependent-dispatch gap (4 us) in front of the scoring pass.  SMPC_NO_BAR_TICK=1: the copy.
-  // (Tick state, not a knob: a device capability, cleared at run time when a hand-over fails.)
-  bool bar_tick = false;
-  volatile uint32_t* hdp_flush = nullptr;   // HDP_MEM_FLUSH_CNTL of this device, or null
-  size_t tick_used = 0;         // bytes of the tick block this tick fills (a multiple of 16)
-  uint32_t tick_no = 0;         // number of the tick block last handed over (its canary word)
-  uint32_t canary_expect = 0;   // != 0: fetch_out checks the pass's echo against it
+  smpc_impl::TickBlock tick;
   bool launched = false;        // kernels of this ctx may still be reading the tick block
   // reductions / outputs
-  float* d_partials = nullptr;
-  float* d_tuple = nullptr;
-  float* d_out = nullptr;       // [SMPC_RESULT_FLOATS(T)]: u, then the result slots (smpc_dev.h)
-  float* d_u_iter = nullptr;    // [3T] the control sequence iteration it > 0 starts from: a copy of d_out, so that a
-                                // second pass of the same iteration (a re-score) reads what the first one read
-  float* h_out = nullptr;       // [SMPC_RESULT_HOST_FLOATS(T)] pinned, device-mapped: kernels write the result here
+  smpc_impl::DevBuf<float> d_partials;
+  smpc_impl::DevBuf<float> d_tuple;
+  smpc_impl::DevBuf<float> d_out;       // [SMPC_RESULT_FLOATS(T)]: u, then the result slots (smpc_dev.h)
+  smpc_impl::DevBuf<float> d_u_iter;    // [3T] the control sequence iteration it > 0 starts from: a copy of d_out, so that a
+                                        // second pass of the same iteration (a re-score) reads what the first one read
+  smpc_impl::PinnedBuf<float> h_out;    // [SMPC_RESULT_HOST_FLOATS(T)] device-mapped: kernels write the result here
   float* h_out_dev = nullptr;   // its device-side address
-  float* d_furthest = nullptr;  // the furthest point, and behind it the other device scratch words (smpc_dev.h: SMPC_SCRATCH_*)
+  smpc_impl::DevBuf<float> d_furthest;  // the furthest point, and behind it the other device scratch words (smpc_dev.h: SMPC_SCRATCH_*)
   int R = 1;                 // horizon in chunks of 64 steps per wave of the wave-per-rollout pass: 1, 2 or 4
   // per-tick prepared state
   SmpcDev dev{};
@@ -370,9 +466,6 @@ struct smpc_ctx {
   // speculation on furthest_reached_path_point: the index this tick is scored with first is pred.hint
   smpc_impl::FurthestPredictor pred;
   uint64_t spec_misses = 0;
-  smpc_tick_in step_in{};       // step-wise sharded API: this tick's inputs (smpc_shard_begin .. smpc_shard_combine),
-  std::vector<float> step_px, step_py;   // with the path it points at copied here
-  bool step_remembered = false;
   // Optimizer::isHolonomic (optimizer.cpp:235).  A non-holonomic model is the Omni data path
   // with the vy noise, control_sequence.vy and state.vy[:,0] all zero: then state.vy = 0,
   // dx = vx cos - 0 sin, the vy gamma term and the weighted vy update are exactly 0 — what the
@@ -383,46 +476,9 @@ struct smpc_ctx {
   uint32_t acker_seq = 0;    // completion word the Ackermann launch publishes this tick
   uint32_t seq = 0, poll_seq = 0;
   uint32_t poll_words = 0;   // > 0: the tick's completion arrives as this many words, from slot SMPC_R_BLOCK_DONE of h_out on
-  // smpc_critic_breakdown (smpc_stats.cpp): buffers of its own, allocated at the first call — the
-  // 13 rows and the totals [14][stats_ld], the pass's partials, a furthest-point word, the result
-  // (one float allocation), and the reduction's double partials
-  float* d_stats = nullptr;
-  double* d_stats_part = nullptr;
-  uint32_t stats_ld = 0;
-  // Acceleration limits (smpc_set_acceleration_limits).  While lim_on, every pass
-  // reads the LIMITED noise of its iteration in place of the stored noise: use_limited_noise
-  // (smpc_api.cpp) makes it, once per iteration and layout, in front of the first pass that reads
-  // that layout.  Buffers: allocated at the first tick that reads their layout.
-  bool lim_on = false;
-  float lim[4] = {0.f, 0.f, 0.f, 0.f};   // ax_max, ax_min, ay_max, az_max
-  float* l_rm[3] = {nullptr, nullptr, nullptr};   // [B,T] each (vy: holonomic models only)
-  float* l_gm = nullptr;                 // group-major, vx | vy | wz back to back like d_tvx (vy of a non-holonomic model: zeros)
-  const float* lim_u_dev = nullptr;      // the iteration's u on the device; null: the tick block's host copy (iteration 0)
-  uint32_t lim_iter = 0;                 // counts iterations (begin_limit_iteration); never 0 once a tick ran
-  uint32_t lim_rm_iter = 0, lim_gm_iter = 0;   // the iteration each layout's buffer holds (0: none)
-  hipEvent_t ev_lim[2] = {};             // SMPC_FLAG_PROFILE: around the last limiter launch
-  // Moving obstacles (smpc_set_moving_obstacles).  While mov_K > 0, every iteration's
-  // passes start their costs from the moving-obstacle term: use_moving_seed (smpc_api.cpp) launches
-  // smpc_moving_cost once per iteration, in front of the first pass, into the buffer the passes read
-  // as costs_prev.  Buffers: allocated by the first smpc_set_moving_obstacles with n > 0, each on its own.
-  uint32_t mov_K = 0;                    // discs in the table; 0: off
-  smpc_moving_obstacles_params mov_par{};
-  float* mov_tab_tk = nullptr;           // [T][K]{x, y, guarded squared reach, radius}: the group-major launch's table;
-                                         // the ONE device allocation the next two point into
-  float* mov_tab_kt = nullptr;           // [K][T]{x, y}: the row-major launch's
-  float* mov_disc = nullptr;             // [K]{radius, radius + margin, guarded squared reach, 0}
-  float* mov_stage = nullptr;            // pinned: the same three regions, what the uploads read
-  hipEvent_t ev_mov_up = nullptr;        // behind the last upload
-  bool mov_up_recorded = false;
-  hipStream_t mov_up_stream = nullptr;   // the stream it went out on (a kernel on another stream waits for the event)
-  float* mov_m = nullptr;                // [B] m of the last scored iteration
-  uint8_t* mov_hit = nullptr;            // [B] its hits
-  float* mov_stats_seed = nullptr;       // [B] the seed of smpc_critic_breakdown's own cost buffer (first use)
-  uint32_t mov_iter = 0;                 // the iteration (lim_iter) whose seed is in place (0: none)
-  bool mov_scored = false;               // mov_m and mov_hit hold a tick's values
-  hipEvent_t ev_mov[2] = {};             // SMPC_FLAG_PROFILE: around the last smpc_moving_cost launch
-  hipEvent_t ev_stats[4] = {};   // SMPC_FLAG_PROFILE: around the scoring pass and around the reduction
-  float stats_pass_ms = 0.f, stats_reduce_ms = 0.f;
+  smpc_impl::BreakdownBufs stats;
+  smpc_impl::Limiter lim;
+  smpc_impl::MovingObstacles mov;
   std::string err;
 };
 
@@ -488,7 +544,7 @@ int refuse_sharded(smpc_ctx* c);
 // the next completion sequence number (never 0), which fetch_out then waits for
 uint32_t next_seq(smpc_ctx* c);
 // device scratch word k of the ctx (smpc_dev.h: SMPC_SCRATCH_*)
-inline uint32_t* scratch_word(const smpc_ctx* c, uint32_t k) {return reinterpret_cast<uint32_t*>(c->d_furthest) + k;}
+inline uint32_t* scratch_word(const smpc_ctx* c, uint32_t k) {return reinterpret_cast<uint32_t*>(c->d_furthest.get()) + k;}
 // The result block of the tick fetched last, read in place in the host mirror (no copy: a later
 // fetch_out of the same tick shows through the same view).
 struct TickResult {
@@ -500,7 +556,7 @@ struct TickResult {
   float F_used() const {return slot[SMPC_R_F_USED];}
   float mark() const {return slot[SMPC_R_MARK];}
 };
-inline TickResult tick_result(const smpc_ctx* c) {return TickResult{c->h_out + SMPC_RESULT_AT(c->cfg.time_steps)};}
+inline TickResult tick_result(const smpc_ctx* c) {return TickResult{c->h_out.get() + SMPC_RESULT_AT(c->cfg.time_steps)};}
 // *out (may be null) of a finished tick.  What differs between the drivers comes in: the fail flag,
 // whether a furthest point was evaluated and the index reported, and a non-colliding count that
 // overrides the block's (null: the block's); device_ms: also the call's GPU time, first upload to

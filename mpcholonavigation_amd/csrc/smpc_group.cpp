@@ -25,7 +25,7 @@ int smpc_group_create(smpc_ctx* const* ctxs, uint32_t n, smpc_group** out)
     delete g;
     return fail(nullptr, SMPC_ERR_DEVICE, "hipSetDevice");
   }
-  g->slot = align_up(static_cast<uint32_t>(c0->tick_cap), 256);
+  g->slot = align_up(static_cast<uint32_t>(c0->tick.cap), 256);
   g->off_dev = g->slot * n;
   g->off_red = g->off_dev + align_up(static_cast<uint32_t>(sizeof(SmpcDev)) * n, 256);
   g->off_geo = g->off_red + align_up(static_cast<uint32_t>(sizeof(SmpcReduceArgs)) * n, 256);
@@ -36,24 +36,19 @@ int smpc_group_create(smpc_ctx* const* ctxs, uint32_t n, smpc_group** out)
   g->off_sdst = g->off_fgeo + align_up(static_cast<uint32_t>(sizeof(SmpcWaveGeom)) * n, 256);
   g->off_sred = g->off_sdst + align_up(static_cast<uint32_t>(sizeof(SmpcStatsDst)) * n, 256);
   g->total_stats = g->off_sred + align_up(static_cast<uint32_t>(sizeof(SmpcStatsReduceArgs)) * n, 256);
-  if (hipHostMalloc(&g->h_all, g->total_stats, hipHostMallocDefault) != hipSuccess ||
-    hipMalloc(&g->d_all, g->total_stats) != hipSuccess)
-  {
-    if (g->h_all) (void)hipHostFree(g->h_all);
+  if (g->h_all.ensure(g->total_stats) != hipSuccess || g->d_all.ensure(g->total_stats) != hipSuccess) {
     delete g;
     return fail(nullptr, SMPC_ERR_NOMEM, "group buffers");
   }
-  g->stream = c0->own_stream;
+  g->stream = c0->own_stream.get();
   for (uint32_t i = 0; i < n; ++i) {
     smpc_ctx* c = ctxs[i];
     (void)hipStreamSynchronize(c->stream);
     g->ctxs.push_back(c);
     g->saved_stream.push_back(c->stream);
-    g->saved_h_tick.push_back(c->h_tick);
-    g->saved_d_tick.push_back(c->d_tick);
     c->stream = g->stream;
-    c->h_tick = g->h_all + g->slot * i;
-    c->d_tick = g->d_all + g->slot * i;
+    c->tick.h_tick = g->h_all.get() + g->slot * i;
+    c->tick.d_tick = g->d_all.get() + g->slot * i;
     c->defer_upload = true;
     c->in_group = true;
     c->lut_valid = false;
@@ -69,17 +64,11 @@ void smpc_group_destroy(smpc_group* g)
   for (size_t i = 0; i < g->ctxs.size(); ++i) {
     smpc_ctx* c = g->ctxs[i];
     c->stream = g->saved_stream[i];
-    c->h_tick = g->saved_h_tick[i];
-    c->d_tick = g->saved_d_tick[i];
+    c->tick.view_own();
     c->defer_upload = false;
     c->in_group = false;
   }
-  if (g->h_all) (void)hipHostFree(g->h_all);
-  if (g->d_all) (void)hipFree(g->d_all);
-  if (g->d_stats) (void)hipFree(g->d_stats);
-  if (g->d_stats_part) (void)hipFree(g->d_stats_part);
-  if (g->h_stats_out) (void)hipHostFree(g->h_stats_out);
-  delete g;
+  delete g;   // its buffers: their holders' destructors (smpc_own.h)
 }
 
 int smpc_group_stats(const smpc_group* g, uint64_t* batched_launches, uint64_t* single_ticks)
@@ -232,9 +221,9 @@ int smpc_group_optimize_some(smpc_group* g, const smpc_tick_in* ins, float* cons
   const uint32_t m = static_cast<uint32_t>(order.size());
   const auto t_prep = now();
   // ---- one upload, one scoring launch per instance, one reduction launch ---------------------
-  SmpcDev* hd = reinterpret_cast<SmpcDev*>(g->h_all + g->off_dev);
-  SmpcReduceArgs* hr = reinterpret_cast<SmpcReduceArgs*>(g->h_all + g->off_red);
-  SmpcWaveGeom* hg = reinterpret_cast<SmpcWaveGeom*>(g->h_all + g->off_geo);
+  SmpcDev* hd = reinterpret_cast<SmpcDev*>(g->h_all.get() + g->off_dev);
+  SmpcReduceArgs* hr = reinterpret_cast<SmpcReduceArgs*>(g->h_all.get() + g->off_red);
+  SmpcWaveGeom* hg = reinterpret_cast<SmpcWaveGeom*>(g->h_all.get() + g->off_geo);
   for (const Launch& l : launches) {
     for (uint32_t j = l.first; j < l.first + l.count; ++j) {
       const uint32_t i = order[j];
@@ -255,8 +244,8 @@ int smpc_group_optimize_some(smpc_group* g, const smpc_tick_in* ins, float* cons
         rc = use_moving_seed(c, hd[j], !l.wave);
         if (rc != SMPC_OK) return rc;
       }
-      hr[j].partials = c->d_partials;
-      hr[j].tuple = c->d_tuple;
+      hr[j].partials = c->d_partials.get();
+      hr[j].tuple = c->d_tuple.get();
       // (a wave member: its own grid — the blocks beyond it wrote nothing; the lane launch: every
       // member's blocks write a partial)
       hr[j].nblk = l.wave ? c->plan.wave.grid : gridx;
@@ -274,19 +263,19 @@ int smpc_group_optimize_some(smpc_group* g, const smpc_tick_in* ins, float* cons
   }
   // one hand-over for every riding member's tick block and parameter block: CPU stores through the
   // BAR (every member's last tick was fetched: nothing reads the buffer), else a copy on the stream
-  if (c0->bar_tick) {
+  if (c0->tick.bar_tick) {
     // (only what this tick wrote: a slot is sized for the longest path, 25 KB, a tick fills ~4)
-    for (uint32_t i : order) bar_copy(g->d_all + g->slot * i, g->h_all + g->slot * i, g->ctxs[i]->tick_used);
-    bar_copy(g->d_all + g->off_dev, g->h_all + g->off_dev, g->total - g->off_dev);
+    for (uint32_t i : order) bar_copy(g->d_all.get() + g->slot * i, g->h_all.get() + g->slot * i, g->ctxs[i]->tick.used);
+    bar_copy(g->d_all.get() + g->off_dev, g->h_all.get() + g->off_dev, g->total - g->off_dev);
     bar_flush(c0);
   }
-  else HIPCK(c0, hipMemcpyAsync(g->d_all, g->h_all, g->total, hipMemcpyHostToDevice, g->stream));
+  else HIPCK(c0, hipMemcpyAsync(g->d_all.get(), g->h_all.get(), g->total, hipMemcpyHostToDevice, g->stream));
   // (the footprint tables of a MODE 4 member and the collision table of any member went out in
   // prepare_tick on c->stream, which is this stream while the context is grouped: in front of these)
   for (const Launch& l : launches) {
-    const SmpcDev* d_dev = reinterpret_cast<const SmpcDev*>(g->d_all + g->off_dev) + l.first;
+    const SmpcDev* d_dev = reinterpret_cast<const SmpcDev*>(g->d_all.get() + g->off_dev) + l.first;
     if (l.wave) {
-      HIPCK(c0, wave_launch_many(l.wave, d_dev, reinterpret_cast<const SmpcWaveGeom*>(g->d_all + g->off_geo) + l.first,
+      HIPCK(c0, wave_launch_many(l.wave, d_dev, reinterpret_cast<const SmpcWaveGeom*>(g->d_all.get() + g->off_geo) + l.first,
                                  l.count, l.grid, l.lds, pass_block(1), g->stream));
     } else {
       HIPCK(c0, lane_launch(inst, c0->dev, d_dev, l.count, L, l.grid, g->ctxs[lane_first]->plan.lane.block, g->stream));
@@ -294,7 +283,7 @@ int smpc_group_optimize_some(smpc_group* g, const smpc_tick_in* ins, float* cons
     g->launched = true;
     if (l.count >= 2) g->batched_launches++;
   }
-  HIPCK(c0, smpc_launch_reduce_many(reinterpret_cast<const SmpcReduceArgs*>(g->d_all + g->off_red), m,
+  HIPCK(c0, smpc_launch_reduce_many(reinterpret_cast<const SmpcReduceArgs*>(g->d_all.get() + g->off_red), m,
                                     T, g->stream));
   g->batched_ticks++;
   const auto t_launch = now();

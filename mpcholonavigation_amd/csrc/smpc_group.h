@@ -13,11 +13,12 @@ extern "C" {
 struct smpc_group {
   std::vector<smpc_ctx*> ctxs;
   std::vector<hipStream_t> saved_stream;
-  std::vector<uint8_t*> saved_h_tick, saved_d_tick;
-  uint8_t* h_all = nullptr;   // pinned: n tick blocks, then SmpcDev[n], SmpcReduceArgs[n], SmpcWaveGeom[n]
-  uint8_t* d_all = nullptr;
+  // n tick blocks, then SmpcDev[n], SmpcReduceArgs[n], SmpcWaveGeom[n].  While the group stands, each
+  // member's tick views (smpc_ctx.h: TickBlock) point at its slot of the two; the group owns them
+  smpc_impl::PinnedBuf<uint8_t> h_all;
+  smpc_impl::DevBuf<uint8_t> d_all;
   size_t slot = 0, off_dev = 0, off_red = 0, off_geo = 0, total = 0;
-  hipStream_t stream = nullptr;
+  hipStream_t stream = nullptr;   // the first member's own stream: not the group's to destroy
   uint64_t batched_ticks = 0, single_ticks = 0;
   uint64_t batched_launches = 0;   // scoring launches that carried two or more members (smpc_group_stats)
   // a batched launch went out and not every riding member's fetch_out has returned since: a round
@@ -31,12 +32,9 @@ struct smpc_group {
   // the members' float regions in ONE allocation (GroupStatsArena in smpc_stats.cpp), sized at the
   // first grouped breakdown and again when the members taken or their batch sizes ask for more; the
   // reduction's double partials likewise; the results' pinned landing place
-  float* d_stats = nullptr;
-  size_t stats_cap = 0;        // floats
-  double* d_stats_part = nullptr;
-  size_t stats_part_cap = 0;   // doubles
-  float* h_stats_out = nullptr;
-  size_t stats_out_cap = 0;    // floats
+  smpc_impl::DevBuf<float> d_stats;
+  smpc_impl::DevBuf<double> d_stats_part;
+  smpc_impl::PinnedBuf<float> h_stats_out;
   bool stats_lds_set = false;
   uint64_t breakdown_batched = 0, breakdown_single = 0;   // member-breakdowns by route (smpc_group_breakdown_counts)
 };

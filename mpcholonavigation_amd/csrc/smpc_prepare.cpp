@@ -266,8 +266,8 @@ void remember_furthest(smpc_ctx* c, const smpc_tick_in* in, float F)
   // drift doubles it (observed: 1.55 scoring passes per tick).  Such ticks update a smoothed
   // estimate instead — the next prediction starts from F' + 0.4 (F - F'), F' the geometric
   // prediction of this tick — and leave the drift alone.
-  const bool fresh_noise = c->noise_gen != c->pred.noise_gen_remembered;
-  c->pred.noise_gen_remembered = c->noise_gen;
+  const bool fresh_noise = c->noise.noise_gen != c->pred.noise_gen_remembered;
+  c->pred.noise_gen_remembered = c->noise.noise_gen;
   float F_next = F;
   if (c->pred.hint_Fp_valid) {
     const float d = F - c->pred.hint_Fp;
@@ -396,7 +396,7 @@ void predict_hint(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
 int check_tick(smpc_ctx* c, const smpc_tick_in* in)
 {
   if (!c || !in) return SMPC_ERR_INVALID;
-  if (!c->have_noise) return fail(c, SMPC_ERR_STATE, "no noise: call smpc_set_noise or smpc_seed");
+  if (!c->noise.have_noise) return fail(c, SMPC_ERR_STATE, "no noise: call smpc_set_noise or smpc_seed");
   if (in->path_len > 0 && (!in->path_x || !in->path_y || !in->path_yaw))
     return fail(c, SMPC_ERR_INVALID, "path arrays missing");
   if (in->path_len > SMPC_MAX_PATH)
@@ -506,7 +506,7 @@ static void path_tables(const HostCostmap& map, const smpc_tick_in* in, uint32_t
       if (!world_to_map(map, px[i], py[i], mx, my)) {
         v = 0;
       } else {
-        const uint8_t cost = map.cells[static_cast<size_t>(my) * map.W + mx];
+        const uint8_t cost = map.cells.get()[static_cast<size_t>(my) * map.W + mx];
         if (cost == SMPC_COST_LETHAL || cost == SMPC_COST_INSCRIBED) v = 0;
         else if (cost == SMPC_COST_NO_INFORMATION) v = map.track_unknown ? 1 : 0;
       }
@@ -634,7 +634,7 @@ static int plan_wave(smpc_ctx* c, uint32_t window_bytes, uint32_t P, uint32_t ns
 static bool lane_eligible(const smpc_ctx* c, uint32_t gates, int mode_now, uint32_t step)
 {
   const uint32_t T = c->cfg.time_steps;
-  return c->use_tpr && (mode_now == 0 || mode_now == 3) && T <= kLaneMaxT &&
+  return c->noise.use_tpr && (mode_now == 0 || mode_now == 3) && T <= kLaneMaxT &&
     lane_select(gates, T, T > 64, false, c->acker_r, false) != nullptr &&
     !((gates & SD_PATH_ANGLE) && c->pang_any) && !((gates & SD_PATH_ALIGN) && step != 4);
 }
@@ -658,7 +658,7 @@ static bool lane_reread_form(const smpc_ctx* c, uint32_t gates)
 static bool lane_power_rows(const smpc_ctx* c, uint32_t gates, int mode_now, uint32_t step, bool rr)
 {
   const uint32_t T = c->cfg.time_steps, B = c->cfg.batch_size;
-  return mode_now == 2 && c->score_mode_for(c->critics) == 2 && c->use_tpr && !rr && T <= 64 && step == 4 &&
+  return mode_now == 2 && c->score_mode_for(c->critics) == 2 && c->noise.use_tpr && !rr && T <= 64 && step == 4 &&
     B >= kLaneMinBatch && !(gates & (SD_STORE_TRAJ | SD_USE_PATH_YAW | SD_EXTRA_CRITICS)) &&
     lane_select(gates, T, false, false, c->acker_r, true) != nullptr;
 }
@@ -852,16 +852,16 @@ static int plan_launch(smpc_ctx* c, const smpc_tick_in* in, uint32_t gates, uint
 // the context.
 
 // the tick block's regions in its host copy (TickLayout's offsets as typed pointers)
-struct TickBlock {
+struct TickFields {
   uint8_t* h;
   float *px, *py, *pyaw, *D;
   uint32_t* pf_idx;
   uint8_t *pvalid, *pa_active, *pang_active, *pal_active;
   float *lut_cost, *prune;
 };
-static TickBlock tick_block(uint8_t* h, const TickLayout& tl)
+static TickFields tick_block(uint8_t* h, const TickLayout& tl)
 {
-  TickBlock b{};
+  TickFields b{};
   b.h = h;
   b.px = reinterpret_cast<float*>(h + tl.px);
   b.py = reinterpret_cast<float*>(h + tl.py);
@@ -878,7 +878,7 @@ static TickBlock tick_block(uint8_t* h, const TickLayout& tl)
 }
 
 // the control sequence (vy row zeroed for a non-holonomic model) and the plan into the tick block
-static void copy_plan(const TickBlock& b, const TickLayout& tl, const smpc_tick_in* in, const float* u_in, uint32_t T,
+static void copy_plan(const TickFields& b, const TickLayout& tl, const smpc_tick_in* in, const float* u_in, uint32_t T,
                       bool holonomic)
 {
   const uint32_t P = in->path_len;
@@ -915,7 +915,7 @@ static FirstPoint first_point(const smpc_tick_in* in, bool holonomic, float dt, 
   if (map.set) {
     unsigned mx, my;
     if (world_to_map(map, x00, y00, mx, my))
-      cost_t0 = map.cells[static_cast<size_t>(my) * map.W + mx];
+      cost_t0 = map.cells.get()[static_cast<size_t>(my) * map.W + mx];
   }
   return FirstPoint{yaw0, cos0, sin0, svx, svy, swz, x00, y00, cost_t0};
 }
@@ -1061,13 +1061,13 @@ static int upload_collision_luts(smpc_ctx* c, const smpc_tick_in* in, uint32_t g
     const uint64_t key = (c->map_version << 20) ^ (c->critics_version << 4) ^ (near_goal ? 1u : 0u) ^
       ((gates & (SD_FP_OBSTACLES | SD_FP_COST)) ? 2u : 0u) ^ (cost_only ? 4u : 0u) ^ (near_goal_cost ? 8u : 0u);
     if (!c->lut_valid || key != c->lut_key) {
-      build_lut(c->map, cr.obstacles, near_goal, c->h_lut, false, false, cost_only ? lut_cost : nullptr);
-      HIPCK(c, hipMemcpyAsync(c->d_lut, c->h_lut, 256 * sizeof(SmpcLut), hipMemcpyHostToDevice,
+      build_lut(c->map, cr.obstacles, near_goal, c->h_lut.get(), false, false, cost_only ? lut_cost : nullptr);
+      HIPCK(c, hipMemcpyAsync(c->d_lut.get(), c->h_lut.get(), 256 * sizeof(SmpcLut), hipMemcpyHostToDevice,
                               c->stream));
       if (gates & (SD_FP_OBSTACLES | SD_FP_COST)) {
-        build_lut(c->map, cr.obstacles, near_goal, c->h_lut_fp, true, false);
-        build_lut(c->map, cr.obstacles, near_goal, c->h_lut_fp + 256, true, true);
-        HIPCK(c, hipMemcpyAsync(c->d_lut_fp, c->h_lut_fp, 512 * sizeof(SmpcLut), hipMemcpyHostToDevice,
+        build_lut(c->map, cr.obstacles, near_goal, c->h_lut_fp.get(), true, false);
+        build_lut(c->map, cr.obstacles, near_goal, c->h_lut_fp.get() + 256, true, true);
+        HIPCK(c, hipMemcpyAsync(c->d_lut_fp.get(), c->h_lut_fp.get(), 512 * sizeof(SmpcLut), hipMemcpyHostToDevice,
                                 c->stream));
       }
       c->lut_key = key;
@@ -1090,7 +1090,7 @@ static int upload_collision_luts(smpc_ctx* c, const smpc_tick_in* in, uint32_t g
 // ends behind that header: 512 bytes less through the BAR on every small tick.
 // Runs after predict_hint (it reads the hint) and before plan_launch: c->plan is still the
 // PREVIOUS tick's.  Returns the bytes of the block to hand over.
-static size_t prune_table_for_tick(smpc_ctx* c, const TickBlock& b, const TickLayout& tl, uint32_t P)
+static size_t prune_table_for_tick(smpc_ctx* c, const TickFields& b, const TickLayout& tl, uint32_t P)
 {
   const float* px = b.px;
   const float* py = b.py;
@@ -1121,7 +1121,7 @@ static size_t prune_table_for_tick(smpc_ctx* c, const TickBlock& b, const TickLa
 
 // how the kernels get the tick block: the base address they read it from, or inside their arguments
 struct HandOver {
-  const uint8_t* base;   // pinned host memory (SMPC_PINNED_TICK=1) or c->d_tick
+  const uint8_t* base;   // pinned host memory (SMPC_PINNED_TICK=1) or c->tick.d_tick
   bool inline_tick;
 };
 // The tick's number and canary, then the block to the device: CPU stores through the BAR, a copy
@@ -1131,25 +1131,25 @@ struct HandOver {
 static int hand_over_tick_block(smpc_ctx* c, uint32_t gates, const TickLayout& tl, size_t tick_bytes, HandOver& ho)
 {
   const uint32_t T = c->cfg.time_steps;
-  uint8_t* h = c->h_tick;
+  uint8_t* h = c->tick.h_tick;
   // small ticks travel inside the kernel arguments (SmpcDev::tick_bytes) instead of a copy of
   // their own; the CostCritic table (general pass only) is not part of that
   // (contexts of the wave-per-rollout pass only: see smpc_lane.hip for why not the other)
-  const bool inline_tick = !c->defer_upload && !c->use_tpr && T <= 64 && tl.lut_cost - tl.px <= SMPC_INLINE_TICK_CAP &&
+  const bool inline_tick = !c->defer_upload && !c->noise.use_tpr && T <= 64 && tl.lut_cost - tl.px <= SMPC_INLINE_TICK_CAP &&
     !c->knobs.no_inline_tick;
   // SMPC_PINNED_TICK=1 (experiment): no copy at all — the kernels read the tick block where the
   // host assembled it, in pinned host memory.  Measured (tools/tail_ab.py SMPC_PINNED_TICK=1) and
   // not the default: every block of the grid fetches its ~2 KB across PCIe, uncached.
   const bool pinned_tick = c->knobs.pinned_tick && !c->defer_upload && !inline_tick;
-  const uint8_t* const tb = pinned_tick ? h : c->d_tick;
+  const uint8_t* const tb = pinned_tick ? h : c->tick.d_tick;
   // the tick block's number: written last, echoed by block 0 of every pass that reads the block
   // from device memory (SmpcDev::canary)
-  if (++c->tick_no == 0) ++c->tick_no;
-  *reinterpret_cast<uint32_t*>(h + tl.canary) = c->tick_no;
-  c->tick_used = tick_bytes;
-  const bool bar = c->bar_tick && !c->defer_upload && !pinned_tick && !inline_tick;
+  if (++c->tick.no == 0) ++c->tick.no;
+  *reinterpret_cast<uint32_t*>(h + tl.canary) = c->tick.no;
+  c->tick.used = tick_bytes;
+  const bool bar = c->tick.bar_tick && !c->defer_upload && !pinned_tick && !inline_tick;
   // (whoever uploads: this ctx or its group; the in-launch reduction experiment does not carry it)
-  c->canary_expect = (!pinned_tick && !inline_tick && !c->knobs.fused_reduce) ? c->tick_no : 0u;
+  c->tick.canary_expect = (!pinned_tick && !inline_tick && !c->knobs.fused_reduce) ? c->tick.no : 0u;
   if (bar) {
     // no kernel of an earlier tick may still read the block (every tick ends with fetch_out;
     // a tick abandoned on an error does not)
@@ -1159,16 +1159,16 @@ static int hand_over_tick_block(smpc_ctx* c, uint32_t gates, const TickLayout& t
     }
     // SMPC_DEBUG_STALE_TICK=n (tests of the guard): tick n's block is NOT handed over — the pass
     // reads the previous tick's, echoes its number, and fetch_out has to fail the tick
-    if (c->knobs.stale_tick && c->tick_no == c->knobs.stale_tick) {
+    if (c->knobs.stale_tick && c->tick.no == c->knobs.stale_tick) {
     } else {
-      bar_copy(c->d_tick, h, tick_bytes);
+      bar_copy(c->tick.d_tick, h, tick_bytes);
       bar_flush(c);
     }
   } else if (!c->defer_upload && !pinned_tick) {
     if (!inline_tick)
-      HIPCK(c, hipMemcpyAsync(c->d_tick, h, tick_bytes, hipMemcpyHostToDevice, c->stream));
+      HIPCK(c, hipMemcpyAsync(c->tick.d_tick, h, tick_bytes, hipMemcpyHostToDevice, c->stream));
     else if (gates & SD_COST)
-      HIPCK(c, hipMemcpyAsync(c->d_tick + tl.lut_cost, h + tl.lut_cost, 256 * sizeof(float), hipMemcpyHostToDevice,
+      HIPCK(c, hipMemcpyAsync(c->tick.d_tick + tl.lut_cost, h + tl.lut_cost, 256 * sizeof(float), hipMemcpyHostToDevice,
                               c->stream));
   }
   ho.base = tb;
@@ -1190,11 +1190,11 @@ static void fill_dev_state(smpc_ctx* c, const smpc_tick_in* in, uint32_t nsamp, 
   d.x0 = in->pose_x; d.y0 = in->pose_y;
   d.yaw0 = fp.yaw0; d.cos0 = fp.cos0; d.sin0 = fp.sin0;
   d.svx = fp.svx; d.svy = fp.svy; d.swz = fp.swz; d.dt = c->cfg.model_dt;
-  d.nvx = c->d_nvx; d.nvy = c->d_nvy; d.nwz = c->d_nwz;
-  d.tvx = c->d_tvx; d.tvy = c->d_tvy; d.twz = c->d_twz;
+  d.nvx = c->noise.cur.nvx.get(); d.nvy = c->noise.cur.nvy.get(); d.nwz = c->noise.cur.nwz.get();
+  d.tvx = c->noise.cur.tvx.get(); d.tvy = c->noise.cur.tvy; d.twz = c->noise.cur.twz;
   d.u = reinterpret_cast<const float*>(tb + tl.u);
-  d.traj_x = c->d_traj[0]; d.traj_y = c->d_traj[1]; d.traj_yaw = c->d_traj[2];
-  d.map = c->d_map; d.W = c->map.W; d.H = c->map.H;
+  d.traj_x = c->d_traj[0].get(); d.traj_y = c->d_traj[1].get(); d.traj_yaw = c->d_traj[2].get();
+  d.map = c->d_map.get(); d.W = c->map.W; d.H = c->map.H;
   d.ox = c->map.ox; d.oy = c->map.oy; d.res = c->map.res;
   d.cost_t0 = fp.cost_t0;
   d.x00f = fp.x00; d.y00f = fp.y00;
@@ -1210,7 +1210,7 @@ static void fill_dev_state(smpc_ctx* c, const smpc_tick_in* in, uint32_t nsamp, 
     const double eps = 2.0 * (e_o * rinv + 3.1 * 5.9604644775390625e-08 * qmax) + 1e-7;
     d.cell_eps = static_cast<float>(std::min(eps, 0.5));
   }
-  d.lut = c->d_lut;
+  d.lut = c->d_lut.get();
   d.px = reinterpret_cast<const float*>(tb + tl.px);
   d.py = reinterpret_cast<const float*>(tb + tl.py);
   d.pyaw = reinterpret_cast<const float*>(tb + tl.pyaw);
@@ -1222,10 +1222,10 @@ static void fill_dev_state(smpc_ctx* c, const smpc_tick_in* in, uint32_t nsamp, 
   d.lut_cost = reinterpret_cast<const float*>(tb + tl.lut_cost);
   d.pang_active = tb + tl.pang_active;
   d.pal_active = tb + tl.pal_active;
-  d.timeline = c->d_timeline;
-  d.canary_echo = c->canary_expect ? 1u : 0u;
-  d.partials = c->d_partials;
-  d.furthest_out = reinterpret_cast<uint32_t*>(c->d_furthest);
+  d.timeline = c->d_timeline.get();
+  d.canary_echo = c->tick.canary_expect ? 1u : 0u;
+  d.partials = c->d_partials.get();
+  d.furthest_out = reinterpret_cast<uint32_t*>(c->d_furthest.get());
 }
 
 // the critics' parameters as the kernels take them, and the optimizer's (gamma terms, temperature)
@@ -1286,9 +1286,9 @@ static void fill_dev_critics(smpc_ctx* c, const smpc_tick_in* in, const float* p
 static void fill_dev_footprint_inline(smpc_ctx* c, uint32_t gates, const TickLayout& tl, bool inline_tick)
 {
   const uint32_t T = c->cfg.time_steps;
-  const uint8_t* h = c->h_tick;
+  const uint8_t* h = c->tick.h_tick;
   SmpcDev& d = c->dev;
-  d.lut_fp = c->d_lut_fp;
+  d.lut_fp = c->d_lut_fp.get();
   d.fp_n = static_cast<uint32_t>(c->fp_x.size());
   for (uint32_t i = 0; i < d.fp_n; ++i) {
     d.fp_x[i] = c->fp_x[i];
@@ -1326,8 +1326,8 @@ int prepare_tick(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
   HIPCK(c, hipSetDevice(c->device));
 
   const TickLayout tl = tick_layout(T, std::max(P, 1u));
-  if (tl.total > c->tick_cap) return fail(c, SMPC_ERR_INVALID, "tick block overflow");
-  const TickBlock b = tick_block(c->h_tick, tl);
+  if (tl.total > c->tick.cap) return fail(c, SMPC_ERR_INVALID, "tick block overflow");
+  const TickFields b = tick_block(c->tick.h_tick, tl);
   copy_plan(b, tl, in, u_in, T, c->holonomic);
 
   uint32_t gates = 0, nsamp = 0;
@@ -1367,7 +1367,7 @@ int prepare_tick(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
   predict_hint(c, in, u_in);
   const size_t tick_bytes = prune_table_for_tick(c, b, tl, P);
   // (the profile's first event: between the prune table and the hand-over)
-  if (c->cfg.flags & SMPC_FLAG_PROFILE) HIPCK(c, hipEventRecord(c->ev0, c->stream));
+  if (c->cfg.flags & SMPC_FLAG_PROFILE) HIPCK(c, hipEventRecord(c->ev0.get(), c->stream));
   HandOver ho{};
   rc = hand_over_tick_block(c, gates, tl, tick_bytes, ho);
   if (rc != SMPC_OK) return rc;

@@ -60,14 +60,14 @@ int smpc_shard_begin(smpc_ctx* c, const smpc_tick_in* in, const float* u_in)
   // What smpc_shard_combine hands to the furthest-point predictor, copied: the caller owns *in
   // and its arrays and may free or reuse them as soon as this call returns (include/smpc.h:
   // "the library copies before returning and never retains host pointers").
-  c->step_in = *in;
-  c->step_px.assign(in->path_x, in->path_x + in->path_len);
-  c->step_py.assign(in->path_y, in->path_y + in->path_len);
-  c->step_in.path_x = c->step_px.data();
-  c->step_in.path_y = c->step_py.data();
-  c->step_in.path_yaw = nullptr;          // (not read after this call)
-  c->step_in.path_pts_valid = nullptr;
-  c->step_remembered = false;
+  c->shard.step_in = *in;
+  c->shard.step_px.assign(in->path_x, in->path_x + in->path_len);
+  c->shard.step_py.assign(in->path_y, in->path_y + in->path_len);
+  c->shard.step_in.path_x = c->shard.step_px.data();
+  c->shard.step_in.path_y = c->shard.step_py.data();
+  c->shard.step_in.path_yaw = nullptr;          // (not read after this call)
+  c->shard.step_in.path_pts_valid = nullptr;
+  c->shard.step_remembered = false;
   return SMPC_OK;
 }
 
@@ -116,12 +116,12 @@ int smpc_shard_combine(smpc_ctx* c, const float* d_tuples, uint32_t n_tuples, fl
   rc = fetch_out(c);
   if (rc != SMPC_OK) return rc;
   const TickResult res = tick_result(c);
-  memcpy(u_out, c->h_out, 3 * c->cfg.time_steps * sizeof(float));
+  memcpy(u_out, c->h_out.get(), 3 * c->cfg.time_steps * sizeof(float));
   // the predictor's state advances once per tick (a re-scored tick combines twice: same value)
   const bool need_f = (c->gate_flags & SD_NEED_FURTHEST) != 0;
-  if (need_f && !c->step_remembered) {
-    remember_furthest(c, &c->step_in, res.F_local());
-    c->step_remembered = true;
+  if (need_f && !c->shard.step_remembered) {
+    remember_furthest(c, &c->shard.step_in, res.F_local());
+    c->shard.step_remembered = true;
   }
   const bool obstacles_scored = (scoring_flags(c, c->fail_in) & (SD_OBSTACLES | SD_COST)) != 0;
   // (the index is reported whether or not a critic asked for it)
@@ -147,27 +147,25 @@ int smpc_shard_comm_init(smpc_ctx* c, const void* id_in, int rank, int world)
   const RcclApi* r = rccl();
   if (!r) return fail(c, SMPC_ERR_UNSUPPORTED, "RCCL (librccl.so) could not be loaded");
   HIPCK(c, hipSetDevice(c->device));
-  if (c->comm) {
-    (void)r->CommDestroy(c->comm);
-    c->comm = nullptr;
+  if (c->shard.comm) {
+    (void)r->CommDestroy(c->shard.comm);
+    c->shard.comm = nullptr;
   }
   ncclUniqueId id;
   memcpy(&id, id_in, sizeof(id));
-  const ncclResult_t e = r->CommInitRank(&c->comm, world, id, rank);
+  const ncclResult_t e = r->CommInitRank(&c->shard.comm, world, id, rank);
   if (e != ncclSuccess) {
-    c->comm = nullptr;
+    c->shard.comm = nullptr;
     return fail(c, SMPC_ERR_DEVICE, std::string("ncclCommInitRank: ") +
                                    (r->GetErrorString ? r->GetErrorString(e) : "error"));
   }
   // the last exchange set up is the one smpc_shard_tick uses: drop the mailboxes
-  for (uint32_t k = 0; k < c->p2p.world; ++k)
-    if (k != c->p2p.rank && c->p2p.peer[k]) (void)hipIpcCloseMemHandle(c->p2p.peer[k]);
-  c->p2p = SmpcP2P{};
-  c->comm_rank = rank;
-  c->comm_world = world;
-  if (c->d_all) (void)hipFree(c->d_all);
-  c->d_all = nullptr;
-  HIPCK(c, hipMalloc(&c->d_all, static_cast<size_t>(world) * smpc_tuple_len(c) * sizeof(float)));
+  for (uint32_t k = 0; k < c->shard.p2p.world; ++k)
+    if (k != c->shard.p2p.rank && c->shard.p2p.peer[k]) (void)hipIpcCloseMemHandle(c->shard.p2p.peer[k]);
+  c->shard.p2p = SmpcP2P{};
+  c->shard.comm_rank = rank;
+  c->shard.comm_world = world;
+  HIPCK(c, c->shard.d_all.ensure(static_cast<size_t>(world) * smpc_tuple_len(c)));
   return SMPC_OK;
 }
 
@@ -177,8 +175,8 @@ static uint32_t p2p_slot_floats(uint32_t T) {return align_up(smpc_tuple_floats(T
 int smpc_shard_p2p_set_timeout(smpc_ctx* c, uint32_t milliseconds)
 {
   if (!c || milliseconds == 0) return fail(c, SMPC_ERR_INVALID, "timeout must be > 0 ms");
-  c->p2p_timeout_ms = milliseconds;
-  c->p2p.timeout_ticks = static_cast<unsigned long long>(milliseconds) * 100000ull;
+  c->shard.p2p_timeout_ms = milliseconds;
+  c->shard.p2p.timeout_ticks = static_cast<unsigned long long>(milliseconds) * 100000ull;
   return SMPC_OK;
 }
 
@@ -187,16 +185,18 @@ int smpc_shard_p2p_handle(smpc_ctx* c, void* handle_out, uint32_t handle_bytes)
   if (!c || !handle_out || handle_bytes < sizeof(hipIpcMemHandle_t))
     return fail(c, SMPC_ERR_INVALID, "handle buffer too small");
   HIPCK(c, hipSetDevice(c->device));
-  if (!c->p2p_mailbox) {
-    const size_t bytes = 2u * SMPC_P2P_MAX_RANKS * p2p_slot_floats(c->cfg.time_steps) * sizeof(float);
+  if (!c->shard.p2p_mailbox) {
+    const size_t floats = 2u * SMPC_P2P_MAX_RANKS * p2p_slot_floats(c->cfg.time_steps), bytes = floats * sizeof(float);
     // fine-grained: stores arriving over xGMI must be visible to this GPU's loads without a
     // cache flush in between
-    HIPCK(c, hipExtMallocWithFlags(reinterpret_cast<void**>(&c->p2p_mailbox), bytes, hipDeviceMallocFinegrained));
-    HIPCK(c, hipMemset(c->p2p_mailbox, 0, bytes));
+    void* box = nullptr;
+    HIPCK(c, hipExtMallocWithFlags(&box, bytes, hipDeviceMallocFinegrained));
+    c->shard.p2p_mailbox.adopt(static_cast<float*>(box), floats);
+    HIPCK(c, hipMemset(c->shard.p2p_mailbox.get(), 0, bytes));
     HIPCK(c, hipDeviceSynchronize());
   }
   hipIpcMemHandle_t h;
-  HIPCK(c, hipIpcGetMemHandle(&h, c->p2p_mailbox));
+  HIPCK(c, hipIpcGetMemHandle(&h, c->shard.p2p_mailbox.get()));
   memcpy(handle_out, &h, sizeof(h));
   return SMPC_OK;
 }
@@ -205,19 +205,19 @@ int smpc_shard_p2p_init(smpc_ctx* c, const void* handles, int rank, int world)
 {
   if (!c || !handles || world < 1 || world > SMPC_P2P_MAX_RANKS || rank < 0 || rank >= world)
     return fail(c, SMPC_ERR_INVALID, "bad rank/world");
-  if (!c->p2p_mailbox) return fail(c, SMPC_ERR_STATE, "smpc_shard_p2p_handle first");
+  if (!c->shard.p2p_mailbox) return fail(c, SMPC_ERR_STATE, "smpc_shard_p2p_handle first");
   // AckermannMotionModel::applyConstraints needs a launch of its own behind the combine
   // (smpc_ackermann_constrain); the exchange kernel is the tick's last launch
   if (c->acker_r >= 0.f)
     return fail(c, SMPC_ERR_UNSUPPORTED, "the mailbox exchange does not carry the Ackermann constraint");
   HIPCK(c, hipSetDevice(c->device));
   HIPCK(c, hipStreamSynchronize(c->stream));   // no exchange of an earlier set-up may still run
-  for (uint32_t r = 0; r < c->p2p.world; ++r)
-    if (r != c->p2p.rank && c->p2p.peer[r]) (void)hipIpcCloseMemHandle(c->p2p.peer[r]);
-  c->p2p = SmpcP2P{};
+  for (uint32_t r = 0; r < c->shard.p2p.world; ++r)
+    if (r != c->shard.p2p.rank && c->shard.p2p.peer[r]) (void)hipIpcCloseMemHandle(c->shard.p2p.peer[r]);
+  c->shard.p2p = SmpcP2P{};
   for (int r = 0; r < world; ++r) {
     if (r == rank) {
-      c->p2p.peer[r] = c->p2p_mailbox;
+      c->shard.p2p.peer[r] = c->shard.p2p_mailbox.get();
       continue;
     }
     hipIpcMemHandle_t h;
@@ -225,30 +225,30 @@ int smpc_shard_p2p_init(smpc_ctx* c, const void* handles, int rank, int world)
     void* p = nullptr;
     const hipError_t e = hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess);
     if (e != hipSuccess) {
-      c->p2p.world = static_cast<uint32_t>(r);   // what has been opened so far is closed with the ctx
-      c->p2p.rank = static_cast<uint32_t>(rank);
+      c->shard.p2p.world = static_cast<uint32_t>(r);   // what has been opened so far is closed with the ctx
+      c->shard.p2p.rank = static_cast<uint32_t>(rank);
       return fail(c, SMPC_ERR_DEVICE, std::string("hipIpcOpenMemHandle (rank ") + std::to_string(r) + "): " +
                                      hipGetErrorString(e));
     }
-    c->p2p.peer[r] = static_cast<float*>(p);
+    c->shard.p2p.peer[r] = static_cast<float*>(p);
   }
-  c->p2p.world = static_cast<uint32_t>(world);
-  c->p2p.rank = static_cast<uint32_t>(rank);
-  c->p2p.slot_floats = p2p_slot_floats(c->cfg.time_steps);
+  c->shard.p2p.world = static_cast<uint32_t>(world);
+  c->shard.p2p.rank = static_cast<uint32_t>(rank);
+  c->shard.p2p.slot_floats = p2p_slot_floats(c->cfg.time_steps);
   // a fresh numbering of the exchanges: no sequence word of an earlier set-up may survive in
   // the own mailbox (the caller synchronises the ranks between this call and the first tick)
-  HIPCK(c, hipMemset(c->p2p_mailbox, 0, 2u * SMPC_P2P_MAX_RANKS * c->p2p.slot_floats * sizeof(float)));
+  HIPCK(c, hipMemset(c->shard.p2p_mailbox.get(), 0, 2u * SMPC_P2P_MAX_RANKS * c->shard.p2p.slot_floats * sizeof(float)));
   // the sticky "an exchange timed out" word (device) and its host-visible mark: only this
   // collective set-up clears them
-  c->p2p.state = scratch_word(c, SMPC_SCRATCH_P2P_STATE);
-  HIPCK(c, hipMemset(c->p2p.state, 0, sizeof(uint32_t)));
+  c->shard.p2p.state = scratch_word(c, SMPC_SCRATCH_P2P_STATE);
+  HIPCK(c, hipMemset(c->shard.p2p.state, 0, sizeof(uint32_t)));
   HIPCK(c, hipDeviceSynchronize());   // (the ctx's stream is non-blocking: not ordered behind the memsets)
-  c->h_out[SMPC_RESULT_AT(c->cfg.time_steps) + SMPC_R_MARK] = SMPC_MARK_NONE;
-  c->p2p_failed = false;
-  c->p2p.timeout_ticks = static_cast<unsigned long long>(c->p2p_timeout_ms) * 100000ull;   // 100 MHz
-  c->p2p_xseq = 0;
-  c->comm_rank = rank;
-  c->comm_world = world;
+  c->h_out.get()[SMPC_RESULT_AT(c->cfg.time_steps) + SMPC_R_MARK] = SMPC_MARK_NONE;
+  c->shard.p2p_failed = false;
+  c->shard.p2p.timeout_ticks = static_cast<unsigned long long>(c->shard.p2p_timeout_ms) * 100000ull;   // 100 MHz
+  c->shard.p2p_xseq = 0;
+  c->shard.comm_rank = rank;
+  c->shard.comm_world = world;
   return SMPC_OK;
 }
 
@@ -260,9 +260,9 @@ int smpc_shard_tick(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_ti
                     int speculate)
 {
   if (!c || !in || !u_inout) return fail(c, SMPC_ERR_INVALID, "null argument");
-  const bool p2p = c->p2p.world > 0;
-  if (!p2p && !c->comm) return fail(c, SMPC_ERR_STATE, "smpc_shard_comm_init or smpc_shard_p2p_init first");
-  if (p2p && c->p2p_failed)
+  const bool p2p = c->shard.p2p.world > 0;
+  if (!p2p && !c->shard.comm) return fail(c, SMPC_ERR_STATE, "smpc_shard_comm_init or smpc_shard_p2p_init first");
+  if (p2p && c->shard.p2p_failed)
     return fail(c, SMPC_ERR_STATE,
                 "an earlier mailbox exchange timed out: this rank no longer publishes (its peers fail at their "
                 "next exchange); set the exchange up again on every rank (smpc_shard_p2p_init) and smpc_reset");
@@ -271,7 +271,7 @@ int smpc_shard_tick(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_ti
   int rc = begin_tick(c, in, u_inout);
   if (rc == SMPC_OK) rc = refuse_sharded(c);
   if (rc != SMPC_OK) return rc;
-  const uint32_t T = c->cfg.time_steps, TL = smpc_tuple_len(c), G = static_cast<uint32_t>(c->comm_world);
+  const uint32_t T = c->cfg.time_steps, TL = smpc_tuple_len(c), G = static_cast<uint32_t>(c->shard.comm_world);
   const TickResult res = tick_result(c);
   auto nccl_ok = [&](ncclResult_t e, const char* what) {
     if (e == ncclSuccess) return SMPC_OK;
@@ -279,13 +279,13 @@ int smpc_shard_tick(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_ti
   };
   // mailbox exchange: publish the tuple to every peer, wait for theirs, combine — one launch
   auto p2p_exchange = [&](int mode, const float* d_used) -> int {
-    SmpcP2P x = c->p2p;
-    x.xseq = ++c->p2p_xseq;
+    SmpcP2P x = c->shard.p2p;
+    x.xseq = ++c->shard.p2p_xseq;
     const uint32_t seq = mode == 0 && c->knobs.poll ? next_seq(c) : 0u;
     // (SMPC_MARK_PEER_LATE, the kernel's "a peer never answered" mark, is cleared by
     // smpc_shard_p2p_init only: the device may write it at any time after a launch)
-    HIPCK(c, smpc_launch_p2p_exchange(c->d_tuple, x, T, mode, c->d_furthest, c->dev.neg_inv_temp, c->c_vx_max,
-                                      c->c_vx_min, c->c_vy, c->c_wz, c->d_out, c->d_out + SMPC_RESULT_AT(T), d_used,
+    HIPCK(c, smpc_launch_p2p_exchange(c->d_tuple.get(), x, T, mode, c->d_furthest.get(), c->dev.neg_inv_temp, c->c_vx_max,
+                                      c->c_vx_min, c->c_vy, c->c_wz, c->d_out.get(), c->d_out.get() + SMPC_RESULT_AT(T), d_used,
                                       c->h_out_dev, seq, c->stream));
     return SMPC_OK;
   };
@@ -293,11 +293,11 @@ int smpc_shard_tick(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_ti
   // mode-0 exchange of the same tick then publishes nothing and reports here
   auto p2p_check = [&]() -> int {
     if (res.mark() == SMPC_MARK_NONE) return SMPC_OK;
-    c->p2p_failed = true;
+    c->shard.p2p_failed = true;
     c->pred.drop_hint();
     char msg[160];
-    snprintf(msg, sizeof(msg), "shard exchange %u: a peer's tuple did not arrive within %u ms", c->p2p_xseq,
-             c->p2p_timeout_ms);
+    snprintf(msg, sizeof(msg), "shard exchange %u: a peer's tuple did not arrive within %u ms", c->shard.p2p_xseq,
+             c->shard.p2p_timeout_ms);
     return fail(c, SMPC_ERR_DEVICE, msg);
   };
   auto gather_combine_fetch = [&](const float* d_used) -> int {
@@ -307,9 +307,9 @@ int smpc_shard_tick(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_ti
       e = fetch_out(c);
       return e != SMPC_OK ? e : p2p_check();
     }
-    int e = nccl_ok(r->AllGather(c->d_tuple, c->d_all, TL, ncclFloat32, c->comm, c->stream), "ncclAllGather");
+    int e = nccl_ok(r->AllGather(c->d_tuple.get(), c->shard.d_all.get(), TL, ncclFloat32, c->shard.comm, c->stream), "ncclAllGather");
     if (e != SMPC_OK) return e;
-    e = launch_combine(c, c->d_all, G, d_used);
+    e = launch_combine(c, c->shard.d_all.get(), G, d_used);
     if (e != SMPC_OK) return e;
     return fetch_out(c);
   };
@@ -318,7 +318,7 @@ int smpc_shard_tick(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_ti
   const bool need_f = (flags & SD_NEED_FURTHEST) != 0;
   if (need_f) flags |= SD_LOCAL_FURTHEST;   // the tuple carries the true local value
   if (speculate && need_f && c->pred.hint_valid) {
-    rc = launch_score(c, flags, nullptr, nullptr, c->pred.hint, c->d_tuple);
+    rc = launch_score(c, flags, nullptr, nullptr, c->pred.hint, c->d_tuple.get());
     if (rc == SMPC_OK) rc = gather_combine_fetch(nullptr);
     if (rc != SMPC_OK) return rc;
     float F_true = res.F_local();
@@ -327,7 +327,7 @@ int smpc_shard_tick(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_ti
       // miss: the gathered tuples carry the true batch-wide furthest point
       c->spec_misses++;
       c->pred.hint = S_true;
-      rc = launch_score(c, flags, nullptr, nullptr, S_true, c->d_tuple);
+      rc = launch_score(c, flags, nullptr, nullptr, S_true, c->d_tuple.get());
       if (rc == SMPC_OK) rc = gather_combine_fetch(nullptr);
       if (rc != SMPC_OK) return rc;
       F_true = res.F_local();
@@ -335,20 +335,20 @@ int smpc_shard_tick(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_ti
     remember_furthest(c, in, F_true);
   } else {
     if (need_f) {
-      rc = launch_furthest(c, c->d_furthest);
+      rc = launch_furthest(c, c->d_furthest.get());
       if (rc != SMPC_OK) return rc;
       if (p2p) {
         // the local furthest point travels in field [2] of an otherwise empty tuple
-        HIPCK(c, hipMemcpyAsync(c->d_tuple + 2, c->d_furthest, sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        HIPCK(c, hipMemcpyAsync(c->d_tuple.get() + 2, c->d_furthest.get(), sizeof(float), hipMemcpyDeviceToDevice, c->stream));
         rc = p2p_exchange(1, nullptr);
       } else {
-        rc = nccl_ok(r->AllReduce(c->d_furthest, c->d_furthest, 1, ncclFloat32, ncclMax, c->comm, c->stream),
+        rc = nccl_ok(r->AllReduce(c->d_furthest.get(), c->d_furthest.get(), 1, ncclFloat32, ncclMax, c->shard.comm, c->stream),
                      "ncclAllReduce");
       }
       if (rc != SMPC_OK) return rc;
     }
-    rc = launch_score(c, flags, nullptr, need_f ? c->d_furthest : nullptr, 0, c->d_tuple);
-    if (rc == SMPC_OK) rc = gather_combine_fetch(need_f ? c->d_furthest : nullptr);
+    rc = launch_score(c, flags, nullptr, need_f ? c->d_furthest.get() : nullptr, 0, c->d_tuple.get());
+    if (rc == SMPC_OK) rc = gather_combine_fetch(need_f ? c->d_furthest.get() : nullptr);
     if (rc != SMPC_OK) return rc;
     if (need_f) remember_furthest(c, in, res.F_local());
   }
@@ -358,7 +358,7 @@ int smpc_shard_tick(smpc_ctx* c, const smpc_tick_in* in, float* u_inout, smpc_ti
     // all rollouts of the WHOLE batch collide: the reference scored nothing past Obstacles
     // (critic_manager.cpp:70-73)
     failed = true;
-    rc = launch_score(c, fail_only_flags(c), nullptr, nullptr, 0, c->d_tuple);
+    rc = launch_score(c, fail_only_flags(c), nullptr, nullptr, 0, c->d_tuple.get());
     if (rc == SMPC_OK) rc = gather_combine_fetch(nullptr);
     if (rc != SMPC_OK) return rc;
   }

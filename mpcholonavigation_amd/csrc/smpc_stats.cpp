@@ -78,15 +78,15 @@ struct StatsBufs {
 };
 static StatsBufs own_bufs(const smpc_ctx* c)
 {
-  const StatsLayout l = stats_layout(c->stats_ld, c->cfg.time_steps);
-  float* base = c->d_stats;
+  const StatsLayout l = stats_layout(c->stats.ld, c->cfg.time_steps);
+  float* base = c->stats.d_stats.get();
   return StatsBufs{base + l.rows, base + l.costs, base + l.partials, base + l.furthest,
-                   reinterpret_cast<SmpcStatsOut*>(base + l.out), c->d_stats_part, c->stats_ld};
+                   reinterpret_cast<SmpcStatsOut*>(base + l.out), c->stats.d_part.get(), c->stats.ld};
 }
 
 static int ensure_buffers(smpc_ctx* c)
 {
-  if (c->d_stats) return SMPC_OK;
+  if (c->stats.d_stats) return SMPC_OK;
   const uint32_t B = c->cfg.batch_size, T = c->cfg.time_steps;
   const uint32_t ld = align_up(B, 4);
   const StatsLayout l = stats_layout(ld, T);
@@ -94,12 +94,10 @@ static int ensure_buffers(smpc_ctx* c)
   const uint32_t S = stats_reduce_slices(B, &slice);
   HIPCK(c, stats_set_lds_limit(static_cast<int>(kLdsPerCu)));
   // (d_stats last: it marks the set complete — a call that failed half way picks up where it stopped)
-  if (!c->d_stats_part)
-    HIPCK(c, hipMalloc(&c->d_stats_part, static_cast<size_t>(SMPC_STATS_ROWS + 1) * S * 4 * sizeof(double)));
-  for (hipEvent_t& e : c->ev_stats)
-    if (!e) HIPCK(c, hipEventCreate(&e));
-  c->stats_ld = ld;
-  HIPCK(c, hipMalloc(&c->d_stats, l.total * sizeof(float)));
+  HIPCK(c, c->stats.d_part.ensure(static_cast<size_t>(SMPC_STATS_ROWS + 1) * S * 4));
+  for (Event& e : c->stats.ev) HIPCK(c, e.ensure());
+  c->stats.ld = ld;
+  HIPCK(c, c->stats.d_stats.ensure(l.total));
   return SMPC_OK;
 }
 
@@ -109,7 +107,7 @@ static uint32_t scored_rows(const smpc_ctx* c, uint32_t flags, uint32_t S)
 {
   const uint32_t P = c->P;
   const TickLayout tl = tick_layout(c->cfg.time_steps, std::max(P, 1u));
-  const uint8_t* h = c->h_tick;
+  const uint8_t* h = c->tick.h_tick;
   if (S >= P) S = P ? P - 1 : 0;
   uint32_t m = 1u << SMPC_STATS_CONTROL;
   auto row = [&](bool on, uint32_t k) {if (on) m |= 1u << k;};
@@ -132,7 +130,7 @@ static uint32_t scored_rows(const smpc_ctx* c, uint32_t flags, uint32_t S)
 static int score_rows(smpc_ctx* c, const StatsBufs& sb, uint32_t flags, const float* d_furthest, SmpcStatsOut* o)
 {
   const uint32_t T = c->cfg.time_steps, ld = sb.ld;
-  const bool prof = (c->cfg.flags & SMPC_FLAG_PROFILE) != 0 && c->ev_stats[0];   // (events: ensure_buffers, a ctx's own breakdown)
+  const bool prof = (c->cfg.flags & SMPC_FLAG_PROFILE) != 0 && c->stats.ev[0].get();   // (events: ensure_buffers, a ctx's own breakdown)
   // rows the pass does not score hold zeros
   HIPCK(c, hipMemsetAsync(sb.rows, 0, static_cast<size_t>(SMPC_STATS_ROWS + 1) * ld * sizeof(float), c->stream));
   SmpcDev d = c->dev;
@@ -158,20 +156,20 @@ static int score_rows(smpc_ctx* c, const StatsBufs& sb, uint32_t flags, const fl
     if (rc != SMPC_OK) return rc;
   }
   c->launched = true;
-  if (prof) HIPCK(c, hipEventRecord(c->ev_stats[0], c->stream));
+  if (prof) HIPCK(c, hipEventRecord(c->stats.ev[0].get(), c->stream));
   HIPCK(c, stats_launch(k, d, g.lds, sb.rows, ld, g.grid, g.block, c->stream));
   if (prof) {
-    HIPCK(c, hipEventRecord(c->ev_stats[1], c->stream));
-    HIPCK(c, hipEventRecord(c->ev_stats[2], c->stream));
+    HIPCK(c, hipEventRecord(c->stats.ev[1].get(), c->stream));
+    HIPCK(c, hipEventRecord(c->stats.ev[2].get(), c->stream));
   }
   HIPCK(c, stats_launch_reduce(sb.rows, ld, sb.costs, d.B, d.k2, sb.part, sb.partials, g.grid, T, sb.out, c->stream));
-  if (prof) HIPCK(c, hipEventRecord(c->ev_stats[3], c->stream));
+  if (prof) HIPCK(c, hipEventRecord(c->stats.ev[3].get(), c->stream));
   HIPCK(c, hipMemcpyAsync(o, sb.out, sizeof(*o), hipMemcpyDeviceToHost, c->stream));
   HIPCK(c, hipStreamSynchronize(c->stream));
   c->launched = false;
   if (prof) {
-    (void)hipEventElapsedTime(&c->stats_pass_ms, c->ev_stats[0], c->ev_stats[1]);
-    (void)hipEventElapsedTime(&c->stats_reduce_ms, c->ev_stats[2], c->ev_stats[3]);
+    (void)hipEventElapsedTime(&c->stats.pass_ms, c->stats.ev[0].get(), c->stats.ev[1].get());
+    (void)hipEventElapsedTime(&c->stats.reduce_ms, c->stats.ev[2].get(), c->stats.ev[3].get());
   }
   return SMPC_OK;
 }
@@ -418,35 +416,17 @@ int smpc_group_critic_breakdown(smpc_group* g, const smpc_tick_in* ins, const fl
     GHIPCK(stats_set_lds_limit(static_cast<int>(kLdsPerCu)));   // (the re-score of a member that collides everywhere)
     g->stats_lds_set = true;
   }
-  if (g->stats_cap < a.total) {
-    // (nothing of an earlier call still runs: every call ends with a wait)
-    if (g->d_stats) (void)hipFree(g->d_stats);
-    g->d_stats = nullptr;
-    g->stats_cap = 0;
-    GHIPCK(hipMalloc(&g->d_stats, a.total * sizeof(float)));
-    g->stats_cap = a.total;
-  }
-  if (g->stats_part_cap < a.part_total) {
-    if (g->d_stats_part) (void)hipFree(g->d_stats_part);
-    g->d_stats_part = nullptr;
-    g->stats_part_cap = 0;
-    GHIPCK(hipMalloc(&g->d_stats_part, a.part_total * sizeof(double)));
-    g->stats_part_cap = a.part_total;
-  }
-  if (g->stats_out_cap < back_floats) {
-    if (g->h_stats_out) (void)hipHostFree(g->h_stats_out);
-    g->h_stats_out = nullptr;
-    g->stats_out_cap = 0;
-    GHIPCK(hipHostMalloc(&g->h_stats_out, back_floats * sizeof(float), hipHostMallocDefault));
-    g->stats_out_cap = back_floats;
-  }
+  // (grown where the members taken ask for more; nothing of an earlier call still runs: every call ends with a wait)
+  GHIPCK(g->d_stats.ensure(a.total));
+  GHIPCK(g->d_stats_part.ensure(a.part_total));
+  GHIPCK(g->h_stats_out.ensure(back_floats));
   // ---- the argument arrays -----------------------------------------------------------------------
-  SmpcDev* hd = reinterpret_cast<SmpcDev*>(g->h_all + g->off_dev);
-  SmpcWaveGeom* hg = reinterpret_cast<SmpcWaveGeom*>(g->h_all + g->off_geo);
-  SmpcDev* hfd = reinterpret_cast<SmpcDev*>(g->h_all + g->off_fdev);
-  SmpcWaveGeom* hfg = reinterpret_cast<SmpcWaveGeom*>(g->h_all + g->off_fgeo);
-  SmpcStatsDst* hdst = reinterpret_cast<SmpcStatsDst*>(g->h_all + g->off_sdst);
-  SmpcStatsReduceArgs* hred = reinterpret_cast<SmpcStatsReduceArgs*>(g->h_all + g->off_sred);
+  SmpcDev* hd = reinterpret_cast<SmpcDev*>(g->h_all.get() + g->off_dev);
+  SmpcWaveGeom* hg = reinterpret_cast<SmpcWaveGeom*>(g->h_all.get() + g->off_geo);
+  SmpcDev* hfd = reinterpret_cast<SmpcDev*>(g->h_all.get() + g->off_fdev);
+  SmpcWaveGeom* hfg = reinterpret_cast<SmpcWaveGeom*>(g->h_all.get() + g->off_fgeo);
+  SmpcStatsDst* hdst = reinterpret_cast<SmpcStatsDst*>(g->h_all.get() + g->off_sdst);
+  SmpcStatsReduceArgs* hred = reinterpret_cast<SmpcStatsReduceArgs*>(g->h_all.get() + g->off_sred);
   std::vector<StatsBufs> bufs(m);
   uint32_t nf = 0, grid_max = 0, lds_max = 0, fgrid_max = 0, flds_max = 0;
   const uint32_t block = pass_block(c0->R);
@@ -454,12 +434,12 @@ int smpc_group_critic_breakdown(smpc_group* g, const smpc_tick_in* ins, const fl
     smpc_ctx* c = g->ctxs[order[j]];
     StatsBufs& sb = bufs[j];
     sb.ld = a.ld[j];
-    sb.rows = g->d_stats + a.rows[j];
+    sb.rows = g->d_stats.get() + a.rows[j];
     sb.costs = sb.rows + static_cast<size_t>(SMPC_STATS_ROWS) * sb.ld;
-    sb.furthest = g->d_stats + a.furthest + 4 * j;
-    sb.out = reinterpret_cast<SmpcStatsOut*>(g->d_stats + a.out + a.out_floats * j);
-    sb.partials = g->d_stats + a.partials + a.partial_floats * j;
-    sb.part = g->d_stats_part + a.part[j];
+    sb.furthest = g->d_stats.get() + a.furthest + 4 * j;
+    sb.out = reinterpret_cast<SmpcStatsOut*>(g->d_stats.get() + a.out + a.out_floats * j);
+    sb.partials = g->d_stats.get() + a.partials + a.partial_floats * j;
+    sb.part = g->d_stats_part.get() + a.part[j];
     const PassGeom& pg = c->plan.wave;   // planned for every tick, whatever pass the tick itself takes
     const bool need_f = (flags[order[j]] & SD_NEED_FURTHEST) != 0;
     if (need_f) {
@@ -512,24 +492,24 @@ int smpc_group_critic_breakdown(smpc_group* g, const smpc_tick_in* ins, const fl
     r.k2 = d.k2;
   }
   // ---- one memset, one upload, the launches, one copy back, one wait -------------------------------
-  GHIPCK(hipMemsetAsync(g->d_stats, 0, a.out * sizeof(float), g->stream));
-  if (c0->bar_tick) {
+  GHIPCK(hipMemsetAsync(g->d_stats.get(), 0, a.out * sizeof(float), g->stream));
+  if (c0->tick.bar_tick) {
     // (every member's last tick or breakdown was waited for: nothing reads the blocks)
-    for (uint32_t i : order) bar_copy(g->d_all + g->slot * i, g->h_all + g->slot * i, g->ctxs[i]->tick_used);
-    bar_copy(g->d_all + g->off_dev, g->h_all + g->off_dev, g->total_stats - g->off_dev);
+    for (uint32_t i : order) bar_copy(g->d_all.get() + g->slot * i, g->h_all.get() + g->slot * i, g->ctxs[i]->tick.used);
+    bar_copy(g->d_all.get() + g->off_dev, g->h_all.get() + g->off_dev, g->total_stats - g->off_dev);
     bar_flush(c0);
   }
-  else GHIPCK(hipMemcpyAsync(g->d_all, g->h_all, g->total_stats, hipMemcpyHostToDevice, g->stream));
+  else GHIPCK(hipMemcpyAsync(g->d_all.get(), g->h_all.get(), g->total_stats, hipMemcpyHostToDevice, g->stream));
   g->launched = true;
   if (nf)
-    GHIPCK(stats_launch_furthest_many(k, reinterpret_cast<const SmpcDev*>(g->d_all + g->off_fdev),
-                                      reinterpret_cast<const SmpcWaveGeom*>(g->d_all + g->off_fgeo), nf, fgrid_max, flds_max, block,
+    GHIPCK(stats_launch_furthest_many(k, reinterpret_cast<const SmpcDev*>(g->d_all.get() + g->off_fdev),
+                                      reinterpret_cast<const SmpcWaveGeom*>(g->d_all.get() + g->off_fgeo), nf, fgrid_max, flds_max, block,
                                       g->stream));
-  GHIPCK(stats_launch_many(k, reinterpret_cast<const SmpcDev*>(g->d_all + g->off_dev),
-                           reinterpret_cast<const SmpcWaveGeom*>(g->d_all + g->off_geo),
-                           reinterpret_cast<const SmpcStatsDst*>(g->d_all + g->off_sdst), m, grid_max, lds_max, block, g->stream));
-  GHIPCK(stats_launch_reduce_many(reinterpret_cast<const SmpcStatsReduceArgs*>(g->d_all + g->off_sred), m, a.slices_max, g->stream));
-  GHIPCK(hipMemcpyAsync(g->h_stats_out, g->d_stats + a.furthest, back_floats * sizeof(float), hipMemcpyDeviceToHost, g->stream));
+  GHIPCK(stats_launch_many(k, reinterpret_cast<const SmpcDev*>(g->d_all.get() + g->off_dev),
+                           reinterpret_cast<const SmpcWaveGeom*>(g->d_all.get() + g->off_geo),
+                           reinterpret_cast<const SmpcStatsDst*>(g->d_all.get() + g->off_sdst), m, grid_max, lds_max, block, g->stream));
+  GHIPCK(stats_launch_reduce_many(reinterpret_cast<const SmpcStatsReduceArgs*>(g->d_all.get() + g->off_sred), m, a.slices_max, g->stream));
+  GHIPCK(hipMemcpyAsync(g->h_stats_out.get(), g->d_stats.get() + a.furthest, back_floats * sizeof(float), hipMemcpyDeviceToHost, g->stream));
   GHIPCK(hipStreamSynchronize(g->stream));
   g->launched = false;
   for (uint32_t i : order) g->ctxs[i]->launched = false;
@@ -539,10 +519,10 @@ int smpc_group_critic_breakdown(smpc_group* g, const smpc_tick_in* ins, const fl
     const uint32_t i = order[j];
     smpc_ctx* c = g->ctxs[i];
     SmpcStatsOut o;
-    memcpy(&o, g->h_stats_out + (a.out - a.furthest) + a.out_floats * j, sizeof(o));
+    memcpy(&o, g->h_stats_out.get() + (a.out - a.furthest) + a.out_floats * j, sizeof(o));
     uint32_t fl = flags[i], S = 0;
     bool fail_flag = c->fail_in;
-    if (fl & SD_NEED_FURTHEST) S = smpc_furthest_index(g->h_stats_out[4 * j]);
+    if (fl & SD_NEED_FURTHEST) S = smpc_furthest_index(g->h_stats_out.get()[4 * j]);
     int rc = SMPC_OK;
     if (!c->fail_in && (fl & (SD_OBSTACLES | SD_COST)) && o.non_colliding == 0.0f) {
       // (critic_manager.cpp:70-73, as the single call: the rows are those of the tick's re-score)
@@ -568,8 +548,8 @@ int smpc_group_critic_breakdown(smpc_group* g, const smpc_tick_in* ins, const fl
 int smpc_debug_stats_ms(const smpc_ctx* c, float* pass_ms, float* reduce_ms)
 {
   if (!c || !pass_ms || !reduce_ms) return SMPC_ERR_INVALID;
-  *pass_ms = c->stats_pass_ms;
-  *reduce_ms = c->stats_reduce_ms;
+  *pass_ms = c->stats.pass_ms;
+  *reduce_ms = c->stats.reduce_ms;
   return SMPC_OK;
 }
 
