@@ -639,7 +639,10 @@ int smpc_shard_combine(smpc_ctx* ctx, const float* d_tuples, uint32_t n_tuples,
 /* ---- several planning instances per launch (multi-robot fleets; BASELINE "multi-query") ----
  * Independent contexts (own noise, costmap, critics, control sequence) on one GPU whose
  * ticks are issued together: one upload, one scoring launch per scoring instance with the member
- * as the second grid dimension, one reduction launch.  Results are exactly those of
+ * as the second grid dimension, one reduction launch — and, for the riding members with moving
+ * obstacles, one launch of the moving-obstacle term per form of it (at most three: the noise
+ * layout and the motion model decide the form) in front of the scoring launches, the member as
+ * the second grid dimension there too.  Results are exactly those of
  * smpc_optimize on each context, bit for bit.
  * Which members ride a batched launch:
  *   - members whose tick takes the lane-per-rollout pass (SMPC_FLAG_LANE_PER_ROLLOUT, or a batch
@@ -683,6 +686,25 @@ int smpc_group_optimize_some(smpc_group* group, const smpc_tick_in* ins, float* 
  * more members, *single_ticks members ticked through smpc_optimize (a re-score after a missed guess
  * included).  Either pointer may be NULL; a NULL group returns SMPC_ERR_INVALID.  (ABI 3) */
 int smpc_group_stats(const smpc_group* group, uint64_t* batched_launches, uint64_t* single_ticks);
+/* smpc_set_moving_obstacles for the members of a group in one call: params[n], xy[n] (member i:
+ * [n_discs[i]][T][2] floats), radius[n] (member i: [n_discs[i]] floats), n_discs[n], take[n] as in
+ * smpc_group_optimize_some (NULL: every member).  For every member taken the meaning is exactly
+ * smpc_set_moving_obstacles(member, &params[i], xy[i], radius[i], n_discs[i]): the same checks, the
+ * same table, n_discs[i] == 0 switches the member's term off (its pointers may be NULL); a member
+ * that is not taken keeps its table, whoever set it.  Every member taken is checked before
+ * anything is written: a call that returns an error has changed no member, the message is in that
+ * member's smpc_last_error and smpc_last_error(NULL) names the member.
+ * What differs is the transport: the tables of all members are packed back to back into ONE pinned
+ * buffer of the group's and go up as ONE copy on the group's stream into ONE device allocation of
+ * the group's, behind one event, nothing waited for — their number does not depend on n.
+ * The last call wins: a later smpc_set_moving_obstacles on a member replaces that member's table
+ * with one in the member's own buffer, as ever.  A table set here belongs to the group:
+ * smpc_group_destroy switches the term off for every member whose table still lives in the
+ * group's buffer (as n == 0 does); a member whose table was set through its own handle keeps it.
+ * (An addition under ABI 3, like smpc_group_optimize_some.) */
+int smpc_group_set_moving_obstacles(smpc_group* group, const smpc_moving_obstacles_params* params,
+                                    const float* const* xy, const float* const* radius,
+                                    const uint32_t* n_discs, const uint8_t* take);
 
 /* smpc_critic_breakdown for the members of a group, the group staying a group: ins[n], u_ins[n]
  * (3*T floats each, read only), take[n] as in smpc_group_optimize_some (NULL: every member),

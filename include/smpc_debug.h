@@ -32,6 +32,17 @@ int smpc_debug_limit_ms(smpc_ctx* ctx, float* ms);
 /* SMPC_FLAG_PROFILE: GPU time of the last moving-obstacle launch */
 int smpc_debug_moving_ms(smpc_ctx* ctx, float* ms);
 
+/* launches of the grouped moving-obstacle kernels (one per form and round,
+ * however many members ride) and uploads of the group's table buffer
+ * (smpc_group_set_moving_obstacles) so far; either pointer may be NULL */
+int smpc_debug_group_moving_launches(const smpc_group* group, uint64_t* grouped_launches, uint64_t* table_uploads);
+
+/* on != 0: the group's riding members with moving obstacles keep one
+ * moving-obstacle launch each, in front of the hand-over, instead of the
+ * grouped launch (the route the grouped one replaced; same results) — for
+ * measuring the two routes in one process (SMPC_FLEET_AVOID=per_member) */
+int smpc_debug_group_moving_per_member(smpc_group* group, int on);
+
 /* SMPC_FLAG_PROFILE: GPU time of the last breakdown's scoring pass and of
  * its reduction */
 int smpc_debug_stats_ms(const smpc_ctx* ctx, float* pass_ms, float* reduce_ms);

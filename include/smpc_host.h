@@ -149,9 +149,15 @@ int sortham_fleet_stats(const sortham_fleet* fleet, uint64_t* batched_launches, 
  * obstacle per other member — a member taken this round as the trajectory of its control sequence
  * from this round's pose, one not taken as a disc standing at its last pose, one never taken left
  * out — with radius robot_radius[i] + robot_radius[j].  robot_radius[n], n the fleet's size;
- * n == 0: off (the default), every member's table cleared. */
+ * n == 0: off (the default), every member's table cleared.  The tables of a round go to the
+ * library in ONE smpc_group_set_moving_obstacles call (one upload for the fleet) and the members
+ * taken ride the group's moving-obstacle launch; SMPC_FLEET_AVOID=per_member in the environment
+ * when the fleet is created keeps one smpc_set_moving_obstacles per member — the same results. */
 int sortham_fleet_set_mutual_avoidance(sortham_fleet* fleet, const smpc_moving_obstacles_params* params,
                                        const float* robot_radius, uint32_t n);
+/* smpc_debug_group_moving_launches summed over the groups the fleet has had: launches of the grouped
+ * moving-obstacle kernels and uploads of a group's table buffer.  Either pointer may be NULL. */
+int sortham_fleet_moving_launches(const sortham_fleet* fleet, uint64_t* grouped_launches, uint64_t* table_uploads);
 /* The table that rule gives member i of n (pure host code, no fleet needed): state[n] 0 never seen,
  * 1 standing, 2 moving; pose[n][3] x, y, yaw; u[n][3][time_steps]; model_dt[n]; holonomic[n];
  * robot_radius[n].  Out: xy [discs][time_steps][2] and radius [discs] (room for n - 1 discs), *discs. */

@@ -331,6 +331,8 @@ PROTOTYPES = {
     "smpc_group_optimize_some": (C.c_int, [_ctx, C.POINTER(SmpcTickIn), C.POINTER(C.c_void_p),
                                            C.POINTER(SmpcTickOut), C.c_void_p]),
     "smpc_group_stats": (C.c_int, [_ctx, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "smpc_group_set_moving_obstacles": (C.c_int, [_ctx, C.POINTER(SmpcMovingObstaclesParams), C.POINTER(C.c_void_p),
+                                                  C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_void_p]),
     "smpc_group_critic_breakdown": (C.c_int, [_ctx, C.POINTER(SmpcTickIn), C.POINTER(C.c_void_p), C.c_void_p,
                                               C.POINTER(SmpcCriticStats), C.POINTER(C.c_void_p),
                                               C.POINTER(C.c_int32)]),
@@ -353,6 +355,8 @@ DEBUG_PROTOTYPES = {
     "smpc_debug_bar_tick": (C.c_int, [_ctx]),
     "smpc_debug_limit_ms": (C.c_int, [_ctx, C.POINTER(C.c_float)]),
     "smpc_debug_moving_ms": (C.c_int, [_ctx, C.POINTER(C.c_float)]),
+    "smpc_debug_group_moving_launches": (C.c_int, [_ctx, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "smpc_debug_group_moving_per_member": (C.c_int, [_ctx, C.c_int]),
     "smpc_debug_stats_ms": (C.c_int, [_ctx, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "smpc_debug_furthest_f": (C.c_int, [_ctx, C.POINTER(C.c_float)]),
     "smpc_debug_tail_timeline": (C.c_int, [_ctx, C.POINTER(C.c_ulonglong)]),

@@ -78,6 +78,9 @@ hipError_t smpc_launch_box_muller(const uint32_t* r0, const uint32_t* r1, uint32
 hipError_t smpc_launch_limit_noise(const SmpcLimitArgs& a, bool group_major, hipStream_t st);
 // smpc_moving.hip: the moving-obstacle term of an iteration into the passes' starting costs, from either layout
 hipError_t smpc_launch_moving_cost(const SmpcMovingArgs& a, bool group_major, hipStream_t st);
+// smpc_moving_many.hip: the same for `count` members of a group that take one form, in one launch
+hipError_t smpc_launch_moving_cost_many(const SmpcMovingMember* d_many, uint32_t count, uint32_t grid, SmpcMovingForm form,
+                                        uint32_t T, hipStream_t st);
 
 namespace smpc_impl {
 
@@ -314,18 +317,23 @@ struct Limiter {
 // Buffers: allocated by the first smpc_set_moving_obstacles with n > 0, each on its own.  Written by
 // the functions of smpc_moving_host.cpp only.  smpc_critic_breakdown seeds through seed_own_costs,
 // which writes stats_seed and leaves iter, scored, m and hit alone: they stay the last tick's.
+// `tk` / `tab_kt` / `disc` are the VIEWS the launches read (like TickBlock's): into the context's own
+// allocation tab_tk, or — after smpc_group_set_moving_obstacles, `group_table` — into the group's
+// (smpc_group.cpp: the group owns that table; smpc_group_destroy switches the term off).
 struct MovingObstacles {
   Event ev_up;                      // behind the last upload
   Event ev[2];                      // SMPC_FLAG_PROFILE: around the last smpc_moving_cost launch
   uint32_t K = 0;                   // discs in the table; 0: off
   smpc_moving_obstacles_params par{};
   DevBuf<float> tab_tk;             // [T][K]{x, y, guarded squared reach, radius}: the group-major launch's table;
-                                    // the ONE device allocation the next two point into
+                                    // the ONE device allocation of the ctx's own table
+  float* tk = nullptr;              // the [T][K] table in use: tab_tk, or a region of a group's allocation
   float* tab_kt = nullptr;          // [K][T]{x, y}: the row-major launch's
   float* disc = nullptr;            // [K]{radius, radius + margin, guarded squared reach, 0}
   PinnedBuf<float> stage;           // the same three regions, what the uploads read
   bool up_recorded = false;
   hipStream_t up_stream = nullptr;  // the stream it went out on (a kernel on another stream waits for the event)
+  bool group_table = false;         // the views point into a group's allocation, uploaded on the group's stream
   DevBuf<float> m;                  // [B] m of the last scored iteration
   DevBuf<uint8_t> hit;              // [B] its hits
   DevBuf<float> stats_seed;         // [B] the seed of smpc_critic_breakdown's own cost buffer (first use)
@@ -580,6 +588,20 @@ int use_limited_noise(smpc_ctx* c, SmpcDev& d, bool group_major);
 // never sees the bit — and, if no pass of the iteration was seeded yet, one smpc_moving_cost launch on
 // c->stream into d.costs_prev, reading the layout the pass reads.  Off, or fail_flag_in: nothing.
 int use_moving_seed(smpc_ctx* c, SmpcDev& d, bool group_major);
+// The same for a member that rides a group's batched launch: use_moving_seed's bookkeeping, and in
+// place of its launch the member's arguments into *mm for the group's ONE smpc_moving_cost_*_many
+// launch per form, which goes out behind the hand-over (u is read from the member's tick block on the
+// device).  *filled: *mm was written and is of form *form.
+int fill_moving_member(smpc_ctx* c, SmpcDev& d, bool group_major, SmpcMovingMember* mm, SmpcMovingForm* form, bool* filled);
+// smpc_set_moving_obstacles in its parts, shared with smpc_group_set_moving_obstacles: the checks of a
+// table with n > 0 (the message to c's last error), the floats the packed table takes, the table
+// packed into `stage` (its three regions, each 16-byte aligned), and the per-member capacity
+int check_moving_table(smpc_ctx* c, const smpc_moving_obstacles_params* p, const float* xy, const float* radius, uint32_t n);
+size_t moving_table_floats(uint32_t T, uint32_t n);
+size_t moving_table_capacity(uint32_t T);
+void pack_moving_table(float* stage, uint32_t T, const smpc_moving_obstacles_params* p, const float* xy, const float* radius, uint32_t n);
+// the term off: K = 0, nothing scored; the views back at the ctx's own allocation
+void moving_off(smpc_ctx* c);
 // the same for a first-iteration pass on the [B,T] noise that keeps costs of its own (the critic
 // breakdown): m into a buffer of the ctx's (allocated at the first call), which becomes
 // d.costs_prev; the tick's own m and hits (smpc_get_moving_obstacle_costs) are left alone

@@ -3,6 +3,7 @@
 // set of contexts.
 #include "smpc_ctx.h"
 #include "smpc_group.h"
+#include "../../include/smpc_debug.h"   // smpc_debug_group_moving_launches
 
 using namespace smpc_impl;
 
@@ -29,7 +30,8 @@ int smpc_group_create(smpc_ctx* const* ctxs, uint32_t n, smpc_group** out)
   g->off_dev = g->slot * n;
   g->off_red = g->off_dev + align_up(static_cast<uint32_t>(sizeof(SmpcDev)) * n, 256);
   g->off_geo = g->off_red + align_up(static_cast<uint32_t>(sizeof(SmpcReduceArgs)) * n, 256);
-  g->total = g->off_geo + align_up(static_cast<uint32_t>(sizeof(SmpcWaveGeom)) * n, 256);
+  g->off_mov = g->off_geo + align_up(static_cast<uint32_t>(sizeof(SmpcWaveGeom)) * n, 256);
+  g->total = g->off_mov + align_up(static_cast<uint32_t>(sizeof(SmpcMovingMember)) * n, 256);
   // behind what a round hands over: the further argument arrays of smpc_group_critic_breakdown
   g->off_fdev = g->total;
   g->off_fgeo = g->off_fdev + align_up(static_cast<uint32_t>(sizeof(SmpcDev)) * n, 256);
@@ -65,6 +67,7 @@ void smpc_group_destroy(smpc_group* g)
     smpc_ctx* c = g->ctxs[i];
     c->stream = g->saved_stream[i];
     c->tick.view_own();
+    if (c->mov.group_table) moving_off(c);   // the table was the group's and goes with it
     c->defer_upload = false;
     c->in_group = false;
   }
@@ -224,6 +227,8 @@ int smpc_group_optimize_some(smpc_group* g, const smpc_tick_in* ins, float* cons
   SmpcDev* hd = reinterpret_cast<SmpcDev*>(g->h_all.get() + g->off_dev);
   SmpcReduceArgs* hr = reinterpret_cast<SmpcReduceArgs*>(g->h_all.get() + g->off_red);
   SmpcWaveGeom* hg = reinterpret_cast<SmpcWaveGeom*>(g->h_all.get() + g->off_geo);
+  // the riding members with moving obstacles, by the form of smpc_moving_cost their pass's layout asks for
+  std::vector<SmpcMovingMember> mov[SMPC_MOVING_FORMS];
   for (const Launch& l : launches) {
     for (uint32_t j = l.first; j < l.first + l.count; ++j) {
       const uint32_t i = order[j];
@@ -239,10 +244,16 @@ int smpc_group_optimize_some(smpc_group* g, const smpc_tick_in* ins, float* cons
         // while grouped) ahead of the grouped pass, and its parameter block points at the limited noise
         int rc = use_limited_noise(c, hd[j], !l.wave);
         if (rc != SMPC_OK) return rc;
-        // a member with moving obstacles: its seed kernel goes out the same way, and the member keeps
-        // riding the batched launch (SD_COST_SEED is set behind the choice of the instance)
-        rc = use_moving_seed(c, hd[j], !l.wave);
+        // a member with moving obstacles keeps riding the batched launch (SD_COST_SEED is set behind
+        // the choice of the instance); its seed comes from the group's ONE smpc_moving_cost_*_many
+        // launch per form, behind the hand-over: here only its arguments
+        SmpcMovingMember mm;
+        SmpcMovingForm form;
+        bool filled = false;
+        rc = g->moving_per_member ? use_moving_seed(c, hd[j], !l.wave)
+                                  : fill_moving_member(c, hd[j], !l.wave, &mm, &form, &filled);
         if (rc != SMPC_OK) return rc;
+        if (filled) mov[form].push_back(mm);
       }
       hr[j].partials = c->d_partials.get();
       hr[j].tuple = c->d_tuple.get();
@@ -261,6 +272,15 @@ int smpc_group_optimize_some(smpc_group* g, const smpc_tick_in* ins, float* cons
       c->last_pass_kind = l.wave ? PassPlan::kWave : PassPlan::kLane;
     }
   }
+  // the moving-obstacle arguments form by form, one run per launch
+  SmpcMovingMember* hm = reinterpret_cast<SmpcMovingMember*>(g->h_all.get() + g->off_mov);
+  {
+    uint32_t at = 0;
+    for (const auto& v : mov) {
+      if (!v.empty()) memcpy(hm + at, v.data(), v.size() * sizeof(SmpcMovingMember));
+      at += static_cast<uint32_t>(v.size());
+    }
+  }
   // one hand-over for every riding member's tick block and parameter block: CPU stores through the
   // BAR (every member's last tick was fetched: nothing reads the buffer), else a copy on the stream
   if (c0->tick.bar_tick) {
@@ -270,6 +290,23 @@ int smpc_group_optimize_some(smpc_group* g, const smpc_tick_in* ins, float* cons
     bar_flush(c0);
   }
   else HIPCK(c0, hipMemcpyAsync(g->d_all.get(), g->h_all.get(), g->total, hipMemcpyHostToDevice, g->stream));
+  // the moving-obstacle term of every riding member that has one: behind the hand-over (u is read
+  // from the tick blocks it delivered), in front of the scoring launches (they start from the seed);
+  // at most one launch per form, however many members
+  {
+    const SmpcMovingMember* d_mov = reinterpret_cast<const SmpcMovingMember*>(g->d_all.get() + g->off_mov);
+    uint32_t at = 0;
+    for (int f = 0; f < SMPC_MOVING_FORMS; ++f) {
+      const uint32_t count = static_cast<uint32_t>(mov[f].size());
+      if (!count) continue;
+      uint32_t grid = 0;
+      for (const SmpcMovingMember& mm : mov[f]) grid = std::max(grid, mm.grid);
+      HIPCK(c0, smpc_launch_moving_cost_many(d_mov + at, count, grid, static_cast<SmpcMovingForm>(f), T, g->stream));
+      g->launched = true;
+      g->moving_launches++;
+      at += count;
+    }
+  }
   // (the footprint tables of a MODE 4 member and the collision table of any member went out in
   // prepare_tick on c->stream, which is this stream while the context is grouped: in front of these)
   for (const Launch& l : launches) {
@@ -328,6 +365,113 @@ int smpc_group_optimize(smpc_group* g, const smpc_tick_in* ins, float* const* u_
                         smpc_tick_out* outs)
 {
   return smpc_group_optimize_some(g, ins, u_inout, outs, nullptr);
+}
+
+// smpc_set_moving_obstacles for every member taken, with ONE staging fill, ONE upload and ONE event
+// for all of them.  Every member is checked before anything is written.
+int smpc_group_set_moving_obstacles(smpc_group* g, const smpc_moving_obstacles_params* params, const float* const* xy,
+                                    const float* const* radius, const uint32_t* n_discs, const uint8_t* take)
+{
+  if (!g) return SMPC_ERR_INVALID;
+  if (!n_discs) return fail(nullptr, SMPC_ERR_INVALID, "null argument");
+  const uint32_t n = static_cast<uint32_t>(g->ctxs.size());
+  auto taken = [&](uint32_t i) {return !take || take[i] != 0;};
+  bool any = false;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!taken(i) || n_discs[i] == 0) continue;
+    smpc_ctx* c = g->ctxs[i];
+    const int rc = (!params || !xy || !radius) ? fail(c, SMPC_ERR_INVALID, "null argument")
+                                               : check_moving_table(c, &params[i], xy[i], radius[i], n_discs[i]);
+    if (rc != SMPC_OK) {
+      (void)fail(nullptr, rc, "smpc_group_set_moving_obstacles: member " + std::to_string(i) + ": " + c->err);
+      return rc;
+    }
+    any = true;
+  }
+  smpc_ctx* c0 = g->ctxs[0];
+  const uint32_t T = c0->cfg.time_steps;
+  if (!any) {
+    // nothing to upload: the members taken switch their term off, the others keep their tables
+    for (uint32_t i = 0; i < n; ++i)
+      if (taken(i)) moving_off(g->ctxs[i]);
+    return SMPC_OK;
+  }
+  // buffers first: a call that fails here has changed no member either
+  HIPCK(c0, hipSetDevice(c0->device));
+  const size_t cap = moving_table_capacity(T) * n;
+  HIPCK(c0, g->mov_tab.ensure(cap));
+  for (auto& st : g->mov_stage) HIPCK(c0, st.ensure(cap));
+  HIPCK(c0, g->mov_ev_up.ensure(hipEventDisableTiming));
+  g->mov_at.resize(n, 0);
+  g->mov_used.resize(n, 0);
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!taken(i) || n_discs[i] == 0) continue;
+    smpc_ctx* c = g->ctxs[i];
+    HIPCK(c, c->mov.hit.ensure(c->cfg.batch_size));
+    HIPCK(c, c->mov.m.ensure(c->cfg.batch_size));
+  }
+  // the upload before this one may still be reading its staging buffer (and the one before that is
+  // older still: the buffer written now)
+  if (g->mov_up_recorded) HIPCK(c0, hipEventSynchronize(g->mov_ev_up.get()));
+  // The tables back to back in member order, each region 16-byte aligned, in the staging buffer the
+  // last upload did not read: a member taken gets its new table, a member not taken whose table
+  // lives in the group's buffer keeps it — its packed bytes move over from the other staging buffer
+  // and travel again, so that the whole is ONE run.
+  const float* src = g->mov_stage[g->mov_cur].get();
+  float* dst = g->mov_stage[g->mov_cur ^ 1].get();
+  size_t at = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    smpc_ctx* c = g->ctxs[i];
+    float* tk = g->mov_tab.get() + at;
+    if (taken(i)) {
+      if (n_discs[i] == 0) {
+        moving_off(c);
+        continue;
+      }
+      pack_moving_table(dst + at, T, &params[i], xy[i], radius[i], n_discs[i]);
+      g->mov_used[i] = moving_table_floats(T, n_discs[i]);
+      const size_t n_tk = static_cast<size_t>(T) * n_discs[i] * 4;
+      const size_t n_kt = (static_cast<size_t>(n_discs[i]) * T * 2 + 3) & ~static_cast<size_t>(3);
+      c->mov.tk = tk;
+      c->mov.tab_kt = tk + n_tk;
+      c->mov.disc = c->mov.tab_kt + n_kt;
+      c->mov.group_table = true;
+      c->mov.par = params[i];
+      c->mov.K = n_discs[i];
+      c->mov.iter = 0;
+      c->mov.scored = false;
+    } else if (c->mov.group_table) {
+      memcpy(dst + at, src + g->mov_at[i], g->mov_used[i] * sizeof(float));
+      c->mov.tab_kt = tk + (c->mov.tab_kt - c->mov.tk);
+      c->mov.disc = tk + (c->mov.disc - c->mov.tk);
+      c->mov.tk = tk;
+    } else {
+      continue;
+    }
+    g->mov_at[i] = at;
+    at += g->mov_used[i];
+  }
+  g->mov_cur ^= 1;
+  HIPCK(c0, hipMemcpyAsync(g->mov_tab.get(), dst, at * sizeof(float), hipMemcpyHostToDevice, g->stream));
+  HIPCK(c0, hipEventRecord(g->mov_ev_up.get(), g->stream));
+  g->mov_up_recorded = true;
+  g->moving_uploads++;
+  return SMPC_OK;
+}
+
+int smpc_debug_group_moving_per_member(smpc_group* g, int on)
+{
+  if (!g) return SMPC_ERR_INVALID;
+  g->moving_per_member = on != 0;
+  return SMPC_OK;
+}
+
+int smpc_debug_group_moving_launches(const smpc_group* g, uint64_t* grouped_launches, uint64_t* table_uploads)
+{
+  if (!g) return SMPC_ERR_INVALID;
+  if (grouped_launches) *grouped_launches = g->moving_launches;
+  if (table_uploads) *table_uploads = g->moving_uploads;
+  return SMPC_OK;
 }
 
 }  // extern "C"

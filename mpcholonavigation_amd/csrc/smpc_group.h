@@ -13,11 +13,11 @@ extern "C" {
 struct smpc_group {
   std::vector<smpc_ctx*> ctxs;
   std::vector<hipStream_t> saved_stream;
-  // n tick blocks, then SmpcDev[n], SmpcReduceArgs[n], SmpcWaveGeom[n].  While the group stands, each
+  // n tick blocks, then SmpcDev[n], SmpcReduceArgs[n], SmpcWaveGeom[n], SmpcMovingMember[n].  While the group stands, each
   // member's tick views (smpc_ctx.h: TickBlock) point at its slot of the two; the group owns them
   smpc_impl::PinnedBuf<uint8_t> h_all;
   smpc_impl::DevBuf<uint8_t> d_all;
-  size_t slot = 0, off_dev = 0, off_red = 0, off_geo = 0, total = 0;
+  size_t slot = 0, off_dev = 0, off_red = 0, off_geo = 0, off_mov = 0, total = 0;
   hipStream_t stream = nullptr;   // the first member's own stream: not the group's to destroy
   uint64_t batched_ticks = 0, single_ticks = 0;
   uint64_t batched_launches = 0;   // scoring launches that carried two or more members (smpc_group_stats)
@@ -25,6 +25,20 @@ struct smpc_group {
   // abandoned on an error leaves it set, and the next round waits for the stream before it writes
   // h_all / d_all again
   bool launched = false;
+  // ---- moving obstacles (smpc_group_set_moving_obstacles; the grouped launch of a round) ----
+  // the members' tables back to back: ONE device allocation (n x the capacity of a member's own), ONE
+  // upload on the group's stream and the event behind it.  The staging buffer comes in two copies
+  // that take turns: a call packs into the one the last upload did not read, and carries the tables
+  // of the members it does not take over from the other (mov_at / mov_used: where a member's table
+  // stands, in floats).  The members' table views (smpc_ctx.h: MovingObstacles) point into mov_tab.
+  smpc_impl::Event mov_ev_up;
+  smpc_impl::PinnedBuf<float> mov_stage[2];
+  int mov_cur = 0;                          // the staging copy the last upload read
+  smpc_impl::DevBuf<float> mov_tab;
+  std::vector<size_t> mov_at, mov_used;
+  bool mov_up_recorded = false;
+  uint64_t moving_launches = 0, moving_uploads = 0;   // smpc_debug_group_moving_launches
+  bool moving_per_member = false;   // smpc_debug_group_moving_per_member: use_moving_seed per rider, no grouped launch
   // ---- smpc_group_critic_breakdown (smpc_stats.cpp) ----
   // further argument arrays in h_all / d_all, behind `total` (a round never uploads them): the
   // pre-pass's parameter blocks and geometry, the members' rows, the reduction's arguments

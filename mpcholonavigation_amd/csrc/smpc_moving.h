@@ -40,4 +40,30 @@ struct SmpcMovingArgs {
   float u_arg[3 * SMPC_MOVING_MAX_T] __attribute__((aligned(16)));
 };
 
+// One member of a grouped launch (smpc_moving_many.hip: the member is blockIdx.y): SmpcMovingArgs
+// without u_arg — an array of these travels in a group's hand-over, 152 bytes a member instead of
+// 3 KB — and with the member's own grid: a block whose blockIdx.x is at or beyond it belongs to a
+// larger member's grid and does nothing.  u_dev is never null: the iteration's control sequence in
+// the member's tick block on the device (or what the limiter was given).  T: the group's.
+struct SmpcMovingMember {
+  const float* n[3];
+  const float* u_dev;
+  const float* tab;
+  const float* disc;
+  float* seed;
+  float* m_out;
+  uint8_t* hit_out;
+  uint32_t B, T, K;
+  uint32_t add;
+  double x0, y0;
+  float yaw0, cos0, sin0, dt;
+  float v0[3];
+  float collision_cost, repulsion_weight, margin;
+  uint32_t grid;      // ceil(B / 4) of the row-major form, ceil(ceil(B / 64) / 4) of the group-major form
+  uint32_t pad;
+};
+
+// the instances of a grouped launch: the row-major form (R from the group's T) and the two group-major forms
+enum SmpcMovingForm { SMPC_MOVING_RM = 0, SMPC_MOVING_GM_VY = 1, SMPC_MOVING_GM = 2, SMPC_MOVING_FORMS = 3 };
+
 #endif  // SMPC_MOVING_H_

@@ -1,8 +1,10 @@
 // fleet.cpp — see fleet.hpp.
 #include "fleet.hpp"
+#include "../../include/smpc_debug.h"   // smpc_debug_group_moving_launches
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <exception>
 
@@ -124,6 +126,11 @@ FleetOptimizer::FleetOptimizer(const std::vector<Optimizer *> & members)
   for (Optimizer * m : members_) {
     m->fleet_ = this;
   }
+  // SMPC_FLEET_AVOID=per_member: mutual avoidance keeps the per-member route (one
+  // setMovingObstacles per member and round) — to measure the two routes in one process, and a way back
+  const char * route = std::getenv("SMPC_FLEET_AVOID");
+  avoid_per_member_ = route && std::string(route) == "per_member";
+  group_table_.assign(members_.size(), 0);
   const int rc = regroup();
   if (rc != SMPC_OK) {
     for (Optimizer * m : members_) {
@@ -158,8 +165,29 @@ void FleetOptimizer::dropGroup()
   smpc_group_stats(group_, &launches, &singles);
   stats_.batched_launches += launches;
   stats_.single_ticks += singles;
+  uint64_t moving = 0, uploads = 0;
+  smpc_debug_group_moving_launches(group_, &moving, &uploads);
+  stats_.grouped_moving_launches += moving;
+  stats_.moving_table_uploads += uploads;
   smpc_group_destroy(group_);
   group_ = nullptr;
+  // a table that lived in the group's buffer went with it (smpc.h): the member gets it back through
+  // its own handle, so that the context goes on holding what the Optimizer remembers
+  for (size_t i = 0; i < members_.size() && i < group_table_.size(); ++i) {
+    Optimizer * m = members_[i];
+    if (!group_table_[i]) {
+      continue;
+    }
+    group_table_[i] = 0;
+    if (m && m->ctx_ && !m->moving_radius_.empty()) {
+      try {
+        m->pushMovingObstacles();
+      } catch (const std::exception &) {
+        // (a device error, or a member in the middle of initialize() with another horizon: what it
+        // remembers stays, and initialize() hands it to the new context or refuses it, as ever)
+      }
+    }
+  }
 }
 
 void FleetOptimizer::memberDestroyed(Optimizer * member)
@@ -190,6 +218,9 @@ int FleetOptimizer::regroup()
   if (rc != SMPC_OK) {
     group_ = nullptr;
     return fail(rc, std::string("smpc_group_create: ") + smpc_last_error(nullptr));
+  }
+  if (avoid_per_member_) {
+    smpc_debug_group_moving_per_member(group_, 1);   // the riders' moving-obstacle launches per member too
   }
   const size_t g = ctxs.size();
   ins_.assign(g, smpc_tick_in{});
@@ -327,22 +358,64 @@ int FleetOptimizer::evalControl(
           &tracks[j * static_cast<size_t>(T) * 2]);
       }
     }
-    std::vector<float> xy, radius;
-    for (size_t i = 0; i < n; ++i) {
-      if (!taken(i)) {
-        continue;
-      }
-      assembleAvoidanceTable(
-        static_cast<uint32_t>(i), static_cast<uint32_t>(n), T, state.data(), tracks.data(), avoid_radius_.data(), xy,
-        radius);
-      try {
-        if (radius.empty()) {
-          members_[i]->clearMovingObstacles();
-        } else {
-          members_[i]->setMovingObstacles(avoid_params_, xy, radius);
+    if (avoid_per_member_) {
+      std::vector<float> xy, radius;
+      for (size_t i = 0; i < n; ++i) {
+        if (!taken(i)) {
+          continue;
         }
-      } catch (const std::exception & e) {
-        return fail(SMPC_ERR_STATE, "member " + std::to_string(i) + ": " + e.what());
+        assembleAvoidanceTable(
+          static_cast<uint32_t>(i), static_cast<uint32_t>(n), T, state.data(), tracks.data(), avoid_radius_.data(), xy,
+          radius);
+        try {
+          if (radius.empty()) {
+            members_[i]->clearMovingObstacles();
+          } else {
+            members_[i]->setMovingObstacles(avoid_params_, xy, radius);
+          }
+          group_table_[i] = 0;
+        } catch (const std::exception & e) {
+          return fail(SMPC_ERR_STATE, "member " + std::to_string(i) + ": " + e.what());
+        }
+      }
+    } else {
+      // every taken member's table as above, then ONE smpc_group_set_moving_obstacles for all of them:
+      // one staging fill, one upload, one event, whatever the fleet's size
+      const size_t g = owner_.size();
+      tab_xy_.resize(n);
+      tab_r_.resize(n);
+      std::vector<smpc_moving_obstacles_params> params(g, avoid_params_);
+      std::vector<const float *> xy_ptr(g, nullptr), r_ptr(g, nullptr);
+      std::vector<uint32_t> discs(g, 0);
+      for (size_t i = 0; i < n; ++i) {
+        if (!taken(i)) {
+          continue;
+        }
+        const size_t s = static_cast<size_t>(slot_[i]);
+        assembleAvoidanceTable(
+          static_cast<uint32_t>(i), static_cast<uint32_t>(n), T, state.data(), tracks.data(), avoid_radius_.data(),
+          tab_xy_[i], tab_r_[i]);
+        xy_ptr[s] = tab_xy_[i].data();
+        r_ptr[s] = tab_r_[i].data();
+        discs[s] = static_cast<uint32_t>(tab_r_[i].size());
+      }
+      const int rc = smpc_group_set_moving_obstacles(
+        group_, params.data(), xy_ptr.data(), r_ptr.data(), discs.data(), take_.data());
+      if (rc != SMPC_OK) {
+        // all or nothing: no context has changed, and no member's remembered table either
+        return fail(rc, smpc_last_error(nullptr));
+      }
+      // what each member remembers of its moving obstacles is what its context holds now (getters,
+      // re-application after a context is rebuilt)
+      for (size_t i = 0; i < n; ++i) {
+        if (!taken(i)) {
+          continue;
+        }
+        Optimizer * m = members_[i];
+        m->moving_params_ = avoid_params_;
+        m->moving_xy_.swap(tab_xy_[i]);
+        m->moving_radius_.swap(tab_r_[i]);
+        group_table_[i] = m->moving_radius_.empty() ? 0 : 1;
       }
     }
   }
@@ -520,6 +593,10 @@ FleetStats FleetOptimizer::stats() const
     smpc_group_stats(group_, &launches, &singles);
     s.batched_launches += launches;
     s.single_ticks += singles;
+    uint64_t moving = 0, uploads = 0;
+    smpc_debug_group_moving_launches(group_, &moving, &uploads);
+    s.grouped_moving_launches += moving;
+    s.moving_table_uploads += uploads;
   }
   return s;
 }

@@ -61,6 +61,9 @@ struct FleetStats
   uint64_t batched_launches{0};   // smpc_group_stats, summed over the groups the fleet has had
   uint64_t single_ticks{0};       // (the retries below included: they are ticked alone)
   uint64_t retries{0};            // optimize() calls of the fallback loop
+  // mutual avoidance on the grouped route (smpc_debug_group_moving_launches, summed like the above):
+  uint64_t grouped_moving_launches{0};   // launches of the grouped moving-obstacle kernels
+  uint64_t moving_table_uploads{0};      // uploads of a group's table buffer (one per round)
 };
 
 // What a fleet knows of member j when it builds the others' obstacle tables.
@@ -120,8 +123,11 @@ public:
     std::vector<MemberCriticStats> & out, const std::vector<float *> & per_rollout = {});
 
   // Mutual avoidance: before a round's ticks every member taken gets the others as moving obstacles
-  // (buildMutualAvoidanceTable; Optimizer::setMovingObstacles, so the table replaces whatever the
-  // member had).  robot_radius: one per member, > 0; empty: off — the default — and every member's
+  // (buildMutualAvoidanceTable; the tables of all members taken go to the library in ONE
+  // smpc_group_set_moving_obstacles call — one upload for the fleet — and each replaces whatever the
+  // member had, in the context and in what the Optimizer remembers alike; with SMPC_FLEET_AVOID=per_member
+  // in the environment when the fleet is created: one Optimizer::setMovingObstacles per member, the
+  // same tables and results).  robot_radius: one per member, > 0; empty: off — the default — and every member's
   // table is cleared.  Throws FleetError(SMPC_ERR_INVALID) for a wrong count or values the library
   // would refuse.  Members share time_steps (smpc_group_create) and are expected to share model_dt:
   // trajectory point t of one member is then the time of point t of another.
@@ -159,6 +165,9 @@ private:
   smpc_moving_obstacles_params avoid_params_{};
   std::vector<float> avoid_radius_;
   std::vector<uint8_t> seen_;
+  bool avoid_per_member_{false};      // SMPC_FLEET_AVOID=per_member, read when the fleet is created
+  std::vector<uint8_t> group_table_;  // per member: its table lives in the group's buffer
+  std::vector<std::vector<float>> tab_xy_, tab_r_;   // per member: the round's table while it is assembled
   std::vector<double> last_pose_;     // [members][3]
   FleetStats stats_{};                // of the groups already dropped, and the retries
   std::string err_;

@@ -228,4 +228,19 @@ int sortham_fleet_stats(
   return SMPC_OK;
 }
 
+int sortham_fleet_moving_launches(const sortham_fleet * f, uint64_t * grouped_launches, uint64_t * table_uploads)
+{
+  if (!f) {
+    return SMPC_ERR_INVALID;
+  }
+  const sortham_ns::FleetStats s = f->fleet->stats();
+  if (grouped_launches) {
+    *grouped_launches = s.grouped_moving_launches;
+  }
+  if (table_uploads) {
+    *table_uploads = s.moving_table_uploads;
+  }
+  return SMPC_OK;
+}
+
 }  // extern "C"

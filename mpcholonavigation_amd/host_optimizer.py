@@ -93,6 +93,7 @@ FLEET_STATS_PROTOTYPES = {
 FLEET_AVOIDANCE_PROTOTYPES = {
     "sortham_fleet_set_mutual_avoidance": (C.c_int, [_ctx, C.POINTER(A.SmpcMovingObstaclesParams), C.c_void_p,
                                                      C.c_uint32]),
+    "sortham_fleet_moving_launches": (C.c_int, [_ctx, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "sortham_fleet_avoidance_table": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.POINTER(C.c_uint32)]),
@@ -476,3 +477,14 @@ class FleetOptimizer:
         if rc != 0:
             raise FleetError(rc, "sortham_fleet_stats")
         return SimpleNamespace(batched_launches=a.value, single_ticks=b.value, retries=c.value)
+
+    def moving_launches(self):
+        """Mutual avoidance on the grouped route so far (smpc_debug_group_moving_launches, summed over
+        the fleet's groups): grouped_launches of the grouped moving-obstacle kernels, table_uploads of
+        a group's table buffer.  Both stay 0 under SMPC_FLEET_AVOID=per_member."""
+        from types import SimpleNamespace
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        rc = self.lib.sortham_fleet_moving_launches(self.h, C.byref(a), C.byref(b))
+        if rc != 0:
+            raise FleetError(rc, "sortham_fleet_moving_launches")
+        return SimpleNamespace(grouped_launches=a.value, table_uploads=b.value)

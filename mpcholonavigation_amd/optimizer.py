@@ -454,6 +454,56 @@ class SmpcGroup:
             raise SmpcError(rc, "smpc_group_stats")
         return types.SimpleNamespace(batched_launches=launches.value, single_ticks=singles.value)
 
+    def set_moving_obstacles(self, tables, take=None):
+        """Smpc.set_moving_obstacles for the members in one call (smpc_group_set_moving_obstacles): one
+        staging fill, one upload and one event for the whole group.  tables: one entry per member —
+        None (the member's term off) or (xy [n, T, 2], radius [n][, params]) with params a dict of
+        collision_cost / repulsion_weight / margin (what is left out keeps the library's default).
+        take: one truth value per member; a member left out keeps its table.  All or nothing: on
+        an error no member has changed."""
+        n = len(self.members)
+        if len(tables) != n:
+            raise ValueError("one table (or None) per member")
+        if take is not None and len(take) != n:
+            raise ValueError("one take entry per member")
+        on = [True] * n if take is None else [bool(v) for v in take]
+        T = self.members[0].T
+        params = (A.SmpcMovingObstaclesParams * n)()
+        xys, radii = [None] * n, [None] * n
+        counts = (C.c_uint32 * n)()
+        for i in range(n):
+            self.lib.smpc_moving_obstacles_params_default(C.byref(params[i]))
+            if not on[i] or tables[i] is None:
+                continue
+            xy, radius = tables[i][0], tables[i][1]
+            for name, v in (tables[i][2] if len(tables[i]) > 2 and tables[i][2] else {}).items():
+                if name not in ("collision_cost", "repulsion_weight", "margin"):
+                    raise ValueError(f"unknown moving-obstacle parameter {name!r}")
+                setattr(params[i], name, v)
+            if xy is None or len(xy) == 0:
+                continue
+            xy = np.ascontiguousarray(xy, dtype=np.float32)
+            radius = np.ascontiguousarray(radius, dtype=np.float32).reshape(-1)
+            if xy.ndim != 3 or xy.shape[1:] != (T, 2) or radius.shape[0] != xy.shape[0]:
+                raise ValueError(f"member {i}: xy must be [n, time_steps, 2] and radius [n]")
+            xys[i], radii[i], counts[i] = xy, radius, xy.shape[0]
+        xptr = (C.c_void_p * n)(*[a.ctypes.data if a is not None else None for a in xys])
+        rptr = (C.c_void_p * n)(*[a.ctypes.data if a is not None else None for a in radii])
+        mask = None if take is None else (C.c_uint8 * n)(*[int(v) for v in on])
+        rc = self.lib.smpc_group_set_moving_obstacles(self.h, params, xptr, rptr, counts, mask)
+        if rc != 0:
+            raise SmpcError(rc, self.lib.smpc_last_error(None).decode())
+
+    def moving_launches(self):
+        """The grouped route of the moving obstacles so far (smpc_debug_group_moving_launches):
+        grouped_launches — launches of the grouped moving-obstacle kernels (one per form and round,
+        whatever the number of members); table_uploads — uploads of the group's table buffer."""
+        launches, uploads = C.c_uint64(0), C.c_uint64(0)
+        rc = self.lib.smpc_debug_group_moving_launches(self.h, C.byref(launches), C.byref(uploads))
+        if rc != 0:
+            raise SmpcError(rc, "smpc_debug_group_moving_launches")
+        return types.SimpleNamespace(grouped_launches=launches.value, table_uploads=uploads.value)
+
     def critic_stats(self, ticks, us, take=None, per_rollout=False):
         """Smpc.critic_stats for the members, the group staying a group (smpc_group_critic_breakdown):
         ticks, us — one per member, as optimize takes them, us read only.  Returns one entry per
