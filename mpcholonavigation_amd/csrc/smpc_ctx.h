@@ -8,7 +8,8 @@
 //   smpc_debug.cpp        the smpc_selftest_* and smpc_debug_* entries (include/smpc_debug.h)
 //   smpc_prepare.cpp      per-tick host work: gates, path tables, lookup tables, LDS carve-up
 //   smpc_shard.cpp        batch-sharded tick, RCCL resolved at run time
-//   smpc_group.cpp        several planning instances per launch (the group object: smpc_group.h)
+//   smpc_group.cpp        several planning instances per launch (the group object: smpc_group.h; where its
+//                         arrays stand and who rides which launch: smpc_group_layout.h)
 //   smpc_stats.cpp        per-critic breakdown of a tick (smpc_critic_breakdown) and of a group's
 //                         members (smpc_group_critic_breakdown)
 // What they allocate is held by the holders of smpc_own.h, as members of the context's parts below.

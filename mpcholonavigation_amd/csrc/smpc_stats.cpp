@@ -266,7 +266,7 @@ struct GroupStatsArena {
   std::vector<uint32_t> ld;
   size_t furthest = 0, out = 0, partials = 0, total = 0;
   size_t out_floats = 0, partial_floats = 0;   // per member
-  std::vector<size_t> part;   // per member, in doubles from d_stats_part
+  std::vector<size_t> part;   // per member, in doubles from the group's d_part (GroupStatsBufs)
   size_t part_total = 0;
   uint32_t slices_max = 0;
 };
@@ -295,6 +295,258 @@ static GroupStatsArena group_arena(const smpc_group* g, const std::vector<uint32
   return a;
 }
 
+// ---- smpc_group_critic_breakdown in its stages ------------------------------------------------------
+namespace {
+
+// What every way out of a grouped breakdown does: when it goes, every member saved is put back as it
+// was found, in reverse (the kernel name the first one saved is the one that stays).  Unless told
+// wait = false — the success path alone, which has waited — it first waits for the group's stream and
+// clears the launched flags: nothing of an abandoned call runs on.
+struct MembersPutBack {
+  smpc_group* g = nullptr;   // null: not armed, nothing to do
+  std::vector<Carried> carried;
+  std::vector<bool> saved;
+  bool wait = true;
+  MembersPutBack() = default;
+  MembersPutBack(const MembersPutBack&) = delete;
+  MembersPutBack& operator=(const MembersPutBack&) = delete;
+  void arm(smpc_group* group)
+  {
+    g = group;
+    carried.resize(g->ctxs.size());
+    saved.assign(g->ctxs.size(), false);
+  }
+  void save(uint32_t i)
+  {
+    carried[i] = save_carried(g->ctxs[i]);
+    saved[i] = true;
+  }
+  ~MembersPutBack()
+  {
+    if (!g) return;
+    if (wait) (void)hipStreamSynchronize(g->stream);
+    for (uint32_t i = static_cast<uint32_t>(saved.size()); i-- > 0;) {
+      if (!saved[i]) continue;
+      if (wait) g->ctxs[i]->launched = false;
+      restore_carried(g->ctxs[i], carried[i]);
+    }
+    if (wait) g->launched = false;
+  }
+};
+
+// the state the stages hand on
+struct GroupBreakdown {
+  // the caller's arrays
+  const smpc_tick_in* ins;
+  const float* const* u_ins;
+  const uint8_t* take;
+  smpc_critic_stats* stats;
+  float* const* per_rollout;
+  int32_t* status;
+  smpc_ctx* c0 = nullptr;   // the first member taken
+  uint32_t n = 0, T = 0;
+  const StatsManyInst* k = nullptr;   // the grouped instance (null: none for this horizon)
+  MembersPutBack put_back;
+  std::vector<uint32_t> order, flags;   // the members that ride, by member index; per member: its scoring flags
+  GroupStatsArena a;
+  std::vector<StatsBufs> bufs;          // per rider: its regions of the arena
+  uint32_t nf = 0;                      // riders that need a furthest point: the pre-pass's members
+  uint32_t grid_max = 0, lds_max = 0, fgrid_max = 0, flds_max = 0, block = 0;
+  size_t back_floats() const {return a.partials - a.furthest;}   // the furthest-point words and the results: one copy
+};
+
+// T > 64: no grouped instance (as smpc_pass_many) — one by one, each with its own upload into its
+// slot of the group's blocks, as a round ticks a member alone
+static int breakdown_one_by_one(smpc_group* g, GroupBreakdown& b)
+{
+  for (uint32_t i = 0; i < b.n; ++i) {
+    if (!group_takes(b.take, i)) continue;
+    smpc_ctx* c = g->ctxs[i];
+    c->defer_upload = false;
+    b.status[i] = b.u_ins[i] ? breakdown_carried(c, &b.ins[i], b.u_ins[i], &b.stats[i], b.per_rollout ? b.per_rollout[i] : nullptr)
+                             : fail(c, SMPC_ERR_INVALID, "null control sequence");
+    c->defer_upload = true;
+    g->count.breakdown_single++;
+    if (b.status[i] == SMPC_ERR_DEVICE) return b.status[i];
+  }
+  return SMPC_OK;
+}
+
+// prepare every member taken, each saved first; a member's own refusal lets the others go on
+static int breakdown_prepare(smpc_group* g, GroupBreakdown& b)
+{
+  b.put_back.arm(g);
+  b.flags.assign(b.n, 0u);
+  for (uint32_t i = 0; i < b.n; ++i) {
+    if (!group_takes(b.take, i)) continue;
+    smpc_ctx* c = g->ctxs[i];
+    b.put_back.save(i);
+    int rc = b.u_ins[i] ? prepare_tick(c, &b.ins[i], b.u_ins[i]) : fail(c, SMPC_ERR_INVALID, "null control sequence");
+    if (rc == SMPC_OK && c->two_coll_fp) rc = fail(c, SMPC_ERR_UNSUPPORTED, kTwoCollFp);
+    if (rc == SMPC_OK) rc = ensure_row_major(c);   // the wave-per-rollout pass reads the [B,T] tensors
+    b.status[i] = rc;
+    if (rc == SMPC_ERR_DEVICE) return rc;
+    if (rc != SMPC_OK) continue;
+    // the first iteration's flags (smpc_optimize), without the trajectory write-out
+    b.flags[i] = scoring_flags(c, c->fail_in) & ~SD_STORE_TRAJ;
+    b.order.push_back(i);
+  }
+  return SMPC_OK;
+}
+
+// the arena for the riders and the group's buffers behind it
+static int breakdown_buffers(smpc_group* g, GroupBreakdown& b)
+{
+  b.a = group_arena(g, b.order);
+  GroupStatsBufs& s = g->stats;
+  if (!s.lds_set) {
+    HIPCK(b.c0, stats_many_set_lds_limit(static_cast<int>(kLdsPerCu)));
+    HIPCK(b.c0, stats_set_lds_limit(static_cast<int>(kLdsPerCu)));   // (the re-score of a member that collides everywhere)
+    s.lds_set = true;
+  }
+  // (grown where the members taken ask for more; nothing of an earlier call still runs: every call ends with a wait)
+  HIPCK(b.c0, s.d_stats.ensure(b.a.total));
+  HIPCK(b.c0, s.d_part.ensure(b.a.part_total));
+  HIPCK(b.c0, s.h_out.ensure(b.back_floats()));
+  return SMPC_OK;
+}
+
+// the argument arrays: per rider the stats pass's parameter block, geometry, rows and reduction
+// arguments; per rider that needs a furthest point the pre-pass's parameter block and geometry
+static int breakdown_fill(smpc_group* g, GroupBreakdown& b)
+{
+  const GroupStatsArena& a = b.a;
+  const uint32_t m = static_cast<uint32_t>(b.order.size()), T = b.T;
+  SmpcDev* hd = g->arr.h_dev();
+  SmpcWaveGeom* hg = g->arr.h_geo();
+  SmpcDev* hfd = g->arr.h_fdev();
+  SmpcWaveGeom* hfg = g->arr.h_fgeo();
+  SmpcStatsDst* hdst = g->arr.h_sdst();
+  SmpcStatsReduceArgs* hred = g->arr.h_sred();
+  float* d_stats = g->stats.d_stats.get();
+  b.bufs.assign(m, StatsBufs{});
+  b.block = pass_block(b.c0->R);
+  for (uint32_t j = 0; j < m; ++j) {
+    smpc_ctx* c = g->ctxs[b.order[j]];
+    StatsBufs& sb = b.bufs[j];
+    sb.ld = a.ld[j];
+    sb.rows = d_stats + a.rows[j];
+    sb.costs = sb.rows + static_cast<size_t>(SMPC_STATS_ROWS) * sb.ld;
+    sb.furthest = d_stats + a.furthest + 4 * j;
+    sb.out = reinterpret_cast<SmpcStatsOut*>(d_stats + a.out + a.out_floats * j);
+    sb.partials = d_stats + a.partials + a.partial_floats * j;
+    sb.part = g->stats.d_part.get() + a.part[j];
+    const PassGeom& pg = c->plan.wave;   // planned for every tick, whatever pass the tick itself takes
+    const bool need_f = (b.flags[b.order[j]] & SD_NEED_FURTHEST) != 0;
+    if (need_f) {
+      // (launch_furthest's parameter block and carve-up, its word this member's own)
+      SmpcDev& d = hfd[b.nf];
+      d = c->dev;
+      const int rc = use_limited_noise(c, d, false);
+      if (rc != SMPC_OK) return rc;
+      d.flags = c->gate_flags & SD_NEED_FURTHEST;
+      d.furthest_out = reinterpret_cast<uint32_t*>(sb.furthest);
+      hfg[b.nf].lds = make_lds(0, c->P, T, b.block / 64, false);
+      hfg[b.nf].grid = pg.grid;
+      b.fgrid_max = std::max(b.fgrid_max, pg.grid);
+      b.flds_max = std::max(b.flds_max, hfg[b.nf].lds.total);
+      b.nf++;
+    }
+    // (score_rows' parameter block)
+    SmpcDev& d = hd[j];
+    d = c->dev;
+    d.flags = b.flags[b.order[j]];
+    d.d_furthest = need_f ? sb.furthest : nullptr;
+    d.furthest_hint = 0;
+    d.costs = sb.costs;
+    d.costs_prev = nullptr;
+    d.partials = sb.partials;
+    d.tail = 0;
+    {
+      int rc = use_limited_noise(c, d, false);
+      if (rc != SMPC_OK) return rc;
+      rc = seed_own_costs(c, d);   // (a member with moving obstacles: its seed kernel on the group's stream, as in a round)
+      if (rc != SMPC_OK) return rc;
+    }
+    hg[j].lds = pg.lds;
+    hg[j].grid = pg.grid;
+    b.grid_max = std::max(b.grid_max, pg.grid);
+    b.lds_max = std::max(b.lds_max, pg.lds.total);
+    hdst[j].stats = sb.rows;
+    hdst[j].ld = sb.ld;
+    SmpcStatsReduceArgs& r = hred[j];
+    r.stats = sb.rows;
+    r.costs = sb.costs;
+    r.part = sb.part;
+    r.pass_partials = sb.partials;
+    r.out = sb.out;
+    r.ld = sb.ld;
+    r.B = d.B;
+    r.S = stats_reduce_slices(d.B, &r.slice);
+    r.nblk = pg.grid;
+    r.TL = 4u + 3u * T;
+    r.k2 = d.k2;
+  }
+  return SMPC_OK;
+}
+
+// one memset, one hand-over, the launches, one copy back, one wait
+static int breakdown_run(smpc_group* g, GroupBreakdown& b)
+{
+  smpc_ctx* c0 = b.c0;
+  const GroupStatsArena& a = b.a;
+  const uint32_t m = static_cast<uint32_t>(b.order.size());
+  float* d_stats = g->stats.d_stats.get();
+  HIPCK(c0, hipMemsetAsync(d_stats, 0, a.out * sizeof(float), g->stream));
+  // (every member's last tick or breakdown was waited for: nothing reads the blocks)
+  const int rc = group_hand_over(g, c0, b.order, g->arr.at.breakdown);
+  if (rc != SMPC_OK) return rc;
+  g->launched = true;
+  if (b.nf)
+    HIPCK(c0, stats_launch_furthest_many(b.k, g->arr.d_fdev(), g->arr.d_fgeo(), b.nf, b.fgrid_max, b.flds_max, b.block, g->stream));
+  HIPCK(c0, stats_launch_many(b.k, g->arr.d_dev(), g->arr.d_geo(), g->arr.d_sdst(), m, b.grid_max, b.lds_max, b.block, g->stream));
+  HIPCK(c0, stats_launch_reduce_many(g->arr.d_sred(), m, a.slices_max, g->stream));
+  HIPCK(c0, hipMemcpyAsync(g->stats.h_out.get(), d_stats + a.furthest, b.back_floats() * sizeof(float), hipMemcpyDeviceToHost, g->stream));
+  HIPCK(c0, hipStreamSynchronize(g->stream));
+  g->launched = false;
+  for (uint32_t i : b.order) g->ctxs[i]->launched = false;
+  g->count.breakdown_batched += m;
+  return SMPC_OK;
+}
+
+// per rider: the struct, the re-score of one that collides everywhere, the rows
+static int breakdown_collect(smpc_group* g, GroupBreakdown& b)
+{
+  const GroupStatsArena& a = b.a;
+  const float* h_out = g->stats.h_out.get();
+  for (uint32_t j = 0; j < b.order.size(); ++j) {
+    const uint32_t i = b.order[j];
+    smpc_ctx* c = g->ctxs[i];
+    SmpcStatsOut o;
+    memcpy(&o, h_out + (a.out - a.furthest) + a.out_floats * j, sizeof(o));
+    uint32_t fl = b.flags[i], S = 0;
+    bool fail_flag = c->fail_in;
+    if (fl & SD_NEED_FURTHEST) S = smpc_furthest_index(h_out[4 * j]);
+    int rc = SMPC_OK;
+    if (!c->fail_in && (fl & (SD_OBSTACLES | SD_COST)) && o.non_colliding == 0.0f) {
+      // (critic_manager.cpp:70-73, as the single call: the rows are those of the tick's re-score)
+      fail_flag = true;
+      fl = fail_only_flags(c) & ~SD_STORE_TRAJ;
+      S = 0;
+      rc = score_rows(c, b.bufs[j], fl, nullptr, &o);
+    }
+    if (rc == SMPC_OK) {
+      fill_stats(c, fl, S, fail_flag, o, &b.stats[i]);
+      if (b.per_rollout && b.per_rollout[i]) rc = fetch_rows(c, b.bufs[j], b.per_rollout[i]);
+    }
+    b.status[i] = rc;
+    if (rc == SMPC_ERR_DEVICE) return rc;
+  }
+  return SMPC_OK;
+}
+
+}  // namespace
+
 }  // namespace smpc_impl
 
 using namespace smpc_impl;
@@ -315,8 +567,8 @@ int smpc_critic_breakdown(smpc_ctx* c, const smpc_tick_in* in, const float* u_in
 int smpc_group_breakdown_counts(const smpc_group* g, uint64_t* batched_members, uint64_t* single_members)
 {
   if (!g) return SMPC_ERR_INVALID;
-  if (batched_members) *batched_members = g->breakdown_batched;
-  if (single_members) *single_members = g->breakdown_single;
+  if (batched_members) *batched_members = g->count.breakdown_batched;
+  if (single_members) *single_members = g->count.breakdown_single;
   return SMPC_OK;
 }
 
@@ -328,218 +580,28 @@ int smpc_group_breakdown_counts(const smpc_group* g, uint64_t* batched_members, 
 // [B,T] copy of a lane member's noise, and the limiter of a member with acceleration limits — as in
 // a round.  Behind it: the re-score of a member whose rollouts all collide, one by one (score_rows:
 // the single call's launches into the member's regions of the arena), and the rows of the members
-// that asked for them.  Every member is put back as it was found (Carried).
+// that asked for them.  Every member is put back as it was found (Carried, MembersPutBack): on every
+// way out behind breakdown_prepare, b's destructor does it.
 int smpc_group_critic_breakdown(smpc_group* g, const smpc_tick_in* ins, const float* const* u_ins, const uint8_t* take,
                                 smpc_critic_stats* stats, float* const* per_rollout, int32_t* status)
 {
   if (!g || !ins || !u_ins || !stats || !status) return fail(nullptr, SMPC_ERR_INVALID, "null argument");
-  const uint32_t n = static_cast<uint32_t>(g->ctxs.size());
-  auto taken = [&](uint32_t i) {return !take || take[i] != 0;};
-  uint32_t first = 0;
-  while (first < n && !taken(first)) ++first;
-  if (first == n) return fail(nullptr, SMPC_ERR_INVALID, "critic breakdown: no member of the group is taken");
-  smpc_ctx* c0 = g->ctxs[first];    // (errors of the call as a whole are reported on the first member taken)
-  HIPCK(c0, hipSetDevice(c0->device));
-  if (g->launched) {
-    // the round before was abandoned between its launch and its last fetch_out (smpc_group_optimize_some)
-    HIPCK(c0, hipStreamSynchronize(g->stream));
-    g->launched = false;
-  }
-  const uint32_t T = c0->cfg.time_steps;
-  const StatsManyInst* k = stats_many_select(c0->R, T);
-  if (!k) {
-    // T > 64: no grouped instance (as smpc_pass_many) — one by one, each with its own upload into
-    // its slot of the group's blocks, as a round ticks a member alone
-    for (uint32_t i = 0; i < n; ++i) {
-      if (!taken(i)) continue;
-      smpc_ctx* c = g->ctxs[i];
-      c->defer_upload = false;
-      status[i] = u_ins[i] ? breakdown_carried(c, &ins[i], u_ins[i], &stats[i], per_rollout ? per_rollout[i] : nullptr)
-                           : fail(c, SMPC_ERR_INVALID, "null control sequence");
-      c->defer_upload = true;
-      g->breakdown_single++;
-      if (status[i] == SMPC_ERR_DEVICE) return status[i];
-    }
-    return SMPC_OK;
-  }
-  // ---- prepare every member taken -------------------------------------------------------------
-  std::vector<Carried> carried(n);
-  std::vector<bool> saved(n, false);
-  // what every way out of here does: nothing of this call runs on, every member as it was found
-  auto put_back = [&](bool wait) {
-    if (wait) (void)hipStreamSynchronize(g->stream);
-    for (uint32_t i = n; i-- > 0;) {   // (in reverse: the kernel name the first one saved is the one that stays)
-      if (!saved[i]) continue;
-      if (wait) g->ctxs[i]->launched = false;
-      restore_carried(g->ctxs[i], carried[i]);
-    }
-    if (wait) g->launched = false;
-  };
-  std::vector<uint32_t> order, flags(n, 0u);
-  for (uint32_t i = 0; i < n; ++i) {
-    if (!taken(i)) continue;
-    smpc_ctx* c = g->ctxs[i];
-    carried[i] = save_carried(c);
-    saved[i] = true;
-    int rc = u_ins[i] ? prepare_tick(c, &ins[i], u_ins[i]) : fail(c, SMPC_ERR_INVALID, "null control sequence");
-    if (rc == SMPC_OK && c->two_coll_fp) rc = fail(c, SMPC_ERR_UNSUPPORTED, kTwoCollFp);
-    if (rc == SMPC_OK) rc = ensure_row_major(c);   // the wave-per-rollout pass reads the [B,T] tensors
-    status[i] = rc;
-    if (rc == SMPC_ERR_DEVICE) {
-      put_back(true);
-      return rc;
-    }
-    if (rc != SMPC_OK) continue;   // this member's own refusal: the others go on
-    // the first iteration's flags (smpc_optimize), without the trajectory write-out
-    flags[i] = scoring_flags(c, c->fail_in) & ~SD_STORE_TRAJ;
-    order.push_back(i);
-  }
-  if (order.empty()) {
-    put_back(true);
-    return SMPC_OK;
-  }
-  const uint32_t m = static_cast<uint32_t>(order.size());
-  auto give_up = [&](int rc) {
-    put_back(true);
-    return rc;
-  };
-#define GHIPCK(call)                                                                                           \
-  do {                                                                                                         \
-    hipError_t e__ = (call);                                                                                   \
-    if (e__ != hipSuccess) return give_up(fail(c0, SMPC_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(e__))); \
-  } while (0)
-  // ---- the arena ---------------------------------------------------------------------------------
-  const GroupStatsArena a = group_arena(g, order);
-  const size_t back_floats = a.partials - a.furthest;   // the furthest-point words and the results: one copy
-  if (!g->stats_lds_set) {
-    GHIPCK(stats_many_set_lds_limit(static_cast<int>(kLdsPerCu)));
-    GHIPCK(stats_set_lds_limit(static_cast<int>(kLdsPerCu)));   // (the re-score of a member that collides everywhere)
-    g->stats_lds_set = true;
-  }
-  // (grown where the members taken ask for more; nothing of an earlier call still runs: every call ends with a wait)
-  GHIPCK(g->d_stats.ensure(a.total));
-  GHIPCK(g->d_stats_part.ensure(a.part_total));
-  GHIPCK(g->h_stats_out.ensure(back_floats));
-  // ---- the argument arrays -----------------------------------------------------------------------
-  SmpcDev* hd = reinterpret_cast<SmpcDev*>(g->h_all.get() + g->off_dev);
-  SmpcWaveGeom* hg = reinterpret_cast<SmpcWaveGeom*>(g->h_all.get() + g->off_geo);
-  SmpcDev* hfd = reinterpret_cast<SmpcDev*>(g->h_all.get() + g->off_fdev);
-  SmpcWaveGeom* hfg = reinterpret_cast<SmpcWaveGeom*>(g->h_all.get() + g->off_fgeo);
-  SmpcStatsDst* hdst = reinterpret_cast<SmpcStatsDst*>(g->h_all.get() + g->off_sdst);
-  SmpcStatsReduceArgs* hred = reinterpret_cast<SmpcStatsReduceArgs*>(g->h_all.get() + g->off_sred);
-  std::vector<StatsBufs> bufs(m);
-  uint32_t nf = 0, grid_max = 0, lds_max = 0, fgrid_max = 0, flds_max = 0;
-  const uint32_t block = pass_block(c0->R);
-  for (uint32_t j = 0; j < m; ++j) {
-    smpc_ctx* c = g->ctxs[order[j]];
-    StatsBufs& sb = bufs[j];
-    sb.ld = a.ld[j];
-    sb.rows = g->d_stats.get() + a.rows[j];
-    sb.costs = sb.rows + static_cast<size_t>(SMPC_STATS_ROWS) * sb.ld;
-    sb.furthest = g->d_stats.get() + a.furthest + 4 * j;
-    sb.out = reinterpret_cast<SmpcStatsOut*>(g->d_stats.get() + a.out + a.out_floats * j);
-    sb.partials = g->d_stats.get() + a.partials + a.partial_floats * j;
-    sb.part = g->d_stats_part.get() + a.part[j];
-    const PassGeom& pg = c->plan.wave;   // planned for every tick, whatever pass the tick itself takes
-    const bool need_f = (flags[order[j]] & SD_NEED_FURTHEST) != 0;
-    if (need_f) {
-      // (launch_furthest's parameter block and carve-up, its word this member's own)
-      SmpcDev& d = hfd[nf];
-      d = c->dev;
-      const int rc = use_limited_noise(c, d, false);
-      if (rc != SMPC_OK) return give_up(rc);
-      d.flags = c->gate_flags & SD_NEED_FURTHEST;
-      d.furthest_out = reinterpret_cast<uint32_t*>(sb.furthest);
-      hfg[nf].lds = make_lds(0, c->P, T, block / 64, false);
-      hfg[nf].grid = pg.grid;
-      fgrid_max = std::max(fgrid_max, pg.grid);
-      flds_max = std::max(flds_max, hfg[nf].lds.total);
-      nf++;
-    }
-    // (score_rows' parameter block)
-    SmpcDev& d = hd[j];
-    d = c->dev;
-    d.flags = flags[order[j]];
-    d.d_furthest = need_f ? sb.furthest : nullptr;
-    d.furthest_hint = 0;
-    d.costs = sb.costs;
-    d.costs_prev = nullptr;
-    d.partials = sb.partials;
-    d.tail = 0;
-    {
-      int rc = use_limited_noise(c, d, false);
-      if (rc != SMPC_OK) return give_up(rc);
-      rc = seed_own_costs(c, d);   // (a member with moving obstacles: its seed kernel on the group's stream, as in a round)
-      if (rc != SMPC_OK) return give_up(rc);
-    }
-    hg[j].lds = pg.lds;
-    hg[j].grid = pg.grid;
-    grid_max = std::max(grid_max, pg.grid);
-    lds_max = std::max(lds_max, pg.lds.total);
-    hdst[j].stats = sb.rows;
-    hdst[j].ld = sb.ld;
-    SmpcStatsReduceArgs& r = hred[j];
-    r.stats = sb.rows;
-    r.costs = sb.costs;
-    r.part = sb.part;
-    r.pass_partials = sb.partials;
-    r.out = sb.out;
-    r.ld = sb.ld;
-    r.B = d.B;
-    r.S = stats_reduce_slices(d.B, &r.slice);
-    r.nblk = pg.grid;
-    r.TL = 4u + 3u * T;
-    r.k2 = d.k2;
-  }
-  // ---- one memset, one upload, the launches, one copy back, one wait -------------------------------
-  GHIPCK(hipMemsetAsync(g->d_stats.get(), 0, a.out * sizeof(float), g->stream));
-  if (c0->tick.bar_tick) {
-    // (every member's last tick or breakdown was waited for: nothing reads the blocks)
-    for (uint32_t i : order) bar_copy(g->d_all.get() + g->slot * i, g->h_all.get() + g->slot * i, g->ctxs[i]->tick.used);
-    bar_copy(g->d_all.get() + g->off_dev, g->h_all.get() + g->off_dev, g->total_stats - g->off_dev);
-    bar_flush(c0);
-  }
-  else GHIPCK(hipMemcpyAsync(g->d_all.get(), g->h_all.get(), g->total_stats, hipMemcpyHostToDevice, g->stream));
-  g->launched = true;
-  if (nf)
-    GHIPCK(stats_launch_furthest_many(k, reinterpret_cast<const SmpcDev*>(g->d_all.get() + g->off_fdev),
-                                      reinterpret_cast<const SmpcWaveGeom*>(g->d_all.get() + g->off_fgeo), nf, fgrid_max, flds_max, block,
-                                      g->stream));
-  GHIPCK(stats_launch_many(k, reinterpret_cast<const SmpcDev*>(g->d_all.get() + g->off_dev),
-                           reinterpret_cast<const SmpcWaveGeom*>(g->d_all.get() + g->off_geo),
-                           reinterpret_cast<const SmpcStatsDst*>(g->d_all.get() + g->off_sdst), m, grid_max, lds_max, block, g->stream));
-  GHIPCK(stats_launch_reduce_many(reinterpret_cast<const SmpcStatsReduceArgs*>(g->d_all.get() + g->off_sred), m, a.slices_max, g->stream));
-  GHIPCK(hipMemcpyAsync(g->h_stats_out.get(), g->d_stats.get() + a.furthest, back_floats * sizeof(float), hipMemcpyDeviceToHost, g->stream));
-  GHIPCK(hipStreamSynchronize(g->stream));
-  g->launched = false;
-  for (uint32_t i : order) g->ctxs[i]->launched = false;
-  g->breakdown_batched += m;
-  // ---- per member: the struct, the re-score of one that collides everywhere, the rows ------------
-  for (uint32_t j = 0; j < m; ++j) {
-    const uint32_t i = order[j];
-    smpc_ctx* c = g->ctxs[i];
-    SmpcStatsOut o;
-    memcpy(&o, g->h_stats_out.get() + (a.out - a.furthest) + a.out_floats * j, sizeof(o));
-    uint32_t fl = flags[i], S = 0;
-    bool fail_flag = c->fail_in;
-    if (fl & SD_NEED_FURTHEST) S = smpc_furthest_index(g->h_stats_out.get()[4 * j]);
-    int rc = SMPC_OK;
-    if (!c->fail_in && (fl & (SD_OBSTACLES | SD_COST)) && o.non_colliding == 0.0f) {
-      // (critic_manager.cpp:70-73, as the single call: the rows are those of the tick's re-score)
-      fail_flag = true;
-      fl = fail_only_flags(c) & ~SD_STORE_TRAJ;
-      S = 0;
-      rc = score_rows(c, bufs[j], fl, nullptr, &o);
-    }
-    if (rc == SMPC_OK) {
-      fill_stats(c, fl, S, fail_flag, o, &stats[i]);
-      if (per_rollout && per_rollout[i]) rc = fetch_rows(c, bufs[j], per_rollout[i]);
-    }
-    status[i] = rc;
-    if (rc == SMPC_ERR_DEVICE) return give_up(rc);
-  }
-#undef GHIPCK
-  put_back(false);
+  GroupBreakdown b{ins, u_ins, take, stats, per_rollout, status};
+  int rc = group_enter(g, take, &b.c0);
+  if (rc != SMPC_OK) return rc;
+  if (!b.c0) return fail(nullptr, SMPC_ERR_INVALID, "critic breakdown: no member of the group is taken");
+  b.n = static_cast<uint32_t>(g->ctxs.size());
+  b.T = b.c0->cfg.time_steps;
+  b.k = stats_many_select(b.c0->R, b.T);
+  if (!b.k) return breakdown_one_by_one(g, b);
+  rc = breakdown_prepare(g, b);
+  if (rc != SMPC_OK || b.order.empty()) return rc;
+  rc = breakdown_buffers(g, b);
+  if (rc == SMPC_OK) rc = breakdown_fill(g, b);
+  if (rc == SMPC_OK) rc = breakdown_run(g, b);
+  if (rc == SMPC_OK) rc = breakdown_collect(g, b);
+  if (rc != SMPC_OK) return rc;
+  b.put_back.wait = false;   // (the success path: the call has waited, in breakdown_run)
   return SMPC_OK;
 }
 
