@@ -558,6 +558,56 @@ typedef struct smpc_critic_stats {
 int smpc_critic_breakdown(smpc_ctx* ctx, const smpc_tick_in* in, const float* u_in,
                           smpc_critic_stats* stats, float* per_rollout);
 
+/* ---- trajectory validation: a collision check of the tick's RESULT -------------------------------
+ * (What upstream Nav2's MPPI controller runs behind optimize() as its optimal-trajectory validator;
+ * the reference fork predates it.)  A tick returns the softmax-weighted mean of the sampled control
+ * sequences and nothing checks that mean: fail_flag fires only when every rollout collides, and a
+ * rollout that hits a moving obstacle is made expensive, never refused.  This call integrates a
+ * control sequence from a pose and checks the poses it passes through.
+ *   poses    the T poses of Optimizer::getOptimizedTrajectory: u = {vx[T], vy[T], wz[T]} ITSELF
+ *            integrated from the pose (no measured-speed first column), float sums,
+ *            x = (float)(pose_x + (double)sum); vy is ignored for DiffDrive and Ackermann;
+ *   checked  the first n = min(T, (uint32_t)floorf(collision_lookahead_time / model_dt)) of them, the
+ *            quotient formed in float (2.0f / 0.05f is 40); n == 0 checks nothing and is valid;
+ *   costmap  CostCritic's own rule on pose t < n [ref cost_critic.cpp:136-146,175-210]: the cost c
+ *            under the centre (Costmap2D::worldToMap; off the map: 255); c < 1 is free; with
+ *            consider_footprint, where c >= the possibly-inscribed cost (findCircumscribedCost) or
+ *            that cost is < 1, c becomes the footprint cost at the pose (footprintCostAtPose, a
+ *            vertex off the map: 254); 254 collides, 253 collides unless consider_footprint, 255
+ *            collides unless the costmap tracks unknown space;
+ *   discs    with moving_obstacles set and a table on the ctx (smpc_set_moving_obstacles), pose t
+ *            hits disc k iff sqrtf(dx*dx + dy*dy) < radius[k] against xy[k][t], in float;
+ *   result   valid; checked = n; first_bad, the least colliding t; cause at first_bad (1 costmap,
+ *            2 disc; the costmap wins); cost, the c above at first_bad; disc, the least k that is
+ *            hit at first_bad (0 when none is).  A valid result has first_bad = cause = disc = 0
+ *            and cost = 0.
+ * xyyaw: NULL, or T*3 floats {x, y, yaw} per pose — all T, whatever n.
+ * One upload, one launch (csrc/smpc_validate.hip) and one wait on the ctx's stream, behind a costmap
+ * upload still pending there.  Changes nothing a tick depends on.  SMPC_ERR_INVALID: a null argument,
+ * a lookahead that is not > 0 and finite; SMPC_ERR_STATE: no costmap yet, consider_footprint without
+ * smpc_set_footprint, a member of a group (as smpc_critic_breakdown).  Buffers (a few KB) are
+ * allocated at the first call.  (Additions under ABI 3.) */
+typedef struct smpc_validation_params {
+  float collision_lookahead_time;   /* seconds; default 2.0 */
+  int32_t consider_footprint;       /* default 0   */
+  int32_t moving_obstacles;         /* default 1   */
+  uint32_t reserved;
+} smpc_validation_params;
+
+#define SMPC_VALIDATION_CAUSE_COSTMAP 1u
+#define SMPC_VALIDATION_CAUSE_DISC 2u
+typedef struct smpc_validation {
+  int32_t valid;
+  uint32_t checked, first_bad, cause, disc;
+  float cost;
+} smpc_validation;
+
+void smpc_validation_params_default(smpc_validation_params* p);
+
+int smpc_validate_trajectory(smpc_ctx* ctx, const smpc_validation_params* p, double pose_x, double pose_y,
+                             float pose_yaw, const float* u, smpc_validation* out,
+                             float* xyyaw /* NULL or T*3 */);
+
 /* Diagnostics: the device sin/cos the rollout uses (integrateStateVelocities,
  * ref src/optimizer.cpp:326-329), evaluated on n host values; tests pin its error. */
 int smpc_selftest_sincos(smpc_ctx* ctx, const float* x, uint32_t n, float* sin_out,
@@ -740,6 +790,27 @@ int smpc_group_critic_breakdown(smpc_group* group, const smpc_tick_in* ins,
  * (time_steps > 64).  Either pointer may be NULL; a NULL group returns SMPC_ERR_INVALID.  (ABI 3) */
 int smpc_group_breakdown_counts(const smpc_group* group, uint64_t* batched_members,
                                 uint64_t* single_members);
+
+/* smpc_validate_trajectory for the members of a group, the group staying a group: params[n],
+ * poses[n][3] ({x, y, yaw} as doubles; yaw is rounded to float), u[n] (3*T floats each, read only),
+ * take[n] as in smpc_group_optimize_some (NULL: every member), out[n], xyyaw (NULL, or n pointers of
+ * which any may be NULL), status[n].  For every member taken out[i] and xyyaw[i] are bit for bit what
+ * smpc_validate_trajectory returns on an identical context that is in no group, and status[i] is
+ * SMPC_OK or the code that call would have returned, the message in that member's smpc_last_error; a
+ * member that fails this way does not fail the others.  Entries of a member that is not taken are
+ * neither read nor written.  ONE upload, ONE launch and ONE wait on the group's stream, whatever n;
+ * a moving-obstacle table the group owns (smpc_group_set_moving_obstacles) is read where it lives.
+ * Changes nothing a later round depends on, the counters of smpc_group_stats included.  Returns an
+ * error only for NULL arguments, when no member is taken, or for a device error; a call that follows
+ * an abandoned round waits for the group's stream first, as a round does.  (ABI 3) */
+int smpc_group_validate_trajectories(smpc_group* group, const smpc_validation_params* params /*[n]*/,
+                                     const double* poses /*[n][3]*/, const float* const* u,
+                                     const uint8_t* take, smpc_validation* out,
+                                     float* const* xyyaw, int32_t* status);
+/* *launches counts the launches of smpc_group_validate_trajectories so far (one per call that had a
+ * member to check), *members the members they carried.  Either pointer may be NULL; a NULL group
+ * returns SMPC_ERR_INVALID.  (ABI 3) */
+int smpc_group_validation_counts(const smpc_group* group, uint64_t* launches, uint64_t* members);
 
 /* ---- the same tick with the exchanges inside the library (RCCL over xGMI) ----
  * One ncclComm per ctx, one call per tick: upload -> score -> ncclAllGather(tuples) ->

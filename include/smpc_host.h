@@ -88,6 +88,17 @@ int sortham_optimizer_set_moving_obstacles(sortham_optimizer* o, const smpc_movi
                                            uint32_t time_steps);
 /* smpc_get_moving_obstacle_costs of the object's context: m [batch_size], hit [batch_size] or NULL */
 int sortham_optimizer_moving_obstacle_costs(sortham_optimizer* o, float* m, uint8_t* hit, uint32_t batch_size);
+/* Optimizer::setTrajectoryValidation / clearTrajectoryValidation (params == NULL): with it on,
+ * eval_control validates the trajectory of the control sequence each optimize() left
+ * (smpc.h: smpc_validate_trajectory) and treats a colliding one as a tick whose rollouts all collide:
+ * reset, retry, and past retry_attempt_limit SORTHAM_ERR_THROWN with the reference's message.  Off by
+ * default.  Before or after initialize; kept across reset and across a re-initialize.  A lookahead
+ * that is not > 0 and finite: SORTHAM_ERR_THROWN, the setting stays what it was. */
+int sortham_optimizer_set_trajectory_validation(sortham_optimizer* o, const smpc_validation_params* params);
+/* The verdict of the object's last validation (valid with nothing checked before the first one), how
+ * many it has run and how many of them came back invalid.  Any of the three may be NULL. */
+int sortham_optimizer_last_validation(const sortham_optimizer* o, smpc_validation* out, uint64_t* run,
+                                      uint64_t* invalid);
 int sortham_optimizer_reset(sortham_optimizer* o);
 /* control_sequence_ as {vx[T], vy[T], wz[T]} */
 int sortham_optimizer_get_control_sequence(sortham_optimizer* o, float* u);
@@ -158,6 +169,14 @@ int sortham_fleet_set_mutual_avoidance(sortham_fleet* fleet, const smpc_moving_o
 /* smpc_debug_group_moving_launches summed over the groups the fleet has had: launches of the grouped
  * moving-obstacle kernels and uploads of a group's table buffer.  Either pointer may be NULL. */
 int sortham_fleet_moving_launches(const sortham_fleet* fleet, uint64_t* grouped_launches, uint64_t* table_uploads);
+/* Trajectory validation in a fleet: a member has it on through its own handle
+ * (sortham_optimizer_set_trajectory_validation).  Behind a round's grouped tick ONE
+ * smpc_group_validate_trajectories call covers the members taken that have it on and did not fail; an
+ * invalid member takes its own retry path (reset, a tick and a validation alone), the others are
+ * untouched.  smpc_group_validation_counts summed over the groups the fleet has had: the grouped
+ * validation calls (one per round, and one per retry of a member alone) and the members they carried.
+ * Either pointer may be NULL. */
+int sortham_fleet_validation_counts(const sortham_fleet* fleet, uint64_t* launches, uint64_t* members);
 /* The table that rule gives member i of n (pure host code, no fleet needed): state[n] 0 never seen,
  * 1 standing, 2 moving; pose[n][3] x, y, yaw; u[n][3][time_steps]; model_dt[n]; holonomic[n];
  * robot_radius[n].  Out: xy [discs][time_steps][2] and radius [discs] (room for n - 1 discs), *discs. */

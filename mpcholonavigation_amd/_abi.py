@@ -271,6 +271,32 @@ class SmpcMovingObstaclesParams(C.Structure):
     ]
 
 
+class SmpcValidationParams(C.Structure):
+    """smpc_validation_params — the trajectory validator's settings (smpc_validate_trajectory)."""
+    _fields_ = [
+        ("collision_lookahead_time", C.c_float),
+        ("consider_footprint", C.c_int32),
+        ("moving_obstacles", C.c_int32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+SMPC_VALIDATION_CAUSE_COSTMAP = 1
+SMPC_VALIDATION_CAUSE_DISC = 2
+
+
+class SmpcValidation(C.Structure):
+    """smpc_validation — the verdict on one control sequence's trajectory."""
+    _fields_ = [
+        ("valid", C.c_int32),
+        ("checked", C.c_uint32),
+        ("first_bad", C.c_uint32),
+        ("cause", C.c_uint32),
+        ("disc", C.c_uint32),
+        ("cost", C.c_float),
+    ]
+
+
 # name -> (restype, argtypes) for every symbol include/smpc.h declares.
 _ctx = C.c_void_p
 PROTOTYPES = {
@@ -310,6 +336,9 @@ PROTOTYPES = {
     "smpc_critic_name": (C.c_char_p, [C.c_uint32]),
     "smpc_critic_breakdown": (C.c_int, [_ctx, C.POINTER(SmpcTickIn), C.c_void_p,
                                         C.POINTER(SmpcCriticStats), C.c_void_p]),
+    "smpc_validation_params_default": (None, [C.POINTER(SmpcValidationParams)]),
+    "smpc_validate_trajectory": (C.c_int, [_ctx, C.POINTER(SmpcValidationParams), C.c_double, C.c_double, C.c_float,
+                                           C.c_void_p, C.POINTER(SmpcValidation), C.c_void_p]),
     "smpc_selftest_sincos": (C.c_int, [_ctx, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "smpc_selftest_philox": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "smpc_selftest_box_muller": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
@@ -337,6 +366,10 @@ PROTOTYPES = {
                                               C.POINTER(SmpcCriticStats), C.POINTER(C.c_void_p),
                                               C.POINTER(C.c_int32)]),
     "smpc_group_breakdown_counts": (C.c_int, [_ctx, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "smpc_group_validate_trajectories": (C.c_int, [_ctx, C.POINTER(SmpcValidationParams), C.POINTER(C.c_double),
+                                                   C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(SmpcValidation),
+                                                   C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]),
+    "smpc_group_validation_counts": (C.c_int, [_ctx, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "smpc_shard_comm_id": (C.c_int, [C.c_void_p, C.c_uint32]),
     "smpc_shard_comm_init": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_int]),
     "smpc_shard_p2p_handle": (C.c_int, [_ctx, C.c_void_p, C.c_uint32]),

@@ -5,6 +5,7 @@
 //   smpc_noise.cpp        the stored noise: smpc_set_noise, the device RNG's draws, the background redraw
 //   smpc_limit_host.cpp   acceleration limits: the setters and the limiter's launch (use_limited_noise)
 //   smpc_moving_host.cpp  moving obstacles: the table's upload and the seed kernel's launch (use_moving_seed)
+//   smpc_validate_host.cpp  the trajectory validator: smpc_validate_trajectory and the group's one call
 //   smpc_debug.cpp        the smpc_selftest_* and smpc_debug_* entries (include/smpc_debug.h)
 //   smpc_prepare.cpp      per-tick host work: gates, path tables, lookup tables, LDS carve-up
 //   smpc_shard.cpp        batch-sharded tick, RCCL resolved at run time
@@ -36,6 +37,7 @@
 #include "smpc_inst.h"   // the scoring-pass instances: tables, selectors, launch
 #include "smpc_limit.h"  // smpc_limit_noise: its arguments
 #include "smpc_moving.h" // smpc_moving_cost: its arguments
+#include "smpc_validate.h" // smpc_validate: its arguments
 #include "smpc_own.h"    // DevBuf, PinnedBuf, Event, Stream
 
 // nothing below is part of the C-ABI: keep it out of the dynamic symbol table
@@ -82,6 +84,8 @@ hipError_t smpc_launch_moving_cost(const SmpcMovingArgs& a, bool group_major, hi
 // smpc_moving_many.hip: the same for `count` members of a group that take one form, in one launch
 hipError_t smpc_launch_moving_cost_many(const SmpcMovingMember* d_many, uint32_t count, uint32_t grid, SmpcMovingForm form,
                                         uint32_t T, hipStream_t st);
+// smpc_validate.hip: the collision check of `count` control sequences' trajectories, a block each
+hipError_t smpc_launch_validate(const SmpcValidateArgs* d_many, uint32_t count, hipStream_t st);
 
 namespace smpc_impl {
 
@@ -371,6 +375,16 @@ struct BreakdownBufs {
   float pass_ms = 0.f, reduce_ms = 0.f;
 };
 
+// The trajectory validator's buffers (smpc_validate_trajectory; a group has a set of its own),
+// allocated at the first call.  Written by smpc_validate_host.cpp only.
+struct ValidateBufs {
+  PinnedBuf<uint8_t> h_in;     // SmpcValidateArgs[cap], then the control sequences [cap][3T]: what the ONE upload reads
+  DevBuf<uint8_t> d_in;
+  PinnedBuf<uint8_t> h_out;    // per member {smpc_validation, xyyaw[T][3]}, mapped into the device: the kernel writes here
+  uint8_t* h_out_dev = nullptr;
+  uint32_t cap = 0;            // members the three hold
+};
+
 // The per-tick block.  `own_d` / `own_h` are the context's own block, allocated by smpc_create and
 // the context's for life.  `d_tick` / `h_tick` are the VIEWS everything else reads and writes
 // (prepare_tick, the kernels' parameter blocks, the limiter's u): the own block, or — while the
@@ -488,6 +502,7 @@ struct smpc_ctx {
   smpc_impl::BreakdownBufs stats;
   smpc_impl::Limiter lim;
   smpc_impl::MovingObstacles mov;
+  smpc_impl::ValidateBufs val;
   std::string err;
 };
 
@@ -603,6 +618,10 @@ size_t moving_table_capacity(uint32_t T);
 void pack_moving_table(float* stage, uint32_t T, const smpc_moving_obstacles_params* p, const float* xy, const float* radius, uint32_t n);
 // the term off: K = 0, nothing scored; the views back at the ctx's own allocation
 void moving_off(smpc_ctx* c);
+// the table went up on the stream the ctx had then: the one it has now waits for it (once)
+int wait_table_upload(smpc_ctx* c);
+// {Obstacles,Cost}Critic::findCircumscribedCost: the possibly-inscribed cost of the footprint; -1 without an inflation layer
+float circumscribed_cost(const HostCostmap& map, double fp_circumscribed_radius, double fp_layer_scale);
 // the same for a first-iteration pass on the [B,T] noise that keeps costs of its own (the critic
 // breakdown): m into a buffer of the ctx's (allocated at the first call), which becomes
 // d.costs_prev; the tick's own m and hits (smpc_get_moving_obstacle_costs) are left alone

@@ -171,6 +171,7 @@ __device__ __forceinline__ uint32_t cost_at(const SmpcDev& p, const CellConsts& 
 // calls, which bring a call stack and a copy of the parameter block into the kernel's scratch.
 // The lean pass with the footprint check (smpc_pass MODE 4) inlines the same text, *_inl, into its
 // rare branch and has neither.
+#define SMPC_FP_DEV SmpcDev
 #define SMPC_FP_ATTR __noinline__
 #define SMPC_FP_NAME(name) name
 #include "smpc_footprint_walk.inc"
@@ -181,5 +182,6 @@ __device__ __forceinline__ uint32_t cost_at(const SmpcDev& p, const CellConsts& 
 #include "smpc_footprint_walk.inc"
 #undef SMPC_FP_ATTR
 #undef SMPC_FP_NAME
+#undef SMPC_FP_DEV
 
 #endif

@@ -1,8 +1,10 @@
 // nav2_costmap_2d's FootprintCollisionChecker::footprintCostAtPose with nav2_util::LineIterator,
 // restated (third party, ROS 2 Humble).  Costs come from the LDS window when the cell is inside it.
-// Included by smpc_device_math.h with SMPC_FP_ATTR (__noinline__ | __forceinline__) and
-// SMPC_FP_NAME (the functions' names) set.
-__device__ SMPC_FP_ATTR uint32_t SMPC_FP_NAME(cell_cost)(const SmpcDev& p, const uint8_t* s_map, uint32_t mx,
+// Included by smpc_device_math.h with SMPC_FP_ATTR (__noinline__ | __forceinline__),
+// SMPC_FP_NAME (the functions' names) and SMPC_FP_DEV (the parameter block the walk reads: SmpcDev
+// for the scoring passes, SmpcValidateArgs for smpc_validate.hip, which includes the text once
+// more) set.
+__device__ SMPC_FP_ATTR uint32_t SMPC_FP_NAME(cell_cost)(const SMPC_FP_DEV& p, const uint8_t* s_map, uint32_t mx,
                                                          uint32_t my)
 {
   const uint32_t lx = mx - (uint32_t)p.win_x0, ly = my - (uint32_t)p.win_y0;
@@ -12,7 +14,7 @@ __device__ SMPC_FP_ATTR uint32_t SMPC_FP_NAME(cell_cost)(const SmpcDev& p, const
   return c;
 }
 
-__device__ SMPC_FP_ATTR float SMPC_FP_NAME(footprint_line_cost)(const SmpcDev& p, const uint8_t* s_map, int x0,
+__device__ SMPC_FP_ATTR float SMPC_FP_NAME(footprint_line_cost)(const SMPC_FP_DEV& p, const uint8_t* s_map, int x0,
                                                                 int x1, int y0, int y1)
 {
   float cost = 0.f;
@@ -42,7 +44,7 @@ __device__ SMPC_FP_ATTR float SMPC_FP_NAME(footprint_line_cost)(const SmpcDev& p
   return cost;
 }
 
-__device__ SMPC_FP_ATTR float SMPC_FP_NAME(footprint_cost_at_pose)(const SmpcDev& p, const uint8_t* s_map,
+__device__ SMPC_FP_ATTR float SMPC_FP_NAME(footprint_cost_at_pose)(const SMPC_FP_DEV& p, const uint8_t* s_map,
                                                                    float xf, float yf, float thetaf)
 {
   const double x = (double)xf, y = (double)yf, theta = (double)thetaf;

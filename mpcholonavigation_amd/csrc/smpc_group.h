@@ -82,6 +82,7 @@ struct GroupCounters {
   uint64_t batched_launches = 0;   // scoring launches that carried two or more members (smpc_group_stats)
   uint64_t moving_launches = 0, moving_uploads = 0;   // smpc_debug_group_moving_launches
   uint64_t breakdown_batched = 0, breakdown_single = 0;   // member-breakdowns by route (smpc_group_breakdown_counts)
+  uint64_t validate_launches = 0, validate_members = 0;   // smpc_group_validation_counts
 };
 
 }  // namespace smpc_impl
@@ -99,6 +100,7 @@ struct smpc_group {
   smpc_impl::GroupArrays arr;
   smpc_impl::GroupMoving mov;
   smpc_impl::GroupStatsBufs stats;
+  smpc_impl::ValidateBufs val;    // smpc_group_validate_trajectories
   smpc_impl::GroupCounters count;
 };
 

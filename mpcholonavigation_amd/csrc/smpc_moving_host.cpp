@@ -14,7 +14,7 @@ namespace smpc_impl {
 // the layout that pass reads; m into `seed` (added to its content when d accumulates).
 // the table went up on the stream the ctx had then: the one it has now waits for it (once).  (A
 // group's table went up on the group's stream, which is the member's for as long as the table holds.)
-static int wait_table_upload(smpc_ctx* c)
+int wait_table_upload(smpc_ctx* c)
 {
   if (!c->mov.group_table && c->mov.up_recorded && c->mov.up_stream != c->stream) {
     HIPCK(c, hipStreamWaitEvent(c->stream, c->mov.ev_up.get(), 0));

@@ -1029,7 +1029,7 @@ static void cost_lut(const smpc_cost_params& q, bool near_goal_c, float* lut_cos
 
 // {Obstacles,Cost}Critic::findCircumscribedCost with InflationLayer::computeCost
 // (nav2_costmap_2d, Humble): the cost at the circumscribed radius, -1 without a layer
-static float circumscribed_cost(const HostCostmap& map, double fp_circumscribed_radius, double fp_layer_scale)
+float circumscribed_cost(const HostCostmap& map, double fp_circumscribed_radius, double fp_layer_scale)
 {
   double result = -1.0;
   if (fp_layer_scale >= 0.0) {

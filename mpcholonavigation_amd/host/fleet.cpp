@@ -169,6 +169,10 @@ void FleetOptimizer::dropGroup()
   smpc_debug_group_moving_launches(group_, &moving, &uploads);
   stats_.grouped_moving_launches += moving;
   stats_.moving_table_uploads += uploads;
+  uint64_t vlaunches = 0, vmembers = 0;
+  smpc_group_validation_counts(group_, &vlaunches, &vmembers);
+  stats_.validation_launches += vlaunches;
+  stats_.validated_members += vmembers;
   smpc_group_destroy(group_);
   group_ = nullptr;
   // a table that lived in the group's buffer went with it (smpc.h): the member gets it back through
@@ -261,6 +265,34 @@ void FleetOptimizer::tickAlone(Optimizer * member, const smpc_tick_in & in, floa
     throw std::runtime_error(std::string("smpc_optimize: ") + smpc_last_error(member->ctx_));
   }
   out = outs_[s];
+}
+
+void FleetOptimizer::validateAlone(
+  Optimizer * member, const smpc_validation_params & params, const double * pose, const float * u,
+  smpc_validation & out)
+{
+  const size_t i = static_cast<size_t>(std::find(members_.begin(), members_.end(), member) - members_.begin());
+  if (!group_ || i >= members_.size() || slot_[i] < 0) {
+    throw std::runtime_error("smpc_validate_trajectory: the member has no slot in its fleet's group");
+  }
+  const size_t s = static_cast<size_t>(slot_[i]), g = owner_.size();
+  std::vector<smpc_validation_params> p(g, params);
+  std::vector<double> ps(3 * g, 0.0);
+  std::vector<const float *> us(g, nullptr);
+  std::vector<uint8_t> tk(g, 0);
+  std::vector<smpc_validation> outs(g);
+  std::vector<int32_t> status(g, SMPC_OK);
+  std::copy(pose, pose + 3, ps.begin() + 3 * s);
+  us[s] = u;
+  tk[s] = 1;
+  const int rc = smpc_group_validate_trajectories(
+    group_, p.data(), ps.data(), us.data(), tk.data(), outs.data(), nullptr, status.data());
+  if (rc != SMPC_OK || status[s] != SMPC_OK) {
+    throw std::runtime_error(
+            std::string("smpc_validate_trajectory: ") + (rc != SMPC_OK && rc != SMPC_ERR_DEVICE ?
+            smpc_last_error(nullptr) : smpc_last_error(member->ctx_)));
+  }
+  out = outs[s];
 }
 
 int FleetOptimizer::evalControl(
@@ -445,19 +477,83 @@ int FleetOptimizer::evalControl(
     }
     return fail(rc, "smpc_group_optimize_some: " + what);
   }
-  // ---- per member: the reference's loop [ref src/optimizer.cpp:143-154,166-183] ---------------
+  // ---- every member's result taken over, then ONE grouped validation of the round's results -----
+  // (the members taken that have trajectory validation on and whose tick did not fail: one upload,
+  // one launch, one wait for all of them)
+  const size_t g = owner_.size();
+  std::vector<uint8_t> vtake(g, 0), checked(n, 0);
+  bool any_v = false;
   for (size_t i = 0; i < n; ++i) {
     if (!taken(i)) {
       continue;
     }
     Optimizer * m = members_[i];
     const size_t s = static_cast<size_t>(slot_[i]);
-    MemberResult & r = results[i];
     try {
       m->takeTick(u_[s].data(), outs_[s]);
-      while (m->fallback(m->fail_flag_)) {
+    } catch (const std::exception & e) {
+      results[i].status = FLEET_THROWN;
+      results[i].error = e.what();
+      continue;
+    }
+    if (m->validate_on_ && !m->fail_flag_) {
+      vtake[s] = 1;
+      any_v = true;
+    }
+  }
+  if (any_v) {
+    // (u_ holds the sequences the round returned: what takeTick copied into the members)
+    std::vector<smpc_validation_params> vp(g);
+    std::vector<double> vpose(3 * g, 0.0);
+    std::vector<const float *> vu(g, nullptr);
+    std::vector<smpc_validation> vout(g);
+    std::vector<int32_t> vstatus(g, SMPC_OK);
+    for (size_t s = 0; s < g; ++s) {
+      if (!vtake[s]) {
+        continue;
+      }
+      const Optimizer * m = members_[owner_[s]];
+      vp[s] = m->validation_params_;
+      vpose[3 * s] = m->pose_.x;
+      vpose[3 * s + 1] = m->pose_.y;
+      vpose[3 * s + 2] = m->pose_.yaw;
+      vu[s] = u_[s].data();
+    }
+    const int vrc = smpc_group_validate_trajectories(
+      group_, vp.data(), vpose.data(), vu.data(), vtake.data(), vout.data(), nullptr, vstatus.data());
+    for (size_t s = 0; s < g; ++s) {
+      if (!vtake[s]) {
+        continue;
+      }
+      const size_t i = owner_[s];
+      if (vrc != SMPC_OK || vstatus[s] != SMPC_OK) {
+        // what evalControl would have thrown for this member
+        results[i].status = FLEET_THROWN;
+        results[i].error = std::string("smpc_validate_trajectory: ") +
+          (vrc != SMPC_OK && vrc != SMPC_ERR_DEVICE ? smpc_last_error(nullptr) : smpc_last_error(members_[i]->ctx_));
+        continue;
+      }
+      members_[i]->takeValidation(vout[s]);
+      checked[i] = 1;
+    }
+  }
+  // ---- per member: the reference's loop [ref src/optimizer.cpp:143-154,166-183] ---------------
+  for (size_t i = 0; i < n; ++i) {
+    if (!taken(i)) {
+      continue;
+    }
+    Optimizer * m = members_[i];
+    MemberResult & r = results[i];
+    r.out = m->last_out_;
+    if (r.status == FLEET_THROWN) {
+      continue;
+    }
+    try {
+      bool failed = m->fail_flag_ || (checked[i] && !m->last_validation_.valid);
+      while (m->fallback(failed)) {
         stats_.retries++;
         m->optimize();   // alone, fail_flag_in sticky (Optimizer::optimize -> tickAlone)
+        failed = m->fail_flag_ || !m->validated();   // (alone too: validateAlone)
       }
       r.twist = m->finishTick();
       r.status = SMPC_OK;
@@ -597,6 +693,10 @@ FleetStats FleetOptimizer::stats() const
     smpc_debug_group_moving_launches(group_, &moving, &uploads);
     s.grouped_moving_launches += moving;
     s.moving_table_uploads += uploads;
+    uint64_t vlaunches = 0, vmembers = 0;
+    smpc_group_validation_counts(group_, &vlaunches, &vmembers);
+    s.validation_launches += vlaunches;
+    s.validated_members += vmembers;
   }
   return s;
 }

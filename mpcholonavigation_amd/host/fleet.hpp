@@ -64,6 +64,10 @@ struct FleetStats
   // mutual avoidance on the grouped route (smpc_debug_group_moving_launches, summed like the above):
   uint64_t grouped_moving_launches{0};   // launches of the grouped moving-obstacle kernels
   uint64_t moving_table_uploads{0};      // uploads of a group's table buffer (one per round)
+  // trajectory validation (smpc_group_validation_counts, summed like the above):
+  uint64_t validation_launches{0};       // grouped validation calls that had a member to check: one per round, and
+                                         // one per retry of a member alone
+  uint64_t validated_members{0};         // the members they carried
 };
 
 // What a fleet knows of member j when it builds the others' obstacle tables.
@@ -102,6 +106,10 @@ public:
   // SMPC_ERR_* of a round that failed as a whole (text in lastError()): then no member's control
   // sequence, filter history or retry counter has moved, and the next round is safe to run.
   // A round that takes a member which was shut down or destroyed is SMPC_ERR_STATE.
+  // Trajectory validation (Optimizer::setTrajectoryValidation on the members): behind the grouped tick
+  // ONE smpc_group_validate_trajectories call covers the members taken that have it on and did not
+  // fail; an invalid member takes its own retry path — reset, a tick and a validation alone — and
+  // the others are untouched.
   int evalControl(
     const std::vector<Pose2D> & poses, const std::vector<Twist2D> & speeds,
     const std::vector<models::Path> & plans, const std::vector<Pose2D> & goals,
@@ -145,6 +153,9 @@ public:
   void memberDestroyed(Optimizer * member) override;
   bool grouped(const Optimizer * member) const override;
   void tickAlone(Optimizer * member, const smpc_tick_in & in, float * u, smpc_tick_out & out) override;
+  void validateAlone(
+    Optimizer * member, const smpc_validation_params & params, const double * pose, const float * u,
+    smpc_validation & out) override;
 
 private:
   int regroup();

@@ -228,6 +228,21 @@ int sortham_fleet_stats(
   return SMPC_OK;
 }
 
+int sortham_fleet_validation_counts(const sortham_fleet * f, uint64_t * launches, uint64_t * members)
+{
+  if (!f) {
+    return SMPC_ERR_INVALID;
+  }
+  const sortham_ns::FleetStats s = f->fleet->stats();
+  if (launches) {
+    *launches = s.validation_launches;
+  }
+  if (members) {
+    *members = s.validated_members;
+  }
+  return SMPC_OK;
+}
+
 int sortham_fleet_moving_launches(const sortham_fleet * f, uint64_t * grouped_launches, uint64_t * table_uploads)
 {
   if (!f) {

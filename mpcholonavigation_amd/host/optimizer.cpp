@@ -433,6 +433,48 @@ smpc_critic_stats Optimizer::getCriticStats(const TickInput & ti, float * per_ro
   return stats;
 }
 
+void Optimizer::setTrajectoryValidation(const smpc_validation_params & params)
+{
+  if (!std::isfinite(params.collision_lookahead_time) || !(params.collision_lookahead_time > 0.0f)) {
+    throw std::runtime_error("setTrajectoryValidation: collision_lookahead_time must be > 0 and finite");
+  }
+  validation_params_ = params;
+  validate_on_ = true;
+}
+
+void Optimizer::takeValidation(const smpc_validation & v)
+{
+  last_validation_ = v;
+  validations_run_++;
+  if (!v.valid) {
+    validations_failed_++;
+  }
+}
+
+bool Optimizer::validated()
+{
+  if (!validate_on_ || fail_flag_) {
+    return true;   // (a failed tick takes the fallback path as it is)
+  }
+  const unsigned int T = settings_.time_steps;
+  std::vector<float> u(3 * T);
+  std::memcpy(u.data(), control_sequence_.vx.data(), T * sizeof(float));
+  std::memcpy(u.data() + T, control_sequence_.vy.data(), T * sizeof(float));
+  std::memcpy(u.data() + 2 * T, control_sequence_.wz.data(), T * sizeof(float));
+  smpc_validation v{};
+  if (fleet_ && fleet_->grouped(this)) {
+    const double pose[3] = {pose_.x, pose_.y, pose_.yaw};
+    fleet_->validateAlone(this, validation_params_, pose, u.data(), v);
+  } else {
+    ck(
+      ctx_, smpc_validate_trajectory(
+        ctx_, &validation_params_, pose_.x, pose_.y, static_cast<float>(pose_.yaw), u.data(), &v, nullptr),
+      "smpc_validate_trajectory");
+  }
+  takeValidation(v);
+  return v.valid != 0;
+}
+
 bool Optimizer::fallback(bool fail)
 {
   if (!fail) {
@@ -455,7 +497,7 @@ Twist2D Optimizer::evalControl(
   prepare(robot_pose, robot_speed, plan, goal);
   do {
     optimize();
-  } while (fallback(fail_flag_));
+  } while (fallback(fail_flag_ || !validated()));
   return finishTick();
 }
 

@@ -154,6 +154,11 @@ public:
   virtual bool grouped(const Optimizer * member) const = 0;
   // one tick of this member alone through the group (smpc_optimize on its slot); throws on error
   virtual void tickAlone(Optimizer * member, const smpc_tick_in & in, float * u, smpc_tick_out & out) = 0;
+  // one trajectory validation of this member alone through the group (smpc_group_validate_trajectories
+  // with this member taken); throws on error
+  virtual void validateAlone(
+    Optimizer * member, const smpc_validation_params & params, const double * pose, const float * u,
+    smpc_validation & out) = 0;
 };
 
 class FleetOptimizer;
@@ -207,6 +212,21 @@ public:
   void clearMovingObstacles();
   // m [B] and hit [B] of the last tick's last iteration (smpc_get_moving_obstacle_costs)
   void getMovingObstacleCosts(std::vector<float> & m, std::vector<uint8_t> & hit);
+  // Trajectory validation (smpc_validate_trajectory; upstream Nav2's optimal-trajectory validator):
+  // with it on, evalControl checks the trajectory of the control sequence each optimize() left —
+  // the costmap under its first collision_lookahead_time / model_dt poses, with the footprint if
+  // asked, and the moving obstacles — and a colliding one takes the path of a tick whose rollouts
+  // all collide: reset, retry, and past retry_attempt_limit the reference's exception.  Off by
+  // default.  Before or after initialize(); kept across reset() and across whatever recreates the
+  // context.  Throws for a lookahead that is not > 0 and finite.
+  void setTrajectoryValidation(const smpc_validation_params & params);
+  void clearTrajectoryValidation() {validate_on_ = false;}
+  bool trajectoryValidation() const {return validate_on_;}
+  // the verdict of the last validation (valid, nothing checked, before the first one)
+  const smpc_validation & lastValidation() const {return last_validation_;}
+  // validations run so far, and those that came back invalid
+  uint64_t validationsRun() const {return validations_run_;}
+  uint64_t validationsFailed() const {return validations_failed_;}
   void reset();                                             // ref :116-132
 
   // ref :345-360: [T][3] x, y, yaw of the optimal sequence
@@ -238,6 +258,9 @@ protected:
   Twist2D finishTick();
   void destroyContext(smpc_ctx * ctx);     // tells the fleet first: its group goes before the context
   bool fallback(bool fail);                // ref :166-183 (retry counter per object)
+  // true unless validation is on, the tick did not fail, and the control sequence's trajectory collides
+  bool validated();
+  void takeValidation(const smpc_validation & v);
   void prepare(const Pose2D &, const Twist2D &, const models::Path &, const Pose2D &);  // ref :185-204
   void shiftControlSequence();             // ref :206-225
   Twist2D getControlFromSequenceAsTwist(); // ref :396-410
@@ -259,6 +282,10 @@ protected:
   std::array<float, 4> accel_limits_{{0.0f, 0.0f, 0.0f, 0.0f}};   // ax_max, ax_min, ay_max, az_max; all zero: off
   smpc_moving_obstacles_params moving_params_{};
   std::vector<float> moving_xy_, moving_radius_;   // empty: off
+  bool validate_on_{false};
+  smpc_validation_params validation_params_{};
+  smpc_validation last_validation_{1, 0, 0, 0, 0, 0.0f};
+  uint64_t validations_run_{0}, validations_failed_{0};
   uint64_t noise_seed_{0};
   bool supplied_noise_{false};
   int device_{-1};

@@ -234,6 +234,29 @@ int sortham_optimizer_moving_obstacle_costs(sortham_optimizer * o, float * m, ui
     });
 }
 
+int sortham_optimizer_set_trajectory_validation(sortham_optimizer * o, const smpc_validation_params * params)
+{
+  if (!o) {return SMPC_ERR_INVALID;}
+  return guarded(
+    o, [&]() {
+      if (params) {
+        o->opt.setTrajectoryValidation(*params);
+      } else {
+        o->opt.clearTrajectoryValidation();
+      }
+    });
+}
+
+int sortham_optimizer_last_validation(
+  const sortham_optimizer * o, smpc_validation * out, uint64_t * run, uint64_t * invalid)
+{
+  if (!o) {return SMPC_ERR_INVALID;}
+  if (out) {*out = o->opt.lastValidation();}
+  if (run) {*run = o->opt.validationsRun();}
+  if (invalid) {*invalid = o->opt.validationsFailed();}
+  return SMPC_OK;
+}
+
 int sortham_optimizer_set_speed_limit(sortham_optimizer * o, double speed_limit, int percentage)
 {
   if (!o) {return SMPC_ERR_INVALID;}

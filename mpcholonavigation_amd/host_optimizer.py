@@ -59,6 +59,9 @@ PROTOTYPES = {
     "sortham_optimizer_set_moving_obstacles": (C.c_int, [_ctx, C.POINTER(A.SmpcMovingObstaclesParams), C.c_void_p,
                                                          C.c_void_p, C.c_uint32, C.c_uint32]),
     "sortham_optimizer_moving_obstacle_costs": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "sortham_optimizer_set_trajectory_validation": (C.c_int, [_ctx, C.POINTER(A.SmpcValidationParams)]),
+    "sortham_optimizer_last_validation": (C.c_int, [_ctx, C.POINTER(A.SmpcValidation), C.POINTER(C.c_uint64),
+                                                    C.POINTER(C.c_uint64)]),
     "sortham_optimizer_reset": (C.c_int, [_ctx]),
     "sortham_optimizer_get_control_sequence": (C.c_int, [_ctx, C.c_void_p]),
     "sortham_optimizer_set_control_sequence": (C.c_int, [_ctx, C.c_void_p]),
@@ -94,6 +97,7 @@ FLEET_AVOIDANCE_PROTOTYPES = {
     "sortham_fleet_set_mutual_avoidance": (C.c_int, [_ctx, C.POINTER(A.SmpcMovingObstaclesParams), C.c_void_p,
                                                      C.c_uint32]),
     "sortham_fleet_moving_launches": (C.c_int, [_ctx, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "sortham_fleet_validation_counts": (C.c_int, [_ctx, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "sortham_fleet_avoidance_table": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.POINTER(C.c_uint32)]),
@@ -312,6 +316,29 @@ class Optimizer:
         self._ck(self.lib.sortham_optimizer_moving_obstacle_costs(self.h, _ptr(m), _ptr(hit), self.B))
         return m, hit.astype(bool)
 
+    def set_trajectory_validation(self, on=True, collision_lookahead_time=None, consider_footprint=None,
+                                  moving_obstacles=None):
+        """Optimizer::setTrajectoryValidation (on false: clearTrajectoryValidation): eval_control then
+        validates the trajectory of every optimize()'s result (optimizer.Smpc.validate_trajectory) and
+        a colliding one is reset and retried like a tick whose rollouts all collide.  Arguments left
+        None keep the library's defaults.  Kept across reset() and a re-initialize."""
+        if not on:
+            self._ck(self.lib.sortham_optimizer_set_trajectory_validation(self.h, None))
+            return
+        from .optimizer import load_library as load_smpc, validation_params
+        p = validation_params(load_smpc(), collision_lookahead_time, consider_footprint, moving_obstacles)
+        self._ck(self.lib.sortham_optimizer_set_trajectory_validation(self.h, C.byref(p)))
+
+    def last_validation(self):
+        """The verdict of the last validation (optimizer.Validation) with `run` and `invalid`: how many
+        validations the object has run and how many of them found a collision."""
+        from .optimizer import validation_from_c
+        v, run, bad = A.SmpcValidation(), C.c_uint64(0), C.c_uint64(0)
+        self._ck(self.lib.sortham_optimizer_last_validation(self.h, C.byref(v), C.byref(run), C.byref(bad)))
+        out = validation_from_c(v)
+        out.run, out.invalid = run.value, bad.value
+        return out
+
     def set_speed_limit(self, speed_limit, percentage):
         self._ck(self.lib.sortham_optimizer_set_speed_limit(self.h, speed_limit, int(percentage)))
 
@@ -477,6 +504,26 @@ class FleetOptimizer:
         if rc != 0:
             raise FleetError(rc, "sortham_fleet_stats")
         return SimpleNamespace(batched_launches=a.value, single_ticks=b.value, retries=c.value)
+
+    def set_trajectory_validation(self, on=True, **kw):
+        """Optimizer.set_trajectory_validation on every member: a round then validates the members'
+        results in one grouped call, and an invalid member retries alone."""
+        for m in self.members:
+            m.set_trajectory_validation(on, **kw)
+
+    def last_validation(self):
+        """Optimizer.last_validation of every member."""
+        return [m.last_validation() for m in self.members]
+
+    def validation_counts(self):
+        """(launches, members) of the fleet's grouped validation calls so far (smpc_group_validation_counts,
+        summed over the fleet's groups): one launch per round, and one per retry of a member alone."""
+        from types import SimpleNamespace
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        rc = self.lib.sortham_fleet_validation_counts(self.h, C.byref(a), C.byref(b))
+        if rc != 0:
+            raise FleetError(rc, "sortham_fleet_validation_counts")
+        return SimpleNamespace(launches=a.value, members=b.value)
 
     def moving_launches(self):
         """Mutual avoidance on the grouped route so far (smpc_debug_group_moving_launches, summed over

@@ -96,6 +96,36 @@ def critic_stats_from_c(st, names, per_rollout=None):
                        effective_samples=float(st.effective_samples), per_rollout=per_rollout, **rows)
 
 
+@dataclasses.dataclass
+class Validation:
+    """smpc_validation (Smpc.validate_trajectory): the verdict on one control sequence's trajectory."""
+    valid: bool
+    checked: int
+    first_bad: int
+    cause: int                  # 0, 1 costmap, 2 moving obstacle
+    disc: int
+    cost: float
+    xyyaw: Optional[np.ndarray] = None   # [T, 3] float32 poses when asked for
+
+
+def validation_params(lib, collision_lookahead_time=None, consider_footprint=None, moving_obstacles=None):
+    """smpc_validation_params with the library's defaults where an argument is None."""
+    p = A.SmpcValidationParams()
+    lib.smpc_validation_params_default(C.byref(p))
+    if collision_lookahead_time is not None:
+        p.collision_lookahead_time = collision_lookahead_time
+    if consider_footprint is not None:
+        p.consider_footprint = int(bool(consider_footprint))
+    if moving_obstacles is not None:
+        p.moving_obstacles = int(bool(moving_obstacles))
+    return p
+
+
+def validation_from_c(v, xyyaw=None):
+    return Validation(valid=bool(v.valid), checked=int(v.checked), first_bad=int(v.first_bad), cause=int(v.cause),
+                      disc=int(v.disc), cost=float(v.cost), xyyaw=xyyaw)
+
+
 def _ptr(a):
     if a is None:
         return None
@@ -268,6 +298,23 @@ class Smpc:
         rows = np.empty((A.SMPC_STATS_ROWS, self.B), np.float32) if per_rollout else None
         self._ck(self.lib.smpc_critic_breakdown(self.h, C.byref(tick.c), _ptr(u), C.byref(st), _ptr(rows)))
         return critic_stats_from_c(st, critic_names(self.lib), rows)
+
+    def validate_trajectory(self, pose, u, collision_lookahead_time=None, consider_footprint=None,
+                            moving_obstacles=None, poses=False):
+        """Collision check of the trajectory the control sequence u [3, T] drives from pose (x, y,
+        yaw) (smpc_validate_trajectory): the costmap under the first lookahead / model_dt poses,
+        with the footprint if asked, and the moving obstacles set on the context.  Arguments left
+        None keep the library's defaults (2.0 s, no footprint, moving obstacles on).  poses: also
+        the [T, 3] poses.  Changes nothing a tick depends on."""
+        u = np.ascontiguousarray(u, dtype=np.float32)
+        if u.shape != (3, self.T):
+            raise ValueError(f"u must be [3, {self.T}]")
+        p = validation_params(self.lib, collision_lookahead_time, consider_footprint, moving_obstacles)
+        out = A.SmpcValidation()
+        xyyaw = np.empty((self.T, 3), np.float32) if poses else None
+        self._ck(self.lib.smpc_validate_trajectory(self.h, C.byref(p), float(pose[0]), float(pose[1]), float(pose[2]),
+                                                   _ptr(u), C.byref(out), _ptr(xyyaw)))
+        return validation_from_c(out, xyyaw)
 
     def selftest_sincos(self, x):
         x = np.ascontiguousarray(x, dtype=np.float32)
@@ -558,6 +605,64 @@ class SmpcGroup:
         if rc != 0:
             raise SmpcError(rc, "smpc_group_breakdown_counts")
         return types.SimpleNamespace(batched_members=b.value, single_members=s.value)
+
+    def validate_trajectories(self, poses, us, params=None, take=None, want_poses=False):
+        """Smpc.validate_trajectory for the members in one upload, one launch and one wait
+        (smpc_group_validate_trajectories).  poses: one (x, y, yaw) per member; us: one [3, T] per
+        member; params: None, one dict of validate_trajectory's keywords for all, or one per member.
+        Returns one entry per member: a Validation; None for a member left out by take; the
+        SmpcError (not raised) for a member the call refused on its own."""
+        n = len(self.members)
+        if len(poses) != n or len(us) != n:
+            raise ValueError("one pose and one control sequence per member")
+        if take is not None and len(take) != n:
+            raise ValueError("one take entry per member")
+        if params is None or isinstance(params, dict):
+            params = [params or {}] * n
+        if len(params) != n:
+            raise ValueError("one parameter dict per member")
+        on = [True] * n if take is None else [bool(v) for v in take]
+        T = self.members[0].T
+        cp = (A.SmpcValidationParams * n)()
+        pose = np.zeros((n, 3), np.float64)
+        ubuf = np.zeros((n, 3, T), np.float32)
+        for i in range(n):
+            cp[i] = validation_params(self.lib, **(params[i] or {}))
+            if on[i]:
+                pose[i] = poses[i]
+                u = np.asarray(us[i], dtype=np.float32)
+                if u.shape != (3, T):
+                    raise ValueError(f"u must be [3, {T}]")
+                ubuf[i] = u
+        xy = [np.empty((T, 3), np.float32) if want_poses and on[i] else None for i in range(n)]
+        uptr = (C.c_void_p * n)(*[ubuf[i].ctypes.data for i in range(n)])
+        xptr = (C.c_void_p * n)(*[a.ctypes.data if a is not None else None for a in xy])
+        out = (A.SmpcValidation * n)()
+        status = (C.c_int32 * n)()
+        mask = None if take is None else (C.c_uint8 * n)(*[int(v) for v in on])
+        rc = self.lib.smpc_group_validate_trajectories(self.h, cp, pose.ctypes.data_as(C.POINTER(C.c_double)), uptr, mask,
+                                                       out, xptr if want_poses else None, status)
+        if rc != 0:
+            msg = next((m.lib.smpc_last_error(m.h).decode() for m in self.members
+                        if m.lib.smpc_last_error(m.h)), "") or self.lib.smpc_last_error(None).decode()
+            raise SmpcError(rc, msg)
+        res = []
+        for i, m in enumerate(self.members):
+            if not on[i]:
+                res.append(None)
+            elif status[i] != 0:
+                res.append(SmpcError(int(status[i]), m.lib.smpc_last_error(m.h).decode()))
+            else:
+                res.append(validation_from_c(A.SmpcValidation.from_buffer_copy(out[i]), xy[i]))
+        return res
+
+    def validation_counts(self):
+        """(launches, members) of validate_trajectories so far (smpc_group_validation_counts)."""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        rc = self.lib.smpc_group_validation_counts(self.h, C.byref(a), C.byref(b))
+        if rc != 0:
+            raise SmpcError(rc, "smpc_group_validation_counts")
+        return types.SimpleNamespace(launches=a.value, members=b.value)
 
     def close(self):
         if self.h:

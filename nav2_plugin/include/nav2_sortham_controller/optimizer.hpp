@@ -69,6 +69,8 @@ protected:
   bool visualize_{false};
   // acceleration limits on the sampled controls (upstream nav2_mppi_controller's names); 0: off
   float ax_max_{0.0f}, ax_min_{0.0f}, ay_max_{0.0f}, az_max_{0.0f};
+  bool validate_trajectory_{false}, validator_consider_footprint_{false};
+  float collision_lookahead_time_{2.0f};
   models::Trajectories generated_trajectories_;
   rclcpp::Logger logger_{rclcpp::get_logger("SORTHAMController")};
 };

@@ -56,6 +56,13 @@ void Optimizer::getParams()
   getParam(motion_model_name_, "motion_model", std::string("DiffDrive"));
   getParam(regenerate_noises_, "regenerate_noises", false);
   getParam(visualize_, "visualize", false);
+  // the optimal-trajectory validator: off unless asked for (an existing YAML keeps its behaviour)
+  getParam(validate_trajectory_, "validate_trajectory", false);
+  {
+    auto getValidator = parameters_handler_->getParamGetter(name_ + ".TrajectoryValidator");
+    getValidator(collision_lookahead_time_, "collision_lookahead_time", 2.0f);
+    getValidator(validator_consider_footprint_, "consider_footprint", false);
+  }
   parameters_handler_->addPostCallback([this]() {reset();});   // :88
   getParentParam(controller_frequency_, "controller_frequency", 0.0, ParameterType::Static);
 }
@@ -83,6 +90,15 @@ void Optimizer::reset()
     host_.setAckermannMinTurningRadius(min_turning_r);
   }
   host_.setAccelerationLimits(ax_max_, ax_min_, ay_max_, az_max_);
+  if (validate_trajectory_) {
+    smpc_validation_params vp;
+    smpc_validation_params_default(&vp);
+    vp.collision_lookahead_time = collision_lookahead_time_;
+    vp.consider_footprint = validator_consider_footprint_ ? 1 : 0;
+    host_.setTrajectoryValidation(vp);
+  } else {
+    host_.clearTrajectoryValidation();
+  }
   host_.initialize(settings_, motion_model_name_, controller_frequency_, cc, regenerate_noises_);
   generated_trajectories_.reset(settings_.batch_size, settings_.time_steps);
   RCLCPP_INFO(logger_, "Optimizer reset");
