@@ -6,7 +6,9 @@
 // Optimizer::evalControl runs around its own smpc_optimize call [ref src/optimizer.cpp:134-225]:
 // fallback / reset / retry / throw, the Savitzky-Golay filter, Twist extraction, the shift.  The
 // pieces are the members' own (Optimizer::fillTick / takeTick / fallback / finishTick): a member of
-// a fleet computes what it computes alone, bit for bit.
+// a fleet computes what it computes alone, bit for bit.  A round is a list of stages (fleet.cpp; DESIGN.md
+// §4.7a): enter -> prepareMembers -> avoidance -> tick -> takeResults -> validateRound -> finishMembers;
+// getCriticStats is enter -> breakdownFill -> breakdownRun.  Their state is one Round, kept between rounds.
 //
 // The caller keeps ownership of the optimizers and goes on using them through their own
 // interface between rounds (setCostmap, setSpeedLimit, reset, setNoise, controlSequence(),
@@ -158,28 +160,82 @@ public:
     smpc_validation & out) override;
 
 private:
+  // the caller's arguments of a round or a statistics call, as the stages pass them on
+  struct Args
+  {
+    const std::vector<Pose2D> & poses;
+    const std::vector<Twist2D> & speeds;
+    const std::vector<models::Path> & plans;
+    const std::vector<Pose2D> & goals;
+    const std::vector<float> & tolerances;
+    const std::vector<uint8_t> & take;
+    bool taken(size_t i) const {return take.empty() || take[i] != 0;}
+  };
+  // What one call's stages hand on.  A member of the fleet, so that its vectors keep their capacity
+  // from round to round: a round in the steady state allocates nothing here.  tickAlone and
+  // validateAlone, a retry's calls, borrow the per-slot arrays once the round is done with them.
+  struct Round
+  {
+    bool any{false}, any_v{false};       // somebody to work on (enter), somebody to validate (takeResults)
+    // per member: taken and with a context (enter); FLEET_PEER_* and the tracks [T][2] (avoidance), the
+    // table while it is assembled; the error text before the grouped tick; its verdict was taken over
+    std::vector<uint8_t> on, peer, checked;
+    std::vector<float> tracks;
+    std::vector<std::vector<float>> tab_xy, tab_r;
+    std::vector<std::string> errs_before;
+    // per group slot, sized by regroup(): the arguments of the grouped tick (u: [3][T] each) ...
+    std::vector<smpc_tick_in> ins;
+    std::vector<smpc_tick_out> outs;
+    std::vector<std::vector<float>> u;
+    std::vector<float *> u_ptr;
+    std::vector<uint8_t> take;
+    // ... of smpc_group_set_moving_obstacles ...
+    std::vector<smpc_moving_obstacles_params> mov_params;
+    std::vector<const float *> xy_ptr, r_ptr;
+    std::vector<uint32_t> discs;
+    // ... of smpc_group_validate_trajectories (vpose: [3] each; one slot: wantValidation) ...
+    std::vector<uint8_t> vtake;
+    std::vector<smpc_validation_params> vp;
+    std::vector<double> vpose;
+    std::vector<const float *> vu;
+    std::vector<smpc_validation> vout;
+    // ... and what smpc_group_critic_breakdown returns
+    std::vector<smpc_critic_stats> stats;
+    std::vector<float *> rows;
+    std::vector<int32_t> vstatus, status;
+    void wantValidation(size_t s, const smpc_validation_params & params, const double * pose, const float * u_s);
+  };
+
   int regroup();
   int fail(int code, const std::string & what);
+  // the member's slot in the group; without one -1, or with `call` given what that call throws
+  int slotOf(const Optimizer * member, const char * call = nullptr) const;
+  void addGroupCounters(FleetStats & s) const;
+  // the stages of a call (fleet.cpp, in this order)
+  int enter(const Args & a, bool sizes_ok, std::vector<MemberCriticStats> * without_context);
+  int prepareMembers(const Args & a);
+  int avoidance(const Args & a);
+  int avoidPerMember();
+  int avoidGrouped();
+  int tick();
+  void takeResults(std::vector<MemberResult> & results);
+  void validateRound(std::vector<MemberResult> & results);
+  void finishMembers(std::vector<MemberResult> & results);
+  int breakdownFill(const Args & a, const std::vector<float *> & per_rollout);
+  int breakdownRun(bool rows, std::vector<MemberCriticStats> & out);
 
   std::vector<Optimizer *> members_;
   smpc_group * group_{nullptr};
   std::vector<int> slot_;             // member -> index in the group, -1: no context
   std::vector<size_t> owner_;         // group index -> member
-  // per group slot, one round's arguments
-  std::vector<smpc_tick_in> ins_;
-  std::vector<smpc_tick_out> outs_;
-  std::vector<std::vector<float>> u_;
-  std::vector<float *> u_ptr_;
-  std::vector<uint8_t> take_;
-  std::vector<std::string> errs_before_;
+  Round round_;
   // mutual avoidance: the parameters, one radius per member (empty: off), and where each member was seen last
   smpc_moving_obstacles_params avoid_params_{};
   std::vector<float> avoid_radius_;
   std::vector<uint8_t> seen_;
   bool avoid_per_member_{false};      // SMPC_FLEET_AVOID=per_member, read when the fleet is created
   std::vector<uint8_t> group_table_;  // per member: its table lives in the group's buffer
-  std::vector<std::vector<float>> tab_xy_, tab_r_;   // per member: the round's table while it is assembled
-  std::vector<double> last_pose_;     // [members][3]
+  std::vector<Pose2D> last_pose_;     // per member
   FleetStats stats_{};                // of the groups already dropped, and the retries
   std::string err_;
 };

@@ -1,13 +1,49 @@
 // fleet_c.cpp — extern "C" face of sortham_ns::FleetOptimizer (include/smpc_host.h).
 #include <algorithm>
 #include <exception>
+#include <initializer_list>
 #include <new>
+#include <utility>
 
 #include "fleet_c.hpp"
 
 namespace
 {
 thread_local std::string g_fleet_err;
+
+// the caller's blocks taken apart into the round's arguments, which the handle keeps between rounds;
+// a member taken whose plan is missing refuses the call (text in f->err)
+int unpackRound(sortham_fleet * f, const smpc_tick_in * ins, const uint8_t * take)
+{
+  for (size_t i = 0; i < f->handles.size(); ++i) {
+    f->take[i] = (!take || take[i]) ? 1 : 0;
+    if (!f->take[i]) {
+      continue;
+    }
+    const smpc_tick_in & in = ins[i];
+    if (in.path_len && (!in.path_x || !in.path_y || !in.path_yaw)) {
+      f->err = "member " + std::to_string(i) + ": null plan";
+      return SMPC_ERR_INVALID;
+    }
+    sortham_ns::tickInputFrom(in, f->poses[i], f->speeds[i], f->plans[i], f->goals[i], f->tolerances[i]);
+  }
+  return SMPC_OK;
+}
+// the fleet's counters asked for, each through a pointer that may be null
+int putCounters(
+  const sortham_fleet * f, std::initializer_list<std::pair<uint64_t *, uint64_t sortham_ns::FleetStats::*>> which)
+{
+  if (!f) {
+    return SMPC_ERR_INVALID;
+  }
+  const sortham_ns::FleetStats s = f->fleet->stats();
+  for (const auto & w : which) {
+    if (w.first) {
+      *w.first = s.*w.second;
+    }
+  }
+  return SMPC_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -69,26 +105,11 @@ int sortham_fleet_eval_control(
   }
   const size_t n = f->handles.size();
   try {
-    for (size_t i = 0; i < n; ++i) {
-      f->take[i] = (!take || take[i]) ? 1 : 0;
-      if (!f->take[i]) {
-        continue;
-      }
-      const smpc_tick_in & in = ins[i];
-      if (in.path_len && (!in.path_x || !in.path_y || !in.path_yaw)) {
-        f->err = "member " + std::to_string(i) + ": null plan";
-        return SMPC_ERR_INVALID;
-      }
-      f->poses[i] = {in.pose_x, in.pose_y, static_cast<double>(in.pose_yaw)};
-      f->goals[i] = {in.goal_x, in.goal_y, 0.0};
-      f->speeds[i] = {in.speed_vx, in.speed_vy, in.speed_wz};
-      f->plans[i].x.assign(in.path_x, in.path_x + in.path_len);
-      f->plans[i].y.assign(in.path_y, in.path_y + in.path_len);
-      f->plans[i].yaws.assign(in.path_yaw, in.path_yaw + in.path_len);
-      f->tolerances[i] = in.goal_checker_xy_tolerance;
+    int rc = unpackRound(f, ins, take);
+    if (rc != SMPC_OK) {
+      return rc;
     }
-    const int rc = f->fleet->evalControl(
-      f->poses, f->speeds, f->plans, f->goals, f->tolerances, f->take, f->results);
+    rc = f->fleet->evalControl(f->poses, f->speeds, f->plans, f->goals, f->tolerances, f->take, f->results);
     if (rc != SMPC_OK) {
       f->err = f->fleet->lastError();
       return rc;
@@ -126,30 +147,15 @@ int sortham_fleet_critic_stats(
   const size_t n = f->handles.size();
   std::vector<sortham_ns::MemberCriticStats> res;
   try {
-    for (size_t i = 0; i < n; ++i) {
-      f->take[i] = (!take || take[i]) ? 1 : 0;
-      if (!f->take[i]) {
-        continue;
-      }
-      const smpc_tick_in & in = ins[i];
-      if (in.path_len && (!in.path_x || !in.path_y || !in.path_yaw)) {
-        f->err = "member " + std::to_string(i) + ": null plan";
-        return SMPC_ERR_INVALID;
-      }
-      f->poses[i] = {in.pose_x, in.pose_y, static_cast<double>(in.pose_yaw)};
-      f->goals[i] = {in.goal_x, in.goal_y, 0.0};
-      f->speeds[i] = {in.speed_vx, in.speed_vy, in.speed_wz};
-      f->plans[i].x.assign(in.path_x, in.path_x + in.path_len);
-      f->plans[i].y.assign(in.path_y, in.path_y + in.path_len);
-      f->plans[i].yaws.assign(in.path_yaw, in.path_yaw + in.path_len);
-      f->tolerances[i] = in.goal_checker_xy_tolerance;
+    int rc = unpackRound(f, ins, take);
+    if (rc != SMPC_OK) {
+      return rc;
     }
     std::vector<float *> rows;
     if (per_rollout) {
       rows.assign(per_rollout, per_rollout + n);
     }
-    const int rc = f->fleet->getCriticStats(
-      f->poses, f->speeds, f->plans, f->goals, f->tolerances, f->take, res, rows);
+    rc = f->fleet->getCriticStats(f->poses, f->speeds, f->plans, f->goals, f->tolerances, f->take, res, rows);
     if (rc != SMPC_OK) {
       f->err = f->fleet->lastError();
       return rc;
@@ -212,50 +218,20 @@ int sortham_fleet_avoidance_table(
 int sortham_fleet_stats(
   const sortham_fleet * f, uint64_t * batched_launches, uint64_t * single_ticks, uint64_t * retries)
 {
-  if (!f) {
-    return SMPC_ERR_INVALID;
-  }
-  const sortham_ns::FleetStats s = f->fleet->stats();
-  if (batched_launches) {
-    *batched_launches = s.batched_launches;
-  }
-  if (single_ticks) {
-    *single_ticks = s.single_ticks;
-  }
-  if (retries) {
-    *retries = s.retries;
-  }
-  return SMPC_OK;
+  using S = sortham_ns::FleetStats;
+  return putCounters(f, {{batched_launches, &S::batched_launches}, {single_ticks, &S::single_ticks}, {retries, &S::retries}});
 }
 
 int sortham_fleet_validation_counts(const sortham_fleet * f, uint64_t * launches, uint64_t * members)
 {
-  if (!f) {
-    return SMPC_ERR_INVALID;
-  }
-  const sortham_ns::FleetStats s = f->fleet->stats();
-  if (launches) {
-    *launches = s.validation_launches;
-  }
-  if (members) {
-    *members = s.validated_members;
-  }
-  return SMPC_OK;
+  using S = sortham_ns::FleetStats;
+  return putCounters(f, {{launches, &S::validation_launches}, {members, &S::validated_members}});
 }
 
 int sortham_fleet_moving_launches(const sortham_fleet * f, uint64_t * grouped_launches, uint64_t * table_uploads)
 {
-  if (!f) {
-    return SMPC_ERR_INVALID;
-  }
-  const sortham_ns::FleetStats s = f->fleet->stats();
-  if (grouped_launches) {
-    *grouped_launches = s.grouped_moving_launches;
-  }
-  if (table_uploads) {
-    *table_uploads = s.moving_table_uploads;
-  }
-  return SMPC_OK;
+  using S = sortham_ns::FleetStats;
+  return putCounters(f, {{grouped_launches, &S::grouped_moving_launches}, {table_uploads, &S::moving_table_uploads}});
 }
 
 }  // extern "C"

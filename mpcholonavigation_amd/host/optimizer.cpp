@@ -2,9 +2,11 @@
 // computeVelocityCommands() tick over the libsmpc C-ABI.
 #include "optimizer.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <stdexcept>
+#include <utility>
 
 namespace SORTHAM_HOST_NS
 {
@@ -49,17 +51,13 @@ void Optimizer::setMotionModel(const std::string & model)
 {
   // DiffDrive, Omni and Ackermann (optimizer.cpp:412-426).  Omni is the model the north star
   // names; the two non-holonomic ones run the same kernels with vy held at zero (smpc.h).
-  if (model == "Omni") {
-    motion_model_ = SMPC_MODEL_OMNI;
-    return;
-  }
-  if (model == "DiffDrive") {
-    motion_model_ = SMPC_MODEL_DIFF_DRIVE;
-    return;
-  }
-  if (model == "Ackermann") {
-    motion_model_ = SMPC_MODEL_ACKERMANN;
-    return;
+  const std::pair<const char *, uint32_t> known[] = {
+    {"Omni", SMPC_MODEL_OMNI}, {"DiffDrive", SMPC_MODEL_DIFF_DRIVE}, {"Ackermann", SMPC_MODEL_ACKERMANN}};
+  for (const auto & k : known) {
+    if (model == k.first) {
+      motion_model_ = k.second;
+      return;
+    }
   }
   throw std::runtime_error(
           std::string(
@@ -108,41 +106,25 @@ void Optimizer::initialize(
   // CriticManager::loadCritics (critic_manager.cpp:42-60): the YAML list decides which
   // critics exist; the ones outside the fused set cannot be scored here
   auto & p = critics_.params;
-  p.obstacles.enabled = p.path_align.enabled = p.path_follow.enabled = 0;
-  p.goal_angle.enabled = p.prefer_forward.enabled = 0;
-  p.cost.enabled = p.goal.enabled = p.constraint.enabled = p.twirling.enabled = 0;
-  p.path_angle.enabled = p.velocity_deadband.enabled = p.path_align_legacy.enabled = 0;
+  const struct {const char * name; int32_t * enabled;} known[] = {
+    {"ObstaclesCritic", &p.obstacles.enabled}, {"PathAlignCritic", &p.path_align.enabled},
+    {"PathFollowCritic", &p.path_follow.enabled}, {"GoalAngleCritic", &p.goal_angle.enabled},
+    {"PreferForwardCritic", &p.prefer_forward.enabled}, {"CostCritic", &p.cost.enabled},
+    {"GoalCritic", &p.goal.enabled}, {"ConstraintCritic", &p.constraint.enabled},
+    {"TwirlingCritic", &p.twirling.enabled}, {"PathAngleCritic", &p.path_angle.enabled},
+    {"VelocityDeadbandCritic", &p.velocity_deadband.enabled}, {"PathAlignLegacyCritic", &p.path_align_legacy.enabled}};
+  for (const auto & k : known) {
+    *k.enabled = 0;
+  }
   for (const auto & name : critics_.critics) {
-    if (name == "ObstaclesCritic") {
-      p.obstacles.enabled = 1;
-    } else if (name == "PathAlignCritic") {
-      p.path_align.enabled = 1;
-    } else if (name == "PathFollowCritic") {
-      p.path_follow.enabled = 1;
-    } else if (name == "GoalAngleCritic") {
-      p.goal_angle.enabled = 1;
-    } else if (name == "PreferForwardCritic") {
-      p.prefer_forward.enabled = 1;
-    } else if (name == "CostCritic") {
-      p.cost.enabled = 1;
-    } else if (name == "GoalCritic") {
-      p.goal.enabled = 1;
-    } else if (name == "ConstraintCritic") {
-      p.constraint.enabled = 1;
-    } else if (name == "TwirlingCritic") {
-      p.twirling.enabled = 1;
-    } else if (name == "PathAngleCritic") {
-      p.path_angle.enabled = 1;
-    } else if (name == "VelocityDeadbandCritic") {
-      p.velocity_deadband.enabled = 1;
-    } else if (name == "PathAlignLegacyCritic") {
-      p.path_align_legacy.enabled = 1;
-    } else {
+    const auto k = std::find_if(std::begin(known), std::end(known), [&](const auto & e) {return name == e.name;});
+    if (k == std::end(known)) {
       // (critics.xml registers twelve classes and all twelve are fused: what is left is a name
       // pluginlib would not find either, critic_manager.cpp:45-57)
       throw std::runtime_error(
               "Critic sortham::critics::" + name + " is not one of the registered critic classes (critics.xml)");
     }
+    *k->enabled = 1;
   }
 
   smpc_config cfg;
@@ -167,36 +149,38 @@ void Optimizer::initialize(
   cfg.flags = (visualize_ ? SMPC_FLAG_STORE_TRAJECTORIES : 0u) | (lane_per_rollout_ ? SMPC_FLAG_LANE_PER_ROLLOUT : 0u);
   if (keep && have_built_ && std::memcmp(&cfg, &built_cfg_, sizeof(cfg)) == 0 && noise_seed_ == built_seed_) {
     // same shapes, model, sampling and seed: only the critics' parameters can differ.  What the
-    // reference's reset() does (src/optimizer.cpp:116-132) is reset() below, noise re-draw included.
+    // reference's reset() does (src/optimizer.cpp:116-132) is the reset() that ends configureContext(),
+    // noise re-draw included.
     ctx_ = keep;
     keep = nullptr;
-    ck(ctx_, smpc_set_critics(ctx_, &critics_.params), "smpc_set_critics");
-    pushAccelerationLimits();
-    pushMovingObstacles();
-    // as a fresh context: noise supplied through setNoise() does not survive initialize(), and the
-    // draw starts from the seed's first epoch again (same seed, same noise as a new object)
+  } else {
+    if (keep) {
+      destroyContext(keep);
+      keep = nullptr;
+    }
+    have_built_ = false;
     supplied_noise_ = false;
-    ck(ctx_, smpc_seed(ctx_, noise_seed_), "smpc_seed");
-    reset();
-    return;
+    if (smpc_create(&cfg, &ctx_) != SMPC_OK) {
+      throw std::runtime_error(std::string("smpc_create: ") + smpc_last_error(nullptr));
+    }
+    built_cfg_ = cfg;
+    built_seed_ = noise_seed_;
+    have_built_ = true;
   }
-  if (keep) {
-    destroyContext(keep);
-    keep = nullptr;
-  }
-  have_built_ = false;
-  supplied_noise_ = false;
-  int rc = smpc_create(&cfg, &ctx_);
-  if (rc != SMPC_OK) {
-    throw std::runtime_error(std::string("smpc_create: ") + smpc_last_error(nullptr));
-  }
-  built_cfg_ = cfg;
-  built_seed_ = noise_seed_;
-  have_built_ = true;
+  configureContext();
+}
+
+// what a context kept and a context just created both get: the critics, the limits and the table the
+// object remembers, the seed's first epoch, the reset
+void Optimizer::configureContext()
+{
   ck(ctx_, smpc_set_critics(ctx_, &critics_.params), "smpc_set_critics");
   pushAccelerationLimits();
   pushMovingObstacles();
-  // NoiseGenerator::initialize draws once (noise_generator.cpp:26-42) ...
+  // as a fresh context: noise supplied through setNoise() does not survive initialize(), and the
+  // draw starts from the seed's first epoch again (same seed, same noise as a new object) ...
+  supplied_noise_ = false;
+  // ... NoiseGenerator::initialize draws once (noise_generator.cpp:26-42) ...
   ck(ctx_, smpc_seed(ctx_, noise_seed_), "smpc_seed");
   // ... and Optimizer::initialize ends in reset(), which draws again (H7)
   reset();
@@ -261,10 +245,7 @@ void Optimizer::setMovingObstacles(
   if (n == 0 ? !xy.empty() : xy.size() % (2 * n) != 0 || (ctx_ && xy.size() != n * settings_.time_steps * 2)) {
     throw std::runtime_error("setMovingObstacles: xy must hold [n][time_steps][2] floats");
   }
-  bool ok = std::isfinite(params.collision_cost) && std::isfinite(params.repulsion_weight) &&
-    std::isfinite(params.margin) && params.collision_cost >= 0.0f && params.repulsion_weight >= 0.0f &&
-    params.margin > 0.0f;
-  for (float r : radius) {ok = ok && std::isfinite(r) && r > 0.0f;}
+  bool ok = movingObstacleValuesOk(params, radius);
   for (float v : xy) {ok = ok && std::isfinite(v);}
   if (n && !ok) {
     throw std::runtime_error(
@@ -303,10 +284,7 @@ void Optimizer::getMovingObstacleCosts(std::vector<float> & m, std::vector<uint8
 void Optimizer::reset()
 {
   control_sequence_.reset(settings_.time_steps);
-  control_history_[0] = {0.0f, 0.0f, 0.0f};
-  control_history_[1] = {0.0f, 0.0f, 0.0f};
-  control_history_[2] = {0.0f, 0.0f, 0.0f};
-  control_history_[3] = {0.0f, 0.0f, 0.0f};
+  control_history_.fill({0.0f, 0.0f, 0.0f});
   settings_.constraints = settings_.base_constraints;
   if (ctx_) {
     ck(ctx_, smpc_reset(ctx_), "smpc_reset");   // costs, noise re-draw (noise_generator.cpp:76-95)
@@ -348,36 +326,14 @@ void Optimizer::prepare(
 
 void Optimizer::fillTick(smpc_tick_in & in, float * u)
 {
-  std::memset(&in, 0, sizeof(in));
-  in.pose_x = pose_.x;
-  in.pose_y = pose_.y;
-  in.pose_yaw = static_cast<float>(pose_.yaw);   // float initial_yaw = tf2::getYaw(...)
-  in.speed_vx = speed_.vx;
-  in.speed_vy = speed_.vy;
-  in.speed_wz = speed_.wz;
-  in.path_x = path_.x.data();
-  in.path_y = path_.y.data();
-  in.path_yaw = path_.yaws.data();
-  in.path_len = static_cast<uint32_t>(path_.x.size());
-  in.goal_x = goal_.x;
-  in.goal_y = goal_.y;
-  in.path_pts_valid = nullptr;
-  in.fail_flag_in = fail_flag_ ? 1 : 0;   // sticky across the retry (critic_manager.cpp:70-73)
-  in.goal_checker_xy_tolerance = goal_checker_xy_tolerance_;
-
-  const unsigned int T = settings_.time_steps;
-  std::memcpy(u, control_sequence_.vx.data(), T * sizeof(float));
-  std::memcpy(u + T, control_sequence_.vy.data(), T * sizeof(float));
-  std::memcpy(u + 2 * T, control_sequence_.wz.data(), T * sizeof(float));
+  in = tickIn(pose_, speed_, path_, goal_, goal_checker_xy_tolerance_, fail_flag_);   // (the flag: sticky across the retry)
+  packControls(control_sequence_, settings_.time_steps, u);
   pushConstraints();
 }
 
 void Optimizer::takeTick(const float * u, const smpc_tick_out & out)
 {
-  const unsigned int T = settings_.time_steps;
-  std::memcpy(control_sequence_.vx.data(), u, T * sizeof(float));
-  std::memcpy(control_sequence_.vy.data(), u + T, T * sizeof(float));
-  std::memcpy(control_sequence_.wz.data(), u + 2 * T, T * sizeof(float));
+  unpackControls(u, settings_.time_steps, control_sequence_);
   last_out_ = out;
   fail_flag_ = last_out_.fail_flag != 0;
   if (regenerate_noises_ && !supplied_noise_) {
@@ -407,26 +363,10 @@ smpc_critic_stats Optimizer::getCriticStats(const TickInput & ti, float * per_ro
 {
   // the smpc_tick_in evalControl's first optimize() would hand over (prepare() clears the fail
   // flag), without touching the per-tick members
-  smpc_tick_in in;
-  std::memset(&in, 0, sizeof(in));
-  in.pose_x = ti.robot_pose.x;
-  in.pose_y = ti.robot_pose.y;
-  in.pose_yaw = static_cast<float>(ti.robot_pose.yaw);
-  in.speed_vx = ti.robot_speed.vx;
-  in.speed_vy = ti.robot_speed.vy;
-  in.speed_wz = ti.robot_speed.wz;
-  in.path_x = ti.plan.x.data();
-  in.path_y = ti.plan.y.data();
-  in.path_yaw = ti.plan.yaws.data();
-  in.path_len = static_cast<uint32_t>(ti.plan.x.size());
-  in.goal_x = ti.goal.x;
-  in.goal_y = ti.goal.y;
-  in.goal_checker_xy_tolerance = ti.goal_checker_xy_tolerance;
-  const unsigned int T = settings_.time_steps;
-  std::vector<float> u(3 * T);
-  std::memcpy(u.data(), control_sequence_.vx.data(), T * sizeof(float));
-  std::memcpy(u.data() + T, control_sequence_.vy.data(), T * sizeof(float));
-  std::memcpy(u.data() + 2 * T, control_sequence_.wz.data(), T * sizeof(float));
+  const smpc_tick_in in =
+    tickIn(ti.robot_pose, ti.robot_speed, ti.plan, ti.goal, ti.goal_checker_xy_tolerance, false);
+  std::vector<float> u(3 * settings_.time_steps);
+  packControls(control_sequence_, settings_.time_steps, u.data());
   pushConstraints();   // (what the tick pushes too: the same values)
   smpc_critic_stats stats;
   ck(ctx_, smpc_critic_breakdown(ctx_, &in, u.data(), &stats, per_rollout), "smpc_critic_breakdown");
@@ -456,11 +396,8 @@ bool Optimizer::validated()
   if (!validate_on_ || fail_flag_) {
     return true;   // (a failed tick takes the fallback path as it is)
   }
-  const unsigned int T = settings_.time_steps;
-  std::vector<float> u(3 * T);
-  std::memcpy(u.data(), control_sequence_.vx.data(), T * sizeof(float));
-  std::memcpy(u.data() + T, control_sequence_.vy.data(), T * sizeof(float));
-  std::memcpy(u.data() + 2 * T, control_sequence_.wz.data(), T * sizeof(float));
+  std::vector<float> u(3 * settings_.time_steps);
+  packControls(control_sequence_, settings_.time_steps, u.data());
   smpc_validation v{};
   if (fleet_ && fleet_->grouped(this)) {
     const double pose[3] = {pose_.x, pose_.y, pose_.yaw};

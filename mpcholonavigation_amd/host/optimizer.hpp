@@ -12,7 +12,9 @@
 #define SORTHAM_HOST_OPTIMIZER_HPP_
 
 #include <array>
+#include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -141,6 +143,81 @@ struct TickInput
   float goal_checker_xy_tolerance{-1.0f};
 };
 
+// What passes between these values and the blocks of the C ABI, once each: the control sequence as
+// u [3][T] (vx, vy, wz), a tick's arguments as a smpc_tick_in and back, the moving obstacles' value rule.
+inline void packControls(const models::ControlSequence & s, size_t T, float * u)
+{
+  std::memcpy(u, s.vx.data(), T * sizeof(float));
+  std::memcpy(u + T, s.vy.data(), T * sizeof(float));
+  std::memcpy(u + 2 * T, s.wz.data(), T * sizeof(float));
+}
+
+// (a sequence that holds T steps already keeps its memory)
+inline void unpackControls(const float * u, size_t T, models::ControlSequence & s)
+{
+  s.vx.assign(u, u + T);
+  s.vy.assign(u + T, u + 2 * T);
+  s.wz.assign(u + 2 * T, u + 3 * T);
+}
+
+// The smpc_tick_in of evalControl's arguments; the plan is pointed at, not copied.  fail_flag_in: sticky
+// across a retry (critic_manager.cpp:70-73).
+inline smpc_tick_in tickIn(
+  const Pose2D & pose, const Twist2D & speed, const models::Path & plan, const Pose2D & goal,
+  float goal_checker_xy_tolerance, bool fail_flag_in)
+{
+  smpc_tick_in in;
+  std::memset(&in, 0, sizeof(in));   // (path_pts_valid stays null)
+  in.pose_x = pose.x;
+  in.pose_y = pose.y;
+  in.pose_yaw = static_cast<float>(pose.yaw);   // float initial_yaw = tf2::getYaw(...)
+  in.speed_vx = speed.vx;
+  in.speed_vy = speed.vy;
+  in.speed_wz = speed.wz;
+  in.path_x = plan.x.data();
+  in.path_y = plan.y.data();
+  in.path_yaw = plan.yaws.data();
+  in.path_len = static_cast<uint32_t>(plan.x.size());
+  in.goal_x = goal.x;
+  in.goal_y = goal.y;
+  in.fail_flag_in = fail_flag_in ? 1 : 0;
+  in.goal_checker_xy_tolerance = goal_checker_xy_tolerance;
+  return in;
+}
+
+// The inverse, for the C faces: a smpc_tick_in taken apart into evalControl's arguments, in place (a
+// plan that is assigned again keeps its capacity).  The goal's yaw is not in the block: 0.
+inline void tickInputFrom(
+  const smpc_tick_in & in, Pose2D & pose, Twist2D & speed, models::Path & plan, Pose2D & goal,
+  float & goal_checker_xy_tolerance)
+{
+  pose = {in.pose_x, in.pose_y, static_cast<double>(in.pose_yaw)};
+  goal = {in.goal_x, in.goal_y, 0.0};
+  speed = {in.speed_vx, in.speed_vy, in.speed_wz};
+  plan.x.assign(in.path_x, in.path_x + in.path_len);
+  plan.y.assign(in.path_y, in.path_y + in.path_len);
+  plan.yaws.assign(in.path_yaw, in.path_yaw + in.path_len);
+  goal_checker_xy_tolerance = in.goal_checker_xy_tolerance;
+}
+
+inline TickInput tickInputFrom(const smpc_tick_in & in)
+{
+  TickInput ti;
+  tickInputFrom(in, ti.robot_pose, ti.robot_speed, ti.plan, ti.goal, ti.goal_checker_xy_tolerance);
+  return ti;
+}
+
+// smpc_set_moving_obstacles' rule for the parameters and the radii, for a table refused before a context sees it
+inline bool movingObstacleValuesOk(const smpc_moving_obstacles_params & p, const std::vector<float> & radius)
+{
+  bool ok = std::isfinite(p.collision_cost) && std::isfinite(p.repulsion_weight) && std::isfinite(p.margin) &&
+    p.collision_cost >= 0.0f && p.repulsion_weight >= 0.0f && p.margin > 0.0f;
+  for (float r : radius) {
+    ok = ok && std::isfinite(r) && r > 0.0f;
+  }
+  return ok;
+}
+
 // What an Optimizer asks of the fleet it is a member of (fleet.hpp: FleetOptimizer, N optimizers
 // ticked through one smpc_group).  An interface, so that this class links without the fleet.
 class FleetLink
@@ -257,6 +334,7 @@ protected:
   // ref :147-154: Savitzky-Golay filter, Twist, shift
   Twist2D finishTick();
   void destroyContext(smpc_ctx * ctx);     // tells the fleet first: its group goes before the context
+  void configureContext();                 // initialize()'s tail, for a context kept and a new one alike
   bool fallback(bool fail);                // ref :166-183 (retry counter per object)
   // true unless validation is on, the tick did not fail, and the control sequence's trajectory collides
   bool validated();

@@ -154,15 +154,9 @@ int sortham_optimizer_eval_control(
   if (!o || !in || !twist_out) {return SMPC_ERR_INVALID;}
   return guarded(
     o, [&]() {
-      sortham_ns::Pose2D pose{in->pose_x, in->pose_y, static_cast<double>(in->pose_yaw)};
-      sortham_ns::Pose2D goal{in->goal_x, in->goal_y, 0.0};
-      sortham_ns::Twist2D speed{in->speed_vx, in->speed_vy, in->speed_wz};
-      sortham_ns::models::Path plan;
-      plan.x.assign(in->path_x, in->path_x + in->path_len);
-      plan.y.assign(in->path_y, in->path_y + in->path_len);
-      plan.yaws.assign(in->path_yaw, in->path_yaw + in->path_len);
+      const sortham_ns::TickInput ti = sortham_ns::tickInputFrom(*in);
       const sortham_ns::Twist2D t =
-        o->opt.evalControl(pose, speed, plan, goal, in->goal_checker_xy_tolerance);
+        o->opt.evalControl(ti.robot_pose, ti.robot_speed, ti.plan, ti.goal, ti.goal_checker_xy_tolerance);
       twist_out[0] = t.vx;
       twist_out[1] = t.vy;
       twist_out[2] = t.wz;
@@ -175,17 +169,7 @@ int sortham_optimizer_critic_stats(
 {
   if (!o || !in || !stats) {return SMPC_ERR_INVALID;}
   return guarded(
-    o, [&]() {
-      sortham_ns::TickInput ti;
-      ti.robot_pose = {in->pose_x, in->pose_y, static_cast<double>(in->pose_yaw)};
-      ti.goal = {in->goal_x, in->goal_y, 0.0};
-      ti.robot_speed = {in->speed_vx, in->speed_vy, in->speed_wz};
-      ti.plan.x.assign(in->path_x, in->path_x + in->path_len);
-      ti.plan.y.assign(in->path_y, in->path_y + in->path_len);
-      ti.plan.yaws.assign(in->path_yaw, in->path_yaw + in->path_len);
-      ti.goal_checker_xy_tolerance = in->goal_checker_xy_tolerance;
-      *stats = o->opt.getCriticStats(ti, per_rollout);
-    });
+    o, [&]() {*stats = o->opt.getCriticStats(sortham_ns::tickInputFrom(*in), per_rollout);});
 }
 
 int sortham_optimizer_last_tick(const sortham_optimizer * o, smpc_tick_out * out)
@@ -273,10 +257,7 @@ int sortham_optimizer_get_control_sequence(sortham_optimizer * o, float * u)
 {
   if (!o || !u) {return SMPC_ERR_INVALID;}
   const auto & cs = o->opt.controlSequence();
-  const size_t T = cs.vx.size();
-  std::memcpy(u, cs.vx.data(), T * sizeof(float));
-  std::memcpy(u + T, cs.vy.data(), T * sizeof(float));
-  std::memcpy(u + 2 * T, cs.wz.data(), T * sizeof(float));
+  sortham_ns::packControls(cs, cs.vx.size(), u);
   return SMPC_OK;
 }
 
@@ -284,10 +265,7 @@ int sortham_optimizer_set_control_sequence(sortham_optimizer * o, const float * 
 {
   if (!o || !u) {return SMPC_ERR_INVALID;}
   auto & cs = o->opt.controlSequence();
-  const size_t T = cs.vx.size();
-  std::memcpy(cs.vx.data(), u, T * sizeof(float));
-  std::memcpy(cs.vy.data(), u + T, T * sizeof(float));
-  std::memcpy(cs.wz.data(), u + 2 * T, T * sizeof(float));
+  sortham_ns::unpackControls(u, cs.vx.size(), cs);
   return SMPC_OK;
 }
 
@@ -320,9 +298,7 @@ int sortham_optimizer_get_optimized_trajectory(sortham_optimizer * o, float * xy
 void sortham_utils_savitsky_golay(float * u, uint32_t T, float * history, int shift)
 {
   sortham_ns::models::ControlSequence cs;
-  cs.vx.assign(u, u + T);
-  cs.vy.assign(u + T, u + 2 * T);
-  cs.wz.assign(u + 2 * T, u + 3 * T);
+  sortham_ns::unpackControls(u, T, cs);
   std::array<sortham_ns::models::Control, 4> h;
   for (int i = 0; i < 4; ++i) {
     h[i] = {history[3 * i], history[3 * i + 1], history[3 * i + 2]};
@@ -330,9 +306,7 @@ void sortham_utils_savitsky_golay(float * u, uint32_t T, float * history, int sh
   sortham_ns::models::OptimizerSettings s;
   s.shift_control_sequence = shift != 0;
   sortham_ns::utils::savitskyGolayFilter(cs, h, s);
-  std::memcpy(u, cs.vx.data(), T * sizeof(float));
-  std::memcpy(u + T, cs.vy.data(), T * sizeof(float));
-  std::memcpy(u + 2 * T, cs.wz.data(), T * sizeof(float));
+  sortham_ns::packControls(cs, T, u);
   for (int i = 0; i < 4; ++i) {
     history[3 * i] = h[i].vx;
     history[3 * i + 1] = h[i].vy;

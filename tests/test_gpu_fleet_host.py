@@ -415,6 +415,9 @@ def test_a_round_that_fails_as_a_whole_moves_nobody_and_the_next_one_is_the_twin
         fleet.eval_control([t, long, t])
     assert e.value.code == A.SMPC_ERR_UNSUPPORTED, str(e.value)
     print(f"[fleet] abandoned round: {e.value}")
+    # lastError() names the call and the member whose context met the error, then the library's own text
+    text = str(e.value).split("] ", 1)[1]
+    assert text.startswith("smpc_group_optimize_some: member 1: ") and "SMPC_MAX_PATH" in text, text
     for m, (u, c, _) in zip(members, state):
         assert np.array_equal(m.get_control_sequence(), u) and np.array_equal(m.get_constraints()[0], c)
     assert fleet.stats().retries == stats.retries

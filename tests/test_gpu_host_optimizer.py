@@ -163,6 +163,29 @@ def test_speed_limit_and_reset():
     assert np.array_equal(h.get_constraints()[0], c0)
 
 
+def test_control_sequence_block_round_trips_row_by_row():
+    """sortham_optimizer_set_control_sequence / get_control_sequence carry a [3][T] block whose rows are
+    vx, vy, wz in that order: three distinct rows come back bit for bit, and a block with one row set
+    moves only that row's coordinate of the integrated trajectory (Omni, from the pose at the origin)."""
+    from mpcholonavigation_amd.host_optimizer import Optimizer
+    T = 56
+    h = Optimizer(default_config(batch_size=256, time_steps=T), default_critics(), 20.0)
+    t = np.arange(T, dtype=np.float32)
+    u = np.stack([0.1 + 0.001 * t, -0.2 + 0.003 * t, 0.5 - 0.007 * t]).astype(np.float32)
+    assert len({r.tobytes() for r in u}) == 3
+    h.set_control_sequence(u)
+    assert np.array_equal(h.get_control_sequence().view(np.uint32), u.view(np.uint32))
+    for row, moved in ((0, 0), (1, 1), (2, 2)):                  # vx -> x, vy -> y, wz -> yaw
+        one = np.zeros((3, T), np.float32)
+        one[row] = 0.25
+        h.set_control_sequence(one)
+        assert np.array_equal(h.get_control_sequence(), one)
+        traj = np.asarray(h.get_optimized_trajectory()).reshape(T, 3)
+        assert np.all(np.diff(traj[:, moved]) > 0) and traj[0, moved] > 0, (row, traj[:3])
+        assert not traj[:, [c for c in range(3) if c != moved]].any(), (row, traj[:3])
+    h.close()
+
+
 def test_initialize_again_keeps_the_device_context_for_an_unchanged_configuration():
     """The plugin's reset() runs Optimizer::initialize() after every idle period
     (src/controller.cpp:89-92, src/optimizer.cpp:116-132).  With the configuration the device
